@@ -23,6 +23,7 @@ Rows are cut into N contiguous shards of equal work; B = A is replicated on ever
 
     python bench.py --gpus N --steps K --warmup W          (spawns its N rank processes itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                 (rank 0's result of the last timed step as .npy)
 
 Prints ONE JSON line on rank 0.
 """
@@ -59,7 +60,11 @@ def parse_args():
     ap.add_argument("--scale", type=int, default=0)
     ap.add_argument("--weak", action="store_true", help="N > 1: scale 22 + log2 N instead of BASELINE cfg4 (scale 24)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write rank 0's C of the last timed step to DIR (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -320,6 +325,30 @@ def pmc_profile(wname, world):
     return None, None
 
 
+DUMP_SAMPLES = {"C_row_ptr": 1 << 20, "C_col_idx": 2 << 20}   # values + their positions in float64: 48 MB at most
+
+
+def dump_outputs(C, dev, out_dir):
+    """Write the result C of the timed path -- what bspgemm_multiply hands its caller, C.row_ptr (int64) and
+    C.col_idx (int32) of this rank's rows -- as float64 DIR/C_row_ptr.npy and DIR/C_col_idx.npy, exact for the
+    values they hold.  An array longer than DUMP_SAMPLES[name] (C.col_idx of the scale-22 matrix holds 1.3e9
+    entries) is written at a fixed sample of positions instead, drawn by a generator seeded with 1, and the
+    positions go to DIR/<name>_index.npy: two builds that compute the same C write the same files."""
+    import numpy as np
+    import torch
+    from bspgemm import dist as bdist
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"C_row_ptr": (C.row_ptr_device, C.rows + 1, torch.int64),
+              "C_col_idx": (C.col_idx_device, C.nnz, torch.int32)}
+    for name, (ptr, size, dtype) in arrays.items():
+        view = bdist.device_tensor(ptr, size, dtype, dev)        # zero-copy view of the result on the GPU
+        if size > DUMP_SAMPLES[name]:
+            idx = np.unique(np.random.default_rng(1).integers(0, size, DUMP_SAMPLES[name]))
+            view = view[torch.from_numpy(idx).to(dev)]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), view.cpu().numpy().astype(np.float64))
+
+
 def main():
     args = parse_args()
     if (args.gpus > 1 or os.environ.get("BSPGEMM_BENCH_FORCE_SPAWN") == "1") and "WORLD_SIZE" not in os.environ:
@@ -430,6 +459,8 @@ def main():
     # per-step HIP-event brackets recorded on the library's streams DURING the timed region
     hist = [ctx.stats(age) for age in range(min(args.steps, MAX_STAT_STEPS))]
     st = hist[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, dev, args.dump_outputs)   # before the untimed steps below free this result
     # the per-class brackets are OFF in the timed steps (an event pair around each of the ~17 class launches costs
     # about 1 %): two extra, untimed steps with them on itemise the classes (roofline.instances)
     ctx.set_class_timing(True)

@@ -14,7 +14,10 @@ Which reference entry point produced which golden:
   *_mat       : SpGEMM_mat        Matlab/inc/BSpGEMM.c:9-47      (A != B)
   *_masked    : SpGEMM_masked     final/SpGEMM_mpi_omp.c:232-288
   *_readcoo   : readCOO           final/utils.c:47-81            (loader, transposing)
+  live_reference : SpGEMM_bigslice and SpGEMM_omp on the inputs of the live tests in test_oracle_pinned.py,
+                   C.row_ptr whole, the inputs and C.col_idx as SHA-256 digests (mint_live_reference)
 """
+import hashlib
 import os
 import shutil
 import sys
@@ -96,6 +99,34 @@ def main():
             f.write("%d %d\n" % (i, j))
     rp, ci, m, n = R.read_mtx(mtx)
     save("loader_case_readcoo", row_ptr=rp, col_idx=ci, m=m, n=n)
+
+    mint_live_reference(R)
+
+
+def sha256(*arrays):
+    """digest of int32 arrays (little-endian), as 32 uint8 -- the same as test_oracle_pinned._sha256"""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a, dtype="<i4").tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8)
+
+
+def mint_live_reference(R):
+    """11. the reference's results on the inputs of test_live_reference_* (test_oracle_pinned.py), so that those
+    tests also run where oracle/_ref cannot be built.  C.col_idx is kept as a digest: whole, the five products
+    would add 2 MB here."""
+    out = {}
+    for maker, args in [(gen.uniform, (3000, 10, 101)), (gen.rmat, (12, 8, (0.57, 0.19, 0.19, 0.05), 102)),
+                        (gen.with_special_rows, (777, 5, 103)), (gen.dups_unsorted, (640, 12, 104)),
+                        (gen.powerlaw, (2048, 12, 105))]:
+        rp, ci, n = maker(*args)
+        crow, ccol = R.bigslice(rp, ci, rp, ci, n, 0, n)
+        key = maker.__name__ + "_bigslice"
+        out.update({key + "_a_sha256": sha256(rp, ci), key + "_c_rp": crow, key + "_c_ci_sha256": sha256(ccol)})
+    rp, ci, n = gen.uniform(2048, 7, 106)
+    crow, ccol = R.omp(rp, ci, rp, ci, n, 128, row0=512, rows=1024)
+    out.update({"uniform_omp_a_sha256": sha256(rp, ci), "uniform_omp_c_rp": crow, "uniform_omp_c_ci_sha256": sha256(ccol)})
+    save("live_reference", **out)
 
 
 if __name__ == "__main__":

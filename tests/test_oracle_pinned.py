@@ -2,10 +2,12 @@
 
 (1) against the committed golden vectors in tests/golden/ -- outputs of the reference itself
     (oracle/_ref, built from /root/reference by oracle/Makefile; script: make_golden.py);
-(2) against the compiled reference live, when oracle/_ref is present, on fresh seeded inputs.
+(2) on fresh seeded inputs, against the reference's results stored in golden/live_reference.npz, and
+    against the compiled reference live where oracle/_ref is built.
 CPU only; no GPU needed.
 """
 import glob
+import hashlib
 import os
 
 import numpy as np
@@ -102,11 +104,22 @@ def test_scipy_second_opinion():
     assert np.array_equal(crow, Cs.indptr) and np.array_equal(ccol, Cs.indices)
 
 
-# ---- live comparison with the compiled reference (this container / prebuilt on the GPU box) ----
-needs_ref = pytest.mark.skipif(O.reference() is None, reason="oracle/_ref not built")
+# ---- fresh seeded inputs: the stored reference results, and the compiled reference live where it is built ----
+def _sha256(*arrays):
+    """the digest make_golden.sha256 stored: int32 arrays, little-endian"""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a, dtype="<i4").tobytes())
+    return np.frombuffer(h.digest(), dtype=np.uint8)
 
 
-@needs_ref
+def _same_as_stored(key, rp, ci, crow, ccol):
+    g = _load("live_reference")
+    assert np.array_equal(_sha256(rp, ci), g[key + "_a_sha256"]), "tests/gen.py no longer makes the input of " + key
+    assert np.array_equal(crow, g[key + "_c_rp"])
+    assert np.array_equal(_sha256(ccol), g[key + "_c_ci_sha256"])
+
+
 @pytest.mark.parametrize("maker,args", [
     (gen.uniform, (3000, 10, 101)),
     (gen.rmat, (12, 8, (0.57, 0.19, 0.19, 0.05), 102)),
@@ -115,20 +128,25 @@ needs_ref = pytest.mark.skipif(O.reference() is None, reason="oracle/_ref not bu
     (gen.powerlaw, (2048, 12, 105)),
 ])
 def test_live_reference_bigslice(maker, args):
-    R = O.reference()
     rp, ci, n = maker(*args)
     crow, ccol = O.spgemm(rp, ci, rp, ci, n)
-    rrow, rcol = R.bigslice(rp, ci, rp, ci, n, 0, n)
-    assert np.array_equal(crow, rrow) and np.array_equal(ccol, rcol)
-
-
-@needs_ref
-def test_live_reference_omp_and_loader(tmp_path):
+    _same_as_stored(maker.__name__ + "_bigslice", rp, ci, crow, ccol)
     R = O.reference()
+    if R is not None:
+        rrow, rcol = R.bigslice(rp, ci, rp, ci, n, 0, n)
+        assert np.array_equal(crow, rrow) and np.array_equal(ccol, rcol)
+
+
+def test_live_reference_omp_and_loader(tmp_path):
     rp, ci, n = gen.uniform(2048, 7, 106)
-    rrow, rcol = R.omp(rp, ci, rp, ci, n, 128, row0=512, rows=1024)
     crow, ccol = O.spgemm_omp(rp, ci, rp, ci, n, 128, 2, row0=512, rows=1024)
-    assert np.array_equal(crow, rrow) and np.array_equal(ccol, rcol)
-    a, b, m, nn = R.read_mtx(os.path.join(GOLDEN, "validity_test.mtx"))
+    _same_as_stored("uniform_omp", rp, ci, crow, ccol)
     c, d, m2, nn2 = O.read_mtx(os.path.join(GOLDEN, "validity_test.mtx"))
-    assert (m, nn) == (m2, nn2) and np.array_equal(a, c) and np.array_equal(b, d)
+    g = _load("validity")                                   # the reference's readCOO of the same file
+    assert (int(g["m"]), int(g["n"])) == (m2, nn2) and np.array_equal(g["a_rp"], c) and np.array_equal(g["a_ci"], d)
+    R = O.reference()
+    if R is not None:
+        rrow, rcol = R.omp(rp, ci, rp, ci, n, 128, row0=512, rows=1024)
+        assert np.array_equal(crow, rrow) and np.array_equal(ccol, rcol)
+        a, b, m, nn = R.read_mtx(os.path.join(GOLDEN, "validity_test.mtx"))
+        assert (m, nn) == (m2, nn2) and np.array_equal(a, c) and np.array_equal(b, d)
