@@ -87,6 +87,7 @@ bspgemm_status ensure_pad(const bspgemm_matrix *m)
     HIPCHK_B(hipGetLastError());
     HIPCHK_B(hipStreamSynchronize(s));
     drop();
+    m->nnz_pad = total;
     m->pad_state = 1;
     return BSPGEMM_OK;
 }
@@ -307,6 +308,7 @@ extern "C" bspgemm_status bspgemm_matrix_invalidate(bspgemm_matrix *m)
     m->d_row_ptr_pad = nullptr;
     m->d_ext = nullptr;
     m->pad_state = 0;
+    m->nnz_pad = 0;
     return BSPGEMM_OK;
 }
 

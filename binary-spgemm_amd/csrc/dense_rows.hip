@@ -187,7 +187,7 @@ __device__ __forceinline__ void gather_sweep(GatherLds<kThreads, kQPT> &L, Gathe
                 for (int u = 0; u < NU; u++) {
                     if (nnzB >= 4) {                               // (uniform)
                         cv[u] = *reinterpret_cast<const Int4U *>(Bcol + base[u]);      // only dword aligned
-                    } else {                                       // a B of one to three entries: base is 0, no vector load fits
+                    } else {                                       // a B.col_idx of one to three entries (never the padded copy: 16+): base is 0, no vector load fits
                         cv[u].x = Bcol[0];
                         cv[u].y = nnzB > 1 ? Bcol[1] : 0;
                         cv[u].z = nnzB > 2 ? Bcol[2] : 0;

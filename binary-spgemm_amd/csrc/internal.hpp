@@ -151,8 +151,11 @@ struct bspgemm_matrix {
     mutable int *d_row_ptr_pad = nullptr;  // rows + 1: where row j starts in d_col_pad
     mutable int2 *d_ext = nullptr;         // {start in d_col_pad, length} per row: gathered by k_row_work when there is no blocked table
     mutable int pad_state = 0;             // 0 undecided, 1 in use, 2 not for this operand
-    // what the accumulate kernels gather from: the padded copy when it exists
+    mutable long long nnz_pad = 0;         // entries of d_col_pad (without its 64 of slack): at least 16 when it exists
+    // what the accumulate kernels gather from: the padded copy when it exists, and how many entries that array holds
+    // (the heavy-row gather picks scalar loads for an array of fewer than four: B->nnz would be wrong for the padded copy)
     const int *gather_col() const { return pad_state == 1 ? d_col_pad : d_col_idx; }
+    long long gather_nnz() const { return pad_state == 1 ? nnz_pad : nnz; }
 };
 
 bspgemm_status ensure_deg8(const bspgemm_matrix *m);

@@ -66,7 +66,7 @@ const char *bspgemm_build_info(void);
  * per context after a multiply (10.7 GB for BASELINE config 3).  bspgemm_destroy releases all.
  * Environment (read once, in bspgemm_create; every knob also has a setter, bspgemm_set_option / _set_flow /
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
- * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=0|1,
+ * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
@@ -152,8 +152,11 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  *                    more; +1.4 x nnz(B) ints of device memory on the bench matrix).  Opt-in: measured worth 8-9 % of the
  *                    numeric phase on matrices whose rows all have 16 entries and nothing on the R-MAT bench matrix
  *                    (DESIGN.md 4.2).  Decided on first use as B, like BLOCKED_EXTENTS.
- *   SMALL_PATH       -1 automatic (default: products of at most 65536 with a cached result buffer take the
- *                    single-launch path), 0 never, 1 whenever the product fits it                       */
+ *   SMALL_PATH       -1 automatic (default), 0 never, 1 whenever the product may fit: the single-read-back path of few
+ *                    launches is tried when the flow is not EXACT (never under it), the range has 1 .. 2^17 rows and the
+ *                    WHOLE of A has at most 32768 nonzeros; -1 also needs nnz(A) x B's mean row length <= 32768.  The
+ *                    device then checks that the product fits (at most 65536 products, 2048 in any row) and otherwise
+ *                    hands it to the general flow (bspgemm_stats.small_path = 0).  No result-cache condition.  */
 typedef enum bspgemm_option {
     BSPGEMM_OPT_CLASS_STREAMS   = 1,
     BSPGEMM_OPT_BLOCKED_EXTENTS = 2,

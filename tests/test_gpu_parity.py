@@ -135,26 +135,10 @@ def test_every_capacity_class_is_exercised(ctx):
     """rows with F_i just below/above each class boundary 64,128,...,2048, 524288 (the small heavy-row shape's cap
     when one window covers the columns) and beyond"""
     n = 6000
-    rng = np.random.default_rng(301)
-    # B: row j has (j % 97) + 1 entries; A rows pick B rows so that F_i sweeps 1..4000
-    b_rows = np.repeat(np.arange(n), (np.arange(n) % 97) + 1)
-    b_cols = rng.integers(0, n, size=b_rows.size)
-    b_rp, b_ci = gen._csr_from_pairs(b_rows, b_cols, n)
-    blen = np.diff(b_rp)
-    caps = [64 * c for c in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32)]   # csrc/kernels.hpp kWaveChunks
-    targets = ([1, 2] + [t for cap in caps for t in (cap - 1, cap, cap + 1)] + [3000, 4000, 100000, 280000, 600000]) * 4
-    a_rows, a_cols = [], []
-    for i, t in enumerate(targets):
-        acc = 0
-        while acc < t:
-            j = int(rng.integers(0, n))
-            if acc + blen[j] <= t + 3:
-                a_rows.append(i)
-                a_cols.append(j)
-                acc += blen[j]
     # (repeated column entries stay: a 6000-column A row could not reach 600000 products without them --
     # rows need not be duplicate-free, SURVEY.md 8a1)
-    a_rp, a_ci = gen._csr_from_pairs(a_rows, a_cols, n, dedup=False)
+    a_rp, a_ci, b_rp, b_ci = gen.class_boundary_rows(repeat=4, seed=301, n=n)
+    caps = gen.WAVE_CAPS
     erp, eci = O.spgemm(a_rp, a_ci, b_rp, b_ci, n)
     crp, cci, st = hip_product(ctx, a_rp, a_ci, n, b_rp, b_ci, n)
     assert_same(crp, cci, erp, eci)
@@ -203,44 +187,11 @@ def test_rank_rows_class(ctx, ncols):
     (csrc/dense_rows.hip k_rank_rows), on wider matrices in spans of 2^20 columns: boundaries of the class, dense column
     clusters (full 32-column slots, full top words), sources of one to three entries (masked quads), more than 512 sources
     (several batches) and more than 4096 quads (several tiles), repeated A entries, the last column"""
-    rng = np.random.default_rng(ncols % 1000 + 77)
     nb = 9000
-    lens = np.concatenate([rng.integers(1, 4, 6000), rng.integers(4, 200, 2000), rng.integers(200, 1500, 1000)])
-    rows, cols = [], []
-    for j, L in enumerate(lens):
-        kind = j % 4
-        if kind == 0:      # a dense cluster somewhere (consecutive columns: whole slots and top words)
-            c0 = int(rng.integers(0, ncols - L))
-            c = np.arange(c0, c0 + L)
-        elif kind == 1:    # the tail of the column range, including the last column
-            c = ncols - 1 - rng.choice(min(ncols, 4 * L + 8), size=L, replace=False)
-        elif kind == 2 and ncols > (1 << 20):   # around a span boundary
-            c = (1 << 20) * int(rng.integers(1, (ncols >> 20) + 1)) - 2 * L + rng.choice(4 * L, size=L, replace=False)
-            c = c[c < ncols]
-            c = np.concatenate([c, rng.choice(1000, size=L - c.size, replace=False)]) if c.size < L else c
-        else:
-            c = rng.permutation(np.unique(rng.integers(0, ncols, size=2 * L)))[:L] if ncols > (1 << 21) else rng.choice(ncols, size=L, replace=False)
-            c = np.concatenate([c, ncols - 1 - np.arange(L - c.size)]) if c.size < L else rng.permutation(c)
-        rows.append(np.full(L, j)); cols.append(c)
-    b_rp, b_ci = gen._csr_from_pairs(np.concatenate(rows), np.concatenate(cols), nb)
-    blen = np.diff(b_rp)
-    short = np.flatnonzero(blen <= 3); longer = np.flatnonzero(blen > 3)
-    a_rows, a_cols = [], []
     targets = [2049, 2100, 3000, 4097, 5000, 6143, 6144, 6145, 7000, 2500, 2049, 6144, 5000]
-    ones = np.flatnonzero(blen == 1)
-    for i, t in enumerate(targets):
-        acc = 0
-        pool = short if i in (3, 4, 9) else longer            # rows 3, 4, 9: thousands of one-to-three-entry sources
-        if i == 12:
-            pool = ones                                       # 5000 one-entry sources: 5000 quads, two tiles of the gather plan
-        while acc < t:
-            j = int(pool[rng.integers(0, pool.size)])
-            if acc + blen[j] <= t:
-                a_rows.append(i); a_cols.append(j); acc += blen[j]
-            elif t - acc <= 3:
-                j = int(short[np.flatnonzero(blen[short] == t - acc)[0]])
-                a_rows.append(i); a_cols.append(j); acc += blen[j]
-    a_rp, a_ci = gen._csr_from_pairs(a_rows, a_cols, len(targets), dedup=False)
+    # rows 3, 4, 9: thousands of one-to-three-entry sources; row 12: 5000 one-entry sources, 5000 quads, two tiles of the gather plan
+    a_rp, a_ci, b_rp, b_ci = gen.rank_rows(ncols, targets, short_rows=(3, 4, 9), ones_rows=(12,), seed=ncols % 1000 + 77)
+    blen = np.diff(b_rp)
     erp, eci = O.spgemm(a_rp, a_ci, b_rp, b_ci, ncols)
     crp, cci, st = hip_product(ctx, a_rp, a_ci, nb, b_rp, b_ci, ncols)
     assert_same(crp, cci, erp, eci)
@@ -251,25 +202,33 @@ def test_rank_rows_class(ctx, ncols):
     assert st["rows_per_bin"][RANK + 1] == sum(1 for t in targets if t > 6144)
 
 
-@pytest.mark.parametrize("nnzb", [1, 2, 3, 5])
-def test_heavy_row_over_a_tiny_b(ctx, nnzb):
+TINY_B_CASES = [(nnzb, b_cols, padded) for nnzb in (1, 2, 3, 5) for b_cols in ((7, 0, 10, 3, 4), (7, 3, 10, 4, 5)) for padded in (0, 1)]
+
+
+@pytest.mark.parametrize("nnzb,b_cols,padded", TINY_B_CASES,
+                         ids=["%d%s%s" % (n, "" if c[1] == 0 else "-cols_off_0", "-padded" if p else "") for n, c, p in TINY_B_CASES])
+def test_heavy_row_over_a_tiny_b(ctx, nnzb, b_cols, padded):
     """the heavy rows gather B in 16-byte quads; a B.col_idx of fewer than four entries has no room for one (scalar loads),
     and the quads of the first sources of a B begin before the array (clamped and masked): a row of 3000-5000 repeated A entries
-    over a B of 1, 2, 3 and 5 nonzeros"""
+    over a B of 1, 2, 3 and 5 nonzeros.  With the padded copy of B.col_idx (BSPGEMM_OPT_PADDED_ROWS) the gathered array has 16
+    entries or more however small B is: the gather must size it by the copy, not by B.nnz (B row 1 lies at entry 16 there).
+    The second column set has no 0, which is what the scalar path fills a quad's fourth lane with."""
     ncols = 11
-    b_rows = [0, 1, 1, 2, 2][:nnzb]
-    b_cols = [7, 0, 10, 3, 4][:nnzb]
-    b_rp, b_ci = gen._csr_from_pairs(b_rows, b_cols, 3)
-    rng = np.random.default_rng(900 + nnzb)
-    nrep = 5000
-    a_rows = np.concatenate([np.zeros(nrep, np.int64), np.ones(3, np.int64)])
-    a_cols = np.concatenate([rng.integers(0, 3, size=nrep), [0, 1, 2]])
-    a_rp, a_ci = gen._csr_from_pairs(a_rows, a_cols, 2, dedup=False)
+    a_rp, a_ci, b_rp, b_ci = gen.tiny_b_heavy(nnzb, b_cols)
     erp, eci = O.spgemm(a_rp, a_ci, b_rp, b_ci, ncols)
-    crp, cci, st = hip_product(ctx, a_rp, a_ci, 3, b_rp, b_ci, ncols)
+    old = ctx.get_option("padded_rows")
+    ctx.set_option("padded_rows", padded)
+    try:
+        crp, cci, st = hip_product(ctx, a_rp, a_ci, 3, b_rp, b_ci, ncols)
+    finally:
+        ctx.set_option("padded_rows", old)
     assert_same(crp, cci, erp, eci)
     if nnzb >= 2:
         assert sum(st["rows_per_bin"][-3:]) == 1, st["rows_per_bin"]      # row 0 is a heavy row (F > 2048)
+    if st["small_path"]:          # (nnzb = 1: row 0 has about 1700 products and the small-product path takes it, unpadded)
+        assert nnzb == 1 and ctx.flow_name != "exact" and st["padded_rows"] == 0
+    else:
+        assert st["padded_rows"] == padded
 
 
 def test_fuzz_small_shapes(ctx):
