@@ -34,7 +34,8 @@ KNOBS = list(itertools.product(("upper-bound", "exact", "auto"), (0, 1), (0, 1),
 MASKED_KNOBS = list(itertools.product((0, 1), (0, 1), (0, 1), (1, 3)))
 # csrc/kernels.hpp: the small-product path's limits, the class layout
 SMALL_MAX_PRODUCTS, SMALL_MAX_ROW, SMALL_MAX_ROWS, SMALL_MAX_NNZ_A = 65536, 2048, 1 << 17, 32768
-NUM_BINS, RANK_BIN, MID_BIN, DENSE_BIN = 20, 17, 18, 19
+RANK_BIN, MID_BIN, DENSE_BIN = gen.RANK_BIN, gen.MID_BIN, gen.DENSE_BIN
+row_products, expected_bins = gen.row_products, gen.expected_bins
 
 
 @pytest.fixture(scope="module")
@@ -46,27 +47,6 @@ def ctx():
 
 
 # ---------------------------------------------------------------- host-side model of the path ---------------
-def row_products(a_rp, a_ci, b_rp, r0, r1):
-    """F_i of rows [r0, r1)"""
-    per = np.diff(np.asarray(b_rp, np.int64))[np.asarray(a_ci, np.int64)]
-    cs = np.concatenate([[0], np.cumsum(per)])
-    a_rp = np.asarray(a_rp, np.int64)
-    return cs[a_rp[r0 + 1:r1 + 1]] - cs[a_rp[r0:r1]]
-
-
-def expected_bins(F, cols):
-    """rows per capacity class as csrc/prepass.hip bin_of places them (BSPGEMM_RANK_ROWS at its default)"""
-    passes = (cols + (1 << 18) - 1) >> 18
-    mid_cap = 524288 if passes <= 1 else max(2048, 524288 // passes)
-    rank_cap = 6144 if (1 << 18) < cols <= (1 << 24) else 0
-    b = np.zeros(F.size, np.int64)
-    wave = (F > 0) & (F <= 2048)
-    b[wave] = 1 + np.searchsorted(np.array(gen.WAVE_CAPS[:-1]), F[wave], side="left")
-    heavy = F > 2048
-    b[heavy] = np.where(F[heavy] <= rank_cap, RANK_BIN, np.where(F[heavy] > mid_cap, DENSE_BIN, MID_BIN))
-    return np.bincount(b, minlength=NUM_BINS).tolist()
-
-
 def small_expected(flow, small, R, nnz_a, nnz_b, b_rows, F):
     """csrc/multiply.hip small_eligible + the device's fit test (csrc/small.hip)"""
     if flow == "exact" or small == 0 or not 0 < R <= SMALL_MAX_ROWS or nnz_a > SMALL_MAX_NNZ_A:
