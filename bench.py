@@ -24,6 +24,12 @@ Rows are cut into N contiguous shards of equal work; B = A is replicated on ever
     python bench.py --gpus N --steps K --warmup W          (spawns its N rank processes itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR                 (rank 0's result of the last timed step as .npy)
+    python bench.py ... --full                             (also the extras below)
+
+A plain run sets up, warms up, times the steps, dumps if asked and prints its line: the headline, the step's
+phase times and algorithmic bytes, all from the timed steps themselves.  --full adds what takes work of its
+own: two untimed class-timed steps and the roofline built on them, the PMC traffic of the committed profile,
+the int32 drop-in `SpGEMM_hip` (dropin_e2e) and, unless --no-cpu-baseline, the CPU baselines (cpu_baseline).
 
 Prints ONE JSON line on rank 0.
 """
@@ -59,7 +65,9 @@ def parse_args():
     ap.add_argument("--workload", default="rmat", choices=["rmat", "rmat-g500", "uniform", "powerlaw"])
     ap.add_argument("--scale", type=int, default=0)
     ap.add_argument("--weak", action="store_true", help="N > 1: scale 22 + log2 N instead of BASELINE cfg4 (scale 24)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, drop-in and CPU-baseline extras, each after the timed steps (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write rank 0's C of the last timed step to DIR (see dump_outputs)")
     args = ap.parse_args()
     if args.steps < 1:
@@ -310,6 +318,36 @@ def cpu_baseline_mpirun(budget_cores, gpu_ctx=None):
     return res
 
 
+def dropin_e2e(rp, ci, n):
+    """--full: the SpGEMM_hip call the reference's driver makes: host int32 arrays in, a malloc'ed Ccol out,
+    PCIe both ways.  Never the headline: reported beside it."""
+    import ctypes
+    import numpy as np
+    import bspgemm
+    try:
+        libc = ctypes.CDLL(None)
+        libc.free.argtypes = [ctypes.c_void_p]
+        L = bspgemm.lib()
+        rp32, ci32 = bspgemm._i32(rp), bspgemm._i32(ci)
+        crow = np.zeros(n + 1, dtype=np.int32)
+        times = []
+        for _ in range(3):
+            cc = ctypes.POINTER(ctypes.c_int)()
+            t = time.perf_counter()
+            rc = L.SpGEMM_hip(ci32, ctypes.c_void_p(rp32.ctypes.data), n, ci32, rp32, n, ctypes.byref(cc), crow, 0)
+            times.append(time.perf_counter() - t)
+            libc.free(ctypes.cast(cc, ctypes.c_void_p))
+            if rc != 0:
+                raise RuntimeError("SpGEMM_hip returned %d" % rc)
+        best = min(times[1:])
+        return {"ms": round(best * 1e3, 1), "GNZ/s": round(int(crow[-1]) / best / 1e9, 3), "nnz_c": int(crow[-1]),
+                "what": "SpGEMM_hip(Acol,Arow,An,Acol,Arow,An,&Ccol,Crow,tBlock): upload A (B = A is a view), "
+                        "multiply, download into the malloc'ed result pinned piecewise under the DMA; "
+                        "best of 2 after one warm-up call"}
+    except Exception as e:
+        return {"error": repr(e)}
+
+
 def pmc_profile(wname, world):
     """the committed rocprofv3 --pmc result of this very command (tools/pmc_run.sh -> profiles/*_pmc_traffic.json)"""
     import glob
@@ -323,6 +361,96 @@ def pmc_profile(wname, world):
         if prof.get("workload") == wname:
             return prof, os.path.relpath(path, ROOT)
     return None, None
+
+
+def roofline_of(C, *, rp, prefix, r0, r1, n, st, phase_ms, steps_averaged, bin_ms, bin_count_ms, prof, prof_path):
+    """--full: roofline of the numeric family (and of the flow's second kernel) on this rank's rows;
+    per-class times from the class-timed steps, `traffic` from the committed PMC profile"""
+    import numpy as np
+    try:
+        # ---- roofline of the dominant kernel (this rank's launches) -------------------------
+        # The dominant kernel is k_wave_rows (csrc/wave_rows.inc), the numeric pass: ONE kernel source,
+        # launched as one template instance per capacity class (16 of them), back to back on two
+        # streams so that one instance's tail overlaps the next one's ramp-up.  Its "launch" is the
+        # whole family: algorithmic bytes of all one-wave rows (SURVEY 8d: 4 B/product + 4 B/output
+        # nonzero + 12 B/A-nonzero + 12 B/row) over the HIP-event time from the first instance's start
+        # to the last one's end on the multiply's stream (bspgemm_stats.ms_numeric).  Per-instance
+        # event brackets are listed next to it; they overlap pairwise, so their sum exceeds the
+        # family's time.  `symbolic` prices the count kernels (the COUNT instances of the same source) the
+        # same way with what they move: 4 B/product + 8 B/A-nonzero + 4 B/row.
+        crp, _ = C.download(col_idx=False)
+        F_row = np.diff(prefix)[r0:r1]
+        a_row = np.diff(rp.astype(np.int64))[r0:r1]
+        c_row = np.diff(crp)
+        caps = st["bin_cap"]
+        DENSE_BIN = 1 + sum(1 for c in caps[1:] if c <= 2048)    # first class that is not one-wave-per-row
+        bins = bin_of(F_row, caps)
+        levels = next((L for L in range(1, 5) if n <= (256 << (5 * L))), 5)      # csrc/kernels.hpp levels_for_cols
+        if levels == 4 and n <= (512 << 15):
+            levels = 3                                                           # ... wave_levels_for_cols
+        wave = (bins >= 1) & (bins < DENSE_BIN)
+        read_wave = int(4 * F_row[wave].sum() + 12 * a_row[wave].sum() + 4 * wave.sum())
+        bytes_wave = read_wave + int(4 * c_row[wave].sum() + 8 * wave.sum())
+        ms_wave = phase_ms["ms_numeric"]
+        achieved = bytes_wave / (ms_wave * 1e-3) / 1e9 if ms_wave > 0 else 0.0
+        instances = []
+        for b in range(1, DENSE_BIN):
+            selb = bins == b
+            if selb.any():
+                by = int(4 * F_row[selb].sum() + 4 * c_row[selb].sum() + 12 * a_row[selb].sum() + 12 * selb.sum())
+                ms_b = float(bin_ms[b])
+                instances.append({"chunks": caps[b] // 64, "rows": int(selb.sum()), "products": int(F_row[selb].sum()),
+                                  "bytes": by, "ms": round(ms_b, 4),          # ms: the class's event bracket
+                                  "count_ms": round(float(bin_count_ms[b]), 4),
+                                  "GBps_while_sharing_the_gpu": round(by / (ms_b * 1e-3) / 1e9, 1) if ms_b > 0 else 0.0})
+        traffic, traffic_src = None, None
+        if prof:
+            fam = [v for k, v in prof.get("kernels", {}).items() if k.startswith("bsp::k_wave_rows<%d," % levels) and not k.rstrip().endswith("true>")]
+            if len(fam) == len(instances):
+                # gfx950's FETCH_SIZE tallies 128-byte read requests at 64 bytes, so it under-counts wide coalesced reads 2x: the
+                # gathers of this kernel are 4-byte accesses, so the raw figure is quoted, uncorrected
+                if all("fetch_bytes_calibrated" in k for k in fam):
+                    # round 4: FETCH_SIZE calibrated on this access (profiles/r04_fetch_calibration_unaligned.txt) and applied to the
+                    # matrix's own row_ptr (tools/gather_traffic_model.py): a request is a 128-byte line's wanted 64-byte sectors,
+                    # tallied as 64 bytes -- the factor says what the gather of THIS matrix moves per byte FETCH_SIZE shows
+                    traffic = int(sum(k["fetch_bytes_calibrated"] + k["write_bytes"] for k in fam))
+                    traffic_src = prof_path + (" (WRITE_SIZE + FETCH_SIZE x %.3f of the %d instances: the counter calibrated on "
+                                               "64-80-byte rows at dword alignment and applied to this matrix's row_ptr; uncorrected "
+                                               "FETCH_SIZE + WRITE_SIZE = %d)" % (prof.get("gather_calibration_factor") or 0.0, len(fam),
+                                                                                  int(sum(k["fetch_bytes"] + k["write_bytes"] for k in fam))))
+                else:
+                    traffic = int(sum(k.get("fetch_bytes_corrected_high", 2 * k["fetch_bytes"]) + k["write_bytes"] for k in fam))
+                    traffic_src = prof_path + (" (WRITE_SIZE + 2 x FETCH_SIZE of the %d instances: gfx950 tallies 128-byte read "
+                                               "requests at 64 bytes; the gathers' 64-byte requests make this the HIGH bound, "
+                                               "low bound %d)" % (len(fam), int(sum(k.get("fetch_bytes_corrected_low", k["fetch_bytes"])
+                                                                                  + k["write_bytes"] for k in fam))))
+        sym_bytes = int(4 * F_row[wave].sum() + 8 * a_row[wave].sum() + 4 * wave.sum())
+        ms_cnt = phase_ms["ms_count"]
+        flow = "exact" if float(np.sum(bin_count_ms)) > 0 else "upper-bound"
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "kernel": "k_wave_rows<LEVELS=%d,*> (numeric pass: %d capacity-class instances, two streams)" % (levels, len(instances)),
+                    "bytes_per_launch": bytes_wave, "ms_per_launch": round(ms_wave, 4),
+                    "read_bytes": read_wave,
+                    "read_frac": round(read_wave / (ms_wave * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_wave > 0 else None,
+                    "launch_rows": int(wave.sum()), "launch_products": int(F_row[wave].sum()),
+                    "steps_averaged": steps_averaged, "instances": instances, "flow": flow}
+        if flow == "exact":
+            roofline["symbolic"] = {"kernel": "k_wave_rows<LEVELS=%d,*,COUNT> (symbolic pass: exact row sizes, the rank bitmap without its emit half)" % levels,
+                                    "bytes_per_launch": sym_bytes, "ms_per_launch": round(ms_cnt, 4),
+                                    "achieved": round(sym_bytes / (ms_cnt * 1e-3) / 1e9, 1) if ms_cnt > 0 else None,
+                                    "frac": round(sym_bytes / (ms_cnt * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_cnt > 0 else None}
+        else:
+            by = int(8 * c_row.sum())                    # the compaction: 4 B read + 4 B written per output nonzero
+            ms_st = phase_ms["ms_stitch"]
+            roofline["compaction"] = {"kernel": "k_compact (upper-bound placed rows -> C.col_idx) + count scan",
+                                      "bytes_per_launch": by, "ms_per_launch": round(ms_st, 4),
+                                      "achieved": round(by / (ms_st * 1e-3) / 1e9, 1) if ms_st > 0 else None,
+                                      "frac": round(by / (ms_st * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_st > 0 else None}
+    except Exception as e:   # the roofline is a reported extra: never lose the metric line to it
+        roofline = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None,
+                    "traffic": None, "error": "%s: %s" % (type(e).__name__, e)}
+    return roofline
 
 
 DUMP_SAMPLES = {"C_row_ptr": 1 << 20, "C_col_idx": 2 << 20}   # values + their positions in float64: 48 MB at most
@@ -460,21 +588,20 @@ def main():
     hist = [ctx.stats(age) for age in range(min(args.steps, MAX_STAT_STEPS))]
     st = hist[0]
     if args.dump_outputs and rank == 0:
-        dump_outputs(last, dev, args.dump_outputs)   # before the untimed steps below free this result
-    # the per-class brackets are OFF in the timed steps (an event pair around each of the ~17 class launches costs
-    # about 1 %): two extra, untimed steps with them on itemise the classes (roofline.instances)
-    ctx.set_class_timing(True)
-    for _ in range(2):
-        rotate()
-    fence()
-    itemised = [ctx.stats(age) for age in range(2)]
-    ctx.set_class_timing(False)
+        dump_outputs(last, dev, args.dump_outputs)   # before any untimed step below frees this result
+    if args.full:
+        # the per-class brackets are OFF in the timed steps (an event pair around each of the ~17 class launches costs
+        # about 1 %): two extra, untimed steps with them on itemise the classes (roofline.instances)
+        ctx.set_class_timing(True)
+        for _ in range(2):
+            rotate()
+        fence()
+        itemised = [ctx.stats(age) for age in range(2)]
+        ctx.set_class_timing(False)
     if older is not None:
         retire(older)
     keys = ("ms_total", "ms_symbolic", "ms_prepass", "ms_count", "ms_numeric", "ms_stitch")
     phase_ms = {k: float(np.mean([h[k] for h in hist])) for k in keys}
-    bin_ms = np.mean([h["ms_bin"] for h in itemised], axis=0)
-    bin_count_ms = np.mean([h["ms_bin_count"] for h in itemised], axis=0)
     if use_dist:
         rdev = torch.device("cpu") if shared_gpu else dev
         t = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
@@ -488,92 +615,7 @@ def main():
                                                               int(st["bytes_read_alg"]))
     ms_per_step = elapsed / args.steps * 1e3
 
-    prof, prof_path = pmc_profile(wname, world)
-    try:
-        # ---- roofline of the dominant kernel (this rank's launches) -------------------------
-        # The dominant kernel is k_wave_rows (csrc/wave_rows.inc), the numeric pass: ONE kernel source,
-        # launched as one template instance per capacity class (16 of them), back to back on two
-        # streams so that one instance's tail overlaps the next one's ramp-up.  Its "launch" is the
-        # whole family: algorithmic bytes of all one-wave rows (4 B/product + 4 B/output
-        # nonzero + 12 B/A-nonzero + 12 B/row) over the HIP-event time from the first instance's start
-        # to the last one's end on the multiply's stream (bspgemm_stats.ms_numeric).  Per-instance
-        # event brackets are listed next to it; they overlap pairwise, so their sum exceeds the
-        # family's time.  `symbolic` prices the count kernels (the COUNT instances of the same source) the
-        # same way with what they move: 4 B/product + 8 B/A-nonzero + 4 B/row.
-        crp, _ = last.download(col_idx=False)
-        F_row = np.diff(prefix)[r0:r1]
-        a_row = np.diff(rp.astype(np.int64))[r0:r1]
-        c_row = np.diff(crp)
-        caps = st["bin_cap"]
-        DENSE_BIN = 1 + sum(1 for c in caps[1:] if c <= 2048)    # first class that is not one-wave-per-row
-        bins = bin_of(F_row, caps)
-        levels = next((L for L in range(1, 5) if n <= (256 << (5 * L))), 5)      # csrc/kernels.hpp levels_for_cols
-        if levels == 4 and n <= (512 << 15):
-            levels = 3                                                           # ... wave_levels_for_cols
-        wave = (bins >= 1) & (bins < DENSE_BIN)
-        read_wave = int(4 * F_row[wave].sum() + 12 * a_row[wave].sum() + 4 * wave.sum())
-        bytes_wave = read_wave + int(4 * c_row[wave].sum() + 8 * wave.sum())
-        ms_wave = phase_ms["ms_numeric"]
-        achieved = bytes_wave / (ms_wave * 1e-3) / 1e9 if ms_wave > 0 else 0.0
-        instances = []
-        for b in range(1, DENSE_BIN):
-            selb = bins == b
-            if selb.any():
-                by = int(4 * F_row[selb].sum() + 4 * c_row[selb].sum() + 12 * a_row[selb].sum() + 12 * selb.sum())
-                ms_b = float(bin_ms[b])
-                instances.append({"chunks": caps[b] // 64, "rows": int(selb.sum()), "products": int(F_row[selb].sum()),
-                                  "bytes": by, "ms": round(ms_b, 4),          # ms: event bracket = rocprofv3 average
-                                  "count_ms": round(float(bin_count_ms[b]), 4),
-                                  "GBps_while_sharing_the_gpu": round(by / (ms_b * 1e-3) / 1e9, 1) if ms_b > 0 else 0.0})
-        traffic, traffic_src = None, None
-        if prof:
-            fam = [v for k, v in prof.get("kernels", {}).items() if k.startswith("bsp::k_wave_rows<%d," % levels) and not k.rstrip().endswith("true>")]
-            if len(fam) == len(instances):
-                # FETCH_SIZE under-counts wide coalesced reads 2x on gfx950 (MI355X_MICROARCH.md, HBM): the
-                # gathers of this kernel are 4-byte accesses, so the raw figure is quoted, uncorrected
-                if all("fetch_bytes_calibrated" in k for k in fam):
-                    # round 4: FETCH_SIZE calibrated on this access (profiles/r04_fetch_calibration_unaligned.txt) and applied to the
-                    # matrix's own row_ptr (tools/gather_traffic_model.py): a request is a 128-byte line's wanted 64-byte sectors,
-                    # tallied as 64 bytes -- the factor says what the gather of THIS matrix moves per byte FETCH_SIZE shows
-                    traffic = int(sum(k["fetch_bytes_calibrated"] + k["write_bytes"] for k in fam))
-                    traffic_src = prof_path + (" (WRITE_SIZE + FETCH_SIZE x %.3f of the %d instances: the counter calibrated on "
-                                               "64-80-byte rows at dword alignment and applied to this matrix's row_ptr; uncorrected "
-                                               "FETCH_SIZE + WRITE_SIZE = %d)" % (prof.get("gather_calibration_factor") or 0.0, len(fam),
-                                                                                  int(sum(k["fetch_bytes"] + k["write_bytes"] for k in fam))))
-                else:
-                    traffic = int(sum(k.get("fetch_bytes_corrected_high", 2 * k["fetch_bytes"]) + k["write_bytes"] for k in fam))
-                    traffic_src = prof_path + (" (WRITE_SIZE + 2 x FETCH_SIZE of the %d instances: gfx950 tallies 128-byte read "
-                                               "requests at 64 bytes; the gathers' 64-byte requests make this the HIGH bound, "
-                                               "low bound %d)" % (len(fam), int(sum(k.get("fetch_bytes_corrected_low", k["fetch_bytes"])
-                                                                                  + k["write_bytes"] for k in fam))))
-        sym_bytes = int(4 * F_row[wave].sum() + 8 * a_row[wave].sum() + 4 * wave.sum())
-        ms_cnt = phase_ms["ms_count"]
-        flow = "exact" if float(np.sum(bin_count_ms)) > 0 else "upper-bound"
-        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                    "kernel": "k_wave_rows<LEVELS=%d,*> (numeric pass: %d capacity-class instances, two streams)" % (levels, len(instances)),
-                    "bytes_per_launch": bytes_wave, "ms_per_launch": round(ms_wave, 4),
-                    "read_bytes": read_wave,
-                    "read_frac": round(read_wave / (ms_wave * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_wave > 0 else None,
-                    "launch_rows": int(wave.sum()), "launch_products": int(F_row[wave].sum()),
-                    "steps_averaged": len(hist), "instances": instances, "flow": flow}
-        if flow == "exact":
-            roofline["symbolic"] = {"kernel": "k_wave_rows<LEVELS=%d,*,COUNT> (symbolic pass: exact row sizes, the rank bitmap without its emit half)" % levels,
-                                    "bytes_per_launch": sym_bytes, "ms_per_launch": round(ms_cnt, 4),
-                                    "achieved": round(sym_bytes / (ms_cnt * 1e-3) / 1e9, 1) if ms_cnt > 0 else None,
-                                    "frac": round(sym_bytes / (ms_cnt * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_cnt > 0 else None}
-        else:
-            by = int(8 * c_row.sum())                    # the compaction: 4 B read + 4 B written per output nonzero
-            ms_st = phase_ms["ms_stitch"]
-            roofline["compaction"] = {"kernel": "k_compact (upper-bound placed rows -> C.col_idx) + count scan",
-                                      "bytes_per_launch": by, "ms_per_launch": round(ms_st, 4),
-                                      "achieved": round(by / (ms_st * 1e-3) / 1e9, 1) if ms_st > 0 else None,
-                                      "frac": round(by / (ms_st * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_st > 0 else None}
-    except Exception as e:   # the roofline is a reported extra: never lose the metric line to it
-        roofline = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None,
-                    "traffic": None, "error": "%s: %s" % (type(e).__name__, e)}
     value = nnz_total * args.steps / elapsed / 1e9
-    step_traffic = (prof.get("step_total_bytes_calibrated") or prof.get("step_total_bytes")) if prof else None
     out = {
         "metric": "output nnz/sec (GNZ/s)", "value": round(value, 4), "unit": "GNZ/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -584,23 +626,31 @@ def main():
                    "shard_rows": [int(b) for b in bounds.tolist()], "priming_steps": priming,
                    "flow": os.environ.get("BSPGEMM_FLOW", "auto"),
                    "allocation": "cached: C.row_ptr/C.col_idx come from the context's cache of freed results "
-                                 "(two results rotate), workspaces persist; a cold first step allocates (hipMalloc)"},
-        "roofline": roofline,
+                                 "(two results rotate), workspaces persist; a cold first step allocates (hipMalloc)",
+                   "full": args.full},
         "whole_job": {"bytes_alg": bytes_total, "bytes_read_alg": read_total,
                       "alg_GBps": round(bytes_total / (ms_per_step * 1e-3) / 1e9, 1),
                       "alg_frac_of_hbm_peak": round(bytes_total / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS / world, 4),
                       "read_frac_of_hbm_peak": round(read_total / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS / world, 4),
-                      "pmc_step_traffic_bytes": step_traffic,
-                      "traffic_ratio": round(step_traffic / bytes_total, 3) if step_traffic else None,
-                      "traffic_source": prof_path if step_traffic else None,
                       "rank0_ms": {"total": round(phase_ms["ms_total"], 4), "symbolic": round(phase_ms["ms_symbolic"], 4),
                                    "prepass": round(phase_ms["ms_prepass"], 4), "count": round(phase_ms["ms_count"], 4),
                                    "numeric": round(phase_ms["ms_numeric"], 4), "stitch": round(phase_ms["ms_stitch"], 4)},
-                      "rank0_ms_per_bin": [round(float(x), 4) for x in bin_ms],
-                      "rank0_count_ms_per_bin": [round(float(x), 4) for x in bin_count_ms],
                       "rank0_rows_per_bin": [int(x) for x in st["rows_per_bin"]],
                       "bin_cap": [int(x) for x in st["bin_cap"]]},
     }
+    if args.full:
+        bin_ms = np.mean([h["ms_bin"] for h in itemised], axis=0)
+        bin_count_ms = np.mean([h["ms_bin_count"] for h in itemised], axis=0)
+        prof, prof_path = pmc_profile(wname, world)
+        out["roofline"] = roofline_of(last, rp=rp, prefix=prefix, r0=r0, r1=r1, n=n, st=st, phase_ms=phase_ms,
+                                      steps_averaged=len(hist), bin_ms=bin_ms, bin_count_ms=bin_count_ms,
+                                      prof=prof, prof_path=prof_path)
+        step_traffic = (prof.get("step_total_bytes_calibrated") or prof.get("step_total_bytes")) if prof else None
+        out["whole_job"].update({"pmc_step_traffic_bytes": step_traffic,
+                                 "traffic_ratio": round(step_traffic / bytes_total, 3) if step_traffic else None,
+                                 "traffic_source": prof_path if step_traffic else None,
+                                 "rank0_ms_per_bin": [round(float(x), 4) for x in bin_ms],
+                                 "rank0_count_ms_per_bin": [round(float(x), 4) for x in bin_count_ms]})
     if use_dist:
         # what the collective layer itself saw: the first 8-GPU run shows "RCCL saw N ranks" from its own output
         seen = torch.ones(1, dtype=torch.int64, device=torch.device("cpu") if shared_gpu else dev)
@@ -608,33 +658,9 @@ def main():
         out["comm"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "ranks_seen": int(seen.item()),
                        "stitch": "all_gather_into_tensor of int32 row lengths (bspgemm/dist.py) + bspgemm_lengths_to_row_ptr"}
     last.free()
-    if rank == 0 and world == 1 and nnz_total <= 2**31 - 1 and os.environ.get("BSPGEMM_BENCH_NO_DROPIN") != "1":
-        # The call the reference's driver makes (final/SpGEMM_mpi_omp.c:322-327): host int32 arrays in, a malloc'ed
-        # Ccol out, PCIe both ways.  Never the headline: reported beside it.
-        try:
-            import ctypes
-            libc = ctypes.CDLL(None)
-            libc.free.argtypes = [ctypes.c_void_p]
-            L = bspgemm.lib()
-            rp32, ci32 = bspgemm._i32(rp), bspgemm._i32(ci)
-            crow = np.zeros(n + 1, dtype=np.int32)
-            times = []
-            for _ in range(3):
-                cc = ctypes.POINTER(ctypes.c_int)()
-                t = time.perf_counter()
-                rc = L.SpGEMM_hip(ci32, ctypes.c_void_p(rp32.ctypes.data), n, ci32, rp32, n, ctypes.byref(cc), crow, 0)
-                times.append(time.perf_counter() - t)
-                libc.free(ctypes.cast(cc, ctypes.c_void_p))
-                if rc != 0:
-                    raise RuntimeError("SpGEMM_hip returned %d" % rc)
-            best = min(times[1:])
-            out["dropin_e2e"] = {"ms": round(best * 1e3, 1), "GNZ/s": round(int(crow[-1]) / best / 1e9, 3), "nnz_c": int(crow[-1]),
-                                 "what": "SpGEMM_hip(Acol,Arow,An,Acol,Arow,An,&Ccol,Crow,tBlock): upload A (B = A is a view), "
-                                         "multiply, download into the malloc'ed result pinned piecewise under the DMA; "
-                                         "best of 2 after one warm-up call"}
-        except Exception as e:
-            out["dropin_e2e"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and nnz_total <= 2**31 - 1 and os.environ.get("BSPGEMM_BENCH_NO_DROPIN") != "1":
+        out["dropin_e2e"] = dropin_e2e(rp, ci, n)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(rp, ci, n, gpu_ctx=ctx)
         except Exception as e:  # the baseline is a reported extra; never lose the GPU line to it

@@ -26,15 +26,15 @@ BSPGEMM_BENCH_NO_DROPIN=1 BSPGEMM_FLOW=exact bash tools/pmc_sq.sh $OUT/sq_exact 
 echo "sq done"
 fi
 if [ "$STAGE" != "pmc" ]; then
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_rmat22.json 2> $OUT/bench_rmat22.err
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_rmat22.json 2> $OUT/bench_rmat22.err
 echo "bench done: $(cut -c1-160 $OUT/bench_rmat22.json)"
-BSPGEMM_FLOW=exact timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_rmat22_exact.json 2> $OUT/bench_rmat22_exact.err
+BSPGEMM_FLOW=exact timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_rmat22_exact.json 2> $OUT/bench_rmat22_exact.err
 ( cd /tmp && export TMPDIR=/tmp && BSPGEMM_BENCH_NO_DROPIN=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/stats -- python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $ROOT/$OUT/stats_bench.json 2> $ROOT/$OUT/stats.err )
 ( cd /tmp && export TMPDIR=/tmp && BSPGEMM_BENCH_NO_DROPIN=1 BSPGEMM_FLOW=exact timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/stats_exact -- python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $ROOT/$OUT/stats_exact_bench.json 2> $ROOT/$OUT/stats_exact.err )
 echo "stats done"
 for w in "rmat --scale 23" "rmat --scale 24" "uniform" "rmat-g500" "powerlaw"; do
   for f in upper-bound exact; do
-    BSPGEMM_BENCH_NO_DROPIN=1 BSPGEMM_FLOW=$f timeout -k 10 400 python3 bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline >> $OUT/other_$f.jsonl 2>> $OUT/other.err
+    BSPGEMM_BENCH_NO_DROPIN=1 BSPGEMM_FLOW=$f timeout -k 10 400 python3 bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline >> $OUT/other_$f.jsonl 2>> $OUT/other.err
   done
 done
 echo "others done"
