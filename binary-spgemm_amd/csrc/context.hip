@@ -146,25 +146,26 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     }
     bspgemm_context *ctx = new (std::nothrow) bspgemm_context();
     if (!ctx) return FAIL(BSPGEMM_ERR_ALLOC, "context");
+    auto bail = [&](bspgemm_status st) { bspgemm_destroy(ctx); return st; };   // (it takes a half-built context)
     ctx->device = device;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+    HIPCHK_B(hipSetDevice(device));
+    HIPCHK_B(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     ctx->own_stream = true;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h), sizeof(HostScalars), hipHostMallocDefault));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->d_prep), sizeof(PrepScalars)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->d_small), sizeof(SmallScalars)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->d_small_tiles), sizeof(SmallTiles)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->d_err), 64));
-    HIPCHK(hipMemset(ctx->d_err, 0, 64));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->bin_count), kNumBins * sizeof(int)));
+    HIPCHK_B(hipHostMalloc(reinterpret_cast<void **>(&ctx->h), sizeof(HostScalars), hipHostMallocDefault));
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_prep), sizeof(PrepScalars)));
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_small), sizeof(SmallScalars)));
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_small_tiles), sizeof(SmallTiles)));
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_err), 64));
+    HIPCHK_B(hipMemset(ctx->d_err, 0, 64));
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->bin_count), kNumBins * sizeof(int)));
     for (auto &sl : ctx->slots) {
-        for (auto &e : sl.ev) HIPCHK(hipEventCreate(&e));
-        for (auto &ph : sl.ev_cls) for (auto &c : ph) for (auto &e : c) HIPCHK(hipEventCreate(&e));
+        for (auto &e : sl.ev) HIPCHK_B(hipEventCreate(&e));
+        for (auto &ph : sl.ev_cls) for (auto &c : ph) for (auto &e : c) HIPCHK_B(hipEventCreate(&e));
     }
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream_c, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    for (auto &t : ctx->ev_tile) for (auto &e : t) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK_B(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
+    HIPCHK_B(hipStreamCreateWithFlags(&ctx->stream_c, hipStreamNonBlocking));
+    HIPCHK_B(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    for (auto &t : ctx->ev_tile) for (auto &e : t) HIPCHK_B(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     ctx->cache_budget = prop.totalGlobalMem / 4;
     if (const char *e = getenv("BSPGEMM_FLOW"))
         ctx->flow = !strcmp(e, "exact") ? BSPGEMM_FLOW_EXACT : (!strcmp(e, "upper-bound") || !strcmp(e, "ub")) ? BSPGEMM_FLOW_UPPER_BOUND : BSPGEMM_FLOW_AUTO;

@@ -15,6 +15,7 @@
 // upper-bound-placed rows into C.col_idx.
 #include "kernels.hpp"
 #include "wave.hpp"
+#include <atomic>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -331,7 +332,7 @@ static hipError_t launch_dense_impl(const int2 *ab, const int *Bcol, long long n
     if (words < 1) words = 1;
     const int bytes = (int)words * 8 * (MASKED ? 2 : 1);
     // the attribute belongs to the (kernel, device) pair: a process may hold contexts on several GPUs
-    static bool attr_set[64] = {};
+    static std::atomic<bool> attr_set[64] = {};          // (contexts on other threads launch this too)
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev)) return e;
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
@@ -379,58 +380,37 @@ int rank_cap_for_cols(long long cols)
 }
 
 static hipError_t launch_rank_rows(const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
-                                   const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, hipStream_t s,
-                                   const int *Frow = nullptr, const int *Fcol = nullptr)
+                                   const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, MaskMode mode,
+                                   const int *Frow, const int *Fcol, hipStream_t s)
 {
     if (nrows <= 0) return hipSuccess;
     const long long span = cols < kRankSpan ? cols : kRankSpan;
     const int topw = (int)(((span + 1023) >> 10) + kRankThreads - 1) / kRankThreads * kRankThreads;   // whole words per thread
     const int bytes = topw * 8 + kRankCap * 4;
     const int nnzB32 = (int)(nnzB > 0x7fffffffll ? 0x7fffffffll : nnzB);
-    if (Fcol) {                                                    // the complemented-mask twin
-        if (cols > kRankSpan)
-            hipLaunchKernelGGL(k_rank_rows_excl<true>, dim3(nrows), dim3(kRankThreads), bytes, s, ab, Bcol, nnzB32, cols, topw, rec,
-                               recpre, row_begin, tmp, cnt, Frow, Fcol);
-        else
-            hipLaunchKernelGGL(k_rank_rows_excl<false>, dim3(nrows), dim3(kRankThreads), bytes, s, ab, Bcol, nnzB32, cols, topw, rec,
-                               recpre, row_begin, tmp, cnt, Frow, Fcol);
-        return hipGetLastError();
-    }
-    if (cols > kRankSpan)
-        hipLaunchKernelGGL(k_rank_rows<true>, dim3(nrows), dim3(kRankThreads), bytes, s, ab, Bcol,
-                           (int)(nnzB > 0x7fffffffll ? 0x7fffffffll : nnzB), cols, topw, rec, recpre, row_begin, tmp, cnt);
+    const bool spans = cols > kRankSpan;
+    if (mode == MaskMode::Drop)                                    // the complemented-mask twin
+        hipLaunchKernelGGL((spans ? k_rank_rows_excl<true> : k_rank_rows_excl<false>), dim3(nrows), dim3(kRankThreads), bytes, s,
+                           ab, Bcol, nnzB32, cols, topw, rec, recpre, row_begin, tmp, cnt, Frow, Fcol);
     else
-        hipLaunchKernelGGL(k_rank_rows<false>, dim3(nrows), dim3(kRankThreads), bytes, s, ab, Bcol,
-                           (int)(nnzB > 0x7fffffffll ? 0x7fffffffll : nnzB), cols, topw, rec, recpre, row_begin, tmp, cnt);
+        hipLaunchKernelGGL((spans ? k_rank_rows<true> : k_rank_rows<false>), dim3(nrows), dim3(kRankThreads), bytes, s,
+                           ab, Bcol, nnzB32, cols, topw, rec, recpre, row_begin, tmp, cnt);
     return hipGetLastError();
 }
 
 hipError_t launch_dense_rows(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols,
                              const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                             int *tmp, int *cnt, hipStream_t s)
+                             int *tmp, int *cnt, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s)
 {
-    if (bin == kRankBin) return launch_rank_rows(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, s);
+    if (mode == MaskMode::Keep)                                    // every masked row, whatever its class
+        return launch_dense_impl<MaskMode::Keep, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
+    if (bin == kRankBin) return launch_rank_rows(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s);
     const bool mid = bin == kMidBin;
-    if (mid)
-        return launch_dense_impl<MaskMode::None, kDenseThreadsMid>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, nullptr, nullptr, s);
-    return launch_dense_impl<MaskMode::None, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, nullptr, nullptr, s);
-}
-
-hipError_t launch_dense_rows_excl(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols,
-                                  const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                                  int *tmp, int *cnt, const int *Frow, const int *Fcol, hipStream_t s)
-{
-    if (bin == kRankBin) return launch_rank_rows(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, s, Frow, Fcol);
-    if (bin == kMidBin)
-        return launch_dense_impl<MaskMode::Drop, kDenseThreadsMid>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
-    return launch_dense_impl<MaskMode::Drop, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
-}
-
-hipError_t launch_dense_rows_masked(const int2 *ab, const int *Bcol, long long nnzB, int cols,
-                                    const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                                    int *tmp, int *cnt, const int *Frow, const int *Fcol, hipStream_t s)
-{
-    return launch_dense_impl<MaskMode::Keep, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
+    if (mode == MaskMode::Drop)
+        return mid ? launch_dense_impl<MaskMode::Drop, kDenseThreadsMid>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s)
+                   : launch_dense_impl<MaskMode::Drop, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
+    return mid ? launch_dense_impl<MaskMode::None, kDenseThreadsMid>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, nullptr, nullptr, s)
+               : launch_dense_impl<MaskMode::None, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, nullptr, nullptr, s);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // kernels.hpp -- launch wrappers of the HIP kernels behind bspgemm_multiply (host-callable).
-// Kernel bodies: prepass.hip (row work, scans, class records), wave_rows.inc (+ wave_rows_L*.hip),
-// wave_masked.hip, dense_rows.hip (heavy rows + compaction).
+// Kernel bodies: prepass.hip (row work, scans, class records), wave_rows.inc (one object per (LEVELS, EXCL) pair,
+// dispatched by wave_rows.hip), wave_masked.hip, dense_rows.hip (heavy rows + compaction).
 // Tuning constants are compile-time constants, not switches: what was tried against them is in profiles/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -139,19 +139,18 @@ void launch_scan_counts(const int *cnt, int n, long long *prefix, long long *par
 // tmp + row_ptr[i - row_begin] (tmp = C.col_idx, sizes known from the symbolic phase, cnt may be
 // NULL); row_ptr == NULL: at its upper-bound offset tmp + recpre[k], |C_i| to cnt (masked product)
 // count_only: the symbolic twin of the same kernel -- nothing is emitted (tmp, recpre, row_ptr unused), cnt[i] = |C_i|
+// mode Drop: the complemented-mask twin (C = !F .* (A*B), upper-bound placement only): the columns of F's row (Frow / Fcol,
+// absolute row ids) are dropped from every row before it is stored.  Keep has no one-wave kernel here (launch_wave_masked),
+// and count_only needs None: both return hipErrorInvalidValue
 // err (device, never NULL): bit 0 is set when a row's gathered product count exceeds its class capacity -- impossible
 // for consistent operands (the classes come from the same extents), seen only when an operand was rewritten under
 // the library; the row is then truncated to its capacity instead of overrunning LDS
 constexpr unsigned kErrCapacity = 1u;     // a row gathered more products than its capacity class holds
 constexpr unsigned kErrStaleTable = 2u;   // an operand's derived tables do not match its row_ptr (bspgemm_matrix_invalidate)
-void launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol, int cols,
-                      const RowRec *rec, const long long *recpre, const long long *row_ptr, int nrows,
-                      int row_begin, int *tmp, int *cnt, unsigned *err, hipStream_t s, bool count_only = false);
-// complemented-mask twin (C = !F .* (A*B), upper-bound placement): the numeric launch above with the columns of F's row
-// (Frow / Fcol, absolute row ids) dropped from every row before it is stored; |C_i| to cnt
-void launch_wave_rows_excl(int bin, int levels, const int2 *ab, const int *Bcol, int cols, const RowRec *rec,
-                           const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err,
-                           const int *Frow, const int *Fcol, hipStream_t s);
+hipError_t launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol, int cols,
+                            const RowRec *rec, const long long *recpre, const long long *row_ptr, int nrows,
+                            int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode, const int *Frow, const int *Fcol,
+                            hipStream_t s, bool count_only = false);
 // debug check (BSPGEMM_OPT_CHECK): deg8[] / blk8[] / the padded row_ptr (each may be NULL) against row_ptr; sets kErrStaleTable in *err
 void launch_check_tables(const int *row_ptr, int rows, const unsigned char *deg8, const int *blk8, const int *pad_ptr, unsigned *err,
                          hipStream_t s);
@@ -160,32 +159,30 @@ void launch_check_tables(const int *row_ptr, int rows, const unsigned char *deg8
 void launch_place_heavy(const int *tmp, const RowRec *rec, const long long *recpre, int nrows,
                         const long long *row_ptr, int row_begin, int *col_idx, hipStream_t s);
 
-// numeric phase, one workgroup per heavy row (windowed dense LDS bitmap); mid: the 512-thread shape
+// numeric phase, one workgroup per heavy row (windowed dense LDS bitmap); mid: the 512-thread shape, rank: the rank bitmap.
+// F's row (Frow / Fcol, absolute row ids): Drop clears its bits from each column window (rank class: from each span's slots)
+// before it is read out, in every shape; Keep admits only its columns, and every row of any class, `bin` ignored, goes through
+// the 1024-thread window kernel
 hipError_t launch_dense_rows(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols,
                              const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                             int *tmp, int *cnt, hipStream_t s);
-
-// complemented-mask twin of launch_dense_rows (rank, small and hub shapes): the bits of F's row are cleared from each
-// column window (rank class: from each span's slots) before it is read out
-hipError_t launch_dense_rows_excl(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols,
-                                  const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                                  int *tmp, int *cnt, const int *Frow, const int *Fcol, hipStream_t s);
+                             int *tmp, int *cnt, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s);
 
 // the heavy rows' records in order of decreasing products (n <= kHeavySortMax), into rec_out / pre_out
 constexpr int kHeavySortMax = 8192;
 void launch_order_heavy(const RowRec *rec, const long long *recpre, int n, RowRec *rec_out, long long *pre_out, hipStream_t s);
-
-// masked variant: C = F .* (A*B); every non-empty row goes through the window kernel, which
-// keeps only the product bits that F's row (absolute row id, F.row_ptr/F.col_idx) admits
-hipError_t launch_dense_rows_masked(const int2 *ab, const int *Bcol, long long nnzB, int cols,
-                                    const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                                    int *tmp, int *cnt, const int *Frow, const int *Fcol, hipStream_t s);
 
 // mask-first one-wave path of the masked product (mask rows <= 2048 entries, cols <= 2^23)
 bool wave_masked_supported(int cols);
 void launch_wave_masked(int bin, const int2 *ab, const int *Bcol, int cols, const int *Frow, const int *Fcol,
                         const RowRec *rec, const long long *recpre, int nrows, int row_begin,
                         int *tmp, int *cnt, hipStream_t s);
+// the rows of class `bin` (upper-bound placement at tmp + recpre[k], |C_i| to cnt), whichever kernel family the class and
+// the mask mode take: one-wave classes launch_wave_rows, heavy classes launch_dense_rows; Keep: a one-wave class takes
+// launch_wave_masked where wave_masked_supported(cols), every other row the 1024-thread window kernel.  count_only (the
+// exact flow's count pass, mode None): the one-wave rows only count, the heavy rows are accumulated into the workspace
+hipError_t launch_class(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
+                        const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode,
+                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only = false);
 // mlen[i] = |F's row i| when row i has products, else 0: what the masked product bins and offsets by
 void launch_mask_lengths(const long long *F, const int *Frow, int row_begin, int n, long long *mlen, hipStream_t s);
 

@@ -18,9 +18,6 @@ static bspgemm_status check_operands(bspgemm_context *ctx, const bspgemm_matrix 
 }
 
 
-// class launch order of a phase: the heavy rows first (few long-running workgroups: started early
-// they finish under the other classes instead of being the phase's tail), then the one-wave
-// classes by capacity
 // Launch order of the classes of one phase: order[1..kNumBins-1], alternating over the class streams.  The heavy
 // rows first (few long-running workgroups: started early they finish under the other classes instead of being
 // the phase's tail), then the one-wave classes LARGEST WORK FIRST (rows x capacity): a phase then ends with its
@@ -70,22 +67,17 @@ static void hub_order(bspgemm_context *ctx, int b, int n, const RowRec *&rec, co
     recpre = ctx->hub_pre;
 }
 
-// BSPGEMM_OPT_CHECK: the device error word is cleared and B's derived tables are verified against its row_ptr before
-// the prepass uses them; check_verdict (after the multiply's last synchronisation) turns a set bit into a failure
-static bspgemm_status check_arm(bspgemm_context *ctx, const bspgemm_matrix *B, hipStream_t s)
+// opens the next stat slot of the context; small: the single-round-trip path (one stream, never checked)
+static bspgemm_context::StatSlot &open_slot(bspgemm_context *ctx, int flow, bool small)
 {
-    if (!ctx->check) return BSPGEMM_OK;
-    HIPCHK(hipMemsetAsync(ctx->d_err, 0, sizeof(unsigned), s));
-    launch_check_tables(B->d_row_ptr, B->rows, B->d_deg8, B->blk8_state == 1 ? B->d_blk8 : nullptr,
-                        B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, ctx->d_err, s);
-    return BSPGEMM_OK;
-}
-static bspgemm_status check_verdict(bspgemm_context *ctx)
-{
-    if (!ctx->check || !ctx->h->err) return BSPGEMM_OK;
-    if (ctx->h->err & kErrStaleTable)
-        return FAIL(BSPGEMM_ERR_INVALID, "operand B was rewritten in place: its derived tables do not match its row_ptr (call bspgemm_matrix_invalidate)");
-    return FAIL(BSPGEMM_ERR_INVALID, "a row gathered more products than its capacity class holds (operand changed during the multiply?)");
+    ctx->slot_head = (ctx->slot_head + 1) % bspgemm_context::kStatSlots;
+    bspgemm_context::StatSlot &slot = ctx->slots[ctx->slot_head];
+    slot.used = false;
+    slot.flow = flow;
+    slot.class_streams = small ? 1 : ctx->class_streams;
+    slot.small = small;
+    slot.checked = !small && ctx->check;
+    return slot;
 }
 
 // closes the multiply's stat slot (its events have all completed: the caller has synchronised)
@@ -104,6 +96,126 @@ static void close_slot(bspgemm_context *ctx, int R, const HostScalars *h, long l
     sl.used = true;
 }
 
+// releases a result of the general flows that failed: nothing of C may still be written when it is released
+static bspgemm_status drop_result(bspgemm_result *C, bspgemm_status st)
+{
+    const bspgemm_context *ctx = C->ctx;
+    hipStreamSynchronize(ctx->stream); hipStreamSynchronize(ctx->stream_b); hipStreamSynchronize(ctx->stream_c);
+    bspgemm_result_free(C);
+    return st;
+}
+
+// C.col_idx with room for `cap` entries
+static hipError_t alloc_col_idx(bspgemm_context *ctx, bspgemm_result *C, long long cap)
+{
+    if (hipError_t e = result_alloc(ctx, reinterpret_cast<void **>(&C->d_col_idx), result_bytes_colidx(cap))) return e;
+    C->col_cap = cap;
+    return hipSuccess;
+}
+// entries of C.col_idx once nnz(C) is known: exactly that, or the flow's bound when it is within 2 % of nnz(C) (the next
+// product of this shape then finds it cached)
+static long long col_cap_for(long long bound, long long nnz_c) { return (bound - nnz_c <= nnz_c / 50 + 4096) ? bound : nnz_c; }
+
+// What both general flows start with: the operands checked (Fm: the mask, or NULL), the per-row workspace sized, the result
+// *C with its row_ptr, the stat slot opened (ev[0]), B's derived tables built on its first use as B (the padded copy, then the
+// blocked table over it; wrapped device arrays: first use) and the prepass launched: F_i and the extents ab[] of the rows.
+static bspgemm_status start_flow(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
+                                 const bspgemm_matrix *Fm, int row_begin, int row_end, int flow, bspgemm_result **out,
+                                 bspgemm_result **Cp)
+{
+    if (!out) return FAIL(BSPGEMM_ERR_INVALID, "result pointer is NULL");
+    *out = nullptr;
+    if (bspgemm_status st = check_operands(ctx, A, B, row_begin, row_end)) return st;
+    if (Fm && (Fm->ctx != ctx || Fm->rows < row_end)) return FAIL(BSPGEMM_ERR_INVALID, "mask has fewer rows than A / wrong context");
+    if (bspgemm_status st = use_device(ctx)) return st;
+    const int R = row_end - row_begin;
+    hipStream_t s = ctx->stream;
+    if (bspgemm_status st = ensure_rows(ctx, (size_t)R + 1)) return st;
+    if (bspgemm_status st = ensure_ab(ctx, (size_t)A->nnz + 1)) return st;
+
+    bspgemm_result *C = new (std::nothrow) bspgemm_result{ctx, R, 0, nullptr, nullptr, 0};
+    if (!C) return FAIL(BSPGEMM_ERR_ALLOC, "result");
+    auto bail = [&](bspgemm_status st) { return drop_result(C, st); };
+    bspgemm_context::StatSlot &slot = open_slot(ctx, flow, false);
+    HIPCHK_B(hipEventRecord(slot.ev[0], s));
+    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_row_ptr), result_bytes_rowptr(R)));
+    if (bspgemm_status st = ensure_pad(B)) return bail(st);
+    if (bspgemm_status st = ensure_blk8(B)) return bail(st);
+    if (ctx->check) {              // BSPGEMM_OPT_CHECK: B's derived tables verified against its row_ptr before the prepass uses them
+        HIPCHK_B(hipMemsetAsync(ctx->d_err, 0, sizeof(unsigned), s));
+        launch_check_tables(B->d_row_ptr, B->rows, B->d_deg8, B->blk8_state == 1 ? B->d_blk8 : nullptr,
+                            B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, ctx->d_err, s);
+    }
+    slot.prepass_kernel = B->blk8_state == 1 ? 1 : 0;
+    slot.padded = B->pad_state == 1;
+    launch_row_work(A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->blk8_state == 1 ? B->d_blk8 : nullptr,
+                    B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, B->pad_state == 1 ? B->d_ext : nullptr, row_begin, row_end,
+                    ctx->F, ctx->ab, s);
+    *Cp = C;
+    return BSPGEMM_OK;
+}
+
+// One phase's class launches (0: the exact flow's count pass, 1: the numeric pass), the classes of h->bin_count in
+// class_order.  The launches are independent (disjoint rows): they alternate over the class streams so that one launch's
+// draining tail overlaps the next one's ramp-up.  The side streams start behind the phase's inputs (fork) and the main
+// stream waits for them at its end (join).  heavy_on_third: the heavy classes run on the third stream, which the phase
+// forks and the caller joins.  launch(b, n, rec, recpre, stream) launches the n rows of class b; cls_n[b] = n.
+template <class Launch>
+static bspgemm_status class_phase(bspgemm_context *ctx, int phase, long long products, int *cls_n, bool heavy_on_third,
+                                  Launch launch)
+{
+    const int *bin_count = ctx->h->bin_count;
+    hipStream_t lanes[3] = {ctx->stream, ctx->stream_b, ctx->stream_c};
+    const int nlanes = ctx->class_streams;
+    hipEvent_t *tile = ctx->ev_tile[phase];
+    hipEvent_t (*ev_cls)[2] = ctx->slots[ctx->slot_head].ev_cls[phase];
+    size_t bin_start[kNumBins + 1] = {0, 0};               // class b's segment of rec[] (class 0 has none)
+    for (int b = 1; b < kNumBins; b++) bin_start[b + 1] = bin_start[b] + (size_t)bin_count[b];
+    int order[kNumBins], lane_of[kNumBins];
+    class_order(bin_count, products, order, lane_of);
+
+    HIPCHK(hipEventRecord(tile[0], lanes[0]));
+    for (int l = 1; l < 3; l++)
+        if (l < nlanes || (l == 2 && heavy_on_third)) HIPCHK(hipStreamWaitEvent(lanes[l], tile[0], 0));
+    for (int pos = 1; pos < kNumBins; pos++) {
+        const int b = order[pos];
+        const int n = bin_count[b];
+        cls_n[b] = n;
+        if (n <= 0) continue;
+        hipStream_t sx = heavy_on_third && b > kWaveBins ? lanes[2] : lanes[lane_of[pos] % nlanes];
+        if (ctx->class_timing) HIPCHK(hipEventRecord(ev_cls[b][0], sx));
+        HIPCHK(launch(b, n, ctx->rec + bin_start[b], ctx->recpre + bin_start[b], sx));
+        if (ctx->class_timing) HIPCHK(hipEventRecord(ev_cls[b][1], sx));
+    }
+    HIPCHK(hipGetLastError());
+    for (int l = 1; l < nlanes; l++) {
+        HIPCHK(hipEventRecord(tile[l], lanes[l]));
+        HIPCHK(hipStreamWaitEvent(lanes[0], tile[l], 0));
+    }
+    return BSPGEMM_OK;
+}
+
+// What both general flows end with once C.col_idx is complete on the main stream: ev[4], the error word read back, the last
+// synchronisation, the verdict, the stat slot closed and C handed out
+static bspgemm_status finish_flow(bspgemm_context *ctx, bspgemm_result *C, const bspgemm_matrix *B, long long products,
+                                  int rank_cap, const int (*cls_n)[kNumBins], bspgemm_result **out)
+{
+    auto bail = [&](bspgemm_status st) { return drop_result(C, st); };
+    hipStream_t s = ctx->stream;
+    HostScalars *h = ctx->h;
+    HIPCHK_B(hipEventRecord(ctx->slots[ctx->slot_head].ev[4], s));
+    if (ctx->check) HIPCHK_B(hipMemcpyAsync(&h->err, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIPCHK_B(hipStreamSynchronize(s));
+    if (ctx->check && h->err)      // (start_flow cleared the error word)
+        return bail(FAIL(BSPGEMM_ERR_INVALID, (h->err & kErrStaleTable)
+            ? "operand B was rewritten in place: its derived tables do not match its row_ptr (call bspgemm_matrix_invalidate)"
+            : "a row gathered more products than its capacity class holds (operand changed during the multiply?)"));
+    C->nnz = h->nnzC;
+    close_slot(ctx, C->rows, h, products, C->nnz, cls_n, mid_cap_for_cols(B->cols), rank_cap);
+    *out = C;
+    return BSPGEMM_OK;
+}
+
 
 // C rows [row_begin,row_end) of A*B:  symbolic (row work -> classes -> EXACT row sizes -> scan =
 // C.row_ptr) then numeric (every one-wave row emitted at its final place in a C.col_idx of exactly
@@ -113,46 +225,17 @@ static void close_slot(bspgemm_context *ctx, int R, const HostScalars *h, long l
 static bspgemm_status multiply_exact(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
                                      int row_begin, int row_end, bspgemm_result **out)
 {
-    if (!out) return FAIL(BSPGEMM_ERR_INVALID, "result pointer is NULL");
-    *out = nullptr;
-    if (bspgemm_status st = check_operands(ctx, A, B, row_begin, row_end)) return st;
-    if (bspgemm_status st = use_device(ctx)) return st;
-    const int R = row_end - row_begin;
-    hipStream_t s = ctx->stream, sB = ctx->stream_b, sC = ctx->stream_c;
-    if (bspgemm_status st = ensure_rows(ctx, (size_t)R + 1)) return st;
-    if (bspgemm_status st = ensure_ab(ctx, (size_t)A->nnz + 1)) return st;
-
-    bspgemm_result *C = new (std::nothrow) bspgemm_result{ctx, R, 0, nullptr, nullptr, 0};
-    if (!C) return FAIL(BSPGEMM_ERR_ALLOC, "result");
-    auto bail = [&](bspgemm_status st) {                  // nothing of C may still be written when it is released
-        hipStreamSynchronize(s); hipStreamSynchronize(sB); hipStreamSynchronize(sC);
-        bspgemm_result_free(C);
-        return st;
-    };
-    ctx->slot_head = (ctx->slot_head + 1) % bspgemm_context::kStatSlots;
+    bspgemm_result *C = nullptr;
+    if (bspgemm_status st = start_flow(ctx, A, B, nullptr, row_begin, row_end, BSPGEMM_FLOW_EXACT, out, &C)) return st;
+    auto bail = [&](bspgemm_status st) { return drop_result(C, st); };
     bspgemm_context::StatSlot &slot = ctx->slots[ctx->slot_head];
-    slot.used = false;
-    slot.flow = BSPGEMM_FLOW_EXACT;
-    slot.class_streams = ctx->class_streams;
-    slot.small = false;
-    slot.checked = ctx->check;
-
-    HIPCHK_B(hipEventRecord(slot.ev[0], s));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_row_ptr), result_bytes_rowptr(R)));
+    const int R = C->rows;
+    hipStream_t s = ctx->stream;
+    const int *Bcol = B->gather_col();                     // B.col_idx, or its padded copy (the extents in ab[] point into it)
 
     // ---- symbolic 1: per-row products, their prefix, capacity classes ---------------------
     const int scan_tiles = (R + 2047) / 2048;
     const int heavy_cols = B->cols > 0 ? B->cols : 1;
-    // the extents ab[] come from the prepass, as in the other flow: both passes of the one-wave classes read them
-    if (bspgemm_status st = ensure_pad(B)) return bail(st);        // (first use as B: the padded copy, then the blocked table over it)
-    if (bspgemm_status st = ensure_blk8(B)) return bail(st);       // (wrapped device arrays: first use)
-    if (bspgemm_status st = check_arm(ctx, B, s)) return bail(st);
-    slot.prepass_kernel = B->blk8_state == 1 ? 1 : 0;
-    slot.padded = B->pad_state == 1;
-    const int *Bcol = B->gather_col();                     // B.col_idx, or its padded copy (the extents in ab[] point into it)
-    launch_row_work(A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->blk8_state == 1 ? B->d_blk8 : nullptr,
-                    B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, B->pad_state == 1 ? B->d_ext : nullptr, row_begin, row_end,
-                    ctx->F, ctx->ab, s);
     launch_scan_and_bin(ctx->F, R, row_begin, A->d_row_ptr, ctx->Fprefix, ctx->partials, ctx->bin_tiles,
                         ctx->bin_count, ctx->rec, ctx->recpre, ctx->cnt, heavy_cols, ctx->hpartials, mid_cap_for_cols(B->cols), rank_cap_for_cols(B->cols), 0, s);
     HostScalars *h = ctx->h;
@@ -166,54 +249,19 @@ static bspgemm_status multiply_exact(bspgemm_context *ctx, const bspgemm_matrix 
     const long long totalF = R > 0 ? h->totalF : 0;
     if (R == 0) { memset(h->bin_count, 0, sizeof h->bin_count); h->heavy_total = 0; }
     if (bspgemm_status st = ensure_tmp(ctx, (size_t)h->heavy_total + 1)) return bail(st);
-
-    size_t bin_start[kNumBins + 1] = {0, 0};               // class b's segment of rec[] (class 0 has none)
-    for (int b = 1; b < kNumBins; b++) bin_start[b + 1] = bin_start[b] + (size_t)h->bin_count[b];
     int cls_n[2][kNumBins] = {};
-    hipStream_t lanes[3] = {s, sB, sC};
-    const int nlanes = ctx->class_streams;
-    // The class launches of a phase are independent (disjoint rows): they alternate over two streams
-    // so that one launch's draining tail overlaps the next one's ramp-up.  The side streams start
-    // behind the phase's inputs (fork) and the main stream waits for them at its end (join).
-    auto fork = [&](hipEvent_t ev) -> hipError_t {
-        if (hipError_t e = hipEventRecord(ev, s)) return e;
-        for (int l = 1; l < 3; l++)
-            if (hipError_t e = hipStreamWaitEvent(lanes[l], ev, 0)) return e;
-        return hipSuccess;
-    };
-    auto join = [&](int l, hipEvent_t ev) -> hipError_t {
-        if (hipError_t e = hipEventRecord(ev, lanes[l])) return e;
-        return hipStreamWaitEvent(s, ev, 0);
-    };
 
     // ---- symbolic 2: exact |C_i| of every row, scanned into C.row_ptr -----------------------
-    int order[kNumBins], lane_of[kNumBins] = {};
     if (R > 0) {
-        class_order(h->bin_count, totalF, order, lane_of);
-        HIPCHK_B(fork(ctx->ev_tile[0][0]));
-        for (int pos = 1; pos < kNumBins; pos++) {
-            const int b = order[pos];
-            const int n = h->bin_count[b];
-            cls_n[0][b] = n;
-            if (n <= 0) continue;
-            hipStream_t sx = lanes[lane_of[pos] % nlanes];
-            const RowRec *rec = ctx->rec + bin_start[b];
-            if (ctx->class_timing) HIPCHK_B(hipEventRecord(slot.ev_cls[0][b][0], sx));
-            if (b <= kWaveBins) {
-                // the numeric kernel without its emit half: |C_i| = F_i as soon as every product is seen to sit alone
-                // in its 32-column slot, the level-0 masks are only built and counted for the other rows
-                launch_wave_rows(b, wave_levels_for_cols(B->cols), ctx->ab, Bcol, B->cols, rec, nullptr, nullptr, n,
-                                 row_begin, nullptr, ctx->cnt, ctx->d_err, sx, true);
-            } else {
-                const long long *hpre = ctx->recpre + bin_start[b];
-                hub_order(ctx, b, n, rec, hpre, sx);
-                HIPCHK_B(launch_dense_rows(b, ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, hpre, n,
-                                           row_begin, ctx->tmp, ctx->cnt, sx));
-            }
-            if (ctx->class_timing) HIPCHK_B(hipEventRecord(slot.ev_cls[0][b][1], sx));
-        }
-        HIPCHK_B(hipGetLastError());
-        for (int l = 1; l < nlanes; l++) HIPCHK_B(join(l, ctx->ev_tile[0][l]));
+        // the numeric kernel without its emit half: |C_i| = F_i as soon as every product is seen to sit alone in its
+        // 32-column slot, the level-0 masks are only built and counted for the other rows.  The heavy rows are
+        // accumulated and read out into their workspace (offsets in recpre)
+        auto count = [&](int b, int n, const RowRec *rec, const long long *recpre, hipStream_t sx) {
+            hub_order(ctx, b, n, rec, recpre, sx);
+            return launch_class(b, ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, recpre, n, row_begin, ctx->tmp, ctx->cnt,
+                                ctx->d_err, MaskMode::None, nullptr, nullptr, sx, true);
+        };
+        if (bspgemm_status st = class_phase(ctx, 0, totalF, cls_n[0], false, count)) return bail(st);
         launch_scan_counts(ctx->cnt, R, C->d_row_ptr, ctx->partials, nullptr, s);
     } else {
         HIPCHK_B(hipMemsetAsync(C->d_row_ptr, 0, sizeof(long long), s));
@@ -223,56 +271,33 @@ static bspgemm_status multiply_exact(bspgemm_context *ctx, const bspgemm_matrix 
 
     // C.col_idx: nnz(C) <= F entries are needed.  A cached buffer that holds F entries is taken
     // without waiting for nnz(C); otherwise the size is read back and exactly that is allocated
-    // (F itself when it is within 2 % of nnz(C): the next product of this shape then finds it cached).
-    bool synced = false;
-    const bool check = ctx->check;                         // development: never emit on unverified sizes
-    if (!check && result_cached(ctx, result_bytes_colidx(totalF))) {
-        HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_col_idx), result_bytes_colidx(totalF)));
-        C->col_cap = totalF;
+    // (or F itself, col_cap_for).  Development (BSPGEMM_OPT_CHECK): never emit on unverified sizes.
+    if (!ctx->check && result_cached(ctx, result_bytes_colidx(totalF))) {
+        HIPCHK_B(alloc_col_idx(ctx, C, totalF));
     } else {
         HIPCHK_B(hipStreamSynchronize(s));
-        synced = true;
         if (h->nnzC < 0 || h->nnzC > totalF) return bail(FAIL(BSPGEMM_ERR_HIP, "symbolic pass counted more outputs than products"));
-        const long long want = (totalF - h->nnzC <= h->nnzC / 50 + 4096) ? totalF : h->nnzC;
-        HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_col_idx), result_bytes_colidx(want)));
-        C->col_cap = want;
+        HIPCHK_B(alloc_col_idx(ctx, C, col_cap_for(totalF, h->nnzC)));
     }
 
-    // ---- numeric: every row emitted at its final place ------------------------------------------
+    // ---- numeric: every row emitted at its final place; the heavy rows' move runs beside the class launches on the third stream
     if (R > 0) {
         const int levels = wave_levels_for_cols(B->cols);
-        HIPCHK_B(fork(ctx->ev_tile[1][0]));
-        for (int pos = 1; pos < kNumBins; pos++) {
-            const int b = order[pos];
-            const int n = h->bin_count[b];
-            cls_n[1][b] = n;
-            if (n <= 0) continue;
-            const RowRec *rec = ctx->rec + bin_start[b];
-            const long long *recpre = ctx->recpre + bin_start[b];
-            // the heavy rows' move runs beside the class launches on the third stream
-            hipStream_t sx = b > kWaveBins ? sC : lanes[lane_of[pos] % nlanes];
-            if (ctx->class_timing) HIPCHK_B(hipEventRecord(slot.ev_cls[1][b][0], sx));
+        auto emit = [&](int b, int n, const RowRec *rec, const long long *recpre, hipStream_t sx) {
             if (b <= kWaveBins)
-                launch_wave_rows(b, levels, ctx->ab, Bcol, B->cols, rec, recpre, C->d_row_ptr, n, row_begin,
-                                 C->d_col_idx, nullptr, ctx->d_err, sx);
-            else
-                launch_place_heavy(ctx->tmp, rec, recpre, n, C->d_row_ptr, row_begin, C->d_col_idx, sx);
-            if (ctx->class_timing) HIPCHK_B(hipEventRecord(slot.ev_cls[1][b][1], sx));
-        }
-        HIPCHK_B(hipGetLastError());
-        for (int l = 1; l < nlanes; l++) HIPCHK_B(join(l, ctx->ev_tile[1][l]));
+                return launch_wave_rows(b, levels, ctx->ab, Bcol, B->cols, rec, recpre, C->d_row_ptr, n, row_begin,
+                                        C->d_col_idx, nullptr, ctx->d_err, MaskMode::None, nullptr, nullptr, sx);
+            launch_place_heavy(ctx->tmp, rec, recpre, n, C->d_row_ptr, row_begin, C->d_col_idx, sx);
+            return hipSuccess;
+        };
+        if (bspgemm_status st = class_phase(ctx, 1, totalF, cls_n[1], true, emit)) return bail(st);
     }
     HIPCHK_B(hipEventRecord(slot.ev[3], s));
-    if (R > 0) HIPCHK_B(join(2, ctx->ev_join));            // the heavy rows' move (third stream)
-    HIPCHK_B(hipEventRecord(slot.ev[4], s));
-    if (ctx->check) HIPCHK_B(hipMemcpyAsync(&h->err, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    HIPCHK_B(hipStreamSynchronize(s));
-    (void)synced;
-    if (bspgemm_status st = check_verdict(ctx)) return bail(st);
-    C->nnz = h->nnzC;
-    close_slot(ctx, R, h, totalF, C->nnz, cls_n, mid_cap_for_cols(B->cols), rank_cap_for_cols(B->cols));
-    *out = C;
-    return BSPGEMM_OK;
+    if (R > 0) {                                           // the heavy rows' move (third stream)
+        HIPCHK_B(hipEventRecord(ctx->ev_join, ctx->stream_c));
+        HIPCHK_B(hipStreamWaitEvent(s, ctx->ev_join, 0));
+    }
+    return finish_flow(ctx, C, B, totalF, rank_cap_for_cols(B->cols), cls_n, out);
 }
 
 
@@ -285,43 +310,14 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
                                            const bspgemm_matrix *B, const bspgemm_matrix *Fm, MaskMode mode,
                                            int row_begin, int row_end, bspgemm_result **out)
 {
-    const bool keep = mode == MaskMode::Keep, drop = mode == MaskMode::Drop;
-    if (!out) return FAIL(BSPGEMM_ERR_INVALID, "result pointer is NULL");
-    *out = nullptr;
-    if (bspgemm_status st = check_operands(ctx, A, B, row_begin, row_end)) return st;
-    if (Fm && (Fm->ctx != ctx || Fm->rows < row_end)) return FAIL(BSPGEMM_ERR_INVALID, "mask has fewer rows than A / wrong context");
-    if (bspgemm_status st = use_device(ctx)) return st;
-    const int R = row_end - row_begin;
-    hipStream_t s = ctx->stream, sB = ctx->stream_b, sC = ctx->stream_c;
-    if (bspgemm_status st = ensure_rows(ctx, (size_t)R + 1)) return st;
-    if (bspgemm_status st = ensure_ab(ctx, (size_t)A->nnz + 1)) return st;
-
-    bspgemm_result *C = new (std::nothrow) bspgemm_result{ctx, R, 0, nullptr, nullptr, 0};
-    if (!C) return FAIL(BSPGEMM_ERR_ALLOC, "result");
-    auto bail = [&](bspgemm_status st) {                  // nothing of C may still be written when it is released
-        hipStreamSynchronize(s); hipStreamSynchronize(sB); hipStreamSynchronize(sC);
-        bspgemm_result_free(C);
-        return st;
-    };
-    ctx->slot_head = (ctx->slot_head + 1) % bspgemm_context::kStatSlots;
+    const bool keep = mode == MaskMode::Keep;
+    bspgemm_result *C = nullptr;
+    if (bspgemm_status st = start_flow(ctx, A, B, Fm, row_begin, row_end, BSPGEMM_FLOW_UPPER_BOUND, out, &C)) return st;
+    auto bail = [&](bspgemm_status st) { return drop_result(C, st); };
     bspgemm_context::StatSlot &slot = ctx->slots[ctx->slot_head];
-    slot.used = false;
-    slot.flow = BSPGEMM_FLOW_UPPER_BOUND;
-    slot.class_streams = ctx->class_streams;
-    slot.small = false;
-    slot.checked = ctx->check;
-
-    HIPCHK_B(hipEventRecord(slot.ev[0], s));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_row_ptr), result_bytes_rowptr(R)));
-    if (bspgemm_status st = ensure_pad(B)) return bail(st);
-    if (bspgemm_status st = ensure_blk8(B)) return bail(st);
-    if (bspgemm_status st = check_arm(ctx, B, s)) return bail(st);
-    slot.prepass_kernel = B->blk8_state == 1 ? 1 : 0;
-    slot.padded = B->pad_state == 1;
+    const int R = C->rows;
+    hipStream_t s = ctx->stream;
     const int *Bcol = B->gather_col();                     // B.col_idx, or its padded copy (the extents in ab[] point into it)
-    launch_row_work(A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->blk8_state == 1 ? B->d_blk8 : nullptr,
-                    B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, B->pad_state == 1 ? B->d_ext : nullptr, row_begin, row_end,
-                    ctx->F, ctx->ab, s);
     HostScalars *h = ctx->h;
     h->products = 0;
     // rows are classified by their products and placed by min(products, B.cols) -- or, masked (Keep), both by
@@ -348,59 +344,18 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
     if (bspgemm_status st = ensure_chunk_rows(ctx, compact_chunk_rows(total))) return bail(st);
     // C.col_idx: a cached buffer of the upper-bound size is taken now (nothing to wait for); else it
     // is allocated with exactly nnz(C) entries once the counts are scanned
-    if (result_cached(ctx, result_bytes_colidx(total))) {
-        HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_col_idx), result_bytes_colidx(total)));
-        C->col_cap = total;
-    }
-    const int levels = wave_levels_for_cols(B->cols);
+    if (result_cached(ctx, result_bytes_colidx(total))) HIPCHK_B(alloc_col_idx(ctx, C, total));
     HIPCHK_B(hipEventRecord(slot.ev[2], s));               // no count phase here: ev[1]..ev[2] is the host's turn-around
 
-    size_t bin_start[kNumBins + 1] = {0, 0};
-    for (int b = 1; b < kNumBins; b++) bin_start[b + 1] = bin_start[b] + (size_t)h->bin_count[b];
     int cls_n[2][kNumBins] = {};
-    hipStream_t lanes[3] = {s, sB, sC};
-    const int nlanes = ctx->class_streams;
     if (R > 0) {
-        HIPCHK_B(hipEventRecord(ctx->ev_tile[0][0], s));
-        for (int l = 1; l < nlanes; l++) HIPCHK_B(hipStreamWaitEvent(lanes[l], ctx->ev_tile[0][0], 0));
-        int order[kNumBins];
-        int lane_of[kNumBins];
-        class_order(h->bin_count, h->products, order, lane_of);
-        for (int pos = 1; pos < kNumBins; pos++) {
-            const int b = order[pos];
-            const int n = h->bin_count[b];
-            cls_n[1][b] = n;
-            if (n <= 0) continue;
-            hipStream_t sx = lanes[lane_of[pos] % nlanes];
-            const RowRec *rec = ctx->rec + bin_start[b];
-            const long long *recpre = ctx->recpre + bin_start[b];
-            if (ctx->class_timing) HIPCHK_B(hipEventRecord(slot.ev_cls[1][b][0], sx));
+        const int *Frow = Fm ? Fm->d_row_ptr : nullptr, *Fcol = Fm ? Fm->d_col_idx : nullptr;
+        auto place = [&](int b, int n, const RowRec *rec, const long long *recpre, hipStream_t sx) {
             if (!keep) hub_order(ctx, b, n, rec, recpre, sx);
-            if (drop && b <= kWaveBins)
-                launch_wave_rows_excl(b, levels, ctx->ab, Bcol, B->cols, rec, recpre, n, row_begin, ctx->tmp, ctx->cnt, ctx->d_err,
-                                      Fm->d_row_ptr, Fm->d_col_idx, sx);
-            else if (drop)
-                HIPCHK_B(launch_dense_rows_excl(b, ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, recpre, n, row_begin, ctx->tmp,
-                                                ctx->cnt, Fm->d_row_ptr, Fm->d_col_idx, sx));
-            else if (!Fm && b <= kWaveBins)
-                launch_wave_rows(b, levels, ctx->ab, Bcol, B->cols, rec, recpre, nullptr, n, row_begin,
-                                 ctx->tmp, ctx->cnt, ctx->d_err, sx);
-            else if (!Fm)
-                HIPCHK_B(launch_dense_rows(b, ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, recpre, n, row_begin, ctx->tmp,
-                                           ctx->cnt, sx));
-            else if (b <= kWaveBins && wave_masked_supported(B->cols))
-                launch_wave_masked(b, ctx->ab, Bcol, B->cols, Fm->d_row_ptr, Fm->d_col_idx, rec, recpre, n,
-                                   row_begin, ctx->tmp, ctx->cnt, sx);
-            else
-                HIPCHK_B(launch_dense_rows_masked(ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, recpre, n, row_begin,
-                                                  ctx->tmp, ctx->cnt, Fm->d_row_ptr, Fm->d_col_idx, sx));
-            if (ctx->class_timing) HIPCHK_B(hipEventRecord(slot.ev_cls[1][b][1], sx));
-        }
-        HIPCHK_B(hipGetLastError());
-        for (int l = 1; l < nlanes; l++) {
-            HIPCHK_B(hipEventRecord(ctx->ev_tile[0][l], lanes[l]));
-            HIPCHK_B(hipStreamWaitEvent(s, ctx->ev_tile[0][l], 0));
-        }
+            return launch_class(b, ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, recpre, n, row_begin, ctx->tmp, ctx->cnt,
+                                ctx->d_err, mode, Frow, Fcol, sx);
+        };
+        if (bspgemm_status st = class_phase(ctx, 1, h->products, cls_n[1], false, place)) return bail(st);
         HIPCHK_B(hipEventRecord(slot.ev[3], s));
         launch_scan_counts(ctx->cnt, R, C->d_row_ptr, ctx->partials, nullptr, s, ctx->chunk_row);
     } else {
@@ -410,22 +365,13 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
     HIPCHK_B(hipMemcpyAsync(&h->nnzC, C->d_row_ptr + R, sizeof(long long), hipMemcpyDeviceToHost, s));
     if (!C->d_col_idx) {
         HIPCHK_B(hipStreamSynchronize(s));
-        const long long want = (total - h->nnzC <= h->nnzC / 50 + 4096) ? total : h->nnzC;
-        HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_col_idx), result_bytes_colidx(want)));
-        C->col_cap = want;
+        HIPCHK_B(alloc_col_idx(ctx, C, col_cap_for(total, h->nnzC)));
     }
     if (R > 0) {
         launch_compact(ctx->tmp, ctx->Fprefix, C->d_row_ptr, 0, R, total, C->d_col_idx, s, ctx->chunk_row);
         HIPCHK_B(hipGetLastError());
     }
-    HIPCHK_B(hipEventRecord(slot.ev[4], s));
-    if (ctx->check) HIPCHK_B(hipMemcpyAsync(&h->err, ctx->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    HIPCHK_B(hipStreamSynchronize(s));
-    if (bspgemm_status st = check_verdict(ctx)) return bail(st);
-    C->nnz = h->nnzC;
-    close_slot(ctx, R, h, R > 0 ? h->products : 0, C->nnz, cls_n, mid_cap_for_cols(B->cols), keep ? 0 : rank_cap_for_cols(B->cols));
-    *out = C;
-    return BSPGEMM_OK;
+    return finish_flow(ctx, C, B, R > 0 ? h->products : 0, keep ? 0 : rank_cap_for_cols(B->cols), cls_n, out);
 }
 
 // Small products (csrc/small.hip): five launches, no size goes to the host before the end, ONE read-back.  *bailed = true
@@ -458,19 +404,13 @@ static bspgemm_status multiply_small(bspgemm_context *ctx, const bspgemm_matrix 
         bspgemm_result_free(C);
         return st;
     };
-    ctx->slot_head = (ctx->slot_head + 1) % bspgemm_context::kStatSlots;
-    bspgemm_context::StatSlot &slot = ctx->slots[ctx->slot_head];
-    slot.used = false;
-    slot.flow = BSPGEMM_FLOW_UPPER_BOUND;                  // (rows are placed by their product count and squeezed together)
-    slot.class_streams = 1;
-    slot.small = true;
-    slot.checked = false;
+    // (the upper-bound flow's kind: rows are placed by their product count and squeezed together)
+    bspgemm_context::StatSlot &slot = open_slot(ctx, BSPGEMM_FLOW_UPPER_BOUND, true);
     slot.prepass_kernel = 2;
     slot.padded = false;                                   // (B.col_idx itself: the path never builds the padded copy)
     HIPCHK_B(hipEventRecord(slot.ev[0], s));
     HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_row_ptr), result_bytes_rowptr(R)));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_col_idx), result_bytes_colidx(kSmallMaxProducts)));
-    C->col_cap = kSmallMaxProducts;
+    HIPCHK_B(alloc_col_idx(ctx, C, kSmallMaxProducts));
     launch_small(A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->d_col_idx, row_begin, R, ctx->F, ctx->Fprefix,
                  reinterpret_cast<int *>(ctx->rec), ctx->cnt, ctx->tmp, C->d_row_ptr, C->d_col_idx, ctx->d_small_tiles, ctx->d_small, s);
     HIPCHK_B(hipGetLastError());

@@ -1,27 +1,20 @@
-// wave_rows.hip -- dispatcher of the one-wave-per-row kernels (bodies: wave_rows.inc, built in
-// wave_rows_L1..L5.hip).  Picks the number of 5-bit levels from B's column count.
+// wave_rows.hip -- dispatcher of the one-wave-per-row kernels (bodies: wave_rows.inc, built once per (LEVELS, EXCL)
+// pair).  Picks the number of 5-bit levels from B's column count; launch_class picks the kernel family of a class.
 #include "kernels.hpp"
 
 namespace bsp {
 
-template <int LEVELS>
+template <int LEVELS, bool EXCL>
 void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec,
                         const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
-                        unsigned *err, hipStream_t s, bool count);
-extern template void launch_wave_levels<1>(int, const int2 *, const int *, int, const RowRec *, const long long *, const long long *, int, int, int *, int *, unsigned *, hipStream_t, bool);
-extern template void launch_wave_levels<2>(int, const int2 *, const int *, int, const RowRec *, const long long *, const long long *, int, int, int *, int *, unsigned *, hipStream_t, bool);
-extern template void launch_wave_levels<3>(int, const int2 *, const int *, int, const RowRec *, const long long *, const long long *, int, int, int *, int *, unsigned *, hipStream_t, bool);
-extern template void launch_wave_levels<4>(int, const int2 *, const int *, int, const RowRec *, const long long *, const long long *, int, int, int *, int *, unsigned *, hipStream_t, bool);
-extern template void launch_wave_levels<5>(int, const int2 *, const int *, int, const RowRec *, const long long *, const long long *, int, int, int *, int *, unsigned *, hipStream_t, bool);
-
-template <int LEVELS>
-void launch_wave_levels_excl(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec, const long long *recpre,
-                             int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, const int *Frow, const int *Fcol,
-                             hipStream_t s);
-#define BSP_EXCL_EXTERN(L) extern template void launch_wave_levels_excl<L>(int, const int2 *, const int *, int, const RowRec *, \
-    const long long *, int, int, int *, int *, unsigned *, const int *, const int *, hipStream_t);
-BSP_EXCL_EXTERN(1) BSP_EXCL_EXTERN(2) BSP_EXCL_EXTERN(3) BSP_EXCL_EXTERN(4) BSP_EXCL_EXTERN(5)
-#undef BSP_EXCL_EXTERN
+                        unsigned *err, const int *Frow, const int *Fcol, hipStream_t s, bool count);
+#define BSP_WAVE_EXTERN(L) \
+    extern template void launch_wave_levels<L, false>(int, const int2 *, const int *, int, const RowRec *, const long long *, \
+        const long long *, int, int, int *, int *, unsigned *, const int *, const int *, hipStream_t, bool); \
+    extern template void launch_wave_levels<L, true>(int, const int2 *, const int *, int, const RowRec *, const long long *, \
+        const long long *, int, int, int *, int *, unsigned *, const int *, const int *, hipStream_t, bool);
+BSP_WAVE_EXTERN(1) BSP_WAVE_EXTERN(2) BSP_WAVE_EXTERN(3) BSP_WAVE_EXTERN(4) BSP_WAVE_EXTERN(5)
+#undef BSP_WAVE_EXTERN
 
 // words of the directly addressed top bitmap: ceil(cols / 32^levels) <= kWaveTopWords
 static int wave_top_words(int levels, int cols)
@@ -30,34 +23,37 @@ static int wave_top_words(int levels, int cols)
     return (int)(((long long)cols + span - 1) / span);
 }
 
-void launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol, int cols,
-                      const RowRec *rec, const long long *recpre, const long long *row_ptr, int nrows, int row_begin,
-                      int *tmp, int *cnt, unsigned *err, hipStream_t s, bool count_only)
+hipError_t launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol, int cols,
+                            const RowRec *rec, const long long *recpre, const long long *row_ptr, int nrows, int row_begin,
+                            int *tmp, int *cnt, unsigned *err, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s,
+                            bool count_only)
 {
-    if (nrows <= 0) return;
-    const int topw = wave_top_words(levels, cols);
-    switch (levels) {
-    case 1: launch_wave_levels<1>(bin, ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count_only); break;
-    case 2: launch_wave_levels<2>(bin, ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count_only); break;
-    case 3: launch_wave_levels<3>(bin, ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count_only); break;
-    case 4: launch_wave_levels<4>(bin, ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count_only); break;
-    default: launch_wave_levels<5>(bin, ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count_only); break;
-    }
+    if (mode == MaskMode::Keep || (count_only && mode != MaskMode::None)) return hipErrorInvalidValue;
+    if (nrows <= 0) return hipSuccess;
+    static const decltype(&launch_wave_levels<1, false>) by_levels[2][5] = {
+        {launch_wave_levels<1, false>, launch_wave_levels<2, false>, launch_wave_levels<3, false>, launch_wave_levels<4, false>,
+         launch_wave_levels<5, false>},
+        {launch_wave_levels<1, true>, launch_wave_levels<2, true>, launch_wave_levels<3, true>, launch_wave_levels<4, true>,
+         launch_wave_levels<5, true>}};
+    by_levels[mode == MaskMode::Drop][(levels < 5 ? levels : 5) - 1](bin, ab, Bcol, wave_top_words(levels, cols), rec, recpre,
+                                                                     row_ptr, nrows, row_begin, tmp, cnt, err, Frow, Fcol, s,
+                                                                     count_only);
+    return hipSuccess;
 }
 
-void launch_wave_rows_excl(int bin, int levels, const int2 *ab, const int *Bcol, int cols, const RowRec *rec,
-                           const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err,
-                           const int *Frow, const int *Fcol, hipStream_t s)
+hipError_t launch_class(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
+                        const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode,
+                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only)
 {
-    if (nrows <= 0) return;
-    const int topw = wave_top_words(levels, cols);
-    switch (levels) {
-    case 1: launch_wave_levels_excl<1>(bin, ab, Bcol, topw, rec, recpre, nrows, row_begin, tmp, cnt, err, Frow, Fcol, s); break;
-    case 2: launch_wave_levels_excl<2>(bin, ab, Bcol, topw, rec, recpre, nrows, row_begin, tmp, cnt, err, Frow, Fcol, s); break;
-    case 3: launch_wave_levels_excl<3>(bin, ab, Bcol, topw, rec, recpre, nrows, row_begin, tmp, cnt, err, Frow, Fcol, s); break;
-    case 4: launch_wave_levels_excl<4>(bin, ab, Bcol, topw, rec, recpre, nrows, row_begin, tmp, cnt, err, Frow, Fcol, s); break;
-    default: launch_wave_levels_excl<5>(bin, ab, Bcol, topw, rec, recpre, nrows, row_begin, tmp, cnt, err, Frow, Fcol, s); break;
-    }
+    if (bin > kWaveBins)
+        return launch_dense_rows(bin, ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s);
+    if (mode != MaskMode::Keep)           // (the count pass emits nothing: no output offsets, no workspace)
+        return launch_wave_rows(bin, wave_levels_for_cols(cols), ab, Bcol, cols, rec, count_only ? nullptr : recpre, nullptr,
+                                nrows, row_begin, count_only ? nullptr : tmp, cnt, err, mode, Frow, Fcol, s, count_only);
+    if (!wave_masked_supported(cols))
+        return launch_dense_rows(bin, ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s);
+    launch_wave_masked(bin, ab, Bcol, cols, Frow, Fcol, rec, recpre, nrows, row_begin, tmp, cnt, s);
+    return hipSuccess;
 }
 
 }  // namespace bsp

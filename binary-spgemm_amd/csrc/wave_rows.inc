@@ -1,5 +1,5 @@
 // wave_rows.inc -- the hot kernel: one wavefront per A-row, rank-bitmap accumulator in LDS.
-// Included by wave_rows_L<k>.hip, one translation unit per LEVELS value (parallel builds).
+// Compiled once per (LEVELS, EXCL) pair by the Makefile (parallel builds); wave_rows.hip dispatches to those objects.
 //
 // Replaces the body of SpGEMM_bigslice (final/SpGEMM_mpi_omp.c:24-52) for rows whose product
 // count F_i fits one wave's capacity (<= 2048):
@@ -257,10 +257,11 @@ static void launch_one(const int2 *ab, const int *Bcol, int topw, const RowRec *
     else if constexpr (LEVELS == 3) launch_cfg<LEVELS, CHUNKS, 8, EXCL>(ab, Bcol, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
 }
 
+// one class of rows (EXCL: the complemented-mask twin, Frow / Fcol: F's CSR); wave_rows.hip picks LEVELS
 template <int LEVELS, bool EXCL>
-static void launch_bin(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec,
-                       const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
-                       unsigned *err, hipStream_t s, bool count, const int *Frow, const int *Fcol)
+void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec,
+                        const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
+                        unsigned *err, const int *Frow, const int *Fcol, hipStream_t s, bool count)
 {
     switch (bin) {
 #define BSP_CASE(b) case b: launch_one<LEVELS, kWaveChunks[b], EXCL>(ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol); break;
@@ -272,21 +273,11 @@ static void launch_bin(int bin, const int2 *ab, const int *Bcol, int topw, const
     }
 }
 
-template <int LEVELS>
-void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec,
-                        const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
-                        unsigned *err, hipStream_t s, bool count)
-{
-    launch_bin<LEVELS, false>(bin, ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, nullptr, nullptr);
-}
-
-// the complemented-mask twins: built in wave_rows_excl_L1..L5.hip
-template <int LEVELS>
-void launch_wave_levels_excl(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec, const long long *recpre,
-                             int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, const int *Frow, const int *Fcol,
-                             hipStream_t s)
-{
-    launch_bin<LEVELS, true>(bin, ab, Bcol, topw, rec, recpre, nullptr, nrows, row_begin, tmp, cnt, err, s, false, Frow, Fcol);
-}
+// the Makefile builds one object per (LEVELS, EXCL) pair, -DBSP_WAVE_LEVELS=1..5 -DBSP_WAVE_EXCL=0|1, so that they compile in parallel
+#ifdef BSP_WAVE_LEVELS
+template void launch_wave_levels<BSP_WAVE_LEVELS, BSP_WAVE_EXCL>(int, const int2 *, const int *, int, const RowRec *, const long long *,
+                                                                 const long long *, int, int, int *, int *, unsigned *, const int *,
+                                                                 const int *, hipStream_t, bool);
+#endif
 
 }  // namespace bsp
