@@ -53,6 +53,7 @@ EXPORTS = [
     "bspgemm_comm_gather_col_idx", "SpGEMM_hip_multi", "bspgemm_device_count", "bspgemm_stats_at",
     "bspgemm_set_flow", "bspgemm_set_class_timing", "bspgemm_build_info", "bspgemm_matrix_invalidate", "bspgemm_comm_agree", "bspgemm_comm_inject_failure",
     "bspgemm_set_option", "bspgemm_get_option", "bspgemm_matrix_uses_blocked_table", "bspgemm_matrix_uses_padded_rows",
+    "bspgemm_matrix_transpose", "bspgemm_matrix_download",
 ]
 
 
@@ -162,6 +163,8 @@ def lib():
     L.bspgemm_matrix_wrap_device.argtypes = [VP, C.c_int, C.c_int, C.c_int64, VP, VP, PVP]
     L.bspgemm_matrix_free.argtypes = [VP]
     L.bspgemm_matrix_free.restype = None
+    L.bspgemm_matrix_transpose.argtypes = [VP, VP, PVP]
+    L.bspgemm_matrix_download.argtypes = [VP, VP, VP, VP]
     L.bspgemm_matrix_rows.argtypes = [VP]
     L.bspgemm_matrix_cols.argtypes = [VP]
     L.bspgemm_matrix_nnz.argtypes = [VP]
@@ -388,6 +391,12 @@ class Context:
         _chk(lib().bspgemm_matrix_from_result(self._h, result._h, cols, C.byref(m)), "matrix_from_result")
         return Matrix(self, m, keep=None)
 
+    def transpose(self, A):
+        """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""
+        m = C.c_void_p()
+        _chk(lib().bspgemm_matrix_transpose(self._h, A._h, C.byref(m)), "matrix_transpose")
+        return Matrix(self, m, keep=None)
+
     def closure(self, A, max_iter=64):
         """reflexive-transitive closure by repeated squaring; returns (Result, products computed)"""
         r, it = C.c_void_p(), C.c_int()
@@ -438,6 +447,14 @@ class Matrix:
     def uses_padded_rows(self):
         """1 / 0 once the operand has been used as B (whether its rows are gathered from the padded copy), -1 before"""
         return lib().bspgemm_matrix_uses_padded_rows(self._h)
+
+    def download(self):
+        """bspgemm_matrix_download: (row_ptr int32[rows+1], col_idx int32[nnz]) as stored on the device"""
+        rp = np.zeros(self.rows + 1, dtype=np.int32)
+        ci = np.zeros(self.nnz, dtype=np.int32)
+        _chk(lib().bspgemm_matrix_download(self.ctx._h, self._h, C.c_void_p(rp.ctypes.data),
+                                           C.c_void_p(ci.ctypes.data) if self.nnz else None), "matrix_download")
+        return rp, ci
 
     def free(self):
         if self._h:

@@ -292,6 +292,18 @@ extern "C" void bspgemm_matrix_free(bspgemm_matrix *m)
     hipFree(m->d_ext);
     delete m;
 }
+extern "C" bspgemm_status bspgemm_matrix_download(bspgemm_context *ctx, const bspgemm_matrix *m, int *row_ptr, int *col_idx)
+{
+    if (!ctx || !m || m->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "matrix_download");
+    if (bspgemm_status st = use_device(ctx)) return st;
+    if (row_ptr)
+        HIPCHK(hipMemcpyAsync(row_ptr, m->d_row_ptr, ((size_t)m->rows + 1) * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (col_idx && m->nnz > 0)
+        HIPCHK(hipMemcpyAsync(col_idx, m->d_col_idx, (size_t)m->nnz * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return BSPGEMM_OK;
+}
+
 extern "C" bspgemm_status bspgemm_matrix_invalidate(bspgemm_matrix *m)
 {
     if (!m) return FAIL(BSPGEMM_ERR_INVALID, "matrix is NULL");

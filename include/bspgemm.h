@@ -99,6 +99,30 @@ bspgemm_status bspgemm_matrix_wrap_device(bspgemm_context *ctx, int rows, int co
  * context's stream first                                                                        */
 bspgemm_status bspgemm_matrix_invalidate(bspgemm_matrix *m);
 void    bspgemm_matrix_free(bspgemm_matrix *m);
+/* Copy an operand to the host as stored: row_ptr[rows+1] (row_ptr[0] = 0) and col_idx[nnz]; either pointer may be
+ * NULL to skip that array (like bspgemm_result_download).  m must belong to ctx.  Synchronises the context's stream. */
+bspgemm_status bspgemm_matrix_download(bspgemm_context *ctx, const bspgemm_matrix *m,
+                                       int *row_ptr /* rows+1, [0] = 0 */, int *col_idx /* nnz */);
+/* AT = pattern(A)^T on the device: AT has A.cols rows and A.rows columns, and row k of AT is
+ * { i : (i,k) in pattern(A) }, strictly ascending and free of duplicates.  nnz(AT) is the number of distinct pairs
+ * (at most nnz(A)); transposing twice gives A with its rows sorted and deduplicated.  The result is deterministic: the
+ * pattern of scipy's A.T.tocsr() after sum_duplicates() and sort_indices(), bit for bit.  The reference converts COO
+ * to CSC on the host (final/coo2csc.c) and its loader hands back the transpose of the file's matrix that way
+ * (final/utils.c:77): a directed graph loaded by bspgemm_readCOO arrives as in-edges, and this call flips it back on
+ * the GPU.
+ *   - A may come from upload (interior row_ptr included), wrap_device, matrix_from_result or an earlier transpose; its
+ *     rows may be unsorted and hold duplicates; any shape, rows == 0, cols == 0 and nnz == 0 included.
+ *   - A column outside [0, A.cols) anywhere in A: BSPGEMM_ERR_INVALID, *AT = NULL, bspgemm_last_error names the cause
+ *     (the kernels check every column; the context stays usable).  More than 2^31 - 8193 nonzeros: BSPGEMM_ERR_OVERFLOW.
+ *   - AT is an owned operand with the layout of an uploaded one (its derived tables as after upload): usable in every
+ *     multiply, masked product and closure; release it with bspgemm_matrix_free.  Its col_idx holds nnz(A) + 1 ints.
+ *   - Runs on the context's stream and returns when AT is complete, after ONE synchronisation (nnz(AT) is known only
+ *     after deduplication).  It does not touch the multiply statistics (bspgemm_last_stats / bspgemm_stats_at).
+ *   - Memory: a stable radix sort of the (column, row) pairs by column, 8 bits per pass, in the context's workspace
+ *     (kept, like the multiply's): 8 bytes per nonzero of A for one key/value array pair, two pairs when A.cols > 256,
+ *     plus 12 bytes per 16 nonzeros for the per-tile digit counts and their scan.  An allocation failure returns
+ *     BSPGEMM_ERR_ALLOC and leaks nothing.                                                                              */
+bspgemm_status bspgemm_matrix_transpose(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_matrix **AT);
 int     bspgemm_matrix_rows(const bspgemm_matrix *m);
 int     bspgemm_matrix_cols(const bspgemm_matrix *m);
 int64_t bspgemm_matrix_nnz(const bspgemm_matrix *m);
