@@ -53,7 +53,7 @@ EXPORTS = [
     "bspgemm_comm_gather_col_idx", "SpGEMM_hip_multi", "bspgemm_device_count", "bspgemm_stats_at",
     "bspgemm_set_flow", "bspgemm_set_class_timing", "bspgemm_build_info", "bspgemm_matrix_invalidate", "bspgemm_comm_agree", "bspgemm_comm_inject_failure",
     "bspgemm_set_option", "bspgemm_get_option", "bspgemm_matrix_uses_blocked_table", "bspgemm_matrix_uses_padded_rows",
-    "bspgemm_matrix_transpose", "bspgemm_matrix_download",
+    "bspgemm_matrix_transpose", "bspgemm_matrix_download", "bspgemm_multiply_accumulate", "bspgemm_closure_ex",
 ]
 
 
@@ -67,6 +67,7 @@ class BspgemmError(RuntimeError):
 MAX_BINS = 20      # BSPGEMM_MAX_BINS
 FLOWS = {"auto": 0, "upper-bound": 1, "exact": 2}                                    # BSPGEMM_FLOW_*
 MASK_COMPLEMENT = 1                                                                      # BSPGEMM_MASK_COMPLEMENT
+CLOSURE_TRANSITIVE = 1                                                                   # BSPGEMM_CLOSURE_TRANSITIVE
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5}    # bspgemm_option
 
 
@@ -184,6 +185,8 @@ def lib():
     L.bspgemm_result_free.restype = None
     L.bspgemm_matrix_from_result.argtypes = [VP, VP, C.c_int, PVP]
     L.bspgemm_closure.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
+    L.bspgemm_multiply_accumulate.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, PVP]
+    L.bspgemm_closure_ex.argtypes = [VP, VP, C.c_uint, C.c_int, PVP, C.POINTER(C.c_int)]
     L.bspgemm_row_work_prefix.argtypes = [VP, VP, VP, _I64P]
     L.bspgemm_partition_rows.argtypes = [VP, VP, VP, C.c_int, _I32P]
     L.bspgemm_last_stats.argtypes = [VP, C.POINTER(Stats)]
@@ -386,6 +389,15 @@ class Context:
              "bspgemm_multiply_masked")
         return Result(self, r)
 
+    def multiply_accumulate(self, A, B, D, row_begin=0, row_end=None):
+        """C = D | (A*B), the OR-accumulating product (bspgemm_multiply_accumulate): D's columns within [0, B.cols) join
+        every row's products.  D is indexed by absolute row; C's row_ptr is slice-local."""
+        row_end = A.rows if row_end is None else row_end
+        r = C.c_void_p()
+        _chk(lib().bspgemm_multiply_accumulate(self._h, A._h, B._h, D._h, row_begin, row_end, C.byref(r)),
+             "bspgemm_multiply_accumulate")
+        return Result(self, r)
+
     def matrix_from_result(self, result, cols):
         m = C.c_void_p()
         _chk(lib().bspgemm_matrix_from_result(self._h, result._h, cols, C.byref(m)), "matrix_from_result")
@@ -397,10 +409,15 @@ class Context:
         _chk(lib().bspgemm_matrix_transpose(self._h, A._h, C.byref(m)), "matrix_transpose")
         return Matrix(self, m, keep=None)
 
-    def closure(self, A, max_iter=64):
-        """reflexive-transitive closure by repeated squaring; returns (Result, products computed)"""
+    def closure(self, A, max_iter=64, transitive=False):
+        """reflexive-transitive closure A* by repeated squaring; transitive=True: A+ (paths of length >= 1) by
+        T = T | T*T (bspgemm_closure_ex with BSPGEMM_CLOSURE_TRANSITIVE).  Returns (Result, products computed)"""
         r, it = C.c_void_p(), C.c_int()
-        _chk(lib().bspgemm_closure(self._h, A._h, max_iter, C.byref(r), C.byref(it)), "bspgemm_closure")
+        if transitive:
+            _chk(lib().bspgemm_closure_ex(self._h, A._h, CLOSURE_TRANSITIVE, max_iter, C.byref(r), C.byref(it)),
+                 "bspgemm_closure_ex")
+        else:
+            _chk(lib().bspgemm_closure(self._h, A._h, max_iter, C.byref(r), C.byref(it)), "bspgemm_closure")
         return Result(self, r), it.value
 
     def lengths_to_row_ptr(self, d_lengths, world, width, bounds, d_row_ptr, hip_stream=None):

@@ -271,6 +271,25 @@ __global__ __launch_bounds__(kDenseThreads, (kDenseThreads == kDenseThreadsBig ?
 #include "dense_rows_body.inc"
 }
 
+// C = D | (A*B) for the heavy rows (Drow / Dcol: D's CSR, absolute row ids): the unmasked window kernel (same window, same
+// LDS) with the columns of D's row set in each window after its gather
+template <int kDenseThreads>
+__global__ __launch_bounds__(kDenseThreads, (kDenseThreads == kDenseThreadsBig ? kBigMinWaves : kMidMinWaves)) void k_dense_rows_acc(const int2 *__restrict__ ab,
+                                                              const int *__restrict__ Bcol, int nnzB,
+                                                              int cols, int wwords,
+                                                              const RowRec *__restrict__ rec,
+                                                              const long long *__restrict__ recpre,
+                                                              int row_begin,
+                                                              int *__restrict__ tmp,
+                                                              int *__restrict__ cnt,
+                                                              const int *__restrict__ Frow,
+                                                              const int *__restrict__ Fcol)
+{
+    constexpr bool MASKED = false;
+    constexpr MaskMode MODE = MaskMode::Insert;
+#include "dense_rows_body.inc"
+}
+
 // ---------------------------------------------------------------------------------------
 // RANK ROWS (class kRankBin): rows of 2048 < F_i <= kRankCap products when the column range is several windows of the
 // small dense shape.  The workgroup's LDS holds a two-level RANK bitmap instead of a dense one -- `top`, one bit per
@@ -296,7 +315,7 @@ __global__ __launch_bounds__(kRankThreads, 8) void k_rank_rows(const int2 *__res
                                                                const long long *__restrict__ recpre,
                                                                int row_begin, int *__restrict__ tmp, int *__restrict__ cnt)
 {
-    constexpr bool DROP = false;
+    constexpr bool DROP = false, INS = false;
     const int *Frow = nullptr, *Fcol = nullptr;
 #include "rank_rows_body.inc"
 }
@@ -312,7 +331,22 @@ __global__ __launch_bounds__(kRankThreads, 8) void k_rank_rows_excl(const int2 *
                                                                     int row_begin, int *__restrict__ tmp, int *__restrict__ cnt,
                                                                     const int *__restrict__ Frow, const int *__restrict__ Fcol)
 {
-    constexpr bool DROP = true;
+    constexpr bool DROP = true, INS = false;
+#include "rank_rows_body.inc"
+}
+
+// C = D | (A*B) for the rank class (Drow / Dcol: D's CSR, absolute row ids): each span's columns of D's row are set as top bits
+// after the span's first sweep and in their slots after its second; the read-out is unchanged
+template <bool kSpans>
+__global__ __launch_bounds__(kRankThreads, 8) void k_rank_rows_acc(const int2 *__restrict__ ab, const int *__restrict__ Bcol, int nnzB,
+                                                                   int cols, int topw,
+                                                                   const RowRec *__restrict__ rec,
+                                                                   const long long *__restrict__ recpre,
+                                                                   int row_begin, int *__restrict__ tmp, int *__restrict__ cnt,
+                                                                   const int *__restrict__ Drow, const int *__restrict__ Dcol)
+{
+    constexpr bool DROP = false, INS = true;
+    const int *Frow = Drow, *Fcol = Dcol;
 #include "rank_rows_body.inc"
 }
 
@@ -322,8 +356,9 @@ static hipError_t launch_dense_impl(const int2 *ab, const int *Bcol, long long n
                                     const int *Frow, const int *Fcol, hipStream_t s)
 {
     constexpr bool MASKED = MODE == MaskMode::Keep;
-    // (the unmasked and the keep kernel are instances of k_dense_rows; the drop twin has its own name)
-    constexpr auto kernel = MODE == MaskMode::Drop ? k_dense_rows_excl<THREADS> : k_dense_rows<MASKED, THREADS>;
+    // (the unmasked and the keep kernel are instances of k_dense_rows; the drop and the accumulate twin have their own names)
+    constexpr auto kernel = MODE == MaskMode::Drop ? k_dense_rows_excl<THREADS>
+                          : MODE == MaskMode::Insert ? k_dense_rows_acc<THREADS> : k_dense_rows<MASKED, THREADS>;
     if (nrows <= 0) return hipSuccess;
     const long long cap_words = THREADS == kDenseThreadsBig ? kDenseMaxWords : kMidMaxWords;
     const long long max_words = MASKED ? cap_words / 2 : cap_words;   // two bitmaps share the window
@@ -392,6 +427,9 @@ static hipError_t launch_rank_rows(const int2 *ab, const int *Bcol, long long nn
     if (mode == MaskMode::Drop)                                    // the complemented-mask twin
         hipLaunchKernelGGL((spans ? k_rank_rows_excl<true> : k_rank_rows_excl<false>), dim3(nrows), dim3(kRankThreads), bytes, s,
                            ab, Bcol, nnzB32, cols, topw, rec, recpre, row_begin, tmp, cnt, Frow, Fcol);
+    else if (mode == MaskMode::Insert)                             // the accumulate twin
+        hipLaunchKernelGGL((spans ? k_rank_rows_acc<true> : k_rank_rows_acc<false>), dim3(nrows), dim3(kRankThreads), bytes, s,
+                           ab, Bcol, nnzB32, cols, topw, rec, recpre, row_begin, tmp, cnt, Frow, Fcol);
     else
         hipLaunchKernelGGL((spans ? k_rank_rows<true> : k_rank_rows<false>), dim3(nrows), dim3(kRankThreads), bytes, s,
                            ab, Bcol, nnzB32, cols, topw, rec, recpre, row_begin, tmp, cnt);
@@ -406,6 +444,9 @@ hipError_t launch_dense_rows(int bin, const int2 *ab, const int *Bcol, long long
         return launch_dense_impl<MaskMode::Keep, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
     if (bin == kRankBin) return launch_rank_rows(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s);
     const bool mid = bin == kMidBin;
+    if (mode == MaskMode::Insert)
+        return mid ? launch_dense_impl<MaskMode::Insert, kDenseThreadsMid>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s)
+                   : launch_dense_impl<MaskMode::Insert, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
     if (mode == MaskMode::Drop)
         return mid ? launch_dense_impl<MaskMode::Drop, kDenseThreadsMid>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s)
                    : launch_dense_impl<MaskMode::Drop, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);

@@ -1,6 +1,7 @@
-// dense_rows_body.inc -- the body of the windowed heavy-row kernels, included inside k_dense_rows and k_dense_rows_excl
-// (dense_rows.hip), which provide kDenseThreads, the arguments, MASKED (keep F's columns: two bitmaps) and MODE
-// (MaskMode::Drop: clear F's columns from each window).  A text body and not a __forceinline__ function, so that
+// dense_rows_body.inc -- the body of the windowed heavy-row kernels, included inside k_dense_rows, k_dense_rows_excl and
+// k_dense_rows_acc (dense_rows.hip), which provide kDenseThreads, the arguments, MASKED (keep F's columns: two bitmaps) and
+// MODE (MaskMode::Drop: clear F's columns from each window; MaskMode::Insert: set the columns of D's row -- passed as
+// Frow / Fcol -- that lie in [0, cols) in each window).  A text body and not a __forceinline__ function, so that
 // k_dense_rows compiles to the same code as before its twin existed (see wave_rows_body.inc).
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     u64 *bmP = reinterpret_cast<u64 *>(lds_raw);                       // products
@@ -38,6 +39,16 @@
             insert_quad(bm32, i0, i1, i2, i3,
                         c0 >> 5, c1 >> 5, c2 >> 5, c3 >> 5, 1u << (c0 & 31), 1u << (c1 & 31), 1u << (c2 & 31), 1u << (c3 & 31), nwin > 1);
         });
+        if constexpr (MODE == MaskMode::Insert) {
+            // set the window's columns of D's row (read coalesced, a workgroup's width at a time) -- in EVERY window: one that
+            // received no product is read out all the same, so D's columns there are not lost
+            const int d0 = Frow[i], d1 = Frow[i + 1];
+            for (int k = d0 + tid; k < d1; k += kDenseThreads) {
+                const u32 c = (u32)Fcol[k], cl = c - (u32)lo32;
+                if (c < (u32)cols && cl < (u32)W) atomicOr(&bm32[cl >> 5], 1u << (cl & 31));
+            }
+            __syncthreads();
+        }
         if constexpr (MODE == MaskMode::Drop) {
             // clear the window's columns of F's row (read coalesced, a workgroup's width at a time); a window that
             // received no product has nothing to clear and is not walked

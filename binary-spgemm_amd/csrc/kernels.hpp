@@ -19,8 +19,9 @@ namespace bsp {
 //                a 512-thread workgroup with a two-level rank bitmap -- LDS and read-out proportional to the row (dense_rows.hip)
 //   kMidBin    : dense-window rows, up to mid_cap_for_cols(cols) products: 512-thread workgroups, four per CU
 //   kDenseBin  : dense-window rows, above that: one 1024-thread workgroup per row
-// what a mask does to a product's rows: none, keep only its columns (C = F .* (A*B)), drop its columns (C = !F .* (A*B))
-enum class MaskMode { None, Keep, Drop };
+// what a second operand does to a product's rows: none, keep only its columns (C = F .* (A*B)), drop its columns
+// (C = !F .* (A*B)), insert its columns (C = D | (A*B), the OR-accumulating product)
+enum class MaskMode { None, Keep, Drop, Insert };
 
 constexpr int kWaveBins = 16;
 constexpr int kNumBins = kWaveBins + 4;
@@ -141,7 +142,8 @@ void launch_scan_counts(const int *cnt, int n, long long *prefix, long long *par
 // count_only: the symbolic twin of the same kernel -- nothing is emitted (tmp, recpre, row_ptr unused), cnt[i] = |C_i|
 // mode Drop: the complemented-mask twin (C = !F .* (A*B), upper-bound placement only): the columns of F's row (Frow / Fcol,
 // absolute row ids) are dropped from every row before it is stored.  Keep has no one-wave kernel here (launch_wave_masked),
-// and count_only needs None: both return hipErrorInvalidValue
+// and count_only needs None: both return hipErrorInvalidValue.  mode Insert: the accumulate twin (C = D | (A*B), upper-bound
+// placement only): the columns of D's row (passed as Frow / Fcol) within [0, cols) join the row's gather as one more source
 // err (device, never NULL): bit 0 is set when a row's gathered product count exceeds its class capacity -- impossible
 // for consistent operands (the classes come from the same extents), seen only when an operand was rewritten under
 // the library; the row is then truncated to its capacity instead of overrunning LDS
@@ -162,7 +164,8 @@ void launch_place_heavy(const int *tmp, const RowRec *rec, const long long *recp
 // numeric phase, one workgroup per heavy row (windowed dense LDS bitmap); mid: the 512-thread shape, rank: the rank bitmap.
 // F's row (Frow / Fcol, absolute row ids): Drop clears its bits from each column window (rank class: from each span's slots)
 // before it is read out, in every shape; Keep admits only its columns, and every row of any class, `bin` ignored, goes through
-// the 1024-thread window kernel
+// the 1024-thread window kernel; Insert sets the columns of D's row (passed as Frow / Fcol) within [0, cols) in each window
+// (rank class: in each span's top bits and slots)
 hipError_t launch_dense_rows(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols,
                              const RowRec *rec, const long long *recpre, int nrows, int row_begin,
                              int *tmp, int *cnt, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s);
@@ -185,6 +188,8 @@ hipError_t launch_class(int bin, const int2 *ab, const int *Bcol, long long nnzB
                         const int *Frow, const int *Fcol, hipStream_t s, bool count_only = false);
 // mlen[i] = |F's row i| when row i has products, else 0: what the masked product bins and offsets by
 void launch_mask_lengths(const long long *F, const int *Frow, int row_begin, int n, long long *mlen, hipStream_t s);
+// size[i] = F[i] + |D's row row_begin + i|: what the accumulating product (C = D | (A*B)) bins and offsets by
+void launch_insert_lengths(const long long *F, const int *Drow, int row_begin, int n, long long *size, hipStream_t s);
 
 // rows [row_lo,row_hi): tmp[Fprefix[r] .. +cnt[r])  ->  col_idx[row_ptr[r] ..).  The output range
 // is read from row_ptr on the device; `max_out` (an upper bound of its length, e.g. the rows'

@@ -301,16 +301,18 @@ static bspgemm_status multiply_exact(bspgemm_context *ctx, const bspgemm_matrix 
 }
 
 
-// C = A*B (mode None, Fm NULL), C = F .* (A*B) (Keep) or C = !F .* (A*B) (Drop), rows placed in an upper-bound workspace
-// and squeezed together by the compaction kernel once the counts are scanned.  Keep: the mask bounds a row (|C_i| <= |F_i|),
-// usually far below its product count, so rows are binned and placed by MASK length.  Drop: the mask bounds nothing
-// (|C_i| <= min(F_i, cols) still), so rows are binned, placed and ordered exactly as unmasked, and each class runs the drop
-// twin of its kernel.
+// C = A*B (mode None, Fm NULL), C = F .* (A*B) (Keep), C = !F .* (A*B) (Drop) or C = D | (A*B) (Insert, Fm = D), rows placed
+// in an upper-bound workspace and squeezed together by the compaction kernel once the counts are scanned.  Keep: the mask
+// bounds a row (|C_i| <= |F_i|), usually far below its product count, so rows are binned and placed by MASK length.  Drop:
+// the mask bounds nothing (|C_i| <= min(F_i, cols) still), so rows are binned, placed and ordered exactly as unmasked, and
+// each class runs the drop twin of its kernel.  Insert: D's row is gathered like one more B row, so rows are binned and
+// placed by F_i + |D_i| (|C_i| <= min(F_i + |D_i|, cols)) -- a row without products but with a row of D is a record too --
+// and each class runs the accumulate twin of its kernel.
 static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_matrix *A,
                                            const bspgemm_matrix *B, const bspgemm_matrix *Fm, MaskMode mode,
                                            int row_begin, int row_end, bspgemm_result **out)
 {
-    const bool keep = mode == MaskMode::Keep;
+    const bool keep = mode == MaskMode::Keep, insert = mode == MaskMode::Insert;
     bspgemm_result *C = nullptr;
     if (bspgemm_status st = start_flow(ctx, A, B, Fm, row_begin, row_end, BSPGEMM_FLOW_UPPER_BOUND, out, &C)) return st;
     auto bail = [&](bspgemm_status st) { return drop_result(C, st); };
@@ -321,15 +323,20 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
     HostScalars *h = ctx->h;
     h->products = 0;
     // rows are classified by their products and placed by min(products, B.cols) -- or, masked (Keep), both by
-    // the mask row's length (|C_i| <= |F_i|); the true product count is summed separately
+    // the mask row's length (|C_i| <= |F_i|), or, accumulating (Insert), by products + |D_i|; the true product count is
+    // summed separately
     const long long *size_by = ctx->F;
     if (keep) {
         launch_mask_lengths(ctx->F, Fm->d_row_ptr, row_begin, R, ctx->Fmask, s);
         size_by = ctx->Fmask;
+    } else if (insert) {
+        launch_insert_lengths(ctx->F, Fm->d_row_ptr, row_begin, R, ctx->Fmask, s);
+        size_by = ctx->Fmask;
     }
     launch_scan_and_bin(size_by, R, row_begin, A->d_row_ptr, ctx->Fprefix, ctx->partials, ctx->bin_tiles,
                         ctx->bin_count, ctx->rec, ctx->recpre, ctx->cnt, 0, ctx->hpartials, mid_cap_for_cols(B->cols),
-                        keep ? 0 : rank_cap_for_cols(B->cols), B->cols > 0 ? B->cols : 1, s, ctx->d_prep, keep ? ctx->F : nullptr);
+                        keep ? 0 : rank_cap_for_cols(B->cols), B->cols > 0 ? B->cols : 1, s, ctx->d_prep,
+                        keep || insert ? ctx->F : nullptr);
     HIPCHK_B(hipMemcpyAsync(&h->prep, ctx->d_prep, sizeof(PrepScalars), hipMemcpyDeviceToHost, s));
     HIPCHK_B(hipEventRecord(slot.ev[1], s));
     HIPCHK_B(hipStreamSynchronize(s));
@@ -338,7 +345,8 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
     h->a_lo = h->prep.a_lo;
     h->a_hi = h->prep.a_hi;
     memcpy(h->bin_count, h->prep.bin_count, sizeof h->bin_count);
-    const long long total = R > 0 ? h->totalF : 0;         // sum of min(products, cols) (Keep: of mask-row lengths): bounds nnz(C)
+    const long long total = R > 0 ? h->totalF : 0;         // sum of min(products, cols) (Keep: of mask-row lengths, Insert: of
+                                                           // products + |D_i|): bounds nnz(C)
     if (R == 0) memset(h->bin_count, 0, sizeof h->bin_count);
     if (bspgemm_status st = ensure_tmp(ctx, (size_t)total + 1)) return bail(st);
     if (bspgemm_status st = ensure_chunk_rows(ctx, compact_chunk_rows(total))) return bail(st);
@@ -490,6 +498,17 @@ extern "C" bspgemm_status bspgemm_multiply_masked_ex(bspgemm_context *ctx, const
     return multiply_upper_bound(ctx, A, B, F, MaskMode::Drop, row_begin, row_end, out);
 }
 
+extern "C" bspgemm_status bspgemm_multiply_accumulate(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
+                                                      const bspgemm_matrix *D, int row_begin, int row_end, bspgemm_result **out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !A || !B || !D || !out) return FAIL(BSPGEMM_ERR_INVALID, "NULL argument");
+    if (D->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "D belongs to another context");
+    if (D->rows < row_end) return FAIL(BSPGEMM_ERR_INVALID, "D has fewer rows than the row range needs");
+    if (D->cols > B->cols) return FAIL(BSPGEMM_ERR_INVALID, "D has more columns than B");
+    return multiply_upper_bound(ctx, A, B, D, MaskMode::Insert, row_begin, row_end, out);
+}
+
 // --------------------------------------------------------------- gathered lengths -> row_ptr -
 extern "C" bspgemm_status bspgemm_lengths_to_row_ptr(bspgemm_context *ctx, const int *d_lengths, int nranks, int width,
                                                      const int *bounds, int64_t *d_row_ptr, void *hip_stream)
@@ -582,6 +601,54 @@ extern "C" bspgemm_status bspgemm_closure(bspgemm_context *ctx, const bspgemm_ma
     if (st) { bspgemm_result_free(C); return st; }
     *T = C;
     return BSPGEMM_OK;
+}
+
+// Transitive closure A+ (paths of length >= 1): T0 = A, T(k+1) = T(k) | T(k)*T(k) through the accumulating product, until
+// nnz stops growing -- T(k) only grows, so equal nnz is equal sets.  The first step never ends it: T0 may hold repeats.
+static bspgemm_status closure_transitive(bspgemm_context *ctx, const bspgemm_matrix *A, int max_iter, bspgemm_result **T,
+                                         int *iterations)
+{
+    if (!ctx || !A || !T || A->ctx != ctx || A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "closure needs a square matrix");
+    *T = nullptr;
+    if (iterations) *iterations = 0;
+    if (max_iter < 1) max_iter = 1;
+    if (bspgemm_status st = use_device(ctx)) return st;
+    const int n = A->rows;
+    const bspgemm_matrix *cur = A;                      // T(k) as an operand (T0: A itself, not owned)
+    bspgemm_matrix *owned = nullptr;
+    long long prev_nnz = -1;
+    bspgemm_result *C = nullptr;
+    bspgemm_status st = BSPGEMM_OK;
+    for (int it = 0; it < max_iter; it++) {
+        bspgemm_result *next = nullptr;
+        st = bspgemm_multiply_accumulate(ctx, cur, cur, cur, 0, n, &next);
+        if (st) break;
+        if (iterations) *iterations = it + 1;
+        bspgemm_result_free(C);
+        C = next;
+        if (C->nnz == prev_nnz) break;                  // T | T*T == T: fixpoint
+        prev_nnz = C->nnz;
+        if (it + 1 == max_iter) break;
+        bspgemm_matrix *nm = nullptr;
+        st = bspgemm_matrix_from_result(ctx, C, n, &nm);
+        if (st) break;
+        bspgemm_matrix_free(owned);
+        owned = nm;
+        cur = nm;
+    }
+    bspgemm_matrix_free(owned);
+    if (st) { bspgemm_result_free(C); return st; }
+    *T = C;
+    return BSPGEMM_OK;
+}
+
+extern "C" bspgemm_status bspgemm_closure_ex(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags, int max_iter,
+                                             bspgemm_result **T, int *iterations)
+{
+    if (T) *T = nullptr;
+    if (flags & ~BSPGEMM_CLOSURE_TRANSITIVE) return FAIL(BSPGEMM_ERR_INVALID, "unknown closure flags");
+    if (flags & BSPGEMM_CLOSURE_TRANSITIVE) return closure_transitive(ctx, A, max_iter, T, iterations);
+    return bspgemm_closure(ctx, A, max_iter, T, iterations);
 }
 
 // ------------------------------------------------------------------ sharding helper ------

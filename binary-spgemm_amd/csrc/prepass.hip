@@ -372,6 +372,21 @@ void launch_row_products(const int *Arow, const int *Acol, const int *Brow, cons
                        row_begin, nrows, F);
 }
 
+// size of a row of the accumulating product C = D | (A*B): its products plus the length of D's row (absolute row id), so that
+// a row with no products but a row of D is a non-empty record of the class its inserts need
+__global__ __launch_bounds__(256) void k_insert_lengths(const long long *__restrict__ F, const int *__restrict__ Drow, int row_begin,
+                                                        int n, long long *__restrict__ size)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) size[i] = F[i] + (long long)(Drow[row_begin + i + 1] - Drow[row_begin + i]);
+}
+
+void launch_insert_lengths(const long long *F, const int *Drow, int row_begin, int n, long long *size, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_insert_lengths, dim3((n + 255) / 256), dim3(256), 0, s, F, Drow, row_begin, n, size);
+}
+
 // ---------------------------------------------------------------------------------------
 // Exclusive scan in three kernels: tile sums -> scan of the tile sums -> apply.
 constexpr int kScanThreads = 256;

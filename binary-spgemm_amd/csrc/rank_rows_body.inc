@@ -1,6 +1,7 @@
-// rank_rows_body.inc -- the body of the rank-class kernels, included inside k_rank_rows and k_rank_rows_excl (dense_rows.hip),
-// which provide kSpans (false: the column range is one span, the common case: one pass, its quads kept in registers), the
-// arguments and DROP (clear F's columns from each span's slots before the read-out).  A text body, so that k_rank_rows
+// rank_rows_body.inc -- the body of the rank-class kernels, included inside k_rank_rows, k_rank_rows_excl and k_rank_rows_acc
+// (dense_rows.hip), which provide kSpans (false: the column range is one span, the common case: one pass, its quads kept in
+// registers), the arguments, DROP (clear F's columns from each span's slots before the read-out) and INS (set the columns of
+// D's row -- passed as Frow / Fcol -- that lie in [0, cols) and in the span: its top bits after sweep 1, its slots after sweep 2).  A text body, so that k_rank_rows
 // compiles to the same code as before its twin existed (see wave_rows_body.inc).
     // (the class is bound by LDS instruction issue -- profiles/r04_rank_rows_phases.log -- so the layout is chosen for few LDS
     // instructions: a top word and its rank are one 8-byte pair, one read in sweep 2)
@@ -55,6 +56,16 @@
         };
         gather_sweep<kRankThreads, kRankQPT, kRankInFlight>(G, g, ab, Bcol, nnzB, a0, a1, sp == 0, top_bits);
         if (!kSpans) held = g.plan_kept && g.QB <= kRankInFlight * kRankThreads;   // (only ever used by sweep 2 of the single span)
+        if constexpr (INS) {
+            // D's row, read coalesced a workgroup's width at a time: its columns in the span are top bits like the products'
+            // (the class was sized by F_i + |D_i|: the slots still fit), whether or not a product reached the span
+            const int d0 = Frow[q.row], d1 = Frow[q.row + 1];
+            for (int k = d0 + tid; k < d1; k += kRankThreads) {
+                const u32 c = (u32)Fcol[k], cl = c - lo;
+                if (c < (u32)cols && cl < (u32)kRankSpan) atomicOr(&tp32[(cl >> 10) * 2u], 1u << ((cl >> 5) & 31));
+            }
+            __syncthreads();
+        }
         // ---- ranks of the top bits: thread t owns the words [t*WPT, (t+1)*WPT) -----------------------------------------
         int nslots = 0, spt = SPT;
         {
@@ -108,6 +119,18 @@
             __syncthreads();
         } else {
             gather_sweep<kRankThreads, kRankQPT, kRankInFlight>(G, g, ab, Bcol, nnzB, a0, a1, false, slot_bits);
+        }
+        if constexpr (INS) {                                       // D's columns into the slots their top bits rank
+            const int d0 = Frow[q.row], d1 = Frow[q.row + 1];
+            for (int k = d0 + tid; k < d1; k += kRankThreads) {
+                const u32 c = (u32)Fcol[k], cl = c - lo;
+                if (c < (u32)cols && cl < (u32)kRankSpan) {
+                    const uint2 x = tp[cl >> 10];
+                    const u32 r = x.y + __popc(__builtin_amdgcn_ubfe(x.x, 0u, (cl >> 5) & 31));
+                    if (r < (u32)kRankCap) atomicOr(&S[r], 1u << (cl & 31));   // (always, on consistent operands)
+                }
+            }
+            __syncthreads();
         }
         if constexpr (DROP) {
             if (nslots > 0) {                                      // (uniform: a span without products has nothing to clear)

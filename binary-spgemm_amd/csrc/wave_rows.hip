@@ -1,20 +1,20 @@
-// wave_rows.hip -- dispatcher of the one-wave-per-row kernels (bodies: wave_rows.inc, built once per (LEVELS, EXCL)
+// wave_rows.hip -- dispatcher of the one-wave-per-row kernels (bodies: wave_rows.inc, built once per (LEVELS, mode)
 // pair).  Picks the number of 5-bit levels from B's column count; launch_class picks the kernel family of a class.
 #include "kernels.hpp"
 
 namespace bsp {
 
-template <int LEVELS, bool EXCL>
-void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec,
+template <int LEVELS, MaskMode MODE>
+void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int cols, int topw, const RowRec *rec,
                         const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
                         unsigned *err, const int *Frow, const int *Fcol, hipStream_t s, bool count);
-#define BSP_WAVE_EXTERN(L) \
-    extern template void launch_wave_levels<L, false>(int, const int2 *, const int *, int, const RowRec *, const long long *, \
-        const long long *, int, int, int *, int *, unsigned *, const int *, const int *, hipStream_t, bool); \
-    extern template void launch_wave_levels<L, true>(int, const int2 *, const int *, int, const RowRec *, const long long *, \
-        const long long *, int, int, int *, int *, unsigned *, const int *, const int *, hipStream_t, bool);
+#define BSP_WAVE_EXTERN1(L, M) \
+    extern template void launch_wave_levels<L, MaskMode::M>(int, const int2 *, const int *, int, int, const RowRec *, \
+        const long long *, const long long *, int, int, int *, int *, unsigned *, const int *, const int *, hipStream_t, bool);
+#define BSP_WAVE_EXTERN(L) BSP_WAVE_EXTERN1(L, None) BSP_WAVE_EXTERN1(L, Drop) BSP_WAVE_EXTERN1(L, Insert)
 BSP_WAVE_EXTERN(1) BSP_WAVE_EXTERN(2) BSP_WAVE_EXTERN(3) BSP_WAVE_EXTERN(4) BSP_WAVE_EXTERN(5)
 #undef BSP_WAVE_EXTERN
+#undef BSP_WAVE_EXTERN1
 
 // words of the directly addressed top bitmap: ceil(cols / 32^levels) <= kWaveTopWords
 static int wave_top_words(int levels, int cols)
@@ -30,14 +30,14 @@ hipError_t launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol
 {
     if (mode == MaskMode::Keep || (count_only && mode != MaskMode::None)) return hipErrorInvalidValue;
     if (nrows <= 0) return hipSuccess;
-    static const decltype(&launch_wave_levels<1, false>) by_levels[2][5] = {
-        {launch_wave_levels<1, false>, launch_wave_levels<2, false>, launch_wave_levels<3, false>, launch_wave_levels<4, false>,
-         launch_wave_levels<5, false>},
-        {launch_wave_levels<1, true>, launch_wave_levels<2, true>, launch_wave_levels<3, true>, launch_wave_levels<4, true>,
-         launch_wave_levels<5, true>}};
-    by_levels[mode == MaskMode::Drop][(levels < 5 ? levels : 5) - 1](bin, ab, Bcol, wave_top_words(levels, cols), rec, recpre,
-                                                                     row_ptr, nrows, row_begin, tmp, cnt, err, Frow, Fcol, s,
-                                                                     count_only);
+#define BSP_WAVE_ROW(M) {launch_wave_levels<1, MaskMode::M>, launch_wave_levels<2, MaskMode::M>, launch_wave_levels<3, MaskMode::M>, \
+                         launch_wave_levels<4, MaskMode::M>, launch_wave_levels<5, MaskMode::M>}
+    static const decltype(&launch_wave_levels<1, MaskMode::None>) by_levels[3][5] = {BSP_WAVE_ROW(None), BSP_WAVE_ROW(Drop),
+                                                                                      BSP_WAVE_ROW(Insert)};
+#undef BSP_WAVE_ROW
+    const int m = mode == MaskMode::Drop ? 1 : (mode == MaskMode::Insert ? 2 : 0);
+    by_levels[m][(levels < 5 ? levels : 5) - 1](bin, ab, Bcol, cols, wave_top_words(levels, cols), rec, recpre, row_ptr, nrows,
+                                                row_begin, tmp, cnt, err, Frow, Fcol, s, count_only);
     return hipSuccess;
 }
 

@@ -1,5 +1,5 @@
 // wave_rows.inc -- the hot kernel: one wavefront per A-row, rank-bitmap accumulator in LDS.
-// Compiled once per (LEVELS, EXCL) pair by the Makefile (parallel builds); wave_rows.hip dispatches to those objects.
+// Compiled once per (LEVELS, mode) pair by the Makefile (parallel builds); wave_rows.hip dispatches to those objects.
 //
 // Replaces the body of SpGEMM_bigslice (final/SpGEMM_mpi_omp.c:24-52) for rows whose product
 // count F_i fits one wave's capacity (<= 2048):
@@ -200,8 +200,11 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                  int nrows, int rpw, int row_begin, int *__restrict__ tmp, int *__restrict__ cnt,
                  unsigned *__restrict__ err)
 {
-    constexpr bool EXCL = false;
+    constexpr bool EXCL = false, ACC = false;
     const int *Frow = nullptr, *Fcol = nullptr;
+    const int cols = 0;
+#define BSP_WAVE_GATHER(c, g) Bcol[g]
+#define BSP_WAVE_OK(x, c) x
 #include "wave_rows_body.inc"
 }
 
@@ -214,14 +217,36 @@ void k_wave_rows_excl(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                       int nrows, int rpw, int row_begin, int *__restrict__ tmp, int *__restrict__ cnt,
                       unsigned *__restrict__ err, const int *__restrict__ Frow, const int *__restrict__ Fcol)
 {
-    constexpr bool COUNT = false, EXCL = true;
+    constexpr bool COUNT = false, EXCL = true, ACC = false;
     const long long *row_ptr = nullptr;
+    const int cols = 0;
+#define BSP_WAVE_GATHER(c, g) Bcol[g]
+#define BSP_WAVE_OK(x, c) x
 #include "wave_rows_body.inc"
 }
 
-// EXCL: the complemented-mask twin (Frow / Fcol: F's CSR; numeric, upper-bound placement only)
-template <int LEVELS, int CHUNKS, int TWP, bool EXCL>
-static void launch_cfg(const int2 *ab, const int *Bcol, const RowRec *rec,
+// C = D | (A*B) for the rows of one class (Drow / Dcol: D's CSR, absolute row ids): the numeric kernel above with D's row
+// as one more source of the gather, after the B rows -- its columns below `cols` are accumulated like products, the others
+// lose their valid bit; placed at its upper-bound offset (recpre), |C_i| to cnt
+template <int LEVELS, int CHUNKS, int TWP>
+__global__ __launch_bounds__((64 * WaveCfg<LEVELS, CHUNKS, TWP>::WAVES))
+void k_wave_rows_acc(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
+                     const RowRec *__restrict__ rec, const long long *__restrict__ recpre,
+                     int nrows, int rpw, int row_begin, int *__restrict__ tmp, int *__restrict__ cnt,
+                     unsigned *__restrict__ err, const int *__restrict__ Drow, const int *__restrict__ Dcol, int cols)
+{
+    constexpr bool COUNT = false, EXCL = false, ACC = true;
+    const long long *row_ptr = nullptr;
+    const int *Frow = Drow, *Fcol = Dcol;
+#define BSP_WAVE_GATHER(c, g) (dsrc[c] ? Dcol : Bcol)[g]
+#define BSP_WAVE_OK(x, c) ((x) && !dsrc[c])
+#include "wave_rows_body.inc"
+}
+
+// MODE Drop: the complemented-mask twin, Insert: the accumulate twin (Frow / Fcol: F's or D's CSR; numeric, upper-bound
+// placement only)
+template <int LEVELS, int CHUNKS, int TWP, MaskMode MODE>
+static void launch_cfg(const int2 *ab, const int *Bcol, int cols, const RowRec *rec,
                        const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
                        unsigned *err, hipStream_t s, bool count, const int *Frow, const int *Fcol)
 {
@@ -234,9 +259,12 @@ static void launch_cfg(const int2 *ab, const int *Bcol, const RowRec *rec,
     if (rpw < 1) rpw = 1;
     const long long rows_per_wg = (long long)Cfg::WAVES * rpw;
     const int grid = (int)((nrows + rows_per_wg - 1) / rows_per_wg);
-    if constexpr (EXCL)
+    if constexpr (MODE == MaskMode::Drop)
         hipLaunchKernelGGL((k_wave_rows_excl<LEVELS, CHUNKS, TWP>), dim3(grid), dim3(64 * Cfg::WAVES), 0, s,
                            ab, Bcol, rec, recpre, nrows, rpw, row_begin, tmp, cnt, err, Frow, Fcol);
+    else if constexpr (MODE == MaskMode::Insert)
+        hipLaunchKernelGGL((k_wave_rows_acc<LEVELS, CHUNKS, TWP>), dim3(grid), dim3(64 * Cfg::WAVES), 0, s,
+                           ab, Bcol, rec, recpre, nrows, rpw, row_begin, tmp, cnt, err, Frow, Fcol, cols);
     else if (count)
         hipLaunchKernelGGL((k_wave_rows<LEVELS, CHUNKS, TWP, true>), dim3(grid), dim3(64 * Cfg::WAVES), 0, s,
                            ab, Bcol, rec, recpre, row_ptr, nrows, rpw, row_begin, tmp, cnt, err);
@@ -245,26 +273,27 @@ static void launch_cfg(const int2 *ab, const int *Bcol, const RowRec *rec,
                            ab, Bcol, rec, recpre, row_ptr, nrows, rpw, row_begin, tmp, cnt, err);
 }
 
-template <int LEVELS, int CHUNKS, bool EXCL>
-static void launch_one(const int2 *ab, const int *Bcol, int topw, const RowRec *rec,
+template <int LEVELS, int CHUNKS, MaskMode MODE>
+static void launch_one(const int2 *ab, const int *Bcol, int cols, int topw, const RowRec *rec,
                        const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
                        unsigned *err, hipStream_t s, bool count, const int *Frow, const int *Fcol)
 {
     // the top bitmap is sized to what the column count needs: 128 or 256 words; 512 at three
     // levels (wave_levels_for_cols)
-    if (topw <= 128) launch_cfg<LEVELS, CHUNKS, 2, EXCL>(ab, Bcol, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
-    else if (topw <= 256) launch_cfg<LEVELS, CHUNKS, 4, EXCL>(ab, Bcol, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
-    else if constexpr (LEVELS == 3) launch_cfg<LEVELS, CHUNKS, 8, EXCL>(ab, Bcol, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
+    if (topw <= 128) launch_cfg<LEVELS, CHUNKS, 2, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
+    else if (topw <= 256) launch_cfg<LEVELS, CHUNKS, 4, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
+    else if constexpr (LEVELS == 3) launch_cfg<LEVELS, CHUNKS, 8, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
 }
 
-// one class of rows (EXCL: the complemented-mask twin, Frow / Fcol: F's CSR); wave_rows.hip picks LEVELS
-template <int LEVELS, bool EXCL>
-void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int topw, const RowRec *rec,
+// one class of rows (MODE None, Drop: the complemented-mask twin, Insert: the accumulate twin; Frow / Fcol: F's or D's CSR);
+// wave_rows.hip picks LEVELS
+template <int LEVELS, MaskMode MODE>
+void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int cols, int topw, const RowRec *rec,
                         const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
                         unsigned *err, const int *Frow, const int *Fcol, hipStream_t s, bool count)
 {
     switch (bin) {
-#define BSP_CASE(b) case b: launch_one<LEVELS, kWaveChunks[b], EXCL>(ab, Bcol, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol); break;
+#define BSP_CASE(b) case b: launch_one<LEVELS, kWaveChunks[b], MODE>(ab, Bcol, cols, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol); break;
     BSP_CASE(1) BSP_CASE(2) BSP_CASE(3) BSP_CASE(4) BSP_CASE(5) BSP_CASE(6) BSP_CASE(7) BSP_CASE(8)
     BSP_CASE(9) BSP_CASE(10) BSP_CASE(11) BSP_CASE(12) BSP_CASE(13) BSP_CASE(14) BSP_CASE(15) BSP_CASE(16)
 #undef BSP_CASE
@@ -273,11 +302,12 @@ void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int topw, cons
     }
 }
 
-// the Makefile builds one object per (LEVELS, EXCL) pair, -DBSP_WAVE_LEVELS=1..5 -DBSP_WAVE_EXCL=0|1, so that they compile in parallel
+// the Makefile builds one object per (LEVELS, mode) pair, -DBSP_WAVE_LEVELS=1..5 -DBSP_WAVE_MODE=None|Drop|Insert, so that
+// they compile in parallel
 #ifdef BSP_WAVE_LEVELS
-template void launch_wave_levels<BSP_WAVE_LEVELS, BSP_WAVE_EXCL>(int, const int2 *, const int *, int, const RowRec *, const long long *,
-                                                                 const long long *, int, int, int *, int *, unsigned *, const int *,
-                                                                 const int *, hipStream_t, bool);
+template void launch_wave_levels<BSP_WAVE_LEVELS, MaskMode::BSP_WAVE_MODE>(int, const int2 *, const int *, int, int, const RowRec *,
+                                                                           const long long *, const long long *, int, int, int *, int *,
+                                                                           unsigned *, const int *, const int *, hipStream_t, bool);
 #endif
 
 }  // namespace bsp

@@ -1,9 +1,14 @@
-// wave_rows_body.inc -- the body of the one-wave kernels, included inside k_wave_rows and k_wave_rows_excl (wave_rows.inc).
-// The including kernel provides the template parameters LEVELS, CHUNKS, TWP, the arguments ab, Bcol, rec, recpre, row_ptr,
-// nrows, rpw, row_begin, tmp, cnt, err, Frow, Fcol, and the constants COUNT (symbolic twin) and EXCL (complemented-mask
-// twin: F's columns are dropped from each staged row before it is stored, drop_mask_cols).  A text body and not a
+// wave_rows_body.inc -- the body of the one-wave kernels, included inside k_wave_rows, k_wave_rows_excl and k_wave_rows_acc
+// (wave_rows.inc).  The including kernel provides the template parameters LEVELS, CHUNKS, TWP, the arguments ab, Bcol, rec,
+// recpre, row_ptr, nrows, rpw, row_begin, tmp, cnt, err, Frow, Fcol, cols, and the constants COUNT (symbolic twin), EXCL
+// (complemented-mask twin: F's columns are dropped from each staged row before it is stored, drop_mask_cols) and ACC
+// (accumulate twin: the row of D -- passed as Frow / Fcol -- is one more source of the gather, read from Fcol; its columns
+// outside [0, cols) lose their valid bit).  A text body and not a
 // __forceinline__ function: with a function the compiler schedules the existing instances differently (1-2 more VGPRs on
 // half of them); included, k_wave_rows compiles to the same code as before the twin existed.
+// The gather's load and the sweeps' product test are macros the including kernel defines (BSP_WAVE_GATHER(c, g),
+// BSP_WAVE_OK(x, c)), so that k_wave_rows and k_wave_rows_excl see the very same tokens as before the accumulate twin
+// (written as `(x) && (!ACC || ...)`, the test changed their schedule); they are undefined at the end.
     using Cfg = WaveCfg<LEVELS, CHUNKS, TWP>;
     constexpr int TOPW = Cfg::TOPW, WAVES = Cfg::WAVES, SW = Cfg::SW, SLOTS = Cfg::SLOTS, FULL = Cfg::FULL;
     // separate objects: no false LDS dependencies between the arrays of one sweep
@@ -76,8 +81,8 @@
         const u32 pre_lo = (u32)wave_bcast((int)(u32)r_pre, kk);
         const u32 pre_hi = (u32)wave_bcast((int)(u32)((unsigned long long)r_pre >> 32), kk);
         int *out = tmp + (long long)(((u64)pre_hi << 32) | pre_lo);
-        int f0 = 0, mlen = 0;                                      // EXCL: F's row (absolute row id)
-        if constexpr (EXCL) {
+        int f0 = 0, mlen = 0;                                      // EXCL: F's row, ACC: D's row (absolute row id)
+        if constexpr (EXCL || ACC) {
             const int i = wave_bcast(r_row, kk);
             f0 = Frow[i];
             mlen = Frow[i + 1] - f0;
@@ -105,6 +110,18 @@
             F += wave_bcast(inc, 63);
             nsrc += __popcll(bal);
         }
+        // ACC: D's row is the last source, products F_B .. F_B + |D_i| (class and capacity were sized by F_B + |D_i|)
+        const int nsrcB = nsrc;
+        if constexpr (ACC) {
+            if (mlen > 0) {
+                if ((unsigned)F < (unsigned)Cfg::CAP && lane == 0) {
+                    delta[nsrc] = f0 - F;                          // D address = delta + product index
+                    atomicOr(&starts[F >> 6], 1ull << (F & 63));
+                }
+                F += mlen;
+                nsrc += 1;
+            }
+        }
         if (F > Cfg::CAP || F < 0) {                               // wave-uniform, never taken on consistent operands
             if (lane == 0) atomicOr(err, kErrCapacity);
             F = F < 0 ? 0 : Cfg::CAP;
@@ -123,6 +140,8 @@
         int col[CHUNKS];
         int rank[CHUNKS];
         int gaddr[CHUNKS];
+        bool dsrc[CHUNKS];                                         // ACC: the product is one of D's row (tail lanes: source 0's kind)
+                                                                   // until sweep 1, then: one of D's row outside [0, cols)
 #pragma unroll
         for (int c = 0; c < CHUNKS; c++) {
             {
@@ -131,6 +150,7 @@
                 const int before = wave_bcast(sbefore, c);
                 int s = before + __popcll(M & mask_le(plane)) - 1;
                 s = (c < FULL || p < F) ? s : 0;
+                if constexpr (ACC) dsrc[c] = s == nsrcB;
                 // unconditional LDS read (tail lanes read source 0 and load its first column): a
                 // select on the loaded value makes the compiler wait after every single read
                 gaddr[c] = delta[s];                               // consumed in the next loop: the
@@ -141,7 +161,7 @@
             {
                 const int p = c * 64 + plane;
                 const int g = gaddr[c] + ((c < FULL || p < F) ? p : 0);
-                col[c] = Bcol[g];
+                col[c] = BSP_WAVE_GATHER(c, g);
             }
         }
         // prefetch the next row's extents: in flight while this row is accumulated
@@ -209,7 +229,8 @@
 #pragma unroll
         for (int c = 0; c < CHUNKS; c++) {
             {
-                const bool ok = c < FULL || c * 64 + plane < F;
+                if constexpr (ACC) dsrc[c] = dsrc[c] && (u32)col[c] >= (u32)cols;   // from here on: a column of D that is dropped
+                const bool ok = BSP_WAVE_OK(c < FULL || c * 64 + plane < F, c);
                 const u32 cc = ok ? (u32)col[c] : 0u;
                 col[c] = (int)cc;                                  // tail lanes: column 0, never OR-ed
                 const u32 tw = cc >> (5 * LEVELS);
@@ -253,7 +274,7 @@
 #pragma unroll
                 for (int c = 0; c < CHUNKS; c++)                   // ... then all the ORs
                     {
-                        const bool ok = c < FULL || c * 64 + plane < F;
+                        const bool ok = BSP_WAVE_OK(c < FULL || c * 64 + plane < F, c);
                         const u32 cc = (u32)col[c];
                         const u32 b = (cc >> (5 * (lev + 1))) & 31;
                         const int r2 = ppre[c] + __popc(__builtin_amdgcn_ubfe(px[c], 0u, b));   // bits below b
@@ -343,4 +364,5 @@
         wave_lds_fence();
     }
     if (cnt && lane < nmine) cnt[r_row - row_begin] = my_cnt;
-
+#undef BSP_WAVE_GATHER
+#undef BSP_WAVE_OK

@@ -224,6 +224,22 @@ bspgemm_status bspgemm_multiply_masked_ex(bspgemm_context *ctx,
                                           const bspgemm_matrix *F, unsigned flags,
                                           int row_begin, int row_end, bspgemm_result **C);
 
+/* C = D | (A*B), the OR-accumulating product of old/BSpGEMM.c:75-126 (SpGEMM_dor; GraphBLAS accum = LOR): a product
+ * added to a matrix already held, the step that closures, visited-set BFS and k-hop reachability repeat.  For rows
+ * [row_begin, row_end): C_i = { c : (i, c) in pattern(D) and 0 <= c < B.cols } | (A*B)_i, ascending and free of duplicates.
+ *   - D is indexed by ABSOLUTE row, like a mask; C.row_ptr is slice-local, as in every multiply.  D's rows may be unsorted
+ *     and hold repeats; its entries outside [0, B.cols) are dropped.  Rows with no products still output D's row.
+ *   - An empty D gives bspgemm_multiply's result, and so does D = pattern(A*B).  The result equals the plain product of
+ *     the stacked operands [A | I] * [B ; D].
+ *   - BSPGEMM_ERR_INVALID with *C = NULL: a NULL argument, D from another context, D.rows < row_end, D.cols > B.cols, and
+ *     the operand and row-range errors of bspgemm_multiply.
+ *   - Flow: always upper-bound placement + compaction (no small path, no EXACT flow, whatever the context asks for).
+ *     Rows are binned and placed by products + |D_i|; every class runs the accumulate twin of its kernel, D's row
+ *     gathered like one more B row.  bspgemm_stats: flow = BSPGEMM_FLOW_UPPER_BOUND, small_path = 0, products = F (D's
+ *     entries not included), rows_per_bin / bin_cap the classes of products + |D_i|, nnz_c = nnz(C).               */
+bspgemm_status bspgemm_multiply_accumulate(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
+                                           const bspgemm_matrix *D, int row_begin, int row_end, bspgemm_result **C);
+
 int            bspgemm_result_rows(const bspgemm_result *C);
 int64_t        bspgemm_result_nnz(const bspgemm_result *C);
 const int64_t *bspgemm_result_row_ptr_device(const bspgemm_result *C);   /* rows+1 entries  */
@@ -245,6 +261,14 @@ bspgemm_status bspgemm_matrix_from_result(bspgemm_context *ctx, const bspgemm_re
  * computed.  The result is T as a product object.                                              */
 bspgemm_status bspgemm_closure(bspgemm_context *ctx, const bspgemm_matrix *A, int max_iter,
                                bspgemm_result **T, int *iterations);
+
+/* The closure with flags: 0 is bspgemm_closure itself.  BSPGEMM_CLOSURE_TRANSITIVE computes A+ (paths of length >= 1)
+ * instead of A*: T0 = A without the diagonal, T(k+1) = T(k) | T(k)*T(k) by bspgemm_multiply_accumulate (the step of
+ * old/BSpGEMM.c:75-126), everything device-resident, until nnz stops growing (the first step never stops it: T0 may
+ * hold repeats).  Node i then reaches itself only if it lies on a cycle.  Any other bit is BSPGEMM_ERR_INVALID.     */
+#define BSPGEMM_CLOSURE_TRANSITIVE 1u   /* A+ (paths of length >= 1) instead of A* */
+bspgemm_status bspgemm_closure_ex(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags, int max_iter,
+                                  bspgemm_result **T, int *iterations);
 
 /* Per-row work F_i = sum_{j in A_i} |B_j| ("products", the flag probes of :36-38) as an
  * exclusive prefix over rows [0,A.rows]: prefix[rows] = F.  Used to cut GPU shards at equal
