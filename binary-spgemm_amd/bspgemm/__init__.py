@@ -54,6 +54,7 @@ EXPORTS = [
     "bspgemm_set_flow", "bspgemm_set_class_timing", "bspgemm_build_info", "bspgemm_matrix_invalidate", "bspgemm_comm_agree", "bspgemm_comm_inject_failure",
     "bspgemm_set_option", "bspgemm_get_option", "bspgemm_matrix_uses_blocked_table", "bspgemm_matrix_uses_padded_rows",
     "bspgemm_matrix_transpose", "bspgemm_matrix_download", "bspgemm_multiply_accumulate", "bspgemm_closure_ex",
+    "bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values",
 ]
 
 
@@ -181,6 +182,10 @@ def lib():
     L.bspgemm_result_col_idx_device.argtypes = [VP]
     L.bspgemm_result_col_idx_device.restype = VP
     L.bspgemm_result_download.argtypes = [VP, VP, VP, VP]
+    L.bspgemm_multiply_masked_count.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, PVP]
+    L.bspgemm_result_values_device.argtypes = [VP]
+    L.bspgemm_result_values_device.restype = VP
+    L.bspgemm_result_download_values.argtypes = [VP, VP, VP]
     L.bspgemm_result_free.argtypes = [VP]
     L.bspgemm_result_free.restype = None
     L.bspgemm_matrix_from_result.argtypes = [VP, VP, C.c_int, PVP]
@@ -398,6 +403,15 @@ class Context:
              "bspgemm_multiply_accumulate")
         return Result(self, r)
 
+    def multiply_masked_count(self, A, B, F, row_begin=0, row_end=None):
+        """C = F .* (A*B) with path counts (bspgemm_multiply_masked_count): the masked product's pattern, and for every
+        entry the number of products that land on it (Result.download_values).  F is indexed by absolute row."""
+        row_end = A.rows if row_end is None else row_end
+        r = C.c_void_p()
+        _chk(lib().bspgemm_multiply_masked_count(self._h, A._h, B._h, F._h, row_begin, row_end, C.byref(r)),
+             "bspgemm_multiply_masked_count")
+        return Result(self, r)
+
     def matrix_from_result(self, result, cols):
         m = C.c_void_p()
         _chk(lib().bspgemm_matrix_from_result(self._h, result._h, cols, C.byref(m)), "matrix_from_result")
@@ -499,6 +513,17 @@ class Result:
     @property
     def col_idx_device(self):
         return lib().bspgemm_result_col_idx_device(self._h)
+
+    @property
+    def values_device(self):
+        """device pointer of the counts of a counted result (Context.multiply_masked_count); None for a pattern-only one"""
+        return lib().bspgemm_result_values_device(self._h)
+
+    def download_values(self):
+        """the counts of a counted result, aligned with download()'s col_idx, as np.int32"""
+        v = np.zeros(self.nnz, dtype=np.int32)
+        _chk(lib().bspgemm_result_download_values(self.ctx._h, self._h, C.c_void_p(v.ctypes.data)), "result_download_values")
+        return v
 
     def download(self, col_idx=True):
         rp = np.zeros(self.rows + 1, dtype=np.int64)

@@ -190,7 +190,7 @@ extern "C" void bspgemm_destroy(bspgemm_context *ctx)
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     hipFree(ctx->F); hipFree(ctx->Fprefix); hipFree(ctx->partials);
-    hipFree(ctx->cnt); hipFree(ctx->bin_tiles); hipFree(ctx->bin_count); hipFree(ctx->tmp);
+    hipFree(ctx->cnt); hipFree(ctx->bin_tiles); hipFree(ctx->bin_count); hipFree(ctx->tmp); hipFree(ctx->tmpv);
     hipFree(ctx->rec); hipFree(ctx->recpre); hipFree(ctx->ab); hipFree(ctx->Fmask); hipFree(ctx->hpartials);
     hipFree(ctx->hub_rec); hipFree(ctx->hub_pre);
     if (ctx->h) hipHostFree(ctx->h);
@@ -397,6 +397,26 @@ bspgemm_status ensure_tmp(bspgemm_context *ctx, size_t ints)
     return BSPGEMM_OK;
 }
 
+// the counting product's values workspace: grows like tmp
+bspgemm_status ensure_tmpv(bspgemm_context *ctx, size_t ints)
+{
+    if (ints <= ctx->tmpv_cap) return BSPGEMM_OK;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->tmpv);
+    ctx->tmpv = nullptr;
+    ctx->tmpv_cap = 0;
+    const size_t cap = ints + ints / 16 + 1024;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->tmpv), cap * sizeof(int));
+    if (e == hipErrorOutOfMemory) {                     // the cache of freed results may hold what is missing
+        for (auto &c : ctx->cache) if (c.p) { hipFree(c.p); c.p = nullptr; }
+        (void)hipGetLastError();
+        e = hipMalloc(reinterpret_cast<void **>(&ctx->tmpv), cap * sizeof(int));
+    }
+    HIPCHK(e);
+    ctx->tmpv_cap = cap;
+    return BSPGEMM_OK;
+}
+
 bspgemm_status ensure_chunk_rows(bspgemm_context *ctx, size_t entries)
 {
     if (entries <= ctx->chunk_cap) return BSPGEMM_OK;
@@ -595,6 +615,7 @@ extern "C" const int64_t *bspgemm_result_row_ptr_device(const bspgemm_result *C)
     return C ? reinterpret_cast<const int64_t *>(C->d_row_ptr) : nullptr;
 }
 extern "C" const int *bspgemm_result_col_idx_device(const bspgemm_result *C) { return C ? C->d_col_idx : nullptr; }
+extern "C" const int *bspgemm_result_values_device(const bspgemm_result *C) { return C ? C->d_values : nullptr; }
 
 extern "C" bspgemm_status bspgemm_result_download(bspgemm_context *ctx, const bspgemm_result *C,
                                                   int64_t *row_ptr, int *col_idx)
@@ -612,12 +633,24 @@ extern "C" bspgemm_status bspgemm_result_download(bspgemm_context *ctx, const bs
     return BSPGEMM_OK;
 }
 
+extern "C" bspgemm_status bspgemm_result_download_values(bspgemm_context *ctx, const bspgemm_result *C, int *values)
+{
+    if (!ctx || !C || !values || C->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "result_download_values");
+    if (!C->d_values) return FAIL(BSPGEMM_ERR_INVALID, "result_download_values: the result holds a pattern only");
+    if (bspgemm_status st = use_device(ctx)) return st;
+    if (C->nnz > 0)
+        HIPCHK(hipMemcpyAsync(values, C->d_values, (size_t)C->nnz * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return BSPGEMM_OK;
+}
+
 extern "C" void bspgemm_result_free(bspgemm_result *C)
 {
     if (!C) return;
     hipSetDevice(C->ctx->device);
     result_release(C->ctx, C->d_row_ptr, result_bytes_rowptr(C->rows));
     result_release(C->ctx, C->d_col_idx, result_bytes_colidx(C->col_cap));
+    result_release(C->ctx, C->d_values, result_bytes_colidx(C->col_cap));   // (NULL: pattern only)
     delete C;
 }
 

@@ -291,6 +291,199 @@ __global__ __launch_bounds__(kDenseThreads, (kDenseThreads == kDenseThreadsBig ?
 }
 
 // ---------------------------------------------------------------------------------------
+// COUNTING (MaskMode::Count): C = F .* (A*B) with the number of products of every entry (PLUS_PAIR under the mask) for the
+// rows the one-wave kernel does not take.  A window of P/K bitmaps cannot hold counts: a u32 per window column would shrink the
+// window sixteen-fold.  Instead a window holds
+//   K     the bitmap of F's columns in the window (set from F's row, coalesced),
+//   pre   the exclusive popcount prefix of K's 32-bit words: a mask column's RANK in the window,
+//   cnt   one u32 counter per DISTINCT mask column of the window, indexed by rank,
+// and the gather adds one to the counter of every product whose K bit is set.  The read-out walks K in column order and
+// emits the columns with a non-zero count, plus their counts.  A window never holds more distinct mask columns than there
+// are counters (kCountSlots): it starts kCountMaxCols wide (2^18 columns), and when F's row puts more distinct columns into
+// it, it is narrowed (at least halved, to about kCountSlots / density of the columns seen, a multiple of 32 columns) and K is
+// set again -- a window of kCountSlots columns or fewer always fits.  The next window keeps the width while the density holds
+// (more than kCountSlots / 2 distinct columns), else it starts twice as wide, up to kCountMaxCols.  Every window but the last
+// (clamped to the last column) is a multiple of 32 columns wide, so windows start on whole K words.  Windows without a mask
+// column are skipped without a product sweep.  LDS: K 32 KiB + pre 16 KiB + counters 80 KiB = the
+// 128 KiB that the window kernels set.
+constexpr int kCountMaxCols = 1 << 18;                 // columns of the widest window
+constexpr int kCountWords = kCountMaxCols / 32;        // 32-bit words of K (and entries of pre)
+constexpr int kCountSlots = 20480;                     // counters: 128 KiB - K - pre
+static_assert(kCountWords * 4 + kCountWords * 2 + kCountSlots * 4 <= kDenseMaxWords * 8, "the window kernels' 128 KiB");
+static_assert(kCountSlots < 65536, "ranks fit pre's 16 bits");
+
+template <int kDenseThreads>
+__global__ __launch_bounds__(kDenseThreads, kBigMinWaves) void k_dense_rows_count(const int2 *__restrict__ ab,
+                                                              const int *__restrict__ Bcol, int nnzB, int cols,
+                                                              const RowRec *__restrict__ rec,
+                                                              const long long *__restrict__ recpre,
+                                                              int row_begin,
+                                                              int *__restrict__ tmp,
+                                                              int *__restrict__ cnt,
+                                                              const int *__restrict__ Frow,
+                                                              const int *__restrict__ Fcol,
+                                                              int *__restrict__ vals)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    u32 *K = reinterpret_cast<u32 *>(lds_raw);
+    unsigned short *pre = reinterpret_cast<unsigned short *>(K + kCountWords);
+    u32 *ctr = reinterpret_cast<u32 *>(pre + kCountWords);
+    constexpr int kWaves = kDenseThreads / 64;
+    constexpr int kQPT = kDenseQuadsPerThreadBig, kInFlight = kDenseInFlightBig;
+    constexpr int kWPT = kCountWords / kDenseThreads;      // words of K per thread, blocked (at the widest window)
+    static_assert(kCountWords % kDenseThreads == 0, "whole words per thread");
+    __shared__ GatherLds<kDenseThreads, kQPT> G;
+    __shared__ int wtot[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int t = tid; t < kCountWords; t += kDenseThreads) K[t] = 0u;
+    gather_init(G);
+    __syncthreads();
+
+    const RowRec q = rec[blockIdx.x];
+    const int i = q.row;
+    const int a0 = q.a0, a1 = q.a0 + q.alen;
+    int *out = tmp + recpre[blockIdx.x];
+    int *vout = vals + recpre[blockIdx.x];
+    const int f0 = Frow[i], f1 = Frow[i + 1];
+    // the sum over the workgroup of every thread's x, and each thread's exclusive prefix (all threads, uniform flow)
+    auto block_scan = [&](int x, int &excl) {
+        const int inc = wave_incl_scan(x);
+        if (lane == 63) wtot[wave] = inc;
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int k = 0; k < kWaves; k++) {
+            const int t = wtot[k];
+            if (k < wave) off += t;
+            tot += t;
+        }
+        excl = off + inc - x;
+        __syncthreads();                                           // (wtot is reused by the next scan)
+        return tot;
+    };
+
+    int total = 0;
+    bool swept = false;
+    GatherState g;
+    long long W = kCountMaxCols;
+    for (long long lo = 0; lo < cols;) {
+        if (W > (long long)cols - lo) W = (long long)cols - lo;   // (the last window ends at the last column)
+        const u32 Wu = (u32)W;
+        const u32 lo32 = (u32)lo;
+        // ---- K: F's columns in [lo, lo + W) ----
+        bool any = false;
+        for (int k = f0 + tid; k < f1; k += kDenseThreads) {
+            const u32 c = (u32)Fcol[k] - lo32;
+            if ((u32)Fcol[k] < (u32)cols && c < Wu) {
+                atomicOr(&K[c >> 5], 1u << (c & 31));
+                any = true;
+            }
+        }
+        if (!__syncthreads_or(any)) {                              // no mask column: nothing to count, K is still zero
+            lo += W;
+            W = W * 2 < kCountMaxCols ? W * 2 : kCountMaxCols;
+            continue;
+        }
+        // ---- pre: ranks of the window's distinct mask columns ----
+        u32 kw[kWPT];
+        int run = 0;
+#pragma unroll
+        for (int k = 0; k < kWPT; k++) {
+            kw[k] = K[tid * kWPT + k];                             // (zero beyond the window)
+            run += __popc(kw[k]);
+        }
+        int excl = 0;
+        const int ndist = block_scan(run, excl);
+        if (ndist > kCountSlots) {
+            // too dense for the counters: clear K and narrow the window to about kCountSlots columns' worth of mask
+            // entries at this density (at least halved; a window of kCountSlots columns or fewer always fits)
+#pragma unroll
+            for (int k = 0; k < kWPT; k++) K[tid * kWPT + k] = 0u;
+            long long Wn = W >> 1;
+            while (Wn > kCountSlots && Wn * ndist > (long long)kCountSlots * W) Wn >>= 1;
+            W = Wn & ~31ll;                                        // (> kCountSlots / 2: never zero)
+            __syncthreads();
+            continue;
+        }
+        {
+            int p = excl;
+#pragma unroll
+            for (int k = 0; k < kWPT; k++) {
+                pre[tid * kWPT + k] = (unsigned short)p;
+                p += __popc(kw[k]);
+            }
+        }
+        for (int t = tid; t < ndist; t += kDenseThreads) ctr[t] = 0u;
+        __syncthreads();
+        // ---- the product sweep: a product on a mask column adds one to the column's counter ----
+        gather_sweep<kDenseThreads, kQPT, kInFlight>(G, g, ab, Bcol, nnzB, a0, a1, !swept, [&](const Int4U &v, u32 vm, int) {
+            const u32 c0 = (u32)v.x - lo32, c1 = (u32)v.y - lo32, c2 = (u32)v.z - lo32, c3 = (u32)v.w - lo32;
+            const bool i0 = (vm & 1u) && c0 < Wu, i1 = (vm & 2u) && c1 < Wu;   // (columns below the window wrap to huge values)
+            const bool i2 = (vm & 4u) && c2 < Wu, i3 = (vm & 8u) && c3 < Wu;
+            if (!__ballot(i0 | i1 | i2 | i3)) return;              // (wave-uniform) nothing of these 64 quads falls into the window
+            auto one = [&](bool in, u32 c) {
+                if (!in) return;
+                const u32 x = K[c >> 5], b = c & 31;
+                if ((x >> b) & 1u) atomicAdd(&ctr[pre[c >> 5] + __popc(x & ((1u << b) - 1u))], 1u);
+            };
+            one(i0, c0);
+            one(i1, c1);
+            one(i2, c2);
+            one(i3, c3);
+        });
+        swept = true;
+        __syncthreads();
+        // ---- read-out in column order: the mask columns with a non-zero count, and their counts ----
+        int mine = 0;
+        for (int t = 0; t < run; t++) mine += ctr[excl + t] != 0u ? 1 : 0;
+        int oexcl = 0;
+        const int wtotal = block_scan(mine, oexcl);
+        {
+            int p = total + oexcl, c = excl;
+#pragma unroll
+            for (int k = 0; k < kWPT; k++) {
+                u32 mk = kw[k];
+                const int base = (int)lo + 32 * (tid * kWPT + k);
+                while (mk) {
+                    const u32 v = ctr[c++];
+                    if (v) {
+                        out[p] = base + (int)__builtin_ctz(mk);
+                        vout[p] = (int)v;
+                        p++;
+                    }
+                    mk &= mk - 1u;
+                }
+                K[tid * kWPT + k] = 0u;                            // the window is all zero again
+            }
+        }
+        total += wtotal;
+        __syncthreads();
+        lo += W;
+        if (ndist <= kCountSlots / 2) W = W * 2 < kCountMaxCols ? W * 2 : kCountMaxCols;   // (else: as dense, as wide)
+    }
+    if (tid == 0) cnt[i - row_begin] = total;
+}
+
+static hipError_t launch_dense_count(const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
+                                     const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt,
+                                     const int *Frow, const int *Fcol, int *vals, hipStream_t s)
+{
+    constexpr auto kernel = k_dense_rows_count<kDenseThreadsBig>;
+    if (nrows <= 0) return hipSuccess;
+    constexpr int bytes = kCountWords * 4 + kCountWords * 2 + kCountSlots * 4;
+    static std::atomic<bool> attr_set[64] = {};          // (per (kernel, device) pair, as in launch_dense_impl)
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3(nrows), dim3(kDenseThreadsBig), bytes, s, ab, Bcol,
+                       (int)(nnzB > 0x7fffffffll ? 0x7fffffffll : nnzB), cols, rec, recpre, row_begin, tmp, cnt, Frow, Fcol, vals);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // RANK ROWS (class kRankBin): rows of 2048 < F_i <= kRankCap products when the column range is several windows of the
 // small dense shape.  The workgroup's LDS holds a two-level RANK bitmap instead of a dense one -- `top`, one bit per
 // 32-column word of the whole column range, and one 32-bit slot per SET top bit, addressed by the bit's rank (the
@@ -438,8 +631,10 @@ static hipError_t launch_rank_rows(const int2 *ab, const int *Bcol, long long nn
 
 hipError_t launch_dense_rows(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols,
                              const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                             int *tmp, int *cnt, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s)
+                             int *tmp, int *cnt, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s, int *vals)
 {
+    if (mode == MaskMode::Count)                                   // every counted row the one-wave kernel does not take
+        return launch_dense_count(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, vals, s);
     if (mode == MaskMode::Keep)                                    // every masked row, whatever its class
         return launch_dense_impl<MaskMode::Keep, kDenseThreadsBig>(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, Frow, Fcol, s);
     if (bin == kRankBin) return launch_rank_rows(ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s);

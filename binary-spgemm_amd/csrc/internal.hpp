@@ -103,6 +103,8 @@ struct bspgemm_context {
     // upper-bound placed rows: the heavy rows of a plain product, every row of a masked one
     size_t tmp_cap = 0;
     int *tmp = nullptr;
+    size_t tmpv_cap = 0;                // the counting product's values, at the same offsets as tmp
+    int *tmpv = nullptr;
     PrepScalars *d_prep = nullptr;      // device side of HostScalars::prep
     bsp::SmallScalars *d_small = nullptr; // device side of HostScalars::small
     bsp::SmallTiles *d_small_tiles = nullptr;   // scan scratch of the small path
@@ -169,6 +171,7 @@ struct bspgemm_result {
     long long *d_row_ptr;
     int *d_col_idx;
     long long col_cap;      // entries allocated for d_col_idx (upper bound F >= nnz)
+    int *d_values = nullptr;  // bspgemm_multiply_masked_count: the count of every entry, col_cap entries; NULL: pattern only
 };
 
 bspgemm_status use_device(bspgemm_context *ctx);
@@ -177,6 +180,7 @@ bspgemm_status use_device(bspgemm_context *ctx);
 bspgemm_status ensure_rows(bspgemm_context *ctx, size_t rows);
 bspgemm_status ensure_ab(bspgemm_context *ctx, size_t pairs);
 bspgemm_status ensure_tmp(bspgemm_context *ctx, size_t ints);
+bspgemm_status ensure_tmpv(bspgemm_context *ctx, size_t ints);
 bspgemm_status ensure_chunk_rows(bspgemm_context *ctx, size_t entries);
 // result buffers: best fit from the context's cache of freed results, else hipMalloc
 bool result_cached(const bspgemm_context *ctx, size_t bytes);

@@ -20,8 +20,9 @@ namespace bsp {
 //   kMidBin    : dense-window rows, up to mid_cap_for_cols(cols) products: 512-thread workgroups, four per CU
 //   kDenseBin  : dense-window rows, above that: one 1024-thread workgroup per row
 // what a second operand does to a product's rows: none, keep only its columns (C = F .* (A*B)), drop its columns
-// (C = !F .* (A*B)), insert its columns (C = D | (A*B), the OR-accumulating product)
-enum class MaskMode { None, Keep, Drop, Insert };
+// (C = !F .* (A*B)), insert its columns (C = D | (A*B), the OR-accumulating product), keep only its columns and count the
+// products of each (C = F .* (A*B) with path counts: the values go to a second workspace at the columns' offsets)
+enum class MaskMode { None, Keep, Drop, Insert, Count };
 
 constexpr int kWaveBins = 16;
 constexpr int kNumBins = kWaveBins + 4;
@@ -121,6 +122,7 @@ struct PrepScalars {
     long long products;
     int a_lo, a_hi;
     int bin_count[kNumBins];
+    unsigned long long max_f;   // the counting product's largest F_i (launch_mask_lengths_count; that flow zeroes it)
 };
 void launch_scan_and_bin(const long long *F, int n, int row_begin, const int *Arow, long long *prefix,
                          long long *partials, int *bin_tiles, int *bin_count, RowRec *rec,
@@ -143,7 +145,8 @@ void launch_scan_counts(const int *cnt, int n, long long *prefix, long long *par
 // mode Drop: the complemented-mask twin (C = !F .* (A*B), upper-bound placement only): the columns of F's row (Frow / Fcol,
 // absolute row ids) are dropped from every row before it is stored.  Keep has no one-wave kernel here (launch_wave_masked),
 // and count_only needs None: both return hipErrorInvalidValue.  mode Insert: the accumulate twin (C = D | (A*B), upper-bound
-// placement only): the columns of D's row (passed as Frow / Fcol) within [0, cols) join the row's gather as one more source
+// placement only): the columns of D's row (passed as Frow / Fcol) within [0, cols) join the row's gather as one more source.
+// Count has no kernel here either (launch_wave_masked, launch_dense_rows): hipErrorInvalidValue
 // err (device, never NULL): bit 0 is set when a row's gathered product count exceeds its class capacity -- impossible
 // for consistent operands (the classes come from the same extents), seen only when an operand was rewritten under
 // the library; the row is then truncated to its capacity instead of overrunning LDS
@@ -165,29 +168,36 @@ void launch_place_heavy(const int *tmp, const RowRec *rec, const long long *recp
 // F's row (Frow / Fcol, absolute row ids): Drop clears its bits from each column window (rank class: from each span's slots)
 // before it is read out, in every shape; Keep admits only its columns, and every row of any class, `bin` ignored, goes through
 // the 1024-thread window kernel; Insert sets the columns of D's row (passed as Frow / Fcol) within [0, cols) in each window
-// (rank class: in each span's top bits and slots)
+// (rank class: in each span's top bits and slots); Count, like Keep for every row and class, runs the counting window kernel
+// (F's columns ranked per window, one counter each) and writes each row's counts to vals at the offsets of its columns in tmp
 hipError_t launch_dense_rows(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols,
                              const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                             int *tmp, int *cnt, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s);
+                             int *tmp, int *cnt, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s,
+                             int *vals = nullptr);
 
 // the heavy rows' records in order of decreasing products (n <= kHeavySortMax), into rec_out / pre_out
 constexpr int kHeavySortMax = 8192;
 void launch_order_heavy(const RowRec *rec, const long long *recpre, int n, RowRec *rec_out, long long *pre_out, hipStream_t s);
 
-// mask-first one-wave path of the masked product (mask rows <= 2048 entries, cols <= 2^23)
+// mask-first one-wave path of the masked product (mask rows <= 2048 entries, cols <= 2^23); vals != NULL: the counting
+// twin, every kept column's product count to vals at the column's offset in tmp
 bool wave_masked_supported(int cols);
 void launch_wave_masked(int bin, const int2 *ab, const int *Bcol, int cols, const int *Frow, const int *Fcol,
                         const RowRec *rec, const long long *recpre, int nrows, int row_begin,
-                        int *tmp, int *cnt, hipStream_t s);
+                        int *tmp, int *cnt, int *vals, hipStream_t s);
 // the rows of class `bin` (upper-bound placement at tmp + recpre[k], |C_i| to cnt), whichever kernel family the class and
 // the mask mode take: one-wave classes launch_wave_rows, heavy classes launch_dense_rows; Keep: a one-wave class takes
 // launch_wave_masked where wave_masked_supported(cols), every other row the 1024-thread window kernel.  count_only (the
-// exact flow's count pass, mode None): the one-wave rows only count, the heavy rows are accumulated into the workspace
+// exact flow's count pass, mode None): the one-wave rows only count, the heavy rows are accumulated into the workspace.
+// Count routes like Keep, to the counting twins, with the values workspace `vals`
 hipError_t launch_class(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
                         const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode,
-                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only = false);
+                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only = false, int *vals = nullptr);
 // mlen[i] = |F's row i| when row i has products, else 0: what the masked product bins and offsets by
 void launch_mask_lengths(const long long *F, const int *Frow, int row_begin, int n, long long *mlen, hipStream_t s);
+// the same for the counting product, and *maxF (device, zeroed by the caller) = the largest F_i of the rows
+void launch_mask_lengths_count(const long long *F, const int *Frow, int row_begin, int n, long long *mlen,
+                               unsigned long long *maxF, hipStream_t s);
 // size[i] = F[i] + |D's row row_begin + i|: what the accumulating product (C = D | (A*B)) bins and offsets by
 void launch_insert_lengths(const long long *F, const int *Drow, int row_begin, int n, long long *size, hipStream_t s);
 

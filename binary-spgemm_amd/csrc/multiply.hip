@@ -307,12 +307,15 @@ static bspgemm_status multiply_exact(bspgemm_context *ctx, const bspgemm_matrix 
 // the mask bounds nothing (|C_i| <= min(F_i, cols) still), so rows are binned, placed and ordered exactly as unmasked, and
 // each class runs the drop twin of its kernel.  Insert: D's row is gathered like one more B row, so rows are binned and
 // placed by F_i + |D_i| (|C_i| <= min(F_i + |D_i|, cols)) -- a row without products but with a row of D is a record too --
-// and each class runs the accumulate twin of its kernel.
+// and each class runs the accumulate twin of its kernel.  Count: Keep's sizes, bins and placement, the counting twin of
+// every kernel, and a second workspace (tmpv) that holds each row's counts at the offsets of its columns in tmp and goes
+// through the same compaction into the result's values.
 static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_matrix *A,
                                            const bspgemm_matrix *B, const bspgemm_matrix *Fm, MaskMode mode,
                                            int row_begin, int row_end, bspgemm_result **out)
 {
-    const bool keep = mode == MaskMode::Keep, insert = mode == MaskMode::Insert;
+    const bool count = mode == MaskMode::Count;
+    const bool keep = mode == MaskMode::Keep || count, insert = mode == MaskMode::Insert;
     bspgemm_result *C = nullptr;
     if (bspgemm_status st = start_flow(ctx, A, B, Fm, row_begin, row_end, BSPGEMM_FLOW_UPPER_BOUND, out, &C)) return st;
     auto bail = [&](bspgemm_status st) { return drop_result(C, st); };
@@ -326,7 +329,11 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
     // the mask row's length (|C_i| <= |F_i|), or, accumulating (Insert), by products + |D_i|; the true product count is
     // summed separately
     const long long *size_by = ctx->F;
-    if (keep) {
+    if (count) {
+        HIPCHK_B(hipMemsetAsync(&ctx->d_prep->max_f, 0, sizeof ctx->d_prep->max_f, s));
+        launch_mask_lengths_count(ctx->F, Fm->d_row_ptr, row_begin, R, ctx->Fmask, &ctx->d_prep->max_f, s);
+        size_by = ctx->Fmask;
+    } else if (keep) {
         launch_mask_lengths(ctx->F, Fm->d_row_ptr, row_begin, R, ctx->Fmask, s);
         size_by = ctx->Fmask;
     } else if (insert) {
@@ -348,7 +355,12 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
     const long long total = R > 0 ? h->totalF : 0;         // sum of min(products, cols) (Keep: of mask-row lengths, Insert: of
                                                            // products + |D_i|): bounds nnz(C)
     if (R == 0) memset(h->bin_count, 0, sizeof h->bin_count);
+    // a count is at most its row's product count: refused before any kernel of the numeric phase when that can exceed int32
+    if (count && R > 0 && h->prep.max_f > (unsigned long long)INT_MAX)
+        return bail(FAIL(BSPGEMM_ERR_OVERFLOW, "a row has more than INT_MAX products: its counts may not fit int32"));
     if (bspgemm_status st = ensure_tmp(ctx, (size_t)total + 1)) return bail(st);
+    if (count)
+        if (bspgemm_status st = ensure_tmpv(ctx, (size_t)total + 1)) return bail(st);
     if (bspgemm_status st = ensure_chunk_rows(ctx, compact_chunk_rows(total))) return bail(st);
     // C.col_idx: a cached buffer of the upper-bound size is taken now (nothing to wait for); else it
     // is allocated with exactly nnz(C) entries once the counts are scanned
@@ -361,7 +373,7 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
         auto place = [&](int b, int n, const RowRec *rec, const long long *recpre, hipStream_t sx) {
             if (!keep) hub_order(ctx, b, n, rec, recpre, sx);
             return launch_class(b, ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, recpre, n, row_begin, ctx->tmp, ctx->cnt,
-                                ctx->d_err, mode, Frow, Fcol, sx);
+                                ctx->d_err, mode, Frow, Fcol, sx, false, count ? ctx->tmpv : nullptr);
         };
         if (bspgemm_status st = class_phase(ctx, 1, h->products, cls_n[1], false, place)) return bail(st);
         HIPCHK_B(hipEventRecord(slot.ev[3], s));
@@ -375,8 +387,12 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
         HIPCHK_B(hipStreamSynchronize(s));
         HIPCHK_B(alloc_col_idx(ctx, C, col_cap_for(total, h->nnzC)));
     }
+    if (count)                                             // as many entries as C.col_idx
+        HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_values), result_bytes_colidx(C->col_cap)));
     if (R > 0) {
         launch_compact(ctx->tmp, ctx->Fprefix, C->d_row_ptr, 0, R, total, C->d_col_idx, s, ctx->chunk_row);
+        if (count)                                         // the counts take the same row shifts as the columns
+            launch_compact(ctx->tmpv, ctx->Fprefix, C->d_row_ptr, 0, R, total, C->d_values, s, ctx->chunk_row);
         HIPCHK_B(hipGetLastError());
     }
     return finish_flow(ctx, C, B, R > 0 ? h->products : 0, keep ? 0 : rank_cap_for_cols(B->cols), cls_n, out);
@@ -496,6 +512,17 @@ extern "C" bspgemm_status bspgemm_multiply_masked_ex(bspgemm_context *ctx, const
         return FAIL(BSPGEMM_ERR_INVALID, "mask is NULL");
     }
     return multiply_upper_bound(ctx, A, B, F, MaskMode::Drop, row_begin, row_end, out);
+}
+
+extern "C" bspgemm_status bspgemm_multiply_masked_count(bspgemm_context *ctx, const bspgemm_matrix *A,
+                                                        const bspgemm_matrix *B, const bspgemm_matrix *F,
+                                                        int row_begin, int row_end, bspgemm_result **out)
+{
+    if (!F) {
+        if (out) *out = nullptr;
+        return FAIL(BSPGEMM_ERR_INVALID, "mask is NULL");
+    }
+    return multiply_upper_bound(ctx, A, B, F, MaskMode::Count, row_begin, row_end, out);
 }
 
 extern "C" bspgemm_status bspgemm_multiply_accumulate(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,

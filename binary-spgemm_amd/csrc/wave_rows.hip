@@ -28,7 +28,7 @@ hipError_t launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol
                             int *tmp, int *cnt, unsigned *err, MaskMode mode, const int *Frow, const int *Fcol, hipStream_t s,
                             bool count_only)
 {
-    if (mode == MaskMode::Keep || (count_only && mode != MaskMode::None)) return hipErrorInvalidValue;
+    if (mode == MaskMode::Keep || mode == MaskMode::Count || (count_only && mode != MaskMode::None)) return hipErrorInvalidValue;
     if (nrows <= 0) return hipSuccess;
 #define BSP_WAVE_ROW(M) {launch_wave_levels<1, MaskMode::M>, launch_wave_levels<2, MaskMode::M>, launch_wave_levels<3, MaskMode::M>, \
                          launch_wave_levels<4, MaskMode::M>, launch_wave_levels<5, MaskMode::M>}
@@ -43,16 +43,17 @@ hipError_t launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol
 
 hipError_t launch_class(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
                         const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode,
-                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only)
+                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only, int *vals)
 {
     if (bin > kWaveBins)
-        return launch_dense_rows(bin, ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s);
-    if (mode != MaskMode::Keep)           // (the count pass emits nothing: no output offsets, no workspace)
+        return launch_dense_rows(bin, ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s, vals);
+    if (mode != MaskMode::Keep && mode != MaskMode::Count)   // (the count pass emits nothing: no output offsets, no workspace)
         return launch_wave_rows(bin, wave_levels_for_cols(cols), ab, Bcol, cols, rec, count_only ? nullptr : recpre, nullptr,
                                 nrows, row_begin, count_only ? nullptr : tmp, cnt, err, mode, Frow, Fcol, s, count_only);
     if (!wave_masked_supported(cols))
-        return launch_dense_rows(bin, ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s);
-    launch_wave_masked(bin, ab, Bcol, cols, Frow, Fcol, rec, recpre, nrows, row_begin, tmp, cnt, s);
+        return launch_dense_rows(bin, ab, Bcol, nnzB, cols, rec, recpre, nrows, row_begin, tmp, cnt, mode, Frow, Fcol, s, vals);
+    launch_wave_masked(bin, ab, Bcol, cols, Frow, Fcol, rec, recpre, nrows, row_begin, tmp, cnt,
+                       mode == MaskMode::Count ? vals : nullptr, s);
     return hipSuccess;
 }
 

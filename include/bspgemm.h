@@ -240,13 +240,39 @@ bspgemm_status bspgemm_multiply_masked_ex(bspgemm_context *ctx,
 bspgemm_status bspgemm_multiply_accumulate(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
                                            const bspgemm_matrix *D, int row_begin, int row_end, bspgemm_result **C);
 
+/* C = F .* (A*B) with path counts: the masked product under the PLUS_PAIR semiring (GraphBLAS C<M> = A plus.pair B), the
+ * counting form of SpGEMM_masked (final/SpGEMM_mpi_omp.c:232-288), which keeps whether a product lands on a column of F's
+ * row and not how many do.  For rows [row_begin, row_end):
+ *     C_ij = #{ (p, q) : p indexes a stored entry (i, k) of A, q indexes a stored entry (k, j) of B }
+ *            for j in pattern(F_i) and 0 <= j < B.cols, stored only where C_ij > 0.
+ *   - Pattern: exactly bspgemm_multiply_masked's on the same arguments (row_ptr, ascending duplicate-free col_idx).  The
+ *     values are int32, one per entry of col_idx (bspgemm_result_values_device, bspgemm_result_download_values).
+ *   - Repeats: repeated entries of A's or B's rows count as stored (scipy's A1 @ B1 with a 1 per stored entry, duplicates
+ *     not merged).  For duplicate-free operands C_ij is the number of k with (i,k) in A and (k,j) in B -- every transpose,
+ *     product and bspgemm_matrix_from_result is duplicate-free.  Repeats in F change nothing (a column is a mask column
+ *     once); F's columns at or above B.cols have no effect.  Triangles: sum(L .* (L*L)) for L the strictly lower triangle.
+ *   - F is indexed by ABSOLUTE row, C.row_ptr is slice-local; F's rows may be unsorted and hold repeats.  The operand, range
+ *     and F checks are bspgemm_multiply_masked's: BSPGEMM_ERR_INVALID with *C = NULL.
+ *   - A count is at most its row's product count F_i: when any row of the range has F_i > 2^31 - 1 the call returns
+ *     BSPGEMM_ERR_OVERFLOW and no result, decided from the prepass before the numeric phase.
+ *   - Flow: always upper-bound placement + compaction, like the masked product (no small path, no EXACT flow); rows are
+ *     binned and placed by mask-row length and every class runs the counting twin of its kernel.  bspgemm_stats reads as for
+ *     the masked product: the same rows_per_bin and bin_cap, flow = BSPGEMM_FLOW_UPPER_BOUND, small_path = 0, products = F,
+ *     nnz_c.  The knobs act as on the masked product and change no result.
+ * bspgemm_result_free releases the values with the pattern; bspgemm_matrix_from_result takes the pattern only. */
+bspgemm_status bspgemm_multiply_masked_count(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
+                                             const bspgemm_matrix *F, int row_begin, int row_end, bspgemm_result **C);
+
 int            bspgemm_result_rows(const bspgemm_result *C);
 int64_t        bspgemm_result_nnz(const bspgemm_result *C);
 const int64_t *bspgemm_result_row_ptr_device(const bspgemm_result *C);   /* rows+1 entries  */
 const int     *bspgemm_result_col_idx_device(const bspgemm_result *C);   /* nnz entries     */
+const int     *bspgemm_result_values_device(const bspgemm_result *C);    /* nnz entries; NULL for a pattern-only result */
 /* copy to host; either pointer may be NULL to skip that array                                */
 bspgemm_status bspgemm_result_download(bspgemm_context *ctx, const bspgemm_result *C,
                                        int64_t *row_ptr, int *col_idx);
+/* values[nnz] of a counted result (bspgemm_multiply_masked_count); BSPGEMM_ERR_INVALID for a pattern-only result */
+bspgemm_status bspgemm_result_download_values(bspgemm_context *ctx, const bspgemm_result *C, int *values /* nnz */);
 void           bspgemm_result_free(bspgemm_result *C);
 
 /* A product becomes the next operand without leaving the GPU (int32 row_ptr copy; fails with
