@@ -191,7 +191,7 @@ extern "C" void bspgemm_destroy(bspgemm_context *ctx)
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     hipFree(ctx->F); hipFree(ctx->Fprefix); hipFree(ctx->partials);
     hipFree(ctx->cnt); hipFree(ctx->bin_tiles); hipFree(ctx->bin_count); hipFree(ctx->tmp); hipFree(ctx->tmpv);
-    hipFree(ctx->rec); hipFree(ctx->recpre); hipFree(ctx->ab); hipFree(ctx->Fmask); hipFree(ctx->hpartials);
+    hipFree(ctx->rec); hipFree(ctx->recpre); hipFree(ctx->ab); hipFree(ctx->tile_row); hipFree(ctx->Fmask); hipFree(ctx->hpartials);
     hipFree(ctx->hub_rec); hipFree(ctx->hub_pre);
     if (ctx->h) hipHostFree(ctx->h);
     hipFree(ctx->d_prep);
@@ -375,6 +375,21 @@ bspgemm_status ensure_ab(bspgemm_context *ctx, size_t pairs)
     const size_t cap = pairs + pairs / 16 + 64;
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->ab), cap * sizeof(int2)));
     ctx->ab_cap = cap;
+    return BSPGEMM_OK;
+}
+
+// the flat prepass's first row per tile: `items` = nonzeros + rows of the row range (csrc/prepass.hip k_tile_rows)
+bspgemm_status ensure_tile_rows(bspgemm_context *ctx, size_t items)
+{
+    const size_t need = items / kRowWorkTile + 2;
+    if (need <= ctx->tile_row_cap) return BSPGEMM_OK;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->tile_row);
+    ctx->tile_row = nullptr;
+    ctx->tile_row_cap = 0;
+    const size_t cap = need + need / 16 + 64;
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->tile_row), cap * sizeof(int)));
+    ctx->tile_row_cap = cap;
     return BSPGEMM_OK;
 }
 

@@ -100,6 +100,8 @@ struct bspgemm_context {
     // per-A-nonzero workspace: (start,length) of the B row behind every A nonzero
     size_t ab_cap = 0;
     int2 *ab = nullptr;
+    size_t tile_row_cap = 0;
+    int *tile_row = nullptr;            // the flat prepass's first row per tile (ensure_tile_rows)
     // upper-bound placed rows: the heavy rows of a plain product, every row of a masked one
     size_t tmp_cap = 0;
     int *tmp = nullptr;
@@ -144,7 +146,7 @@ struct bspgemm_matrix {
     // device layout: built when the operand is created (lazily for wrapped device arrays).
     mutable unsigned char *d_deg8 = nullptr;
     // blocked extents table {row_ptr of every 8th row, 8 clamped lengths}: what k_row_work gathers per
-    // A-nonzero instead of a B.row_ptr pair (csrc/prepass.hip: k_row_work_blk); built on first use as B
+    // A-nonzero instead of a B.row_ptr pair (csrc/prepass.hip: k_row_work_flat); built on first use as B
     mutable int *d_blk8 = nullptr;
     mutable int blk8_state = 0;          // 0 undecided, 1 in use, 2 not worth it for this operand
     // padded copy of col_idx: every row on a 64-byte boundary (padded to a multiple of 16 entries), so that a gathered B row
@@ -179,6 +181,7 @@ bspgemm_status use_device(bspgemm_context *ctx);
 // ------------------------------------------------------------------ workspace (context.hip) ---
 bspgemm_status ensure_rows(bspgemm_context *ctx, size_t rows);
 bspgemm_status ensure_ab(bspgemm_context *ctx, size_t pairs);
+bspgemm_status ensure_tile_rows(bspgemm_context *ctx, size_t items);
 bspgemm_status ensure_tmp(bspgemm_context *ctx, size_t ints);
 bspgemm_status ensure_tmpv(bspgemm_context *ctx, size_t ints);
 bspgemm_status ensure_chunk_rows(bspgemm_context *ctx, size_t entries);

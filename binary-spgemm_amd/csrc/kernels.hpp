@@ -88,8 +88,11 @@ struct RowRec {
 //                   positions in the PADDED copy of B.col_idx
 //   else Bext       the per-row table {start in the padded copy, length}
 //   else            a B.row_ptr pair (starts in B.col_idx itself)
+// With Bblk8 the pass is flat, in tiles of kRowWorkTile merged positions (each row's nonzeros and one end item):
+// nnz_bound (host) bounds the range's nonzeros, tile_row has room for (nnz_bound + rows) / kRowWorkTile + 2 ints.
+constexpr int kRowWorkTile = 4096;
 void launch_row_work(const int *Arow, const int *Acol, const int *Brow, const int *Bblk8, const int *Bpad, const int2 *Bext,
-                     int row_begin, int row_end, long long *F, int2 *ab, hipStream_t s);
+                     int row_begin, int row_end, long long nnz_bound, int *tile_row, long long *F, int2 *ab, hipStream_t s);
 // blk[3b..3b+2] = {start_ptr[8b] (NULL: row_ptr), lengths of rows 8b..8b+7 clamped to 255, one byte each}
 // *clamped_nnz (device, zeroed by the caller) += nonzeros in rows of 255 or more
 void launch_blk8(const int *row_ptr, const int *start_ptr, int n, int *blk, unsigned long long *clamped_nnz, hipStream_t s);

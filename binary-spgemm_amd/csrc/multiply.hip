@@ -132,6 +132,7 @@ static bspgemm_status start_flow(bspgemm_context *ctx, const bspgemm_matrix *A, 
     hipStream_t s = ctx->stream;
     if (bspgemm_status st = ensure_rows(ctx, (size_t)R + 1)) return st;
     if (bspgemm_status st = ensure_ab(ctx, (size_t)A->nnz + 1)) return st;
+    if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)A->nnz + (size_t)R)) return st;
 
     bspgemm_result *C = new (std::nothrow) bspgemm_result{ctx, R, 0, nullptr, nullptr, 0};
     if (!C) return FAIL(BSPGEMM_ERR_ALLOC, "result");
@@ -150,7 +151,7 @@ static bspgemm_status start_flow(bspgemm_context *ctx, const bspgemm_matrix *A, 
     slot.padded = B->pad_state == 1;
     launch_row_work(A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->blk8_state == 1 ? B->d_blk8 : nullptr,
                     B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, B->pad_state == 1 ? B->d_ext : nullptr, row_begin, row_end,
-                    ctx->F, ctx->ab, s);
+                    A->nnz, ctx->tile_row, ctx->F, ctx->ab, s);
     *Cp = C;
     return BSPGEMM_OK;
 }

@@ -149,98 +149,201 @@ void launch_blk8(const int *row_ptr, const int *start_ptr, int n, int *blk, unsi
     hipLaunchKernelGGL(k_blk8, dim3((nb + 255) / 256), dim3(256), 0, s, row_ptr, start_ptr ? start_ptr : row_ptr, n, blk, clamped_nnz);
 }
 
-// PAD: the table's `base` is the block's first row in the PADDED copy of B.col_idx and a row starts behind the padded
-// lengths below it -- ceil(len / 16) * 16, summed over the bytes in SWAR form; rows behind a clamped byte are looked up in
-// the padded row_ptr (Bpad) and B.row_ptr.
+// One blocked-table entry decoded for B row j: where the row starts (PAD: in the padded copy of B.col_idx; the table's `base`
+// is then the block's first row there and a row starts behind the padded lengths below it -- ceil(len / 16) * 16, summed over
+// the bytes in SWAR form) and its length.  sat: a clamped byte at or below the row, so both come from B.row_ptr (and Bpad).
 template <bool PAD>
-__global__ __launch_bounds__(256) void k_row_work_blk(const int *__restrict__ Arow,
-                                                      const int *__restrict__ Acol,
-                                                      const int *__restrict__ Brow,
-                                                      const int *__restrict__ Bblk,
-                                                      const int *__restrict__ Bpad,
-                                                      int row_begin, int nrows,
-                                                      long long *__restrict__ F,
-                                                      int2 *__restrict__ ab)
+__device__ __forceinline__ void blk8_extent(const Blk8 &w, int j, int &start, int &len, bool &sat)
 {
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int r = (int)(gid >> 3);
-    const int sub = (int)(gid & 7);
-    int a0 = 0, a1 = 0;
-    if (r < nrows) { a0 = Arow[row_begin + r]; a1 = Arow[row_begin + r + 1]; }
-    constexpr int U = kRowWorkUnroll;
-    auto sweep = [&](long long first, long long end, int stride) {
-        long long sum = 0;
-        for (long long jj = first; jj < end; jj += (long long)stride * U) {
-            int j[U];
+    const int k = j & 7;
+    const u64 d = ((u64)w.hi << 32) | (u64)w.lo;
+    const u64 below = d & ((1ull << (8 * k)) - 1ull);
+    const u64 upto = (k == 7) ? d : (d & ((1ull << (8 * k + 8)) - 1ull));
+    const u64 v = ~upto;                                           // a 255 byte at or below the row -> a zero byte here
+    sat = ((v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull) != 0ull;
+    if (PAD) {
+        // sixteenths of each length below the row, rounded up: (len >> 4) + ((len & 15) != 0), byte by byte
+        const u64 m0f = 0x0f0f0f0f0f0f0f0full, m01 = 0x0101010101010101ull;
+        const u64 units = ((below >> 4) & m0f) + ((((below & m0f) + m0f) >> 4) & m01);
+        start = w.base + 16 * ((int)__builtin_amdgcn_sad_u8((unsigned)units, 0u, 0u)
+                               + (int)__builtin_amdgcn_sad_u8((unsigned)(units >> 32), 0u, 0u));
+    } else {
+        start = w.base + (int)__builtin_amdgcn_sad_u8((unsigned)below, 0u, 0u)
+                + (int)__builtin_amdgcn_sad_u8((unsigned)(below >> 32), 0u, 0u);
+    }
+    len = (int)((d >> (8 * k)) & 255ull);
+}
+
+// ---------------------------------------------------------------------------------------
+// The blocked-table pass, flat and load-balanced: merge-path tiles.  Row r of the range is its nonzeros followed by one
+// END item, at merged positions [a0 + r, a1 + r] (a0, a1: its nonzero bounds relative to the range's first); a workgroup
+// owns kFlatTile consecutive merged positions, so it holds at most kFlatTile nonzeros AND row ends together.  A hub row no
+// longer holds up one wave, a run of empty rows is spread over tiles like nonzeros are, and every lane has kFlatK table
+// gathers in flight at once (the row-per-8-lanes form above had 4 slots per lane, half of them empty at ~16 nonzeros per
+// row, and three dependent round trips per 128 nonzeros).
+//
+// k_tile_rows finds each tile's first row by a scatter over the rows (tile_row[t] = the row whose merged positions hold
+// t * kFlatTile) and zeroes F of the rows whose positions reach over a tile boundary: every tile they touch adds its part.
+constexpr int kFlatTile = kRowWorkTile;
+constexpr int kFlatK = kFlatTile / 256;         // positions per lane: the independent table gathers it has in flight
+
+__global__ __launch_bounds__(256) void k_tile_rows(const int *__restrict__ Arow, int row_begin, int nrows,
+                                                   int *__restrict__ tile_row, long long *__restrict__ F)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nrows) return;
+    const long long lo = Arow[row_begin];
+    const long long m0 = Arow[row_begin + r] - lo + r, m1 = Arow[row_begin + r + 1] - lo + r;   // first item, end item
+    for (long long t = (m0 + kFlatTile - 1) / kFlatTile; t * kFlatTile <= m1; t++) tile_row[t] = r;
+    if (m0 / kFlatTile != m1 / kFlatTile) F[r] = 0;
+}
+
+// Per tile, merged positions [d0, d1), nonzeros [j0, j1) (relative): (1) lane t takes nonzeros j0 + t + 256k (A.col_idx
+// coalesced), issues all kFlatK gathers, then decodes and writes ab[] coalesced; (2) the lengths go to LDS and come back as
+// kFlatK consecutive ones per lane, whose running sums and one workgroup scan give the tile's prefix P[q] = sum of its first
+// q lengths; (3) every row whose end item lies in the tile, and the row that reaches over its end, takes P[end] - P[start]
+// of its nonzeros in the tile: a plain store when the row's positions lie inside the tile, an atomic add when they cross a
+// boundary.  At most kFlatTile + 1 rows per tile, kFlatK + 1 per lane, their bounds loaded in one batch.
+// Nonzero positions stay below INT_MAX (A.row_ptr is int); merged positions are 64-bit.
+template <bool PAD>
+__global__ __launch_bounds__(256) void k_row_work_flat(const int *__restrict__ Arow,
+                                                       const int *__restrict__ Acol,
+                                                       const int *__restrict__ Brow,
+                                                       const int *__restrict__ Bblk,
+                                                       const int *__restrict__ Bpad,
+                                                       int row_begin, int nrows,
+                                                       const int *__restrict__ tile_row,
+                                                       long long *__restrict__ F,
+                                                       int2 *__restrict__ ab)
+{
+    constexpr int K = kFlatK, NB = kFlatTile, RV = kFlatK + 1;
+    constexpr int LSTRIDE = K + 4;              // lengths staged with 4 ints of padding per lane's run: 16-B reads, no conflicts
+    // P[q] at q + q / 16 (one pad per 16: each lane's 8-B prefix stores fall on distinct banks); the staged lengths
+    // (256 * LSTRIDE ints) live in the same bytes before the prefix is written
+    __shared__ __attribute__((aligned(16))) long long P[NB + NB / 16 + 1];
+    __shared__ long long wsum[4];
+    static_assert(256 * LSTRIDE * sizeof(int) <= sizeof(P), "staged lengths do not fit the prefix array");
+    int *L = reinterpret_cast<int *>(P);
+    auto pidx = [](int q) { return q + (q >> 4); };
+
+    const int tid = threadIdx.x;
+    const int *rp = Arow + row_begin;
+    const long long lo = rp[0], nnz = rp[nrows] - lo, total = nnz + nrows;
+    const long long d0 = (long long)blockIdx.x * NB;
+    if (d0 >= total) return;                                       // workgroup-uniform: the grid is sized by a bound
+    const bool last = d0 + NB >= total;
+    const long long d1 = last ? total : d0 + NB;
+    // rows visited: the one holding d0 .. the one holding d1 (or the last row)
+    const int rb = tile_row[blockIdx.x];
+    const int rl = last ? nrows - 1 : tile_row[blockIdx.x + 1];
+    const long long j0 = d0 - rb, j1 = last ? nnz : d1 - rl;      // the tile's nonzeros, relative
+    const int n = (int)(j1 - j0);
+    const long long g0 = lo + j0;
+    // the lane's first row: its bounds are loaded beside the gathers
+    int fa0 = 0, fa1 = 0;
+    if (rb + tid <= rl) { fa0 = rp[rb + tid]; fa1 = rp[rb + tid + 1]; }
+
+    int j[K];
 #pragma unroll
-            for (int u = 0; u < U; u++) j[u] = (jj + stride * u < end) ? Acol[jj + stride * u] : -1;
-            Blk8 w[U];
+    for (int k = 0; k < K; k++) j[k] = tid + 256 * k < n ? Acol[g0 + tid + 256 * k] : -1;
+    Blk8 w[K];
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                w[u].base = 0; w[u].lo = w[u].hi = 0u;
-                if (j[u] >= 0) w[u] = *reinterpret_cast<const Blk8 *>(Bblk + 3 * (j[u] >> 3));
-            }
-            int start[U], len[U];
-            bool sat[U];
+    for (int k = 0; k < K; k++) {
+        w[k].base = 0; w[k].lo = w[k].hi = 0u;
+        if (j[k] >= 0) w[k] = *reinterpret_cast<const Blk8 *>(Bblk + 3 * (j[k] >> 3));
+    }
+    int start[K], len[K];
+    bool sat[K];
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                const int k = j[u] & 7;
-                const u64 d = ((u64)w[u].hi << 32) | (u64)w[u].lo;
-                const u64 below = d & ((1ull << (8 * k)) - 1ull);
-                const u64 upto = (k == 7) ? d : (d & ((1ull << (8 * k + 8)) - 1ull));
-                const u64 v = ~upto;                                // a 255 byte at or below the row -> a zero byte here
-                sat[u] = j[u] >= 0 && ((v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull) != 0ull;
-                if (PAD) {
-                    // sixteenths of each length below the row, rounded up: (len >> 4) + ((len & 15) != 0), byte by byte
-                    const u64 m0f = 0x0f0f0f0f0f0f0f0full, m01 = 0x0101010101010101ull;
-                    const u64 units = ((below >> 4) & m0f) + ((((below & m0f) + m0f) >> 4) & m01);
-                    start[u] = w[u].base + 16 * ((int)__builtin_amdgcn_sad_u8((unsigned)units, 0u, 0u)
-                                                 + (int)__builtin_amdgcn_sad_u8((unsigned)(units >> 32), 0u, 0u));
-                } else {
-                    start[u] = w[u].base + (int)__builtin_amdgcn_sad_u8((unsigned)below, 0u, 0u)
-                               + (int)__builtin_amdgcn_sad_u8((unsigned)(below >> 32), 0u, 0u);
-                }
-                len[u] = (int)((d >> (8 * k)) & 255ull);
-            }
-            // clamped lengths (B rows of 255+ nonzeros -- the hubs of a skewed graph, so these reads hit
-            // L2): the exact pairs, again issued together
-            Int2U pr[U];
-            int ps[U];
+    for (int k = 0; k < K; k++) {
+        blk8_extent<PAD>(w[k], j[k], start[k], len[k], sat[k]);
+        sat[k] = sat[k] && j[k] >= 0;
+    }
+    // clamped lengths (B rows of 255+ nonzeros -- the hubs of a skewed graph, so these reads hit L2): the exact pairs,
+    // again issued together
+    Int2U pr[K];
+    int ps[K];
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                pr[u].x = pr[u].y = 0;
-                ps[u] = 0;
-                if (sat[u]) {
-                    pr[u] = *reinterpret_cast<const Int2U *>(Brow + j[u]);
-                    if (PAD) ps[u] = Bpad[j[u]];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++)
-                if (j[u] >= 0) {
-                    if (sat[u]) { start[u] = PAD ? ps[u] : pr[u].x; len[u] = pr[u].y - pr[u].x; }
-                    ab[jj + stride * u] = make_int2(start[u], len[u]);
-                    sum += (long long)len[u];
-                }
+    for (int k = 0; k < K; k++) {
+        pr[k].x = pr[k].y = 0;
+        ps[k] = 0;
+        if (sat[k]) {
+            pr[k] = *reinterpret_cast<const Int2U *>(Brow + j[k]);
+            if (PAD) ps[k] = Bpad[j[k]];
         }
-        return sum;
-    };
-    const long long sum = rows_of_a_wave(a0, a1, sub, sweep);
-    if (r < nrows && sub == 0) F[r] = sum;
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const int p = tid + 256 * k;
+        if (sat[k]) { start[k] = PAD ? ps[k] : pr[k].x; len[k] = pr[k].y - pr[k].x; }
+        if (j[k] < 0) len[k] = 0;
+        else ab[g0 + p] = make_int2(start[k], len[k]);
+        L[p + 4 * (p / K)] = len[k];
+    }
+    __syncthreads();
+
+    // this lane's K consecutive lengths: running sums, then the workgroup's exclusive scan of the lane totals
+    int mine[K];
+#pragma unroll
+    for (int i = 0; i < K; i += 4) {
+        const int4 v = *reinterpret_cast<const int4 *>(L + LSTRIDE * tid + i);
+        mine[i] = v.x; mine[i + 1] = v.y; mine[i + 2] = v.z; mine[i + 3] = v.w;
+    }
+    long long tot = 0;
+#pragma unroll
+    for (int i = 0; i < K; i++) tot += mine[i];
+    const long long inc = wave_incl_scan64(tot);
+    const int lane = tid & 63, wv = tid >> 6;
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();                                               // also: every lane's staged lengths are read
+    long long off = inc - tot;
+    for (int k = 0; k < wv; k++) off += wsum[k];
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        off += mine[i];
+        P[pidx(K * tid + i + 1)] = off;
+    }
+    if (tid == 0) P[0] = 0;
+    // the lane's other rows (a tile of many short or empty rows): their bounds in one batch
+    int ra0[RV], ra1[RV];
+    ra0[0] = fa0;
+    ra1[0] = fa1;
+#pragma unroll
+    for (int i = 1; i < RV; i++)
+        if (rb + tid + 256 * i <= rl) { ra0[i] = rp[rb + tid + 256 * i]; ra1[i] = rp[rb + tid + 256 * i + 1]; }
+    __syncthreads();
+
+#pragma unroll
+    for (int i = 0; i < RV; i++) {
+        const int r = rb + tid + 256 * i;
+        if (r > rl) break;
+        const long long a0 = ra0[i] - lo, a1 = ra1[i] - lo;
+        const long long s = a0 > j0 ? a0 : j0, e = a1 < j1 ? a1 : j1;
+        const long long v = e > s ? P[pidx((int)(e - j0))] - P[pidx((int)(s - j0))] : 0;
+        if (a0 + r >= d0 && a1 + r < d1) F[r] = v;                // the row's positions inside the tile (empty rows too)
+        else if (v != 0) atomicAdd(reinterpret_cast<unsigned long long *>(F + r), (unsigned long long)v);
+    }
 }
 
 void launch_row_work(const int *Arow, const int *Acol, const int *Brow, const int *Bblk8, const int *Bpad, const int2 *Bext,
-                     int row_begin, int row_end, long long *F, int2 *ab, hipStream_t s)
+                     int row_begin, int row_end, long long nnz_bound, int *tile_row, long long *F, int2 *ab, hipStream_t s)
 {
     const int nrows = row_end - row_begin;
     if (nrows <= 0) return;
+    if (Bblk8) {
+        hipLaunchKernelGGL(k_tile_rows, dim3((nrows + 255) / 256), dim3(256), 0, s, Arow, row_begin, nrows, tile_row, F);
+        const int tiles = (int)((nnz_bound + nrows + kFlatTile - 1) / kFlatTile);
+        if (Bpad)
+            hipLaunchKernelGGL(k_row_work_flat<true>, dim3(tiles), dim3(256), 0, s, Arow, Acol, Brow, Bblk8, Bpad, row_begin, nrows,
+                               tile_row, F, ab);
+        else
+            hipLaunchKernelGGL(k_row_work_flat<false>, dim3(tiles), dim3(256), 0, s, Arow, Acol, Brow, Bblk8, nullptr, row_begin,
+                               nrows, tile_row, F, ab);
+        return;
+    }
     const long long threads = (long long)nrows * 8;
     const int grid = (int)((threads + 255) / 256);
-    if (Bblk8 && Bpad)
-        hipLaunchKernelGGL(k_row_work_blk<true>, dim3(grid), dim3(256), 0, s, Arow, Acol, Brow, Bblk8, Bpad, row_begin, nrows, F, ab);
-    else if (Bblk8)
-        hipLaunchKernelGGL(k_row_work_blk<false>, dim3(grid), dim3(256), 0, s, Arow, Acol, Brow, Bblk8, nullptr, row_begin, nrows, F, ab);
-    else if (Bext)
+    if (Bext)
         hipLaunchKernelGGL(k_row_work<true>, dim3(grid), dim3(256), 0, s, Arow, Acol, Brow, Bext, row_begin, nrows, F, ab);
     else
         hipLaunchKernelGGL(k_row_work<false>, dim3(grid), dim3(256), 0, s, Arow, Acol, Brow, nullptr, row_begin, nrows, F, ab);

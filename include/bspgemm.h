@@ -340,7 +340,7 @@ typedef struct bspgemm_stats {
                                 mask-row length); 0 for [0], INT32_MAX for the heavy class   */
     /* which path produced the result (so that a test of a knob can assert that the knob took) */
     int     flow;            /* BSPGEMM_FLOW_UPPER_BOUND or BSPGEMM_FLOW_EXACT: the flow that ran     */
-    int     prepass_kernel;  /* 0 k_row_work (B.row_ptr pairs), 1 k_row_work_blk (blocked extents table),
+    int     prepass_kernel;  /* 0 k_row_work (B.row_ptr pairs), 1 k_row_work_flat (blocked extents table),
                                 2 the single-launch small path's own prepass                          */
     int     class_streams;   /* streams the class launches alternated over                           */
     int     small_path;      /* 1: the single-launch path for small products ran                      */
