@@ -1,6 +1,8 @@
 // kernels.hpp -- launch wrappers of the HIP kernels behind bspgemm_multiply (host-callable).
-// Kernel bodies: prepass.hip (row work, scans, class records), wave_rows.inc (one object per (LEVELS, EXCL) pair,
-// dispatched by wave_rows.hip), wave_masked.hip, dense_rows.hip (heavy rows + compaction).
+// Kernels: prepass.hip (row work, scans, class records), wave_rows.inc (k_wave_rows; one object per (LEVELS, mask mode) pair,
+// dispatched by wave_rows.hip), wave_masked.hip (k_wave_masked), dense_rows.hip (k_dense_rows, k_dense_rows_count,
+// k_rank_rows) over the heavy rows' gather in heavy_gather.hpp, compact.hip (compaction, heavy-row moves),
+// small.hip, transpose.hip.  A family is ONE template kernel with the mask mode as a template parameter.
 // Tuning constants are compile-time constants, not switches: what was tried against them is in profiles/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -144,10 +146,10 @@ void launch_scan_counts(const int *cnt, int n, long long *prefix, long long *par
 // numeric phase, one wave per row (rank-bitmap accumulator).  row_ptr != NULL: row i is written at
 // tmp + row_ptr[i - row_begin] (tmp = C.col_idx, sizes known from the symbolic phase, cnt may be
 // NULL); row_ptr == NULL: at its upper-bound offset tmp + recpre[k], |C_i| to cnt (masked product)
-// count_only: the symbolic twin of the same kernel -- nothing is emitted (tmp, recpre, row_ptr unused), cnt[i] = |C_i|
-// mode Drop: the complemented-mask twin (C = !F .* (A*B), upper-bound placement only): the columns of F's row (Frow / Fcol,
+// count_only: the COUNT instances of the same kernel -- nothing is emitted (tmp, recpre, row_ptr unused), cnt[i] = |C_i|
+// mode Drop: the Drop instances (C = !F .* (A*B), upper-bound placement only): the columns of F's row (Frow / Fcol,
 // absolute row ids) are dropped from every row before it is stored.  Keep has no one-wave kernel here (launch_wave_masked),
-// and count_only needs None: both return hipErrorInvalidValue.  mode Insert: the accumulate twin (C = D | (A*B), upper-bound
+// and count_only needs None: both return hipErrorInvalidValue.  mode Insert: the Insert instances (C = D | (A*B), upper-bound
 // placement only): the columns of D's row (passed as Frow / Fcol) within [0, cols) join the row's gather as one more source.
 // Count has no kernel here either (launch_wave_masked, launch_dense_rows): hipErrorInvalidValue
 // err (device, never NULL): bit 0 is set when a row's gathered product count exceeds its class capacity -- impossible
@@ -183,7 +185,7 @@ constexpr int kHeavySortMax = 8192;
 void launch_order_heavy(const RowRec *rec, const long long *recpre, int n, RowRec *rec_out, long long *pre_out, hipStream_t s);
 
 // mask-first one-wave path of the masked product (mask rows <= 2048 entries, cols <= 2^23); vals != NULL: the counting
-// twin, every kept column's product count to vals at the column's offset in tmp
+// instances (k_wave_masked<.., true>), every kept column's product count to vals at the column's offset in tmp
 bool wave_masked_supported(int cols);
 void launch_wave_masked(int bin, const int2 *ab, const int *Bcol, int cols, const int *Frow, const int *Fcol,
                         const RowRec *rec, const long long *recpre, int nrows, int row_begin,
@@ -192,7 +194,7 @@ void launch_wave_masked(int bin, const int2 *ab, const int *Bcol, int cols, cons
 // the mask mode take: one-wave classes launch_wave_rows, heavy classes launch_dense_rows; Keep: a one-wave class takes
 // launch_wave_masked where wave_masked_supported(cols), every other row the 1024-thread window kernel.  count_only (the
 // exact flow's count pass, mode None): the one-wave rows only count, the heavy rows are accumulated into the workspace.
-// Count routes like Keep, to the counting twins, with the values workspace `vals`
+// Count routes like Keep, to the counting kernels, with the values workspace `vals`
 hipError_t launch_class(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
                         const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode,
                         const int *Frow, const int *Fcol, hipStream_t s, bool count_only = false, int *vals = nullptr);

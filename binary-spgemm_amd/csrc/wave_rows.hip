@@ -1,4 +1,4 @@
-// wave_rows.hip -- dispatcher of the one-wave-per-row kernels (bodies: wave_rows.inc, built once per (LEVELS, mode)
+// wave_rows.hip -- dispatcher of the one-wave-per-row kernels (the kernel: wave_rows.inc, built once per (LEVELS, mode)
 // pair).  Picks the number of 5-bit levels from B's column count; launch_class picks the kernel family of a class.
 #include "kernels.hpp"
 
