@@ -55,6 +55,8 @@ EXPORTS = [
     "bspgemm_set_option", "bspgemm_get_option", "bspgemm_matrix_uses_blocked_table", "bspgemm_matrix_uses_padded_rows",
     "bspgemm_matrix_transpose", "bspgemm_matrix_download", "bspgemm_multiply_accumulate", "bspgemm_closure_ex",
     "bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values",
+    "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
+    "bspgemm_ktruss",
 ]
 
 
@@ -69,6 +71,8 @@ MAX_BINS = 20      # BSPGEMM_MAX_BINS
 FLOWS = {"auto": 0, "upper-bound": 1, "exact": 2}                                    # BSPGEMM_FLOW_*
 MASK_COMPLEMENT = 1                                                                      # BSPGEMM_MASK_COMPLEMENT
 CLOSURE_TRANSITIVE = 1                                                                   # BSPGEMM_CLOSURE_TRANSITIVE
+SELECT_OPS = {"tril": 1, "triu": 2, "offdiag": 3}                                       # bspgemm_select
+COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5}    # bspgemm_option
 
 
@@ -189,6 +193,11 @@ def lib():
     L.bspgemm_result_free.argtypes = [VP]
     L.bspgemm_result_free.restype = None
     L.bspgemm_matrix_from_result.argtypes = [VP, VP, C.c_int, PVP]
+    L.bspgemm_matrix_select.argtypes = [VP, VP, C.c_int, PVP]
+    L.bspgemm_matrix_from_result_where.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, PVP]
+    L.bspgemm_result_values_sum.argtypes = [VP, VP, C.POINTER(C.c_int64)]
+    L.bspgemm_triangle_count.argtypes = [VP, VP, C.POINTER(C.c_int64)]
+    L.bspgemm_ktruss.argtypes = [VP, VP, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_closure.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
     L.bspgemm_multiply_accumulate.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, PVP]
     L.bspgemm_closure_ex.argtypes = [VP, VP, C.c_uint, C.c_int, PVP, C.POINTER(C.c_int)]
@@ -417,6 +426,34 @@ class Context:
         _chk(lib().bspgemm_matrix_from_result(self._h, result._h, cols, C.byref(m)), "matrix_from_result")
         return Matrix(self, m, keep=None)
 
+    def matrix_from_result_where(self, result, cols, cmp, threshold):
+        """bspgemm_matrix_from_result_where: the entries of a counted result whose count satisfies `count cmp threshold`
+        (cmp: ">=" | ">" | "<=" | "<" | "==" | "!=") as a new operand, filtered on the device"""
+        m = C.c_void_p()
+        _chk(lib().bspgemm_matrix_from_result_where(self._h, result._h, cols, COMPARES[cmp], int(threshold), C.byref(m)),
+             "matrix_from_result_where")
+        return Matrix(self, m, keep=None)
+
+    def select(self, A, op):
+        """bspgemm_matrix_select: the entries of A below ("tril") / above ("triu") / off ("offdiag") the diagonal as a new
+        operand; a stable filter on the device (order and repeats of every row kept)"""
+        m = C.c_void_p()
+        _chk(lib().bspgemm_matrix_select(self._h, A._h, SELECT_OPS[op], C.byref(m)), "matrix_select")
+        return Matrix(self, m, keep=None)
+
+    def triangle_count(self, A):
+        """bspgemm_triangle_count: triangles of the undirected graph of A's strictly lower triangle, device-resident"""
+        t = C.c_int64()
+        _chk(lib().bspgemm_triangle_count(self._h, A._h, C.byref(t)), "triangle_count")
+        return t.value
+
+    def ktruss(self, A, k, max_iter=0):
+        """bspgemm_ktruss: (T as a Matrix, counted products computed, converged) -- the maximal subgraph in which every
+        edge lies in at least k - 2 triangles, by repeated counted products and on-device selects; max_iter <= 0: no cap"""
+        m, it, conv = C.c_void_p(), C.c_int(), C.c_int()
+        _chk(lib().bspgemm_ktruss(self._h, A._h, int(k), int(max_iter), C.byref(m), C.byref(it), C.byref(conv)), "ktruss")
+        return Matrix(self, m, keep=None), it.value, bool(conv.value)
+
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""
         m = C.c_void_p()
@@ -518,6 +555,12 @@ class Result:
     def values_device(self):
         """device pointer of the counts of a counted result (Context.multiply_masked_count); None for a pattern-only one"""
         return lib().bspgemm_result_values_device(self._h)
+
+    def values_sum(self):
+        """bspgemm_result_values_sum: the exact sum of a counted result's counts, reduced on the device"""
+        t = C.c_int64()
+        _chk(lib().bspgemm_result_values_sum(self.ctx._h, self._h, C.byref(t)), "result_values_sum")
+        return t.value
 
     def download_values(self):
         """the counts of a counted result, aligned with download()'s col_idx, as np.int32"""

@@ -2,7 +2,7 @@
 // Kernels: prepass.hip (row work, scans, class records), wave_rows.inc (k_wave_rows; one object per (LEVELS, mask mode) pair,
 // dispatched by wave_rows.hip), wave_masked.hip (k_wave_masked), dense_rows.hip (k_dense_rows, k_dense_rows_count,
 // k_rank_rows) over the heavy rows' gather in heavy_gather.hpp, compact.hip (compaction, heavy-row moves),
-// small.hip, transpose.hip.  A family is ONE template kernel with the mask mode as a template parameter.
+// small.hip, transpose.hip, select.hip.  A family is ONE template kernel with the mask mode as a template parameter.
 // Tuning constants are compile-time constants, not switches: what was tried against them is in profiles/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -239,6 +239,28 @@ void launch_small(const int *Arow, const int *Acol, const int *Brow, const int *
 void launch_narrow_row_ptr(const long long *src, int *dst, int n, hipStream_t s);
 // T = A or I as CSR: row i gets column i appended (duplicates are legal in operands)
 void launch_add_diagonal(const int *Arow, const int *Acol, int n, int *Trow, int *Tcol, hipStream_t s);
+
+// ---- stable select of CSR entries and the reduction of values (select.hip) --------------------------
+// A select over nnz entries works in tiles of kSelTile entries and keeps, per 64 entries, one flag word (bit b of word w:
+// entry 64 w + b is kept) and its popcount: select_words(nnz) of each, whole tiles (the words past the last entry are 0).
+constexpr int kSelTile = kRowWorkTile;     // the structural select borrows the flat prepass's tile_row (ensure_tile_rows(nnz))
+inline size_t select_words(long long nnz) { return (size_t)((nnz + kSelTile - 1) / kSelTile) * (kSelTile / 64); }
+// pass 1, structural: entry (r, c) is kept when c < r (op 1, BSPGEMM_SELECT_TRIL), c > r (2, TRIU), c != r (3, OFFDIAG);
+// tile_row: nnz / kSelTile + 1 ints of scratch
+void launch_select_flags_struct(const int *row_ptr, const int *col_idx, int rows, long long nnz, int op, int *tile_row,
+                                unsigned long long *flags, int *cnt, hipStream_t s);
+// pass 1, by value: entry e is kept when vals[e] cmp threshold (cmp: a bspgemm_compare)
+void launch_select_flags_value(const int *vals, long long nnz, int cmp, int threshold, unsigned long long *flags, int *cnt,
+                               hipStream_t s);
+// pass 2: out[prefix[w] + (kept entries of word w before e)] = src[e] for every kept entry; prefix = the exclusive scan
+// of cnt (launch_scan_counts), select_words(nnz) + 1 entries
+void launch_select_scatter(const int *src, long long nnz, const unsigned long long *flags, const long long *prefix, int *out,
+                           hipStream_t s);
+// out[r] = kept entries before position row_ptr[r], r in [0, rows]; the unfiltered row_ptr is row_ptr32, or (NULL) row_ptr64
+void launch_select_row_ptr(const int *row_ptr32, const long long *row_ptr64, int rows, long long nnz,
+                           const unsigned long long *flags, const long long *prefix, int *out, hipStream_t s);
+// *sum (device, zeroed by the caller) += vals[0 .. nnz), exact in 64 bits
+void launch_values_sum(const int *vals, long long nnz, unsigned long long *sum, hipStream_t s);
 
 // row_ptr rebasing helper for interior-pointer uploads
 void launch_rebase_i32(int *row_ptr, int n, int base, hipStream_t s);

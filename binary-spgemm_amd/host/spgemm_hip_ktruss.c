@@ -1,0 +1,70 @@
+/*
+ * spgemm_hip_ktruss.c -- triangle count and k-truss of an undirected graph, everything resident on the GPU: the
+ * applications the counting masked product was added for (include/bspgemm.h: bspgemm_triangle_count, bspgemm_ktruss),
+ * beside the closure driver (spgemm_hip_closure.c).
+ *
+ *     SpGEMM_hip_ktruss  file.mtx  k  [out.mtx]
+ *
+ * Prints one CSV line: n,nnz,triangles,k,truss_nnz,iterations,converged,ms.  file.mtx is read with
+ * BSPGEMM_READ_EXPAND_SYMMETRIC, so a file that stores one triangle of a symmetric matrix gives the whole graph (nnz is the
+ * expanded count); the loader hands back the transpose of the file's matrix (readCOO, final/utils.c:47-81), which for a
+ * symmetric pattern is the matrix itself, and bspgemm_write_mtx writes T such that the loader reconstructs exactly T.
+ * ms: wall time of the triangle count and the k-truss together, operands already on the device.
+ */
+#include "../../include/bspgemm.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <time.h>
+
+#define CHECK(st, what)                                                                         \
+    do {                                                                                        \
+        bspgemm_status s_ = (st);                                                               \
+        if (s_ != BSPGEMM_OK) {                                                                 \
+            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
+            exit(1);                                                                            \
+        }                                                                                       \
+    } while (0)
+
+int main(int argc, char **argv)
+{
+    if (argc != 3 && argc != 4) {
+        printf("usage: SpGEMM_hip_ktruss  path-to-matrix  k  [path-to-truss]\n");
+        exit(1);
+    }
+    const int k = atoi(argv[2]);
+    uint32_t *Arow, *Acol, M, N, nnz;
+    bspgemm_status st = bspgemm_readCOO_ex(argv[1], BSPGEMM_READ_EXPAND_SYMMETRIC, &Arow, &Acol, &M, &N, &nnz);
+    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
+    if (st != BSPGEMM_OK) exit(1);
+    if (M != N) { fprintf(stderr, "k-truss needs a square matrix (%ux%u)\n", M, N); exit(1); }
+    const char *devenv = getenv("BSPGEMM_DEVICE");
+    bspgemm_context *ctx;
+    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    bspgemm_matrix *A, *T;
+    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    int64_t triangles = 0;
+    int iterations = 0, converged = 0;
+    CHECK(bspgemm_triangle_count(ctx, A, &triangles), "bspgemm_triangle_count");
+    CHECK(bspgemm_ktruss(ctx, A, k, 0, &T, &iterations, &converged), "bspgemm_ktruss");
+    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    const long long tn = bspgemm_matrix_nnz(T);
+    printf("%u,%u,%lld,%d,%lld,%d,%d,%.3f\n", M, nnz, (long long)triangles, k, tn, iterations, converged, ms);
+    if (argc == 4) {
+        int *rp = malloc(((size_t)M + 1) * sizeof(int));
+        int *ci = malloc((size_t)(tn > 0 ? tn : 1) * sizeof(int));
+        if (!rp || !ci) exit(1);
+        CHECK(bspgemm_matrix_download(ctx, T, rp, ci), "download");
+        CHECK(bspgemm_write_mtx(argv[3], (int)M, (int)M, rp, ci), "write");
+        free(rp); free(ci);
+    }
+    bspgemm_matrix_free(T);
+    bspgemm_matrix_free(A);
+    bspgemm_destroy(ctx);
+    free(Arow); free(Acol);
+    return 0;
+}

@@ -280,6 +280,66 @@ void           bspgemm_result_free(bspgemm_result *C);
 bspgemm_status bspgemm_matrix_from_result(bspgemm_context *ctx, const bspgemm_result *C, int cols,
                                           bspgemm_matrix **out);
 
+/* A stable filter of an operand's entries by their place: out = the entries (r, c) of A that `op` keeps, in A's shape.
+ *   - Stable: the kept entries of each row keep their order and repeats are kept -- neither a sort nor a dedup
+ *     (transposing twice does that).  The pattern is scipy's tril(A, -1) / triu(A, 1) / both, entry for entry as stored.
+ *   - A may come from upload (interior row_ptr included), wrap_device, matrix_from_result, transpose or an earlier select;
+ *     any shape, rows == 0 and nnz == 0 included.
+ *   - out is an owned operand with the layout of an uploaded one (its derived tables as after upload, nnz + 1 ints of
+ *     col_idx): usable in every product; release it with bspgemm_matrix_free.
+ *   - Runs on the context's stream with ONE synchronisation (the kept count is known only after the count pass); out is
+ *     complete on that stream when the call returns.  It does not touch the multiply statistics.
+ *   - Work is spread over entries, not rows (a hub row costs what its entries cost).  Scratch: 12 bytes per 64 entries
+ *     of A and the 8-byte scan of the counts, in the context's workspace (kept, like the transpose's).  An allocation
+ *     failure returns BSPGEMM_ERR_ALLOC and leaks nothing.
+ *   - BSPGEMM_ERR_INVALID with *out = NULL: an unknown op, a NULL argument, A from another context.                     */
+typedef enum bspgemm_select { BSPGEMM_SELECT_TRIL = 1,      /* col <  row  (strictly lower) */
+                              BSPGEMM_SELECT_TRIU = 2,      /* col >  row  (strictly upper) */
+                              BSPGEMM_SELECT_OFFDIAG = 3 }  /* col != row                   */ bspgemm_select;
+bspgemm_status bspgemm_matrix_select(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_select op, bspgemm_matrix **out);
+
+/* bspgemm_matrix_from_result with a filter on the values of a counted result (bspgemm_multiply_masked_count): out = the
+ * pattern of the entries of C with  value cmp threshold, rows still ascending.  GE with threshold <= 1 gives exactly
+ * bspgemm_matrix_from_result's operand (a counted result stores only counts > 0).  `cols` = number of columns of C.
+ *   - The int32 limit applies to the KEPT count, not to nnz(C): a result above 2^31 - 1 entries whose selection fits is
+ *     accepted (positions are 64-bit inside the kernels); more than INT_MAX kept entries: BSPGEMM_ERR_OVERFLOW, nothing
+ *     is leaked.
+ *   - BSPGEMM_ERR_INVALID with *out = NULL: a pattern-only result (bspgemm_result_values_device(C) == NULL), an unknown
+ *     comparison, a NULL argument, C from another context.
+ *   - Stream, synchronisation, scratch, statistics and the finished operand: as bspgemm_matrix_select.                   */
+typedef enum bspgemm_compare { BSPGEMM_CMP_GE = 1, BSPGEMM_CMP_GT, BSPGEMM_CMP_LE, BSPGEMM_CMP_LT, BSPGEMM_CMP_EQ, BSPGEMM_CMP_NE } bspgemm_compare;
+bspgemm_status bspgemm_matrix_from_result_where(bspgemm_context *ctx, const bspgemm_result *C, int cols,
+                                                bspgemm_compare cmp, int threshold, bspgemm_matrix **out);
+
+/* *sum = the exact int64 sum of the values of a counted result, reduced on the device (integer addition: the order does
+ * not matter); 8 bytes come back.  A pattern-only result: BSPGEMM_ERR_INVALID, *sum untouched.                           */
+bspgemm_status bspgemm_result_values_sum(bspgemm_context *ctx, const bspgemm_result *C, int64_t *sum);
+
+/* Triangles of the undirected simple graph whose edges are the {i, j} with i > j and (i, j) stored in A (A square; for a
+ * symmetric A that is A's graph).  The diagonal and the upper triangle are not read, repeated entries count once.
+ * L = the strictly lower triangle (bspgemm_matrix_select) with sorted duplicate-free rows (transposed twice),
+ * C = L .* (L*L) with counts (bspgemm_multiply_masked_count), *triangles = the sum of C's values: everything stays on the
+ * device except the final 8 bytes.  bspgemm_last_stats afterwards describes that counted product.
+ * BSPGEMM_ERR_INVALID: a non-square A, a NULL argument, A from another context.                                           */
+bspgemm_status bspgemm_triangle_count(bspgemm_context *ctx, const bspgemm_matrix *A, int64_t *triangles);
+
+/* k-truss, everything device-resident (the loop that bspgemm_closure is for squaring): S0 = A without its diagonal, rows
+ * sorted and duplicate-free; a step is C = S .* (S*S) with counts over all rows, then S' = the entries of C with a count
+ * of k - 2 or more (bspgemm_matrix_from_result_where; the counted product stores only counts > 0 and k - 2 >= 1, so edges
+ * without support drop out by themselves).  S' is a subset of S, so equal nnz means equal sets.  A must be square.
+ *   - k == 2: T = S0, *iterations = 0, *converged = 1.
+ *   - k >= 3: the loop ends when a step removes nothing (*converged = 1, T = that S), when a step leaves nothing
+ *     (*converged = 1, T empty, no further product), or after max_iter steps when max_iter > 0 (*converged = 0, T = the
+ *     last S').  max_iter <= 0: no cap -- every step but the last removes an entry, so the loop ends.
+ *   - *iterations = counted products computed.  iterations and converged may be NULL.
+ *   - A symmetric A: T is the k-truss in the usual convention, the maximal subgraph in which every edge lies in at least
+ *     k - 2 triangles: symmetric, rows sorted and duplicate-free, nnz(T) = 2 x edges.  A non-symmetric A: T is simply the
+ *     fixpoint of the iteration above (symmetry is not checked).
+ *   - T is an owned operand (bspgemm_matrix_free).  Any failure inside the loop frees every intermediate.
+ *   - BSPGEMM_ERR_INVALID with *T = NULL: k < 2, a non-square A, a NULL argument, A from another context.               */
+bspgemm_status bspgemm_ktruss(bspgemm_context *ctx, const bspgemm_matrix *A, int k, int max_iter,
+                              bspgemm_matrix **T, int *iterations, int *converged);
+
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
  * an OR-accumulating variant for it): T0 = A or I, T(k+1) = T(k)*T(k) until nnz stops growing
