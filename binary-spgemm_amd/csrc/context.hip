@@ -93,26 +93,31 @@ bspgemm_status ensure_pad(const bspgemm_matrix *m)
 }
 
 // Whether products with `m` as B go through the blocked table.  It pays when B.row_ptr is several
-// times an XCD's 4 MB L2 (R-MAT scale 22: 16.8 MB, k_row_work 1.20 -> 0.92 ms) and the operand is not
-// dominated by rows of 255+ nonzeros, whose lengths the table clamps (power-law n = 2^20: B.row_ptr
-// fits L2 anyway and 10 % of the lookups fall through: 2.0 -> 3.0 ms; Graph500 skew: 70 % fall through).
+// times an XCD's 4 MB L2 (R-MAT scale 22: 16.8 MB against a table of 4.2 MB) and the operand is not
+// dominated by rows of 63+ nonzeros, whose lengths the table clamps: a quarter of the nonzeros in such
+// rows at the most.  Measured at 2^21 rows (prepass phase, table forbidden / forced): R-MAT
+// (0.30,0.25,0.25,0.20) edge factor 16, 0.4 % of the nonzeros in clamped rows, 0.52 / 0.30 ms; R-MAT
+// (0.45,0.22,0.22,0.11) edge factor 4, 15 % (a third of the look-ups fall through to B.row_ptr),
+// 0.33 / 0.14 ms.  Graph500 skew (77 %, nine look-ups of ten fall through) stays with B.row_ptr: the bound is
+// a cautious one, on the upper quarter of its rows (the whole product does not fit a card) the forced table
+// was faster as well, 0.22 / 0.06 ms.
 // Decided once per operand: one 8-byte read-back when the table is built.
-bspgemm_status ensure_blk8(const bspgemm_matrix *m)
+bspgemm_status ensure_blk16(const bspgemm_matrix *m)
 {
-    if (m->blk8_state) return BSPGEMM_OK;
-    m->blk8_state = 2;
+    if (m->blk16_state) return BSPGEMM_OK;
+    m->blk16_state = 2;
     const int force = m->ctx->rw_blk;                              // 0 never, 1 always, -1 decide per operand
     if (force == 0 || (force < 0 && m->rows < (1 << 21))) return BSPGEMM_OK;
-    const size_t ints = (size_t)3 * (((size_t)m->rows + 7) / 8 + 1);
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_blk8), (ints + 4) * sizeof(int)));
-    unsigned long long *d_clamped = reinterpret_cast<unsigned long long *>(m->d_blk8 + ((ints + 1) & ~(size_t)1));
+    const size_t ints = (size_t)4 * (((size_t)m->rows + 15) / 16 + 1);   // 16-byte entries (hipMalloc aligns them), one spare
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_blk16), (ints + 4) * sizeof(int)));
+    unsigned long long *d_clamped = reinterpret_cast<unsigned long long *>(m->d_blk16 + ints);
     HIPCHK(hipMemsetAsync(d_clamped, 0, sizeof(unsigned long long), m->ctx->stream));
-    launch_blk8(m->d_row_ptr, m->pad_state == 1 ? m->d_row_ptr_pad : nullptr, m->rows, m->d_blk8, d_clamped, m->ctx->stream);
+    launch_blk16(m->d_row_ptr, m->pad_state == 1 ? m->d_row_ptr_pad : nullptr, m->rows, m->d_blk16, d_clamped, m->ctx->stream);
     HIPCHK(hipGetLastError());
     unsigned long long clamped = 0;
     HIPCHK(hipMemcpyAsync(&clamped, d_clamped, sizeof(clamped), hipMemcpyDeviceToHost, m->ctx->stream));
     HIPCHK(hipStreamSynchronize(m->ctx->stream));
-    if (force == 1 || clamped * 8ull <= (unsigned long long)m->nnz) m->blk8_state = 1;
+    if (force == 1 || clamped * 4ull <= (unsigned long long)m->nnz) m->blk16_state = 1;
     return BSPGEMM_OK;
 }
 
@@ -286,7 +291,7 @@ extern "C" void bspgemm_matrix_free(bspgemm_matrix *m)
         hipFree(m->d_col_idx);
     }
     hipFree(m->d_deg8);
-    hipFree(m->d_blk8);
+    hipFree(m->d_blk16);
     hipFree(m->d_col_pad);
     hipFree(m->d_row_ptr_pad);
     hipFree(m->d_ext);
@@ -310,13 +315,13 @@ extern "C" bspgemm_status bspgemm_matrix_invalidate(bspgemm_matrix *m)
     if (bspgemm_status st = use_device(m->ctx)) return st;
     HIPCHK(hipStreamSynchronize(m->ctx->stream));          // a multiply may still be reading the tables
     hipFree(m->d_deg8);
-    hipFree(m->d_blk8);
+    hipFree(m->d_blk16);
     hipFree(m->d_col_pad);
     hipFree(m->d_row_ptr_pad);
     hipFree(m->d_ext);
     m->d_deg8 = nullptr;
-    m->d_blk8 = nullptr;
-    m->blk8_state = 0;
+    m->d_blk16 = nullptr;
+    m->blk16_state = 0;
     m->d_col_pad = nullptr;
     m->d_row_ptr_pad = nullptr;
     m->d_ext = nullptr;
@@ -612,8 +617,8 @@ extern "C" int bspgemm_matrix_uses_padded_rows(const bspgemm_matrix *m)
 
 extern "C" int bspgemm_matrix_uses_blocked_table(const bspgemm_matrix *m)
 {
-    if (!m || m->blk8_state == 0) return -1;
-    return m->blk8_state == 1 ? 1 : 0;
+    if (!m || m->blk16_state == 0) return -1;
+    return m->blk16_state == 1 ? 1 : 0;
 }
 
 extern "C" bspgemm_status bspgemm_set_flow(bspgemm_context *ctx, int flow)

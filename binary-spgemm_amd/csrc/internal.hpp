@@ -145,10 +145,10 @@ struct bspgemm_matrix {
     // per A-nonzero to size its rows (csrc/prepass.hip: k_row_products).  Part of the operand's
     // device layout: built when the operand is created (lazily for wrapped device arrays).
     mutable unsigned char *d_deg8 = nullptr;
-    // blocked extents table {row_ptr of every 8th row, 8 clamped lengths}: what k_row_work gathers per
+    // blocked extents table {row_ptr of every 16th row, 16 clamped lengths}: what the prepass gathers per
     // A-nonzero instead of a B.row_ptr pair (csrc/prepass.hip: k_row_work_flat); built on first use as B
-    mutable int *d_blk8 = nullptr;
-    mutable int blk8_state = 0;          // 0 undecided, 1 in use, 2 not worth it for this operand
+    mutable int *d_blk16 = nullptr;
+    mutable int blk16_state = 0;          // 0 undecided, 1 in use, 2 not worth it for this operand
     // padded copy of col_idx: every row on a 64-byte boundary (padded to a multiple of 16 entries), so that a gathered B row
     // touches ceil(len / 16) 64-byte sectors instead of one more; built on first use as B (ensure_pad) when it pays
     mutable int *d_col_pad = nullptr;
@@ -163,8 +163,8 @@ struct bspgemm_matrix {
 };
 
 bspgemm_status ensure_deg8(const bspgemm_matrix *m);
-bspgemm_status ensure_blk8(const bspgemm_matrix *m);
-bspgemm_status ensure_pad(const bspgemm_matrix *m);   // before ensure_blk8: the blocked table carries padded bases
+bspgemm_status ensure_blk16(const bspgemm_matrix *m);
+bspgemm_status ensure_pad(const bspgemm_matrix *m);   // before ensure_blk16: the blocked table carries padded bases
 
 struct bspgemm_result {
     bspgemm_context *ctx;

@@ -86,18 +86,18 @@ struct RowRec {
 
 // F_i = sum_{j in A_i} |B_j| for rows [row_begin,row_end)  ->  F[i-row_begin];
 // ab[jj] = (start of B row A.col_idx[jj], |B_j|) for every A-nonzero of those rows.  What is gathered per A-nonzero:
-//   Bblk8 != NULL   B's blocked extents table (launch_blk8); with Bpad (the padded row_ptr) its bases and the starts are
+//   Bblk16 != NULL   B's blocked extents table (launch_blk16); with Bpad (the padded row_ptr) its bases and the starts are
 //                   positions in the PADDED copy of B.col_idx
 //   else Bext       the per-row table {start in the padded copy, length}
 //   else            a B.row_ptr pair (starts in B.col_idx itself)
-// With Bblk8 the pass is flat, in tiles of kRowWorkTile merged positions (each row's nonzeros and one end item):
+// With Bblk16 the pass is flat, in tiles of kRowWorkTile merged positions (each row's nonzeros and one end item):
 // nnz_bound (host) bounds the range's nonzeros, tile_row has room for (nnz_bound + rows) / kRowWorkTile + 2 ints.
 constexpr int kRowWorkTile = 4096;
-void launch_row_work(const int *Arow, const int *Acol, const int *Brow, const int *Bblk8, const int *Bpad, const int2 *Bext,
+void launch_row_work(const int *Arow, const int *Acol, const int *Brow, const int *Bblk16, const int *Bpad, const int2 *Bext,
                      int row_begin, int row_end, long long nnz_bound, int *tile_row, long long *F, int2 *ab, hipStream_t s);
-// blk[3b..3b+2] = {start_ptr[8b] (NULL: row_ptr), lengths of rows 8b..8b+7 clamped to 255, one byte each}
-// *clamped_nnz (device, zeroed by the caller) += nonzeros in rows of 255 or more
-void launch_blk8(const int *row_ptr, const int *start_ptr, int n, int *blk, unsigned long long *clamped_nnz, hipStream_t s);
+// blk[4g..4g+3] = {start_ptr[16g] (NULL: row_ptr), lengths of rows 16g..16g+15 clamped to 63, six bits each}: 16-byte aligned
+// *clamped_nnz (device, zeroed by the caller) += nonzeros in rows of 63 or more
+void launch_blk16(const int *row_ptr, const int *start_ptr, int n, int *blk, unsigned long long *clamped_nnz, hipStream_t s);
 // padded copy of an operand's col_idx (rows on 64-byte boundaries): plen[j] = ceil(len_j / 16) * 16; then, with pad_ptr =
 // its exclusive scan, the rows copied to col_pad and (ext != NULL) ext[j] = {pad_ptr[j], len_j}
 void launch_pad_lengths(const int *row_ptr, int n, int *plen, hipStream_t s);
@@ -161,8 +161,8 @@ hipError_t launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol
                             const RowRec *rec, const long long *recpre, const long long *row_ptr, int nrows,
                             int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode, const int *Frow, const int *Fcol,
                             hipStream_t s, bool count_only = false);
-// debug check (BSPGEMM_OPT_CHECK): deg8[] / blk8[] / the padded row_ptr (each may be NULL) against row_ptr; sets kErrStaleTable in *err
-void launch_check_tables(const int *row_ptr, int rows, const unsigned char *deg8, const int *blk8, const int *pad_ptr, unsigned *err,
+// debug check (BSPGEMM_OPT_CHECK): deg8[] / blk16[] / the padded row_ptr (each may be NULL) against row_ptr; sets kErrStaleTable in *err
+void launch_check_tables(const int *row_ptr, int rows, const unsigned char *deg8, const int *blk16, const int *pad_ptr, unsigned *err,
                          hipStream_t s);
 
 // heavy rows: workspace -> final place (one workgroup per heavy row)

@@ -141,15 +141,15 @@ static bspgemm_status start_flow(bspgemm_context *ctx, const bspgemm_matrix *A, 
     HIPCHK_B(hipEventRecord(slot.ev[0], s));
     HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&C->d_row_ptr), result_bytes_rowptr(R)));
     if (bspgemm_status st = ensure_pad(B)) return bail(st);
-    if (bspgemm_status st = ensure_blk8(B)) return bail(st);
+    if (bspgemm_status st = ensure_blk16(B)) return bail(st);
     if (ctx->check) {              // BSPGEMM_OPT_CHECK: B's derived tables verified against its row_ptr before the prepass uses them
         HIPCHK_B(hipMemsetAsync(ctx->d_err, 0, sizeof(unsigned), s));
-        launch_check_tables(B->d_row_ptr, B->rows, B->d_deg8, B->blk8_state == 1 ? B->d_blk8 : nullptr,
+        launch_check_tables(B->d_row_ptr, B->rows, B->d_deg8, B->blk16_state == 1 ? B->d_blk16 : nullptr,
                             B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, ctx->d_err, s);
     }
-    slot.prepass_kernel = B->blk8_state == 1 ? 1 : 0;
+    slot.prepass_kernel = B->blk16_state == 1 ? 1 : 0;
     slot.padded = B->pad_state == 1;
-    launch_row_work(A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->blk8_state == 1 ? B->d_blk8 : nullptr,
+    launch_row_work(A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->blk16_state == 1 ? B->d_blk16 : nullptr,
                     B->pad_state == 1 ? B->d_row_ptr_pad : nullptr, B->pad_state == 1 ? B->d_ext : nullptr, row_begin, row_end,
                     A->nnz, ctx->tile_row, ctx->F, ctx->ab, s);
     *Cp = C;

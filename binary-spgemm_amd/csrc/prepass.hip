@@ -105,73 +105,92 @@ __global__ __launch_bounds__(256) void k_row_work(const int *__restrict__ Arow,
 }
 
 // ---------------------------------------------------------------------------------------
-// The same pass through B's BLOCKED extents table: per 8 rows of B one 12-byte entry
-// {row_ptr of the block's first row, the 8 row lengths clamped to 255}.  The table is 1.5 B per
-// row (6.3 MB at 4.2 M rows against 16.8 MB of B.row_ptr), so most of it stays in an XCD's 4 MB L2
-// on a skewed input and the 64-byte sectors that do come from the fabric are shared by 5 blocks
-// = 40 rows instead of 16.  start = base + sum of the lengths below the row in its block (two
-// v_sad_u8), length = the row's byte; a block with a clamped byte at or below the row is looked up
-// in B.row_ptr itself (rows of 255+ nonzeros: rare).
-struct __attribute__((packed, aligned(4))) Blk8 { int base; unsigned lo, hi; };   // 12 B, only dword aligned
+// The same pass through B's BLOCKED extents table: per 16 rows of B one 16-byte entry
+// {row_ptr of the group's first row, w0, w1, w2}: the 16 row lengths clamped to 63, six bits each.  Row 5i + s of the group
+// (s < 5) is the field at bit 6s of w_i; the two top bits of w0, w1, w2 together hold the 16th length, which is never part
+// of a sum.  The table is 1 B per row (4.19 MB at 4.2 M rows against 16.8 MB of B.row_ptr), about what an XCD's 4 MB L2 holds
+// beside the streams: the 8-row form of 12 bytes (1.5 B per row, 6.3 MB) missed on a third of its look-ups, and its gather
+// alone took 0.555 ms on the bench matrix against 0.472 ms for this one (tools/micro/prepass_gather.hip).  One aligned
+// 16-byte gather per look-up, never across a 64-byte sector.  start = base + sum of the lengths below the row in its group
+// (SWAR over the 6-bit fields), length = the row's field; a group with a clamped field at or below the row is looked up in
+// B.row_ptr itself (rows of 63+ nonzeros: 0.1 % of the bench matrix's rows, 2.3 % of its look-ups).
+constexpr int kBlkClamp = 63;
 
-__global__ __launch_bounds__(256) void k_blk8(const int *__restrict__ row_ptr, const int *__restrict__ start_ptr, int n,
-                                              int *__restrict__ blk, unsigned long long *__restrict__ clamped_nnz)
+__device__ __forceinline__ unsigned blk16_field(int d) { return (unsigned)(d < kBlkClamp ? d : kBlkClamp); }
+
+__global__ __launch_bounds__(256) void k_blk16(const int *__restrict__ row_ptr, const int *__restrict__ start_ptr, int n,
+                                               int4 *__restrict__ blk, unsigned long long *__restrict__ clamped_nnz)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b * 8 >= n) return;
-    const int r0 = b * 8;
-    unsigned lo = 0u, hi = 0u;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if ((long long)g * 16 >= n) return;
+    const int r0 = g * 16;
+    unsigned w[3] = {0u, 0u, 0u};
     long long clamped = 0;
     int prev = row_ptr[r0];
-    const int base = start_ptr[r0];                                // where the block's first row starts (B.col_idx or its padded copy)
+    const int base = start_ptr[r0];                                // where the group's first row starts (B.col_idx or its padded copy)
 #pragma unroll
-    for (int k = 0; k < 8; k++) {
+    for (int k = 0; k < 16; k++) {
         int d = 0;
         if (r0 + k < n) {
             const int nx = row_ptr[r0 + k + 1];
             d = nx - prev;
             prev = nx;
         }
-        const unsigned byte = (unsigned)(d < 255 ? d : 255);
-        if (d >= 255) clamped += d;
-        if (k < 4) lo |= byte << (8 * k); else hi |= byte << (8 * (k - 4));
+        const unsigned f = blk16_field(d);
+        if (d >= kBlkClamp) clamped += d;
+        if (k < 15) w[k / 5] |= f << (6 * (k % 5));
+        else { w[0] |= (f & 3u) << 30; w[1] |= ((f >> 2) & 3u) << 30; w[2] |= (f >> 4) << 30; }
     }
-    // nonzeros that live in clamped rows: how skewed the operand is (the caller's switch, see api.hip)
+    // nonzeros that live in clamped rows: how skewed the operand is (the caller's switch, see context.hip)
     if (clamped > 0) atomicAdd(clamped_nnz, (unsigned long long)clamped);
-    blk[3 * b] = base;
-    blk[3 * b + 1] = (int)lo;
-    blk[3 * b + 2] = (int)hi;
+    blk[g] = make_int4(base, (int)w[0], (int)w[1], (int)w[2]);
 }
-void launch_blk8(const int *row_ptr, const int *start_ptr, int n, int *blk, unsigned long long *clamped_nnz, hipStream_t s)
+void launch_blk16(const int *row_ptr, const int *start_ptr, int n, int *blk, unsigned long long *clamped_nnz, hipStream_t s)
 {
     if (n <= 0) return;
-    const int nb = (n + 7) / 8;
-    hipLaunchKernelGGL(k_blk8, dim3((nb + 255) / 256), dim3(256), 0, s, row_ptr, start_ptr ? start_ptr : row_ptr, n, blk, clamped_nnz);
+    const int ng = (n + 15) / 16;
+    hipLaunchKernelGGL(k_blk16, dim3((ng + 255) / 256), dim3(256), 0, s, row_ptr, start_ptr ? start_ptr : row_ptr, n,
+                       reinterpret_cast<int4 *>(blk), clamped_nnz);
 }
 
-// One blocked-table entry decoded for B row j: where the row starts (PAD: in the padded copy of B.col_idx; the table's `base`
-// is then the block's first row there and a row starts behind the padded lengths below it -- ceil(len / 16) * 16, summed over
-// the bytes in SWAR form) and its length.  sat: a clamped byte at or below the row, so both come from B.row_ptr (and Bpad).
-template <bool PAD>
-__device__ __forceinline__ void blk8_extent(const Blk8 &w, int j, int &start, int &len, bool &sat)
+// the 16th length of a group
+__device__ __forceinline__ unsigned blk16_last(unsigned w0, unsigned w1, unsigned w2)
 {
-    const int k = j & 7;
-    const u64 d = ((u64)w.hi << 32) | (u64)w.lo;
-    const u64 below = d & ((1ull << (8 * k)) - 1ull);
-    const u64 upto = (k == 7) ? d : (d & ((1ull << (8 * k + 8)) - 1ull));
-    const u64 v = ~upto;                                           // a 255 byte at or below the row -> a zero byte here
-    sat = ((v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull) != 0ull;
+    return (w0 >> 30) | ((w1 >> 30) << 2) | ((w2 >> 30) << 4);
+}
+
+// One blocked-table entry decoded for B row j: where the row starts and its length.  x_i = the fields of w_i below the row
+// (the two top bits cleared with them).  The sum: even fields of the three words added up in 12-bit lanes at bits 0, 12, 24
+// (3 * 63 fits the top lane's 8 bits), odd ones at 6 and 18, then the five lanes.  PAD: the table's `base` is the group's
+// first row in the padded copy of B.col_idx and a row starts behind the padded lengths below it, ceil(len / 16) sixteenths
+// each = (len >> 4) + ((len & 15) != 0), at most 4 per field: these stay in their 6-bit fields, the three words add up
+// without a carry (12 per field) and one multiply sums the five fields into the top one (at most 60).
+// sat: a clamped field at or below the row, so both come from B.row_ptr (and Bpad).
+template <bool PAD>
+__device__ __forceinline__ void blk16_extent(const int4 &g, int j, int &start, int &len, bool &sat)
+{
+    const unsigned w0 = (unsigned)g.y, w1 = (unsigned)g.z, w2 = (unsigned)g.w;
+    const int k = j & 15, t = 6 * k;
+    const int b0 = min(t, 30), b1 = min(max(t - 30, 0), 30), b2 = min(max(t - 60, 0), 30);
+    const unsigned x0 = w0 & ((1u << b0) - 1u), x1 = w1 & ((1u << b1) - 1u), x2 = w2 & ((1u << b2) - 1u);
     if (PAD) {
-        // sixteenths of each length below the row, rounded up: (len >> 4) + ((len & 15) != 0), byte by byte
-        const u64 m0f = 0x0f0f0f0f0f0f0f0full, m01 = 0x0101010101010101ull;
-        const u64 units = ((below >> 4) & m0f) + ((((below & m0f) + m0f) >> 4) & m01);
-        start = w.base + 16 * ((int)__builtin_amdgcn_sad_u8((unsigned)units, 0u, 0u)
-                               + (int)__builtin_amdgcn_sad_u8((unsigned)(units >> 32), 0u, 0u));
+        auto units = [](unsigned x) {
+            return ((x >> 4) & 0x030c30c3u) + ((((x & 0x0f3cf3cfu) + 0x0f3cf3cfu) >> 4) & 0x01041041u);
+        };
+        const unsigned u = units(x0) + units(x1) + units(x2);
+        start = g.x + 16 * (int)(((u * 0x01041041u) >> 24) & 63u);
     } else {
-        start = w.base + (int)__builtin_amdgcn_sad_u8((unsigned)below, 0u, 0u)
-                + (int)__builtin_amdgcn_sad_u8((unsigned)(below >> 32), 0u, 0u);
+        const unsigned me = 0x3f03f03fu, mo = 0x00fc0fc0u;
+        const unsigned e = (x0 & me) + (x1 & me) + (x2 & me), o = (x0 & mo) + (x1 & mo) + (x2 & mo);
+        start = g.x + (int)((e & 0xfffu) + ((e >> 12) & 0xfffu) + (e >> 24) + ((o >> 6) & 0xfffu) + (o >> 18));
     }
-    len = (int)((d >> (8 * k)) & 255ull);
+    const unsigned wk = k < 5 ? w0 : (k < 10 ? w1 : w2);
+    const int sh = t - (k < 5 ? 0 : (k < 10 ? 30 : 60));
+    len = k == 15 ? (int)blk16_last(w0, w1, w2) : (int)((wk >> sh) & 63u);
+    // a field of 63 below the row: its six bits are ones, so the complement's field is zero (the classic zero-field test;
+    // a false flag can only stand above a true one)
+    auto full = [](unsigned x) { return (~x - 0x01041041u) & x & 0x20820820u; };
+    sat = ((full(x0) | full(x1) | full(x2)) != 0u) || len == kBlkClamp;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -243,23 +262,26 @@ __global__ __launch_bounds__(256) void k_row_work_flat(const int *__restrict__ A
     int fa0 = 0, fa1 = 0;
     if (rb + tid <= rl) { fa0 = rp[rb + tid]; fa1 = rp[rb + tid + 1]; }
 
+    // A.col_idx in and ab[] out are streamed past the L2 (non-temporal): what should stay there is B's table, which is
+    // about the L2's size.  All K gathers of a lane are in flight at once: 8 at a time at four waves per SIMD instead of
+    // three was 0.03 ms slower on the bench matrix, streaming the two arrays 0.05 ms faster.
     int j[K];
 #pragma unroll
-    for (int k = 0; k < K; k++) j[k] = tid + 256 * k < n ? Acol[g0 + tid + 256 * k] : -1;
-    Blk8 w[K];
+    for (int k = 0; k < K; k++) j[k] = tid + 256 * k < n ? __builtin_nontemporal_load(Acol + g0 + tid + 256 * k) : -1;
+    int4 w[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        w[k].base = 0; w[k].lo = w[k].hi = 0u;
-        if (j[k] >= 0) w[k] = *reinterpret_cast<const Blk8 *>(Bblk + 3 * (j[k] >> 3));
+        w[k] = make_int4(0, 0, 0, 0);
+        if (j[k] >= 0) w[k] = reinterpret_cast<const int4 *>(Bblk)[j[k] >> 4];
     }
     int start[K], len[K];
     bool sat[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        blk8_extent<PAD>(w[k], j[k], start[k], len[k], sat[k]);
+        blk16_extent<PAD>(w[k], j[k], start[k], len[k], sat[k]);
         sat[k] = sat[k] && j[k] >= 0;
     }
-    // clamped lengths (B rows of 255+ nonzeros -- the hubs of a skewed graph, so these reads hit L2): the exact pairs,
+    // clamped lengths (B rows of 63+ nonzeros -- the hubs of a skewed graph, so these reads hit L2): the exact pairs,
     // again issued together
     Int2U pr[K];
     int ps[K];
@@ -277,7 +299,9 @@ __global__ __launch_bounds__(256) void k_row_work_flat(const int *__restrict__ A
         const int p = tid + 256 * k;
         if (sat[k]) { start[k] = PAD ? ps[k] : pr[k].x; len[k] = pr[k].y - pr[k].x; }
         if (j[k] < 0) len[k] = 0;
-        else ab[g0 + p] = make_int2(start[k], len[k]);
+        else                                                       // {start, len} as one 8-byte streamed store
+            __builtin_nontemporal_store((long long)(((u64)(unsigned)len[k] << 32) | (u64)(unsigned)start[k]),
+                                        reinterpret_cast<long long *>(ab + g0 + p));
         L[p + 4 * (p / K)] = len[k];
     }
     __syncthreads();
@@ -325,19 +349,19 @@ __global__ __launch_bounds__(256) void k_row_work_flat(const int *__restrict__ A
     }
 }
 
-void launch_row_work(const int *Arow, const int *Acol, const int *Brow, const int *Bblk8, const int *Bpad, const int2 *Bext,
+void launch_row_work(const int *Arow, const int *Acol, const int *Brow, const int *Bblk16, const int *Bpad, const int2 *Bext,
                      int row_begin, int row_end, long long nnz_bound, int *tile_row, long long *F, int2 *ab, hipStream_t s)
 {
     const int nrows = row_end - row_begin;
     if (nrows <= 0) return;
-    if (Bblk8) {
+    if (Bblk16) {
         hipLaunchKernelGGL(k_tile_rows, dim3((nrows + 255) / 256), dim3(256), 0, s, Arow, row_begin, nrows, tile_row, F);
         const int tiles = (int)((nnz_bound + nrows + kFlatTile - 1) / kFlatTile);
         if (Bpad)
-            hipLaunchKernelGGL(k_row_work_flat<true>, dim3(tiles), dim3(256), 0, s, Arow, Acol, Brow, Bblk8, Bpad, row_begin, nrows,
+            hipLaunchKernelGGL(k_row_work_flat<true>, dim3(tiles), dim3(256), 0, s, Arow, Acol, Brow, Bblk16, Bpad, row_begin, nrows,
                                tile_row, F, ab);
         else
-            hipLaunchKernelGGL(k_row_work_flat<false>, dim3(tiles), dim3(256), 0, s, Arow, Acol, Brow, Bblk8, nullptr, row_begin,
+            hipLaunchKernelGGL(k_row_work_flat<false>, dim3(tiles), dim3(256), 0, s, Arow, Acol, Brow, Bblk16, nullptr, row_begin,
                                nrows, tile_row, F, ab);
         return;
     }
@@ -451,18 +475,20 @@ __global__ __launch_bounds__(256) void k_check_tables(const int *__restrict__ ro
     bool bad = d < 0;
     if (deg8) bad = bad || deg8[i] != want;
     if (blk) {
-        const int b = i >> 3, k = i & 7;
-        const unsigned w = (unsigned)blk[3 * b + 1 + (k >> 2)];
-        bad = bad || ((w >> (8 * (k & 3))) & 255u) != want || (k == 0 && blk[3 * b] != (pad_ptr ? pad_ptr[i] : row_ptr[i]));
+        const int4 g = reinterpret_cast<const int4 *>(blk)[i >> 4];
+        const int k = i & 15;
+        const unsigned w = (unsigned)(k < 5 ? g.y : (k < 10 ? g.z : g.w));
+        const unsigned f = k == 15 ? blk16_last((unsigned)g.y, (unsigned)g.z, (unsigned)g.w) : (w >> (6 * (k % 5))) & 63u;
+        bad = bad || f != blk16_field(d) || (k == 0 && g.x != (pad_ptr ? pad_ptr[i] : row_ptr[i]));
     }
     if (pad_ptr) bad = bad || pad_ptr[i + 1] - pad_ptr[i] != ((d + 15) & ~15);
     if (bad) atomicOr(err, kErrStaleTable);
 }
-void launch_check_tables(const int *row_ptr, int rows, const unsigned char *deg8, const int *blk8, const int *pad_ptr, unsigned *err,
+void launch_check_tables(const int *row_ptr, int rows, const unsigned char *deg8, const int *blk16, const int *pad_ptr, unsigned *err,
                          hipStream_t s)
 {
-    if (rows <= 0 || (!deg8 && !blk8 && !pad_ptr)) return;
-    hipLaunchKernelGGL(k_check_tables, dim3((rows + 255) / 256), dim3(256), 0, s, row_ptr, rows, deg8, blk8, pad_ptr, err);
+    if (rows <= 0 || (!deg8 && !blk16 && !pad_ptr)) return;
+    hipLaunchKernelGGL(k_check_tables, dim3((rows + 255) / 256), dim3(256), 0, s, row_ptr, rows, deg8, blk16, pad_ptr, err);
 }
 
 void launch_row_products(const int *Arow, const int *Acol, const int *Brow, const unsigned char *Bdeg8,

@@ -163,7 +163,7 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  * (prepass_kernel, class_streams, flow, small_path), so that a test can tell that the path it asked for ran.
  *   CLASS_STREAMS    1..3  HIP streams the capacity-class launches of a phase alternate over (default 2)
  *   BLOCKED_EXTENTS  -1 decide per operand (default: B of 2^21 rows or more and not dominated by rows of
- *                    255+ nonzeros), 0 never, 1 always: whether the prepass gathers B's blocked extents table
+ *                    63+ nonzeros), 0 never, 1 always: whether the prepass gathers B's blocked extents table
  *                    instead of B.row_ptr pairs.  Decided when an operand is first used as B, so set it
  *                    before that (or call bspgemm_matrix_invalidate on the operand).
  *   CHECK            0/1   debug checks: the exact flow never emits on unverified sizes, and the accumulate
