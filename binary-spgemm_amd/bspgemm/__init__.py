@@ -56,7 +56,7 @@ EXPORTS = [
     "bspgemm_matrix_transpose", "bspgemm_matrix_download", "bspgemm_multiply_accumulate", "bspgemm_closure_ex",
     "bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values",
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
-    "bspgemm_ktruss",
+    "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
 ]
 
 
@@ -72,6 +72,8 @@ FLOWS = {"auto": 0, "upper-bound": 1, "exact": 2}                               
 MASK_COMPLEMENT = 1                                                                      # BSPGEMM_MASK_COMPLEMENT
 CLOSURE_TRANSITIVE = 1                                                                   # BSPGEMM_CLOSURE_TRANSITIVE
 SELECT_OPS = {"tril": 1, "triu": 2, "offdiag": 3}                                       # bspgemm_select
+SETOPS = {"or": 1, "and": 2, "andnot": 3, "xor": 4}                                     # bspgemm_setop
+SYMMETRIZE_DROP_DIAGONAL = 1                                                             # BSPGEMM_SYMMETRIZE_DROP_DIAGONAL
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5}    # bspgemm_option
 
@@ -198,6 +200,9 @@ def lib():
     L.bspgemm_result_values_sum.argtypes = [VP, VP, C.POINTER(C.c_int64)]
     L.bspgemm_triangle_count.argtypes = [VP, VP, C.POINTER(C.c_int64)]
     L.bspgemm_ktruss.argtypes = [VP, VP, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
+    L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
+    L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
     L.bspgemm_closure.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
     L.bspgemm_multiply_accumulate.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, PVP]
     L.bspgemm_closure_ex.argtypes = [VP, VP, C.c_uint, C.c_int, PVP, C.POINTER(C.c_int)]
@@ -439,6 +444,27 @@ class Context:
         operand; a stable filter on the device (order and repeats of every row kept)"""
         m = C.c_void_p()
         _chk(lib().bspgemm_matrix_select(self._h, A._h, SELECT_OPS[op], C.byref(m)), "matrix_select")
+        return Matrix(self, m, keep=None)
+
+    def setop(self, A, B, op):
+        """bspgemm_matrix_setop: the patterns of A and B combined row by row, "or" | "and" | "andnot" | "xor" (or the
+        bspgemm_setop value), as a new operand with sorted duplicate-free rows"""
+        m = C.c_void_p()
+        _chk(lib().bspgemm_matrix_setop(self._h, A._h, B._h, SETOPS[op] if isinstance(op, str) else int(op), C.byref(m)),
+             "matrix_setop")
+        return Matrix(self, m, keep=None)
+
+    def matrix_equal(self, A, B):
+        """bspgemm_matrix_equal: whether the two patterns are equal as sets, decided on the device"""
+        eq = C.c_int()
+        _chk(lib().bspgemm_matrix_equal(self._h, A._h, B._h, C.byref(eq)), "matrix_equal")
+        return bool(eq.value)
+
+    def symmetrize(self, A, drop_diagonal=False):
+        """bspgemm_matrix_symmetrize: A | A^T of a square operand, without the diagonal when drop_diagonal"""
+        m = C.c_void_p()
+        _chk(lib().bspgemm_matrix_symmetrize(self._h, A._h, SYMMETRIZE_DROP_DIAGONAL if drop_diagonal else 0, C.byref(m)),
+             "matrix_symmetrize")
         return Matrix(self, m, keep=None)
 
     def triangle_count(self, A):

@@ -1,6 +1,6 @@
 // select.hip -- stable filters of CSR entries on the device, the reduction of a counted result's values, and the two loops
 // built on them: bspgemm_matrix_select, bspgemm_matrix_from_result_where, bspgemm_result_values_sum, bspgemm_triangle_count,
-// bspgemm_ktruss (include/bspgemm.h).
+// bspgemm_ktruss (include/bspgemm.h).  The loads, the flag-word join and the row search are in sel_rows.hpp (also setop.hip's).
 //
 // One design serves the structural select (col against row) and the value select (count against a threshold).  Work is
 // spread over ENTRIES: a workgroup owns kSelTile consecutive entries whatever rows they belong to, so a hub row of 10^5
@@ -18,62 +18,9 @@
 //                           O(1) per row, empty rows need nothing special
 // Positions are 64-bit throughout: a counted result may hold more than 2^31 entries as long as the kept ones fit an operand.
 #include "internal.hpp"
-#include "wave.hpp"
+#include "sel_rows.hpp"
 
 namespace bsp {
-
-constexpr int kSelThreads = 256;                      // four waves
-constexpr int kSelGroup = 256;                        // entries of one wave step: four per lane, four flag words
-constexpr int kSelSteps = 4;                          // steps per wave: the 16-byte loads a lane has in flight
-constexpr int kSelWaveSpan = kSelSteps * kSelGroup;   // consecutive entries of one wave
-constexpr int kSelStage = 4096;                       // rows of the tile's row_ptr window that are staged in LDS
-static_assert(kSelTile == 4 * kSelWaveSpan, "a workgroup's four waves cover one tile");
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// entries e .. e + 3 of p (e a multiple of four); vec: p is 16-byte aligned.  Entries at or past E read as 0.
-template <bool NT>
-__device__ __forceinline__ v4i load4(const int *__restrict__ p, long long e, long long E, bool vec)
-{
-    if (vec && e + 3 < E) {
-        const v4i *q = reinterpret_cast<const v4i *>(p + e);
-        return NT ? __builtin_nontemporal_load(q) : *q;
-    }
-    v4i v = {0, 0, 0, 0};
-    if (e < E) v.x = p[e];
-    if (e + 1 < E) v.y = p[e + 1];
-    if (e + 2 < E) v.z = p[e + 2];
-    if (e + 3 < E) v.w = p[e + 3];
-    return v;
-}
-
-// The flag word of the 64 entries that a DPP row of 16 lanes holds, four per lane (nib: the lane's four flags): complete
-// in lane 15 of the row.  The nibbles occupy disjoint bits, so the row's inclusive sum is their OR.  Full EXEC.
-__device__ __forceinline__ u64 row_flag_word(unsigned nib, int lane)
-{
-    const int sh = 4 * (lane & 15);
-    int lo = sh < 32 ? (int)(nib << sh) : 0;
-    int hi = sh >= 32 ? (int)(nib << (sh - 32)) : 0;
-    lo += dpp_or_zero<0x111, 0xF>(lo);
-    hi += dpp_or_zero<0x111, 0xF>(hi);
-    lo += dpp_or_zero<0x112, 0xF>(lo);
-    hi += dpp_or_zero<0x112, 0xF>(hi);
-    lo += dpp_or_zero<0x114, 0xF>(lo);
-    hi += dpp_or_zero<0x114, 0xF>(hi);
-    lo += dpp_or_zero<0x118, 0xF>(lo);
-    hi += dpp_or_zero<0x118, 0xF>(hi);
-    return ((u64)(u32)hi << 32) | (u64)(u32)lo;
-}
-
-__device__ __forceinline__ void store_flag_word(u64 word, long long first_entry, int lane, u64 *__restrict__ flags,
-                                                int *__restrict__ cnt)
-{
-    if ((lane & 15) == 15) {
-        const long long w = (first_entry >> 6) + (lane >> 4);
-        flags[w] = word;
-        cnt[w] = __popcll(word);
-    }
-}
 
 __device__ __forceinline__ bool keep_value(int v, int cmp, int thr)
 {
@@ -121,18 +68,6 @@ __global__ __launch_bounds__(256) void k_sel_tile_rows(const int *__restrict__ r
     if (r >= rows) return;
     const long long a0 = row_ptr[r], a1 = row_ptr[r + 1];
     for (long long t = (a0 + kSelTile - 1) / kSelTile; t * kSelTile < a1; t++) tile_row[t] = r;
-}
-
-// largest r in [lo, hi] with rp[r] <= e: the row that holds entry e (empty rows share their row_ptr with the next row)
-template <typename P>
-__device__ __forceinline__ int sel_row_of(P rp, int lo, int hi, int e)
-{
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (rp[mid] <= e) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 // pass 1 of the structural select.  col_idx is read again by pass 2, so these loads stay temporal.
@@ -247,6 +182,11 @@ __global__ __launch_bounds__(256) void k_values_sum(const int *__restrict__ vals
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int sel_tiles(long long nnz) { return (int)((nnz + kSelTile - 1) / kSelTile); }
+
+void launch_select_tile_rows(const int *row_ptr, int rows, int *tile_row, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sel_tile_rows, dim3((rows + 255) / 256), dim3(256), 0, s, row_ptr, rows, tile_row);
+}
 
 void launch_select_flags_struct(const int *row_ptr, const int *col_idx, int rows, long long nnz, int op, int *tile_row,
                                 unsigned long long *flags, int *cnt, hipStream_t s)

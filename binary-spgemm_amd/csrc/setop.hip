@@ -1,0 +1,383 @@
+// setop.hip -- entry-wise set operations on the patterns of two CSR operands, on the device: bspgemm_matrix_setop
+// (A | B, A & B, A \ B, A ^ B), bspgemm_matrix_equal and bspgemm_matrix_symmetrize (include/bspgemm.h).
+//
+// The passes are select.hip's (sel_rows.hpp holds what the two files share): work is spread over ENTRIES, a workgroup owns
+// kSelTile consecutive entries of one operand X whatever rows they belong to, and what is kept is described by 64-bit flag
+// words, their popcounts and one scan.  For operands whose rows are strictly ascending ("canonical"):
+//   pass 1  k_set_flags     every lane takes four consecutive entries of X (one 16-byte load) and finds their row like the
+//                           structural select.  It CHECKS them -- 0 <= col < cols, and col[p] > col[p - 1] unless p starts a
+//                           row -- into an error word, and binary-searches each column in the same row of the other operand
+//                           Y: lb = the position in Y.col_idx of the first entry of that row that is not below the column,
+//                           common = Y holds the column.  The common bits become the flag word and its popcount (12 bytes per
+//                           64 entries); OR and XOR also keep lb, 4 bytes per entry, because with it pass 2 needs no row.
+//   scan    launch_scan_counts over the per-word counts: cX(p) = common entries of X before p
+//   pass 2  AND / ANDNOT    select's scatter and row pass over A's flags (ANDNOT: pass 1 wrote them inverted)
+//           OR / XOR        k_set_place, once per operand: entry p of X goes to p + lb[p] - k cX(p), k = 1 (OR: all of A, the
+//                           non-common entries of B) or 2 (XOR: the non-common entries of both).  That is base[r] + i + ...
+//                           of the row-wise formula with the row's terms cancelled: p counts the X-entries before it, lb
+//                           the Y-entries of earlier rows and the smaller ones of this row, and cX(p) those counted twice.
+//   rows    k_set_row_ptr   row_ptr'[r] = rpA[r] + rpB[r] - k cA(rpA[r]): O(1) per row
+// The one synchronisation reads the error word and the common count (the result's size follows from it).  An operand that
+// the check found not canonical is brought to that form by transposing it twice and the passes run again; a column out of
+// range fails the call.  Positions are 64-bit inside the kernels.
+#include "internal.hpp"
+#include "sel_rows.hpp"
+
+namespace bsp {
+
+constexpr unsigned kSetErrRange = 1u;    // a column outside [0, cols)
+constexpr unsigned kSetErrOrder = 2u;    // a row that is not strictly ascending
+constexpr int kSetErrShiftB = 2;         // operand B's two bits
+
+// first position in [lo, hi) of y whose column is not below c
+__device__ __forceinline__ int set_lower_bound(const int *__restrict__ y, int lo, int hi, int c)
+{
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (y[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// pass 1 over operand X.  SEARCH false: the check alone (nothing but *err is written).  The columns are read again by pass
+// 2, so the loads stay temporal.  invert: the flags are the NON-common entries (ANDNOT).  lbs (may be NULL): lb per entry.
+template <bool SEARCH>
+__global__ __launch_bounds__(kSelThreads) void k_set_flags(const int *__restrict__ rpX, const int *__restrict__ colX, int rows,
+                                                          int cols, long long E, bool vec, const int *__restrict__ tile_row,
+                                                          const int *__restrict__ rpY, const int *__restrict__ colY,
+                                                          bool invert, int err_shift, u64 *__restrict__ flags,
+                                                          int *__restrict__ cnt, int *__restrict__ lbs,
+                                                          unsigned *__restrict__ err)
+{
+    __shared__ int srp[kSelStage + 1];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const SelTileRows tr = sel_stage_tile_rows(rpX, rows, E, tile_row, srp);
+    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
+    v4i v[kSelSteps];
+    int before[kSelSteps];                                               // the column in front of the lane's four
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e = w0 + j * kSelGroup + 4 * lane;
+        v[j] = load4<false>(colX, e, E, vec);
+        before[j] = e > 0 && e < E ? colX[e - 1] : -1;
+    }
+    unsigned bad = 0;
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e0 = w0 + j * kSelGroup + 4 * lane;
+        unsigned nib = 0;
+        if (e0 < E) {
+            const int c[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+            int lb[4] = {0, 0, 0, 0};
+            int r = tr.find(tr.rb, (int)e0);                             // one search per lane and step, then a walk
+            int beg = tr.row_begin(r), end = tr.row_end(r);
+            int from = 0, yend = 0;                                      // what is left of Y's row: X ascends, so does lb
+            if (SEARCH) {
+                from = rpY[r];
+                yend = rpY[r + 1];
+            }
+            int pc = before[j];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const long long p = e0 + k;
+                if (p >= E) break;
+                if (p >= end) {
+                    r = tr.find(r + 1, (int)p);
+                    beg = tr.row_begin(r);
+                    end = tr.row_end(r);
+                    if (SEARCH) {
+                        from = rpY[r];
+                        yend = rpY[r + 1];
+                    }
+                }
+                if ((unsigned)c[k] >= (unsigned)cols) bad |= kSetErrRange;
+                if (p > beg && c[k] <= pc) bad |= kSetErrOrder;
+                pc = c[k];
+                if (SEARCH) {
+                    from = set_lower_bound(colY, from, yend, c[k]);
+                    const bool common = from < yend && colY[from] == c[k];
+                    if (common != invert) nib |= 1u << k;
+                    lb[k] = from;
+                }
+            }
+            if (SEARCH && lbs) *reinterpret_cast<v4i *>(lbs + e0) = v4i{lb[0], lb[1], lb[2], lb[3]};   // (whole tiles)
+        }
+        if (SEARCH) store_flag_word(row_flag_word(nib, lane), w0 + j * kSelGroup, lane, flags, cnt);
+    }
+    if (bad) atomicOr(err, bad << err_shift);
+}
+
+// pass 2 of OR and XOR over operand X: entry p goes to p + lb[p] - k * (common entries before p); all: the common entries
+// are placed too (the A side of OR), else only the others.  flags: the COMMON entries.
+__global__ __launch_bounds__(kSelThreads) void k_set_place(const int *__restrict__ colX, long long E, bool vec,
+                                                          const u64 *__restrict__ flags, const long long *__restrict__ pre,
+                                                          const int *__restrict__ lbs, int k, bool all, int *__restrict__ out)
+{
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
+    u64 word[kSelSteps];
+    long long base[kSelSteps];
+    v4i v[kSelSteps], g[kSelSteps];
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e = w0 + j * kSelGroup + 4 * lane;
+        word[j] = flags[e >> 6];
+        base[j] = pre[e >> 6];
+        v[j] = load4<true>(colX, e, E, vec);
+        g[j] = *reinterpret_cast<const v4i *>(lbs + e);                  // (whole tiles)
+    }
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e = w0 + j * kSelGroup + 4 * lane;
+        const int bit = (4 * lane) & 63;
+        const unsigned nib = (unsigned)(word[j] >> bit) & 0xfu;
+        long long common = base[j] + __popcll(word[j] & mask_lt(bit));
+        const int c[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+        const int lb[4] = {g[j].x, g[j].y, g[j].z, g[j].w};
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (e + q >= E) break;
+            const bool is_common = (nib >> q) & 1u;
+            if (all || !is_common) out[e + q + lb[q] - k * common] = c[q];
+            common += is_common;
+        }
+    }
+}
+
+// row_ptr of A | B (k = 1) or A ^ B (k = 2) from A's flags of common entries; EA == 0: nothing is common
+__global__ __launch_bounds__(256) void k_set_row_ptr(const int *__restrict__ rpA, const int *__restrict__ rpB, int rows,
+                                                    long long EA, long long wordsA, const u64 *__restrict__ flags,
+                                                    const long long *__restrict__ pre, int k, int *__restrict__ out)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > rows) return;
+    const long long p = rpA[r];
+    long long common = 0;
+    if (EA > 0) common = p >= EA ? pre[wordsA] : pre[p >> 6] + __popcll(flags[p >> 6] & mask_lt((int)(p & 63)));
+    out[r] = (int)(p + rpB[r] - k * common);
+}
+
+static inline bool set_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline int set_tiles(long long nnz) { return (int)((nnz + kSelTile - 1) / kSelTile); }
+
+void launch_setop_flags(const int *rpX, const int *colX, int rows, int cols, long long nnzX, const int *rpY, const int *colY,
+                        bool search, bool invert, bool second, int *tile_row, unsigned long long *flags, int *cnt, int *lbs,
+                        unsigned *err, hipStream_t s)
+{
+    if (nnzX <= 0) return;
+    launch_select_tile_rows(rpX, rows, tile_row, s);
+    const dim3 grid(set_tiles(nnzX)), block(kSelThreads);
+    const int shift = second ? kSetErrShiftB : 0;
+    if (search)
+        hipLaunchKernelGGL(k_set_flags<true>, grid, block, 0, s, rpX, colX, rows, cols, nnzX, set_aligned16(colX), tile_row, rpY,
+                           colY, invert, shift, flags, cnt, lbs, err);
+    else
+        hipLaunchKernelGGL(k_set_flags<false>, grid, block, 0, s, rpX, colX, rows, cols, nnzX, set_aligned16(colX), tile_row, rpY,
+                           colY, invert, shift, flags, cnt, lbs, err);
+}
+
+void launch_setop_place(const int *colX, long long nnzX, const unsigned long long *flags, const long long *prefix,
+                        const int *lbs, int k, bool all, int *out, hipStream_t s)
+{
+    if (nnzX <= 0) return;
+    hipLaunchKernelGGL(k_set_place, dim3(set_tiles(nnzX)), dim3(kSelThreads), 0, s, colX, nnzX, set_aligned16(colX), flags,
+                       prefix, lbs, k, all, out);
+}
+
+void launch_setop_row_ptr(const int *rpA, const int *rpB, int rows, long long nnzA, const unsigned long long *flags,
+                          const long long *prefix, int k, int *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_set_row_ptr, dim3((unsigned)(((long long)rows + 1 + 255) / 256)), dim3(256), 0, s, rpA, rpB, rows,
+                       nnzA, (long long)select_words(nnzA), flags, prefix, k, out);
+}
+
+}  // namespace bsp
+
+using namespace bsp;
+
+// ------------------------------------------------------------------ the host side --------
+// Scratch of one operand's passes, carved from the context's upper-bound workspace (kept, like select's): the flag words,
+// the scan of their counts, the scan's partials, the counts, and (OR, XOR) lb per entry in whole tiles.
+struct SetSide {
+    unsigned long long *flags;
+    long long *pre, *part;
+    int *cnt, *lbs;
+    int words;
+};
+struct SetLayout {
+    size_t o_flags, o_pre, o_part, o_cnt, o_lbs;
+};
+
+// offsets in ints, every array on a 16-byte boundary; returns the end
+static size_t set_layout(size_t at, size_t W, bool lbs, SetLayout *l)
+{
+    auto take = [&](size_t ints) { const size_t o = at; at += (ints + 3) & ~(size_t)3; return o; };
+    l->o_flags = take(2 * W);
+    l->o_pre = take(2 * (W + 1));
+    l->o_part = take(2 * (W / 2048 + 4));
+    l->o_cnt = take(W);
+    l->o_lbs = take(lbs ? W * 64 : 0);
+    return at;
+}
+
+static SetSide set_side(int *tmp, const SetLayout &l, size_t W, bool lbs)
+{
+    SetSide sd;
+    sd.flags = reinterpret_cast<unsigned long long *>(tmp + l.o_flags);
+    sd.pre = reinterpret_cast<long long *>(tmp + l.o_pre);
+    sd.part = reinterpret_cast<long long *>(tmp + l.o_part);
+    sd.cnt = tmp + l.o_cnt;
+    sd.lbs = lbs ? tmp + l.o_lbs : nullptr;
+    sd.words = (int)W;
+    return sd;
+}
+
+// sorted duplicate-free copy of X: transposed twice
+static bspgemm_status set_canonical(bspgemm_context *ctx, const bspgemm_matrix *X, bspgemm_matrix **out)
+{
+    bspgemm_matrix *t = nullptr;
+    bspgemm_status st = bspgemm_matrix_transpose(ctx, X, &t);
+    if (!st) st = bspgemm_matrix_transpose(ctx, t, out);
+    bspgemm_matrix_free(t);
+    return st;
+}
+
+// op: a bspgemm_setop, or 0 for the comparison (*equal).  The arguments are checked by the callers.  canonical: both
+// operands are known to have strictly ascending rows (the second round).
+static bspgemm_status setop_run(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B, int op,
+                                bspgemm_matrix **out, int *equal, const char *who, bool canonical)
+{
+    if (bspgemm_status st = use_device(ctx)) return st;
+    hipStream_t s = ctx->stream;
+    const long long EA = A->nnz, EB = B->nnz;
+    const int rows = A->rows, cols = A->cols;
+    const bool both = op == BSPGEMM_SETOP_OR || op == BSPGEMM_SETOP_XOR;      // B contributes entries: both sides are searched
+    const int k = op == BSPGEMM_SETOP_XOR ? 2 : 1;
+    const size_t WA = select_words(EA), WB = both ? select_words(EB) : 0;
+    if (WA > (size_t)INT_MAX || WB > (size_t)INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "setop: too many entries for the word scan");
+    SetLayout la, lb;
+    const size_t o_b = set_layout(4, WA, both, &la);                          // the first four ints: the error word
+    const size_t total = set_layout(o_b, WB, both, &lb);
+    if (bspgemm_status st = ensure_tmp(ctx, total)) return st;
+    if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)(EA > EB ? EA : EB))) return st;
+    unsigned *d_err = reinterpret_cast<unsigned *>(ctx->tmp);
+    const SetSide sa = set_side(ctx->tmp, la, WA, both), sb = set_side(ctx->tmp, lb, WB, both);
+
+    // A's flags: its common entries (ANDNOT: the others).  The kernels of the two sides follow each other on the stream,
+    // so they share tile_row.
+    HIPCHK(hipMemsetAsync(d_err, 0, 4 * sizeof(int), s));
+    launch_setop_flags(A->d_row_ptr, A->d_col_idx, rows, cols, EA, B->d_row_ptr, B->d_col_idx, true, op == BSPGEMM_SETOP_ANDNOT,
+                       false, ctx->tile_row, sa.flags, sa.cnt, sa.lbs, d_err, s);
+    if (EA > 0) launch_scan_counts(sa.cnt, sa.words, sa.pre, sa.part, nullptr, s);
+    launch_setop_flags(B->d_row_ptr, B->d_col_idx, rows, cols, EB, A->d_row_ptr, A->d_col_idx, both, false, true, ctx->tile_row,
+                       sb.flags, sb.cnt, sb.lbs, d_err, s);
+    if (both && EB > 0) launch_scan_counts(sb.cnt, sb.words, sb.pre, sb.part, nullptr, s);
+    HIPCHK(hipGetLastError());
+    long long flagged = 0;                                                    // entries of A that pass 1 flagged
+    unsigned err = 0;
+    if (EA > 0) HIPCHK(hipMemcpyAsync(&flagged, sa.pre + sa.words, sizeof flagged, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                                          // the call's one synchronisation
+
+    const unsigned range = kSetErrRange | (kSetErrRange << kSetErrShiftB), order = kSetErrOrder | (kSetErrOrder << kSetErrShiftB);
+    if (err & range) {
+        snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) in operand %s", who, cols, (err & kSetErrRange) ? "A" : "B");
+        return BSPGEMM_ERR_INVALID;
+    }
+    if (err & order) {
+        if (canonical) return FAIL(BSPGEMM_ERR_HIP, "setop: a transposed operand is not in ascending order");
+        // what pass 1 left is discarded: the operands whose rows are unsorted or hold repeats are transposed twice
+        bspgemm_matrix *ca = nullptr, *cb = nullptr;
+        bspgemm_status st = BSPGEMM_OK;
+        const bool same = A == B;
+        if (same || (err & kSetErrOrder)) st = set_canonical(ctx, A, &ca);
+        if (same) cb = ca;
+        else if (!st && (err & (kSetErrOrder << kSetErrShiftB))) st = set_canonical(ctx, B, &cb);
+        if (!st) st = setop_run(ctx, ca ? ca : A, cb ? cb : B, op, out, equal, who, true);
+        if (cb != ca) bspgemm_matrix_free(cb);
+        bspgemm_matrix_free(ca);
+        return st;
+    }
+    if (op == 0) {
+        *equal = EA == EB && flagged == EA;
+        return BSPGEMM_OK;
+    }
+    const long long kept = both ? EA + EB - k * flagged : flagged;
+    if (kept > INT_MAX) {
+        snprintf(g_err, sizeof g_err, "%s: %lld entries in the result: more than INT_MAX, not usable as an int32 operand", who, kept);
+        return BSPGEMM_ERR_OVERFLOW;
+    }
+    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, rows, cols, 0, nullptr, nullptr, true};
+    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)rows + 1) * sizeof(int)));
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)kept + 1) * sizeof(int)));
+    if (both ? EA + EB == 0 : EA == 0) {
+        HIPCHK_B(hipMemsetAsync(m->d_row_ptr, 0, ((size_t)rows + 1) * sizeof(int), s));
+    } else if (both) {
+        launch_setop_place(A->d_col_idx, EA, sa.flags, sa.pre, sa.lbs, k, op == BSPGEMM_SETOP_OR, m->d_col_idx, s);
+        launch_setop_place(B->d_col_idx, EB, sb.flags, sb.pre, sb.lbs, k, false, m->d_col_idx, s);
+        launch_setop_row_ptr(A->d_row_ptr, B->d_row_ptr, rows, EA, sa.flags, sa.pre, k, m->d_row_ptr, s);
+    } else {
+        launch_select_scatter(A->d_col_idx, EA, sa.flags, sa.pre, m->d_col_idx, s);
+        launch_select_row_ptr(A->d_row_ptr, nullptr, rows, EA, sa.flags, sa.pre, m->d_row_ptr, s);
+    }
+    HIPCHK_B(hipGetLastError());
+    m->nnz = kept;
+    if (bspgemm_status st = ensure_deg8(m)) return bail(st);
+    *out = m;
+    return BSPGEMM_OK;
+}
+
+// what setop and equal ask of their operands; who: the function's name
+static bspgemm_status setop_operands(const bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B, const char *who)
+{
+    const char *what = nullptr;
+    if (A->ctx != ctx || B->ctx != ctx) what = "an operand belongs to another context";
+    else if (A->rows != B->rows || A->cols != B->cols) what = "the operands differ in shape";
+    else if ((A->nnz > 0 && (A->rows <= 0 || !A->d_col_idx)) || (B->nnz > 0 && !B->d_col_idx)) what = "nonzeros without rows";
+    if (!what) return BSPGEMM_OK;
+    snprintf(g_err, sizeof g_err, "%s: %s", who, what);
+    return BSPGEMM_ERR_INVALID;
+}
+
+extern "C" bspgemm_status bspgemm_matrix_setop(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
+                                               bspgemm_setop op, bspgemm_matrix **out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !A || !B || !out) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_setop: NULL argument");
+    if (op != BSPGEMM_SETOP_OR && op != BSPGEMM_SETOP_AND && op != BSPGEMM_SETOP_ANDNOT && op != BSPGEMM_SETOP_XOR)
+        return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_setop: unknown set operation");
+    if (bspgemm_status st = setop_operands(ctx, A, B, "bspgemm_matrix_setop")) return st;
+    return setop_run(ctx, A, B, (int)op, out, nullptr, "bspgemm_matrix_setop", false);
+}
+
+extern "C" bspgemm_status bspgemm_matrix_equal(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B, int *equal)
+{
+    if (!ctx || !A || !B || !equal) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_equal: NULL argument");
+    if (bspgemm_status st = setop_operands(ctx, A, B, "bspgemm_matrix_equal")) return st;
+    int eq = 0;
+    if (bspgemm_status st = setop_run(ctx, A, B, 0, nullptr, &eq, "bspgemm_matrix_equal", false)) return st;
+    *equal = eq;
+    return BSPGEMM_OK;
+}
+
+extern "C" bspgemm_status bspgemm_matrix_symmetrize(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags,
+                                                    bspgemm_matrix **out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !A || !out) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize: NULL argument");
+    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize: operand belongs to another context");
+    if (flags & ~BSPGEMM_SYMMETRIZE_DROP_DIAGONAL) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize: unknown flag");
+    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize needs a square matrix");
+    bspgemm_matrix *off = nullptr, *t = nullptr;
+    bspgemm_status st = BSPGEMM_OK;
+    if (flags & BSPGEMM_SYMMETRIZE_DROP_DIAGONAL) st = bspgemm_matrix_select(ctx, A, BSPGEMM_SELECT_OFFDIAG, &off);
+    const bspgemm_matrix *src = off ? off : A;
+    if (!st) st = bspgemm_matrix_transpose(ctx, src, &t);
+    if (!st) st = bspgemm_matrix_setop(ctx, src, t, BSPGEMM_SETOP_OR, out);
+    bspgemm_matrix_free(t);
+    bspgemm_matrix_free(off);
+    return st;
+}

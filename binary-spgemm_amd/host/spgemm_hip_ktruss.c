@@ -3,18 +3,22 @@
  * applications the counting masked product was added for (include/bspgemm.h: bspgemm_triangle_count, bspgemm_ktruss),
  * beside the closure driver (spgemm_hip_closure.c).
  *
- *     SpGEMM_hip_ktruss  file.mtx  k  [out.mtx]
+ *     SpGEMM_hip_ktruss  [--symmetrize]  file.mtx  k  [out.mtx]
  *
  * Prints one CSV line: n,nnz,triangles,k,truss_nnz,iterations,converged,ms.  file.mtx is read with
  * BSPGEMM_READ_EXPAND_SYMMETRIC, so a file that stores one triangle of a symmetric matrix gives the whole graph (nnz is the
  * expanded count); the loader hands back the transpose of the file's matrix (readCOO, final/utils.c:47-81), which for a
  * symmetric pattern is the matrix itself, and bspgemm_write_mtx writes T such that the loader reconstructs exactly T.
+ * --symmetrize: the uploaded operand is replaced by A | A^T without its diagonal (bspgemm_matrix_symmetrize) before the
+ * timer starts, so a `general` file of a directed graph gives the triangles and the truss of its underlying undirected
+ * graph; nnz stays the loader's count.
  * ms: wall time of the triangle count and the k-truss together, operands already on the device.
  */
 #include "../../include/bspgemm.h"
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <time.h>
 
 #define CHECK(st, what)                                                                         \
@@ -28,6 +32,11 @@
 
 int main(int argc, char **argv)
 {
+    const int symmetrize = argc > 1 && strcmp(argv[1], "--symmetrize") == 0;
+    if (symmetrize) {
+        argv++;
+        argc--;
+    }
     if (argc != 3 && argc != 4) {
         printf("usage: SpGEMM_hip_ktruss  path-to-matrix  k  [path-to-truss]\n");
         exit(1);
@@ -43,6 +52,13 @@ int main(int argc, char **argv)
     CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
     bspgemm_matrix *A, *T;
     CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
+    if (symmetrize) {
+        bspgemm_matrix *U;
+        CHECK(bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &U), "bspgemm_matrix_symmetrize");
+        bspgemm_matrix_free(A);
+        A = U;
+        CHECK(bspgemm_synchronize(ctx), "synchronize");
+    }
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     int64_t triangles = 0;

@@ -311,6 +311,45 @@ typedef enum bspgemm_compare { BSPGEMM_CMP_GE = 1, BSPGEMM_CMP_GT, BSPGEMM_CMP_L
 bspgemm_status bspgemm_matrix_from_result_where(bspgemm_context *ctx, const bspgemm_result *C, int cols,
                                                 bspgemm_compare cmp, int threshold, bspgemm_matrix **out);
 
+/* Entry-wise set operations on the PATTERNS of two operands of one shape: row i of out is pattern(A_i) op pattern(B_i).
+ *   - out's rows are strictly ascending and duplicate-free, whatever the inputs look like: A and B may come from upload
+ *     (interior row_ptr included), wrap_device (arrays that are not 16-byte aligned included), matrix_from_result,
+ *     transpose, select or an earlier setop, and their rows may be unsorted and hold repeats.  A == B (one handle) is
+ *     allowed.  Any shape, rows == 0, cols == 0 and nnz == 0 on either or both sides included.
+ *   - out is an owned operand with the layout of an uploaded one (its derived tables as after upload, nnz + 1 ints of
+ *     col_idx): usable in every product, transpose, select and closure; release it with bspgemm_matrix_free.
+ *   - Runs on the context's stream; out is complete on that stream when the call returns.  It does not touch the multiply
+ *     statistics.  When both operands have sorted duplicate-free rows -- every product, transpose and from_result* has,
+ *     and select preserves them -- the call costs ONE synchronisation, the result's size.  The kernels check that form
+ *     together with the columns' range; an operand that fails it is first transposed twice (bspgemm_matrix_transpose,
+ *     with its synchronisations and workspace) and the passes run again.
+ *   - Work is spread over entries, not rows (a hub row costs what its entries cost): each entry is searched in the other
+ *     operand's row.  Scratch, in the context's workspace (kept, like the select's): 12 bytes per 64 entries and the 8-byte
+ *     scan of the counts for A (OR and XOR: for B too), and for OR and XOR 4 bytes per entry of A and B.
+ *   - BSPGEMM_ERR_INVALID with *out = NULL, bspgemm_last_error naming the function and the cause: a NULL argument, an
+ *     unknown op, an operand of another context, operands of different shapes, a column outside [0, cols) anywhere in
+ *     either operand (the kernels check every column, as the transpose does).  BSPGEMM_ERR_OVERFLOW: the RESULT has more
+ *     than INT_MAX entries (OR, XOR; positions are 64-bit inside the kernels).  BSPGEMM_ERR_ALLOC: an allocation failed.
+ *     Nothing is leaked and the context stays usable.                                                                     */
+typedef enum bspgemm_setop { BSPGEMM_SETOP_OR = 1,      /* A | B:  in A or in B          */
+                             BSPGEMM_SETOP_AND = 2,     /* A & B:  in both               */
+                             BSPGEMM_SETOP_ANDNOT = 3,  /* A \ B:  in A, not in B        */
+                             BSPGEMM_SETOP_XOR = 4 }    /* (A \ B) | (B \ A)             */ bspgemm_setop;
+bspgemm_status bspgemm_matrix_setop(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B, bspgemm_setop op, bspgemm_matrix **out);
+
+/* *equal = 1 when the two patterns are equal as sets (order and repeats inside a row do not matter), else 0: the answer of
+ * nnz(A XOR B) == 0 without a result -- the check and count pass of bspgemm_matrix_setop over A alone, 12 bytes read
+ * back.  Shapes, column range, contexts and the treatment of unsorted rows as there; *equal is untouched on failure.      */
+bspgemm_status bspgemm_matrix_equal(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B, int *equal);
+
+/* out = A | A^T for a square A, rows sorted and duplicate-free; with BSPGEMM_SYMMETRIZE_DROP_DIAGONAL without the
+ * diagonal: the simple undirected graph that bspgemm_triangle_count and bspgemm_ktruss expect, e.g. from the in-edges that
+ * bspgemm_readCOO hands back for a `general` file.  Composed of bspgemm_matrix_select (OFFDIAG), bspgemm_matrix_transpose
+ * and bspgemm_matrix_setop (OR); every intermediate is freed on every path.  BSPGEMM_ERR_INVALID with *out = NULL: a
+ * non-square A, any other flag bit, a NULL argument, A from another context; otherwise the errors of the three calls.    */
+#define BSPGEMM_SYMMETRIZE_DROP_DIAGONAL 1u
+bspgemm_status bspgemm_matrix_symmetrize(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags, bspgemm_matrix **out);
+
 /* *sum = the exact int64 sum of the values of a counted result, reduced on the device (integer addition: the order does
  * not matter); 8 bytes come back.  A pattern-only result: BSPGEMM_ERR_INVALID, *sum untouched.                           */
 bspgemm_status bspgemm_result_values_sum(bspgemm_context *ctx, const bspgemm_result *C, int64_t *sum);
