@@ -75,7 +75,8 @@ SELECT_OPS = {"tril": 1, "triu": 2, "offdiag": 3}                               
 SETOPS = {"or": 1, "and": 2, "andnot": 3, "xor": 4}                                     # bspgemm_setop
 SYMMETRIZE_DROP_DIAGONAL = 1                                                             # BSPGEMM_SYMMETRIZE_DROP_DIAGONAL
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
-OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5}    # bspgemm_option
+OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
+           "shared_slots": 6}    # bspgemm_option
 
 
 class Stats(C.Structure):
@@ -363,7 +364,8 @@ class Context:
         _chk(lib().bspgemm_set_flow(self._h, FLOWS[flow]), "set_flow")
 
     def set_option(self, name, value):
-        """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1"""
+        """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
+        "shared_slots" -1/0/k"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):

@@ -180,6 +180,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     if (const char *e = getenv("BSPGEMM_RW_BLK")) ctx->rw_blk = atoi(e) ? 1 : 0;
     if (const char *e = getenv("BSPGEMM_SMALL")) ctx->small = atoi(e) ? 1 : 0;
     if (const char *e = getenv("BSPGEMM_PAD_ROWS")) { const int v = atoi(e); ctx->pad_rows = v < 0 ? -1 : (v ? 1 : 0); }
+    if (const char *e = getenv("BSPGEMM_SHARED_SLOTS")) { const int v = atoi(e); ctx->shared_slots = v < 0 ? -1 : (v > kSharedSlotsMax ? kSharedSlotsMax : v); }
     ctx->debug_alloc = getenv("BSPGEMM_DEBUG_ALLOC") != nullptr;
     ctx->dropin_timing = getenv("BSPGEMM_DROPIN_TIMING") != nullptr;
     if (ctx->debug_alloc)
@@ -592,6 +593,10 @@ extern "C" bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_optio
         if (value < -1 || value > 1) return FAIL(BSPGEMM_ERR_INVALID, "padded rows: -1, 0 or 1");
         ctx->pad_rows = value;
         return BSPGEMM_OK;
+    case BSPGEMM_OPT_SHARED_SLOTS:
+        if (value < -1) return FAIL(BSPGEMM_ERR_INVALID, "shared slots: -1, 0 or a count");
+        ctx->shared_slots = value > kSharedSlotsMax ? kSharedSlotsMax : value;
+        return BSPGEMM_OK;
     }
     return FAIL(BSPGEMM_ERR_INVALID, "unknown option");
 }
@@ -605,6 +610,7 @@ extern "C" int bspgemm_get_option(const bspgemm_context *ctx, bspgemm_option opt
     case BSPGEMM_OPT_CHECK: return ctx->check ? 1 : 0;
     case BSPGEMM_OPT_SMALL_PATH: return ctx->small;
     case BSPGEMM_OPT_PADDED_ROWS: return ctx->pad_rows;
+    case BSPGEMM_OPT_SHARED_SLOTS: return ctx->shared_slots;
     }
     return INT_MIN;
 }

@@ -127,6 +127,7 @@ struct bspgemm_context {
     int rw_blk = -1;                    // BSPGEMM_RW_BLK: 0 never / 1 always use the blocked extents table (default: per operand)
     int pad_rows = 0;                   // BSPGEMM_PAD_ROWS / BSPGEMM_OPT_PADDED_ROWS: 0 never (default), 1 always, -1 per operand: gather from a padded copy of B.col_idx
     int small = -1;                     // BSPGEMM_SMALL / BSPGEMM_OPT_SMALL_PATH: -1 automatic, 0 never, 1 whenever the product fits
+    int shared_slots = -1;              // BSPGEMM_SHARED_SLOTS / BSPGEMM_OPT_SHARED_SLOTS: -1 per class (wave_shared_max), 0 off, k: up to k shared slots in every class
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
 };

@@ -155,12 +155,18 @@ void launch_scan_counts(const int *cnt, int n, long long *prefix, long long *par
 // err (device, never NULL): bit 0 is set when a row's gathered product count exceeds its class capacity -- impossible
 // for consistent operands (the classes come from the same extents), seen only when an operand was rewritten under
 // the library; the row is then truncated to its capacity instead of overrunning LDS
+// shared_slots (BSPGEMM_OPT_SHARED_SLOTS; the emitting instances of 2+ levels and up to 16 chunks): a row with 1 .. shared_max
+// products more than level-0 slots -- a sparse row but for a few slots that hold several columns -- is put in order from
+// its columns alone and never builds its level-0 masks.  -1: shared_max from the per-class table (wave_shared_max),
+// 0: no such rows, k: shared_max = min(k, kSharedSlotsMax) in every class.  The result is the same for every value.
+constexpr int kSharedSlotsMax = 16;
+int wave_shared_max(int bin, int shared_slots);
 constexpr unsigned kErrCapacity = 1u;     // a row gathered more products than its capacity class holds
 constexpr unsigned kErrStaleTable = 2u;   // an operand's derived tables do not match its row_ptr (bspgemm_matrix_invalidate)
 hipError_t launch_wave_rows(int bin, int levels, const int2 *ab, const int *Bcol, int cols,
                             const RowRec *rec, const long long *recpre, const long long *row_ptr, int nrows,
                             int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode, const int *Frow, const int *Fcol,
-                            hipStream_t s, bool count_only = false);
+                            hipStream_t s, bool count_only = false, int shared_slots = 0);
 // debug check (BSPGEMM_OPT_CHECK): deg8[] / blk16[] / the padded row_ptr (each may be NULL) against row_ptr; sets kErrStaleTable in *err
 void launch_check_tables(const int *row_ptr, int rows, const unsigned char *deg8, const int *blk16, const int *pad_ptr, unsigned *err,
                          hipStream_t s);
@@ -197,7 +203,8 @@ void launch_wave_masked(int bin, const int2 *ab, const int *Bcol, int cols, cons
 // Count routes like Keep, to the counting kernels, with the values workspace `vals`
 hipError_t launch_class(int bin, const int2 *ab, const int *Bcol, long long nnzB, int cols, const RowRec *rec,
                         const long long *recpre, int nrows, int row_begin, int *tmp, int *cnt, unsigned *err, MaskMode mode,
-                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only = false, int *vals = nullptr);
+                        const int *Frow, const int *Fcol, hipStream_t s, bool count_only = false, int *vals = nullptr,
+                        int shared_slots = 0);
 // mlen[i] = |F's row i| when row i has products, else 0: what the masked product bins and offsets by
 void launch_mask_lengths(const long long *F, const int *Frow, int row_begin, int n, long long *mlen, hipStream_t s);
 // the same for the counting product, and *maxF (device, zeroed by the caller) = the largest F_i of the rows

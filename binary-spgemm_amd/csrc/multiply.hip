@@ -287,7 +287,8 @@ static bspgemm_status multiply_exact(bspgemm_context *ctx, const bspgemm_matrix 
         auto emit = [&](int b, int n, const RowRec *rec, const long long *recpre, hipStream_t sx) {
             if (b <= kWaveBins)
                 return launch_wave_rows(b, levels, ctx->ab, Bcol, B->cols, rec, recpre, C->d_row_ptr, n, row_begin,
-                                        C->d_col_idx, nullptr, ctx->d_err, MaskMode::None, nullptr, nullptr, sx);
+                                        C->d_col_idx, nullptr, ctx->d_err, MaskMode::None, nullptr, nullptr, sx, false,
+                                        ctx->shared_slots);
             launch_place_heavy(ctx->tmp, rec, recpre, n, C->d_row_ptr, row_begin, C->d_col_idx, sx);
             return hipSuccess;
         };
@@ -374,7 +375,7 @@ static bspgemm_status multiply_upper_bound(bspgemm_context *ctx, const bspgemm_m
         auto place = [&](int b, int n, const RowRec *rec, const long long *recpre, hipStream_t sx) {
             if (!keep) hub_order(ctx, b, n, rec, recpre, sx);
             return launch_class(b, ctx->ab, Bcol, B->gather_nnz(), B->cols, rec, recpre, n, row_begin, ctx->tmp, ctx->cnt,
-                                ctx->d_err, mode, Frow, Fcol, sx, false, count ? ctx->tmpv : nullptr);
+                                ctx->d_err, mode, Frow, Fcol, sx, false, count ? ctx->tmpv : nullptr, ctx->shared_slots);
         };
         if (bspgemm_status st = class_phase(ctx, 1, h->products, cls_n[1], false, place)) return bail(st);
         HIPCHK_B(hipEventRecord(slot.ev[3], s));

@@ -208,9 +208,10 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                  const RowRec *__restrict__ rec, const long long *__restrict__ recpre,
                  const long long *__restrict__ row_ptr,
                  int nrows, int rpw, int row_begin, int *__restrict__ tmp, int *__restrict__ cnt,
-                 unsigned *__restrict__ err, const int *__restrict__ Frow, const int *__restrict__ Fcol, int cols)
+                 unsigned *__restrict__ err, const int *__restrict__ Frow, const int *__restrict__ Fcol, int cols, int shared_max)
 {
     constexpr bool EXCL = MODE == MaskMode::Drop, ACC = MODE == MaskMode::Insert;
+    constexpr bool FEW = !COUNT && LEVELS >= 2 && CHUNKS <= 16;    // the few-shared-slots emit exists (else shared_max is unused)
     static_assert(!COUNT || MODE == MaskMode::None, "the symbolic pass has no masked form");
     using Cfg = WaveCfg<LEVELS, CHUNKS, TWP>;
     constexpr int TOPW = Cfg::TOPW, WAVES = Cfg::WAVES, SW = Cfg::SW, SLOTS = Cfg::SLOTS, FULL = Cfg::FULL;
@@ -448,6 +449,8 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
 
         u32 *S0;                     // level-0 slots (32-column masks) of this row
         int nslots0 = 0;             // how many of them the row uses (LEVELS >= 2)
+        bool few = false;            // wave-uniform: 1 .. shared_max products more than level-0 slots (FEW instances)
+        int nlose = 0;               // few: the distinct columns that share a slot and are not the one left beside it
         if (LEVELS == 1) {
             S0 = top;
         } else {
@@ -464,6 +467,8 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                 // as many level-0 slots as products: every product sits alone in its 32-column slot
                 // (wave-uniform; nslots0 counts the slots of level `lev` here)
                 const bool sparse = lev == 0 && nslots0 == F;
+                // nearly sparse: the row never touches its masks either, and is put in order from the columns alone (below)
+                if constexpr (FEW) few = lev == 0 && nslots0 != F && F - nslots0 <= shared_max;
                 // level `lev` slot buffers alternate: lev even -> SA/preA, lev odd -> SB/preB
                 u32 *S = (lev & 1) ? SB : SA;
                 unsigned short *Spre = (lev & 1) ? preB : preA;
@@ -487,7 +492,7 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                             if (lev == 0) {
                                 // a sparse row -- known since the scan of the level above -- never reads
                                 // its masks: only the column beside the mask is kept
-                                if (!sparse) atomicOr(&S[r2], bit);
+                                if (!sparse && !few) atomicOr(&S[r2], bit);
                                 if (!COUNT) L0w[r2] = cc;          // any product of the slot: same cc >> 5
                             } else {
                                 atomicOr(&S[r2], bit);
@@ -510,14 +515,63 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
             S0 = SA;                                               // level 0 is even
         }
 
+        // ---- few shared slots: F - nslots0 <= shared_max products more than slots.  Such a row is a sparse row but for
+        // a slot or two that hold several columns; the mask level (OR, blocked reads, clear, expansion) is not needed to
+        // sort it.  L0w[r2] holds the column of ONE product of the slot, the winner; the other products of a slot with m
+        // distinct columns read back a column that is not theirs: its losers, m - 1 distinct columns.  Slots ascend with
+        // the columns, so the place of product x among the row's distinct columns is its slot, plus one if it lost to a
+        // smaller column, plus the distinct loser columns below its own -- a handful of wave-uniform broadcasts, as in the
+        // count pass's settle loop.  A repeat reads back what its first copy reads: alone in its slot it is no loser, and
+        // as a loser it is passed over when an earlier loser (chunk, lane) has its column -- every product of a loser's
+        // column is a loser of the same slot.  Either way the copies get one place and one value.  S0 is never touched.
+        if constexpr (FEW) {
+            if (few) {
+                u32 v[CHUNKS];                                     // the winner's column
+                u64 lm[CHUNKS];                                    // the losers of each chunk
+#pragma unroll
+                for (int c = 0; c < CHUNKS; c++) v[c] = L0w[rank[c]];   // (every lane: tail lanes read slot 0)
+#pragma unroll
+                for (int c = 0; c < CHUNKS; c++) {
+                    const bool ok = ACC ? ((c < FULL || c * 64 + plane < F) && !dsrc[c]) : (c < FULL || c * 64 + plane < F);
+                    lm[c] = __ballot(ok && v[c] != (u32)col[c]);
+                    rank[c] += v[c] < (u32)col[c] ? 1 : 0;         // (tail lanes: column 0, never placed)
+                }
+                wave_lds_fence();                                  // every winner is read: L0w becomes the row
+#pragma unroll
+                for (int c = 0; c < CHUNKS; c++) {
+                    u64 m = lm[c];
+                    while (m) {                                    // (wave-uniform: m is a ballot)
+                        const int l = (int)__builtin_ctzll(m);
+                        m &= m - 1ull;
+                        const u32 x = (u32)__builtin_amdgcn_readlane(col[c], l);
+                        u64 earlier = __ballot((u32)col[c] == x) & lm[c] & mask_lt(l);
+#pragma unroll
+                        for (int c2 = 0; c2 < c; c2++) earlier |= __ballot((u32)col[c2] == x) & lm[c2];
+                        if (earlier == 0ull) {
+                            nlose++;
+#pragma unroll
+                            for (int c2 = 0; c2 < CHUNKS; c2++) rank[c2] += (u32)col[c2] > x ? 1 : 0;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < CHUNKS; c++) {
+                    const bool ok = ACC ? ((c < FULL || c * 64 + plane < F) && !dsrc[c]) : (c < FULL || c * 64 + plane < F);
+                    if (ok) L0w[rank[c]] = (u32)col[c];
+                }
+                wave_lds_fence();
+            }
+        }
+
         // ---- emit: lane l expands its own W consecutive level-0 slots (ascending columns) into
         // the LDS staging row at the rank given by one wave scan, then the wave streams the
         // staged row to memory fully coalesced.
         constexpr int W0 = (LEVELS == 1) ? TW : SW;
-        if (LEVELS >= 2 && nslots0 == F) {
+        if (LEVELS >= 2 && (nslots0 == F || few)) {
             // Sparse row (the common case when cols >> F_i): every level-0 slot holds ONE column,
-            // so slot index = output position and L0w already is the sorted row.
-            running = nslots0;                                     // (the masks were never written)
+            // so slot index = output position and L0w already is the sorted row.  A row of few shared slots was
+            // brought into the same form above.
+            running = nslots0 + (few ? nlose : 0);                 // (the masks were never written)
             if constexpr (EXCL)
                 if (running > 0 && mlen > 0) running = drop_mask_cols<CHUNKS, false>(L0w, running, top, Fcol, f0, mlen, lane);
             if (!COUNT) store_row<CHUNKS, false>(out, running, L0w, lane);
@@ -574,7 +628,7 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
 template <int LEVELS, int CHUNKS, int TWP, MaskMode MODE>
 static void launch_cfg(const int2 *ab, const int *Bcol, int cols, const RowRec *rec,
                        const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
-                       unsigned *err, hipStream_t s, bool count, const int *Frow, const int *Fcol)
+                       unsigned *err, hipStream_t s, bool count, const int *Frow, const int *Fcol, int shared_max)
 {
     using Cfg = WaveCfg<LEVELS, CHUNKS, TWP>;
     // rows per wave: the class maximum when the class has rows to spare; a class with few rows is
@@ -590,29 +644,29 @@ static void launch_cfg(const int2 *ab, const int *Bcol, int cols, const RowRec *
     if constexpr (MODE == MaskMode::None)
         if (count) kernel = k_wave_rows<LEVELS, CHUNKS, TWP, MODE, true>;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * Cfg::WAVES), 0, s,
-                       ab, Bcol, rec, recpre, row_ptr, nrows, rpw, row_begin, tmp, cnt, err, Frow, Fcol, cols);
+                       ab, Bcol, rec, recpre, row_ptr, nrows, rpw, row_begin, tmp, cnt, err, Frow, Fcol, cols, shared_max);
 }
 
 template <int LEVELS, int CHUNKS, MaskMode MODE>
 static void launch_one(const int2 *ab, const int *Bcol, int cols, int topw, const RowRec *rec,
                        const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
-                       unsigned *err, hipStream_t s, bool count, const int *Frow, const int *Fcol)
+                       unsigned *err, hipStream_t s, bool count, const int *Frow, const int *Fcol, int shared_max)
 {
     // the top bitmap is sized to what the column count needs: 128 or 256 words; 512 at three
     // levels (wave_levels_for_cols)
-    if (topw <= 128) launch_cfg<LEVELS, CHUNKS, 2, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
-    else if (topw <= 256) launch_cfg<LEVELS, CHUNKS, 4, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
-    else if constexpr (LEVELS == 3) launch_cfg<LEVELS, CHUNKS, 8, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol);
+    if (topw <= 128) launch_cfg<LEVELS, CHUNKS, 2, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol, shared_max);
+    else if (topw <= 256) launch_cfg<LEVELS, CHUNKS, 4, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol, shared_max);
+    else if constexpr (LEVELS == 3) launch_cfg<LEVELS, CHUNKS, 8, MODE>(ab, Bcol, cols, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol, shared_max);
 }
 
 // one class of rows (MODE None, Drop, Insert; Frow / Fcol: F's or D's CSR); wave_rows.hip picks LEVELS
 template <int LEVELS, MaskMode MODE>
 void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int cols, int topw, const RowRec *rec,
                         const long long *recpre, const long long *row_ptr, int nrows, int row_begin, int *tmp, int *cnt,
-                        unsigned *err, const int *Frow, const int *Fcol, hipStream_t s, bool count)
+                        unsigned *err, const int *Frow, const int *Fcol, hipStream_t s, bool count, int shared_max)
 {
     switch (bin) {
-#define BSP_CASE(b) case b: launch_one<LEVELS, kWaveChunks[b], MODE>(ab, Bcol, cols, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol); break;
+#define BSP_CASE(b) case b: launch_one<LEVELS, kWaveChunks[b], MODE>(ab, Bcol, cols, topw, rec, recpre, row_ptr, nrows, row_begin, tmp, cnt, err, s, count, Frow, Fcol, shared_max); break;
     BSP_CASE(1) BSP_CASE(2) BSP_CASE(3) BSP_CASE(4) BSP_CASE(5) BSP_CASE(6) BSP_CASE(7) BSP_CASE(8)
     BSP_CASE(9) BSP_CASE(10) BSP_CASE(11) BSP_CASE(12) BSP_CASE(13) BSP_CASE(14) BSP_CASE(15) BSP_CASE(16)
 #undef BSP_CASE
@@ -626,7 +680,7 @@ void launch_wave_levels(int bin, const int2 *ab, const int *Bcol, int cols, int 
 #ifdef BSP_WAVE_LEVELS
 template void launch_wave_levels<BSP_WAVE_LEVELS, MaskMode::BSP_WAVE_MODE>(int, const int2 *, const int *, int, int, const RowRec *,
                                                                            const long long *, const long long *, int, int, int *, int *,
-                                                                           unsigned *, const int *, const int *, hipStream_t, bool);
+                                                                           unsigned *, const int *, const int *, hipStream_t, bool, int);
 #endif
 
 }  // namespace bsp

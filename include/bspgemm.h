@@ -67,6 +67,7 @@ const char *bspgemm_build_info(void);
  * Environment (read once, in bspgemm_create; every knob also has a setter, bspgemm_set_option / _set_flow /
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
+ * BSPGEMM_SHARED_SLOTS=-1|0|k,
  * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
@@ -180,13 +181,18 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  *                    launches is tried when the flow is not EXACT (never under it), the range has 1 .. 2^17 rows and the
  *                    WHOLE of A has at most 32768 nonzeros; -1 also needs nnz(A) x B's mean row length <= 32768.  The
  *                    device then checks that the product fits (at most 65536 products, 2048 in any row) and otherwise
- *                    hands it to the general flow (bspgemm_stats.small_path = 0).  No result-cache condition.  */
+ *                    hands it to the general flow (bspgemm_stats.small_path = 0).  No result-cache condition.
+ *   SHARED_SLOTS     -1 per capacity class (default), 0 off, k: k in every class (at most 16): the one-wave kernel emits a
+ *                    row that has up to that many products more than 32-column slots -- a row whose products sit alone in
+ *                    their slots but for a few -- from its columns alone, without building the slots' masks (env
+ *                    BSPGEMM_SHARED_SLOTS).  Read at every multiply.  */
 typedef enum bspgemm_option {
     BSPGEMM_OPT_CLASS_STREAMS   = 1,
     BSPGEMM_OPT_BLOCKED_EXTENTS = 2,
     BSPGEMM_OPT_CHECK           = 3,
     BSPGEMM_OPT_SMALL_PATH      = 4,
-    BSPGEMM_OPT_PADDED_ROWS     = 5
+    BSPGEMM_OPT_PADDED_ROWS     = 5,
+    BSPGEMM_OPT_SHARED_SLOTS    = 6
 } bspgemm_option;
 bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_option opt, int value);
 /* current value of a knob (INT32_MIN for an unknown option or a NULL context) */
