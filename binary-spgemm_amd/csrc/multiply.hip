@@ -445,6 +445,8 @@ static bspgemm_status multiply_small(bspgemm_context *ctx, const bspgemm_matrix 
     for (int e = 1; e <= 4; e++) HIPCHK_B(hipEventRecord(slot.ev[e], s));   // one phase: everything is "total"
     HIPCHK_B(hipStreamSynchronize(s));
     if (h->small.bail) {
+        // the attempt is no multiply of its own: its stat slot goes back, the general flow opens the same one again
+        ctx->slot_head = (ctx->slot_head + bspgemm_context::kStatSlots - 1) % bspgemm_context::kStatSlots;
         bspgemm_result_free(C);
         *bailed = true;
         return BSPGEMM_OK;

@@ -454,7 +454,8 @@ typedef struct bspgemm_stats {
 } bspgemm_stats;
 bspgemm_status bspgemm_last_stats(const bspgemm_context *ctx, bspgemm_stats *out);
 /* ... and of earlier ones: age 0 = the last multiply, 1 = the one before, ... up to 15.  The
- * HIP events of a multiply are its own, so K timed steps can be read back after the timed region. */
+ * HIP events of a multiply are its own, so K timed steps can be read back after the timed region.
+ * A small-path attempt that bailed to the general flow is not a multiply of its own: the two share one age. */
 bspgemm_status bspgemm_stats_at(const bspgemm_context *ctx, int age, bspgemm_stats *out);
 
 /* ---------------------------------------------------------------- int32 drop-ins ------

@@ -590,3 +590,312 @@ def wave_rows_case(cols, plan, seed, residue=(4, 1)):
     b_rp = np.concatenate([[0], np.cumsum(b_len)])
     return dict(a_rp=a_rp.astype(np.int32), a_ci=a_ci.astype(np.int32), b_rp=b_rp.astype(np.int32),
                 b_ci=np.concatenate(b_cols).astype(np.int32), ncols=cols, nnz_c=before + T, tail=len(tail))
+
+
+# ---- the small-product path (csrc/small.hip, csrc/multiply.hip multiply_small): limits, host model, shapes ---------------
+SMALL_MAX_PRODUCTS, SMALL_MAX_ROW, SMALL_MAX_ROWS, SMALL_MAX_NNZ_A = 65536, 2048, 1 << 17, 32768   # csrc/kernels.hpp kSmall*
+SMALL_TINY = 16                 # kSmallTiny: products of a row that one lane handles alone
+SMALL_BIN = 16                  # multiply_small counts every non-empty row in class kWaveBins
+# the row sizes around the lane/wave split and around every padding N of the bitonic sort; 10116 products
+SMALL_LADDER = (1, 2, 15, 16, 17, 18, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048)
+SMALL_CONTENTS = ("distinct", "same", "pairs", "to16", "to17", "edges")
+SMALL_SPLITS = ("one", "ones", "s64", "s65", "holes", "repeat", "mixed")
+
+
+def small_fits(F):
+    """the device's fit test (csrc/small.hip k_small_plan)"""
+    F = np.asarray(F, np.int64)
+    return F.size > 0 and int(F.sum()) <= SMALL_MAX_PRODUCTS and int(F.max()) <= SMALL_MAX_ROW
+
+
+def small_expected(flow, small, R, nnz_a, nnz_b, b_rows, F):
+    """csrc/multiply.hip small_eligible + the device's fit test (csrc/small.hip)"""
+    if flow == "exact" or small == 0 or not 0 < R <= SMALL_MAX_ROWS or nnz_a > SMALL_MAX_NNZ_A:
+        return False
+    mean_b = nnz_b / b_rows if b_rows > 0 else 0.0
+    if small == -1 and nnz_a * mean_b > 0.5 * SMALL_MAX_PRODUCTS:
+        return False
+    return small_fits(F)
+
+
+def small_model(a_rp, a_ci, b_rp, r0=0, r1=None):
+    """What the small path does with rows [r0, r1), from A and B's row_ptr only, the way csrc/small.hip derives it.
+    Per row: F, lane (one lane sorts it), wave (the whole wave does), N (the bitonic sort's padded size, 0 for the others),
+    steps (trips of the 64-source gather loop, wave-rows only).  list: the non-empty rows in order (k_small_plan).
+    Per 32-row tile (k_small_sizes): f32, nz32, mx32; per 256-row tile (k_small_plan's workgroups): f256, nz256, and before256,
+    the products before the tile.  plan_trips: trips of k_small_plan's strided loop over the 32-row sums.  fits."""
+    a_rp = np.asarray(a_rp, np.int64)
+    r1 = a_rp.size - 1 if r1 is None else r1
+    R = r1 - r0
+    F = row_products(a_rp, a_ci, b_rp, r0, r1)
+    alen = np.diff(a_rp[r0:r1 + 1])
+    lane = (F > 0) & (F <= SMALL_TINY)
+    wave = F > SMALL_TINY
+    N = np.where(wave, np.maximum(64, 1 << np.ceil(np.log2(np.maximum(F, 1))).astype(np.int64)), 0)
+    assert np.all((N[wave] >= F[wave]) & ((N[wave] == 64) | (N[wave] < 2 * F[wave])))
+    steps = np.where(wave, -(-alen // 64), 0)
+
+    def tiles(x, w, op):
+        n = -(-R // w)
+        pad = np.zeros(n * w, np.int64)
+        pad[:R] = x
+        return op(pad.reshape(n, w), axis=1)
+
+    f256 = tiles(F, 256, np.sum)
+    return dict(R=R, F=F, alen=alen, lane=lane, wave=wave, N=N, steps=steps, list=np.flatnonzero(F > 0),
+                f32=tiles(F, 32, np.sum), nz32=tiles(F > 0, 32, np.sum), mx32=tiles(F, 32, np.max),
+                f256=f256, nz256=tiles(F > 0, 256, np.sum), before256=np.cumsum(f256) - f256,
+                plan_trips=-(-(-(-R // 32)) // 256), fits=small_fits(F))
+
+
+def small_reference(a_rp, a_ci, b_rp, b_ci, r0=0, r1=None):
+    """rows [r0, r1) of the boolean product as (row_ptr int64, col_idx int32), slice-local: every row is np.unique of its
+    concatenated B rows (one np.unique over (row, column) keys).  Independent of the C oracle."""
+    a_rp = np.asarray(a_rp, np.int64)
+    b_rp = np.asarray(b_rp, np.int64)
+    r1 = a_rp.size - 1 if r1 is None else r1
+    R = r1 - r0
+    lo, hi = int(a_rp[r0]), int(a_rp[r1])
+    aci = np.asarray(a_ci[lo:hi], np.int64)
+    L = (b_rp[1:] - b_rp[:-1])[aci]
+    arow = _seg_ids(np.diff(a_rp[r0:r1 + 1]))
+    cs = np.cumsum(L)
+    tot = int(cs[-1]) if cs.size else 0
+    src = np.repeat(b_rp[:-1][aci] - (cs - L), L) + np.arange(tot)
+    key = np.unique((np.repeat(arow, L) << 32) | np.asarray(b_ci, np.int64)[src].astype(np.uint32))
+    rp = np.concatenate([[0], np.cumsum(np.bincount(key >> 32, minlength=R))]).astype(np.int64)
+    return rp, (key & 0xFFFFFFFF).astype(np.int32)
+
+
+def small_targets(reps, extra=(), seed=0):
+    """`reps` ladders and `extra`, shuffled: lane-rows and wave-rows share the 64-row batches of k_small_rows"""
+    t = np.array(list(SMALL_LADDER) * reps + list(extra), np.int64)
+    return t[np.random.default_rng(seed).permutation(t.size)]
+
+
+def _small_distinct(content, F):
+    """distinct columns of a row of F products"""
+    return {"same": 1, "pairs": max(1, F // 2), "to16": min(F, 16), "to17": min(F, 17)}.get(content, F)
+
+
+def _small_columns(rng, content, n, F, cols, periodic):
+    """n rows x F product columns in gather order; periodic: column k % u at place k (for the `repeat` split), otherwise
+    scrambled -- but `distinct`, which is gathered in descending order"""
+    u = _small_distinct(content, F)
+    base = _strata(rng, n, u, 0, cols)
+    if content == "edges":                              # column 0 and the last column (a one-product row: one of the two)
+        base[:, 0] = 0
+        base[:, u - 1] = cols - 1
+        if u == 1:
+            base[::2, 0] = 0
+    if content == "distinct":
+        return base[:, ::-1].copy()
+    if periodic:
+        return base[:, rng.permutation(u)][:, np.arange(F) % u]
+    return _scramble(rng, base[:, np.arange(F) % u])
+
+
+def _small_split(rng, split, F):
+    """source lengths (0: an empty B row) of a row of F products"""
+    if split == "one":
+        return [F]
+    if split == "ones":
+        return [1] * F
+    if split in ("s64", "s65"):                         # exactly 64 / 65 A-entries
+        K = int(split[1:])
+        if F >= K:
+            return list(1 + rng.multinomial(F - K, np.full(K, 1.0 / K)))
+        L = np.zeros(K, np.int64)
+        L[rng.permutation(K)[:F]] = 1
+        return list(L)
+    assert split == "holes", split                      # A-entries on empty B rows before, between and behind the others
+    L = [0]
+    while sum(L) < F:
+        L += [min(int(rng.integers(1, F // 3 + 2)), F - sum(L)), 0] + [0] * int(rng.integers(0, 2))
+    return L
+
+
+def small_rows_case(targets, content, split, cols, seed):
+    """A (R x nB) and B (nB x cols) for the small path: row i of A has exactly targets[i] products (0: an empty row; -1: two
+    A-entries on an empty B row, no product).  Shuffle the targets (small_targets) to mix lane-rows and wave-rows in the
+    64-row batches.  Every A row has B rows of its own, numbered in shuffled order, so A, B and the gathered products are
+    unsorted.
+    content   distinct: all columns differ, gathered in descending order; same: one column repeated; pairs: every column
+              twice (F odd: one of them three times); to16 / to17: exactly 16 / 17 distinct columns (F below that: F);
+              edges: distinct, column 0 and column cols - 1 among them
+    split     one: one A-entry on a B row of F entries; ones: F A-entries on one-entry B rows; s64 / s65: exactly 64 / 65
+              A-entries (empty B rows among them when F is smaller); holes: A-entries on empty B rows interleaved;
+              repeat: the same B row of the row's distinct columns referenced again and again (not for distinct / edges);
+              mixed: the rows of one size take the splits in turn
+    Returns a_rp, a_ci, b_rp, b_ci (int32)."""
+    assert content in SMALL_CONTENTS and split in SMALL_SPLITS and not (split == "repeat" and content in ("distinct", "edges"))
+    rng = np.random.default_rng(seed)
+    targets = np.asarray(targets, np.int64)
+    R = targets.size
+    turn = [s for s in SMALL_SPLITS[:-1] if s != "repeat" or content not in ("distinct", "edges")] if split == "mixed" else [split]
+    alen = np.zeros(R, np.int64)
+    g_pos, g_acols, b_lens, b_cols = [], [], [], []
+    nb = 1                                              # B row 0 stays empty: the rows of target -1 point at it
+    dead = np.flatnonzero(targets == -1)
+    alen[dead] = 2
+    g_pos.append(dead)
+    g_acols.append(np.zeros(2 * dead.size, np.int64))
+    b_lens.append(np.zeros(1, np.int64))
+    for F in np.unique(targets[targets > 0]):
+        F = int(F)
+        rows = np.flatnonzero(targets == F)
+        for v, sp in enumerate(turn):
+            pos = rows[v::len(turn)]
+            n = pos.size
+            if n == 0:
+                continue
+            c = _small_columns(rng, content, n, F, cols, sp == "repeat")
+            if sp == "repeat":                          # B row 0 of the block: the distinct columns; B row 1: the first F % u
+                u = _small_distinct(content, F)
+                k, rem = F // u, F % u
+                src = np.array([0] * (k // 2) + ([1] if rem else []) + [0] * (k - k // 2))
+                blen = np.array([u] + ([rem] if rem else []))
+                bidx = np.concatenate([np.arange(u), np.arange(rem)])
+            else:                                       # source s of the row is B row perm[s] of the block
+                L = np.asarray(_small_split(rng, sp, F), np.int64)
+                src = rng.permutation(L.size)
+                order = np.argsort(src)
+                start = np.cumsum(L) - L
+                blen = L[order]
+                bidx = np.repeat(start[order] - (np.cumsum(blen) - blen), blen) + np.arange(F)
+            alen[pos] = src.size
+            g_pos.append(pos)
+            g_acols.append((nb + blen.size * np.arange(n)[:, None] + src[None, :]).ravel())
+            b_lens.append(np.tile(blen, n))
+            b_cols.append(c[:, bidx].ravel())
+            nb += n * blen.size
+    a_rp = np.concatenate([[0], np.cumsum(alen)])
+    a_ci = np.zeros(int(a_rp[-1]), np.int64)
+    pos = np.concatenate(g_pos)
+    a_ci[np.repeat(a_rp[pos] - (np.cumsum(alen[pos]) - alen[pos]), alen[pos]) + np.arange(a_ci.size)] = np.concatenate(g_acols)
+    renum = np.concatenate([[0], 1 + rng.permutation(nb - 1)])            # B's rows in shuffled order
+    lens = np.zeros(nb, np.int64)
+    lens[renum] = np.concatenate(b_lens)
+    b_rp = np.concatenate([[0], np.cumsum(lens)])
+    old_cols = np.concatenate(b_cols) if b_cols else np.zeros(0, np.int64)
+    old_lens = np.concatenate(b_lens)
+    b_ci = np.zeros(int(b_rp[-1]), np.int64)
+    b_ci[np.repeat(b_rp[renum] - (np.cumsum(old_lens) - old_lens), old_lens) + np.arange(b_ci.size)] = old_cols
+    assert cols <= 0x7fffffff and (b_ci.size == 0 or int(b_ci.max()) < cols)
+    return a_rp.astype(np.int32), renum[a_ci].astype(np.int32), b_rp.astype(np.int32), b_ci.astype(np.int32)
+
+
+# ---- the products of tests/test_gpu_small_path.py, checked without a GPU by tests/test_small_path_shapes.py ------------------
+def _small_case(targets, content, split, cols, seed, **kw):
+    a_rp, a_ci, b_rp, b_ci = small_rows_case(targets, content, split, cols, seed)
+    return dict(a_rp=a_rp, a_ci=a_ci, b_rp=b_rp, b_ci=b_ci, ncols=cols, content=content, split=split, **kw)
+
+
+SMALL_LADDER_PLAN = (       # (content, split, columns, ladders): `ones` and same x repeat have one A-entry per product
+    ("distinct", "one", 6000, 6), ("distinct", "s65", 6000, 6), ("distinct", "mixed", 6000, 6), ("same", "ones", 6000, 3),
+    ("same", "repeat", 6000, 3), ("pairs", "s64", 6000, 6), ("pairs", "holes", 6000, 6), ("to16", "repeat", 6000, 6),
+    ("to16", "one", 6000, 6), ("to17", "s65", 6000, 6), ("to17", "mixed", 6000, 6), ("edges", "holes", 6000, 6),
+    ("edges", "ones", 6000, 3),
+    ("distinct", "ones", 600_000_000, 3), ("same", "s64", 600_000_000, 6), ("pairs", "repeat", 600_000_000, 6),
+    ("to16", "s65", 600_000_000, 6), ("to17", "holes", 600_000_000, 6), ("edges", "one", 600_000_000, 6),
+    ("edges", "mixed", 2**31 - 1, 6),       # the largest column, 2^31 - 2, against the sort's sentinel: the small path only
+)
+
+
+def small_ladder_cases():
+    """{name: builder} of the row-ladder products: every size of SMALL_LADDER `ladders` times and 1 .. 16 twice, shuffled"""
+    out = {}
+    for k, (content, split, cols, reps) in enumerate(SMALL_LADDER_PLAN):
+        out["ladder_%s_%s_%d" % (content, split, cols)] = lambda k=k, a=(content, split, cols), reps=reps: _small_case(
+            small_targets(reps, list(range(1, 17)) * 2, seed=2100 + k), *a, seed=2200 + k, reps=reps, small_only=a[2] > 600_000_000)
+    return out
+
+
+def _sprinkle(R, n, value, seed, forced=()):
+    """targets of R rows: `value` at `n` rows (the `forced` ones first, the others random), 0 elsewhere"""
+    rng = np.random.default_rng(seed)
+    t = np.zeros(R, np.int64)
+    forced = np.array(sorted(set(int(r) for r in forced if 0 <= r < R)), np.int64)
+    free = np.setdiff1d(np.arange(R), forced)
+    t[np.concatenate([forced, rng.permutation(free)[:max(0, n - forced.size)]])[:max(n, 0)]] = value
+    return t
+
+
+def _fit_total(total):
+    """R = 2^17, 32768 one-entry rows on two-entry B rows, all distinct: 65536 products = nnz(C); the last non-empty row
+    one product more or less for 65537 / 65535"""
+    t = _sprinkle(SMALL_MAX_ROWS, 32768, 2, 2301, forced=(0, SMALL_MAX_ROWS - 1))
+    t[np.flatnonzero(t)[-2]] += total - 65536
+    return _small_case(t, "distinct", "one", 6000, 2302, total=total)
+
+
+def _fit_row(big):
+    """one row of `big` products among 300 rows of 1 .. 3, at row 8250: its 32-row tile is number 257, which k_small_plan's
+    strided loop reaches on its second trip"""
+    t = _sprinkle(8300, 300, 1, 2311, forced=(0, 8191, 8192, 8299))
+    nz = np.flatnonzero(t)
+    t[nz] = 1 + np.arange(nz.size) % 3
+    t[8250] = big
+    return _small_case(t, "pairs", "s65", 600_000_000, 2312, big_row=8250)
+
+
+def _fit_nnz_a(nnz_a):
+    """`nnz_a` one-entry rows on one-entry B rows among 2^17: the host's limit on A-nonzeros"""
+    return _small_case(_sprinkle(SMALL_MAX_ROWS, nnz_a, 1, 2321), "distinct", "one", 6000, 2322)
+
+
+def _fit_rows(R):
+    return _small_case(_sprinkle(R, 500, 5, 2331, forced=(0, R - 1)), "pairs", "holes", 6000, 2332)
+
+
+def _fit_auto(extra):
+    """256 x 16 A-entries on rows 0 .. 62 of a 64 x 8 B: 4096 x 8.0 = 32768, the automatic choice's limit; `extra` more
+    entries in B's unreferenced row 63 put the estimate above it (same product)"""
+    rng = np.random.default_rng(2341)
+    b_len = np.full(64, 8)
+    b_len[63] += extra
+    b_rp = np.concatenate([[0], np.cumsum(b_len)]).astype(np.int32)
+    a_rp = (16 * np.arange(257)).astype(np.int32)
+    a_ci = rng.integers(0, 63, size=4096).astype(np.int32)
+    b_ci = rng.integers(0, 1000, size=int(b_rp[-1])).astype(np.int32)
+    return dict(a_rp=a_rp, a_ci=a_ci, b_rp=b_rp, b_ci=b_ci, ncols=1000)
+
+
+def small_fit_cases():
+    return {"fit_total_65536": lambda: _fit_total(65536), "fit_total_65537": lambda: _fit_total(65537),
+            "fit_total_65535": lambda: _fit_total(65535), "fit_row_2049": lambda: _fit_row(2049), "fit_row_2048": lambda: _fit_row(2048),
+            "fit_nnz_a_32769": lambda: _fit_nnz_a(32769), "fit_rows_131073": lambda: _fit_rows(SMALL_MAX_ROWS + 1),
+            "fit_auto_at_limit": lambda: _fit_auto(0), "fit_auto_above_limit": lambda: _fit_auto(1)}
+
+
+SMALL_TILE_ROWS = (1, 31, 32, 33, 255, 256, 257, 8191, 8192, 8193, 65537)
+SMALL_TILE_NONEMPTY = {255: 63, 256: 64, 257: 65}          # the list is 63, 64, 65 rows long: one batch of k_small_rows +- 1
+
+
+def _tile_case(R):
+    """R rows, the non-empty ones at the 32-, 256- and 8192-row tile edges and at random places: sizes 1 .. 40 (lane-rows and
+    wave-rows), every seventh other row with A-entries on an empty B row only (no product: not listed)"""
+    edge = [r for r in (0, 31, 32, 255, 256, 257, 8191, 8192, R - 1) if r < R]
+    n = SMALL_TILE_NONEMPTY.get(R, min(R, max(len(edge), 1) + min(R // 3, 120)))
+    t = _sprinkle(R, n, 1, 2400 + R, forced=edge)
+    nz = np.flatnonzero(t)
+    t[nz] = 1 + (7 * np.arange(nz.size) + R) % 40
+    dead = np.flatnonzero(t == 0)[::7]
+    t[dead] = -1
+    return _small_case(t, "pairs", "mixed", 6000, 2500 + R, edge=edge, nonempty=n)
+
+
+def small_tile_cases():
+    return {"tile_rows_%d" % R: (lambda R=R: _tile_case(R)) for R in SMALL_TILE_ROWS}
+
+
+SMALL_RANGES = ((5, 6), (37, 70), (101, 358))              # r0 % 32 != 0, r1 - r0 = 1, 33, 257
+
+
+def small_range_case():
+    """700 rows of 0 .. 40 products, some without a product, rows 5 and 300 of 600: the operand of the row-range products"""
+    rng = np.random.default_rng(2601)
+    t = rng.integers(-1, 41, size=700)
+    t[5], t[300], t[37], t[69], t[101], t[357] = 600, 600, 17, 16, 2, 33
+    t[[40, 110]], t[[41, 111]] = 0, -1
+    return _small_case(t, "pairs", "mixed", 6000, 2602, ranges=SMALL_RANGES)

@@ -32,10 +32,9 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FLOW_ID = {"upper-bound": 1, "exact": 2, "auto": 1}              # bspgemm_stats.flow (auto runs upper-bound here)
 KNOBS = list(itertools.product(("upper-bound", "exact", "auto"), (0, 1), (0, 1), (-1, 0, 1), (0, 1), (1, 3)))
 MASKED_KNOBS = list(itertools.product((0, 1), (0, 1), (0, 1), (1, 3)))
-# csrc/kernels.hpp: the small-product path's limits, the class layout
-SMALL_MAX_PRODUCTS, SMALL_MAX_ROW, SMALL_MAX_ROWS, SMALL_MAX_NNZ_A = 65536, 2048, 1 << 17, 32768
+# csrc/kernels.hpp: the class layout; the small-product path's limits and the model of which products take it: tests/gen.py
 RANK_BIN, MID_BIN, DENSE_BIN = gen.RANK_BIN, gen.MID_BIN, gen.DENSE_BIN
-row_products, expected_bins = gen.row_products, gen.expected_bins
+row_products, expected_bins, small_expected = gen.row_products, gen.expected_bins, gen.small_expected
 
 
 @pytest.fixture(scope="module")
@@ -47,16 +46,6 @@ def ctx():
 
 
 # ---------------------------------------------------------------- host-side model of the path ---------------
-def small_expected(flow, small, R, nnz_a, nnz_b, b_rows, F):
-    """csrc/multiply.hip small_eligible + the device's fit test (csrc/small.hip)"""
-    if flow == "exact" or small == 0 or not 0 < R <= SMALL_MAX_ROWS or nnz_a > SMALL_MAX_NNZ_A:
-        return False
-    mean_b = nnz_b / b_rows if b_rows > 0 else 0.0
-    if small == -1 and nnz_a * mean_b > 0.5 * SMALL_MAX_PRODUCTS:
-        return False
-    return int(F.sum()) <= SMALL_MAX_PRODUCTS and int(F.max()) <= SMALL_MAX_ROW
-
-
 def padded_misreads(b_rp, b_ci):
     """{B row: the columns the heavy-row gather read for it} for the rows it read wrong from the padded copy of B.col_idx
     while it sized that array by B.nnz: under four entries it took scalar loads of the array's first three entries as if
