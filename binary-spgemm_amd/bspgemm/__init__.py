@@ -57,6 +57,7 @@ EXPORTS = [
     "bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values",
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
+    "bspgemm_bfs",
 ]
 
 
@@ -201,6 +202,7 @@ def lib():
     L.bspgemm_result_values_sum.argtypes = [VP, VP, C.POINTER(C.c_int64)]
     L.bspgemm_triangle_count.argtypes = [VP, VP, C.POINTER(C.c_int64)]
     L.bspgemm_ktruss.argtypes = [VP, VP, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_bfs.argtypes = [VP, VP, C.c_int, VP, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -481,6 +483,16 @@ class Context:
         m, it, conv = C.c_void_p(), C.c_int(), C.c_int()
         _chk(lib().bspgemm_ktruss(self._h, A._h, int(k), int(max_iter), C.byref(m), C.byref(it), C.byref(conv)), "ktruss")
         return Matrix(self, m, keep=None), it.value, bool(conv.value)
+
+    def bfs(self, A, sources, max_depth=0):
+        """bspgemm_bfs: (levels as a Result, depth, complete) -- row s of the result holds the vertices reachable from
+        sources[s] along A's out-edges, Result.download_values() their BFS levels; device-resident, one complement
+        product per level; max_depth <= 0: no cap"""
+        src = _i32(sources).ravel()
+        r, depth, complete = C.c_void_p(), C.c_int(), C.c_int()
+        _chk(lib().bspgemm_bfs(self._h, A._h, int(src.size), C.c_void_p(src.ctypes.data) if src.size else None,
+                               int(max_depth), C.byref(r), C.byref(depth), C.byref(complete)), "bspgemm_bfs")
+        return Result(self, r), depth.value, bool(complete.value)
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

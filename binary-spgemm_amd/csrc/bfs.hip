@@ -1,0 +1,305 @@
+// bfs.hip -- multi-source breadth-first search with a level per reached vertex, everything device-resident: bspgemm_bfs
+// (include/bspgemm.h).  The loop is the one the complemented mask was built for,
+//     V0 = F0 = one entry (s, sources[s]) per row, level 0
+//     level d:  N = !V .* (F * A)      the complement product: what the frontier reaches and V does not hold yet
+//               Nm = N as an operand   bspgemm_matrix_from_result: the next frontier
+//               V' = V u Nm            the merge below; the entries of Nm get the value d
+// and it ends when a frontier comes back empty, when V holds every vertex in every row, or at the depth cap.
+//
+// The merge is setop.hip's OR for two operands that are canonical (rows strictly ascending) and DISJOINT, with a value per
+// entry -- both hold by construction here, V and N are products and N is masked by !V.  Then nothing of the general union
+// is needed: no common entries means no flag words, no scan and no read-back (the size is |V| + |N| before anything runs),
+// and an entry's place p + lb (DESIGN.md 4.11 with c = 0: p counts the entries of its own operand before it, lb those of the
+// other operand in earlier rows and the smaller ones of its row) is used where it is computed instead of being stored.
+//   k_merge_disjoint   once per side X against the other side Y, in select's geometry (sel_rows.hpp): a workgroup owns
+//                      kSelTile consecutive entries of X whatever rows they belong to, a lane four of them (one 16-byte
+//                      load of the columns, one of the values), the tile's window of X.row_ptr is staged in LDS.  Each
+//                      column is binary-searched in Y's row, a lane's next entry of the same row from the previous lower
+//                      bound on; column and value (V side: the entry's own, N side: the constant d) go to p + lb.
+//                      4 + 4 bytes read and 4 + 4 written per entry of V, 4 read and 8 written per entry of N, and the
+//                      probes of the searches, which stay in L2: neighbouring entries walk the same Y row.
+//   k_merge_row_ptr    row_ptr'[r] = rpV[r] + rpN[r]: O(1) per row, int32 (V' is the next product's mask)
+//   k_widen_row_ptr    int32 -> int64, once, for the result object
+// BSPGEMM_OPT_CHECK: the kernel also tests whether a search hit its column and ORs a bit into a device word, which the host
+// then reads (one synchronisation per level, under the option only).
+#include "internal.hpp"
+#include "sel_rows.hpp"
+
+namespace bsp {
+
+// first position in [lo, hi) of y whose column is not below c
+__device__ __forceinline__ int merge_lower_bound(const int *__restrict__ y, int lo, int hi, int c)
+{
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (y[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// VALS: the entries' values come from valsX (the V side), else every entry gets `level` (the N side).  X's columns and
+// values are read once (non-temporal); Y's columns are probed by many lanes and stay temporal.  The destinations
+// p + lb < E + nnz(Y) for consistent row_ptrs: lb <= rpY[rows] = nnz(Y).
+template <bool VALS, bool CHECK>
+__global__ __launch_bounds__(kSelThreads) void k_merge_disjoint(const int *__restrict__ rpX, const int *__restrict__ colX,
+                                                               const int *__restrict__ valsX, int level, int rows, long long E,
+                                                               bool vec, bool vecv, const int *__restrict__ tile_row,
+                                                               const int *__restrict__ rpY, const int *__restrict__ colY,
+                                                               int *__restrict__ out_col, int *__restrict__ out_val,
+                                                               unsigned *__restrict__ hit)
+{
+    __shared__ int srp[kSelStage + 1];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const SelTileRows tr = sel_stage_tile_rows(rpX, rows, E, tile_row, srp);
+    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
+    v4i v[kSelSteps], x[kSelSteps];
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e = w0 + j * kSelGroup + 4 * lane;
+        v[j] = load4<true>(colX, e, E, vec);
+        if (VALS) x[j] = load4<true>(valsX, e, E, vecv);
+    }
+    bool common = false;
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e0 = w0 + j * kSelGroup + 4 * lane;
+        if (e0 >= E) continue;
+        const int c[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+        const int val[4] = {VALS ? x[j].x : level, VALS ? x[j].y : level, VALS ? x[j].z : level, VALS ? x[j].w : level};
+        int r = tr.find(tr.rb, (int)e0);                                 // one search per lane and step, then a walk
+        int end = tr.row_end(r);
+        int from = rpY[r], yend = rpY[r + 1];                            // what is left of Y's row: X ascends, so does lb
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const long long p = e0 + k;
+            if (p >= E) break;
+            if (p >= end) {
+                r = tr.find(r + 1, (int)p);
+                end = tr.row_end(r);
+                from = rpY[r];
+                yend = rpY[r + 1];
+            }
+            from = merge_lower_bound(colY, from, yend, c[k]);            // (an empty row of Y: nothing is read)
+            if (CHECK && from < yend && colY[from] == c[k]) common = true;
+            const long long dst = p + from;
+            out_col[dst] = c[k];
+            out_val[dst] = val[k];
+        }
+    }
+    if (CHECK && common) atomicOr(hit, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_merge_row_ptr(const int *__restrict__ rpV, const int *__restrict__ rpN, int rows,
+                                                      int *__restrict__ out)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r <= rows) out[r] = rpV[r] + rpN[r];
+}
+
+__global__ __launch_bounds__(256) void k_widen_row_ptr(const int *__restrict__ src, int n, long long *__restrict__ dst)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+
+// V0: row s holds sources[s] alone -- row_ptr = 0 .. rows
+__global__ __launch_bounds__(256) void k_bfs_unit_row_ptr(int rows, int *__restrict__ row_ptr)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r <= rows) row_ptr[r] = r;
+}
+
+static inline bool merge_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// one side of the merge: the nnzX > 0 entries of X (vals: their values, or NULL for the constant `level`) to their places
+// in out_col / out_val.  tile_row: nnzX / kSelTile + 1 ints of scratch; hit: NULL, or the device word of the check.
+static void launch_merge_side(const int *rpX, const int *colX, const int *vals, int level, int rows, long long nnzX,
+                              const int *rpY, const int *colY, int *tile_row, int *out_col, int *out_val, unsigned *hit,
+                              hipStream_t s)
+{
+    if (nnzX <= 0) return;
+    launch_select_tile_rows(rpX, rows, tile_row, s);
+    const dim3 grid((unsigned)((nnzX + kSelTile - 1) / kSelTile)), block(kSelThreads);
+    const bool vec = merge_aligned16(colX), vecv = vals && merge_aligned16(vals);
+#define BSP_MERGE(VALS, CHECK)                                                                                            \
+    hipLaunchKernelGGL((k_merge_disjoint<VALS, CHECK>), grid, block, 0, s, rpX, colX, vals, level, rows, nnzX, vec, vecv, \
+                       tile_row, rpY, colY, out_col, out_val, hit)
+    if (vals) {
+        if (hit) BSP_MERGE(true, true);
+        else BSP_MERGE(true, false);
+    } else {
+        if (hit) BSP_MERGE(false, true);
+        else BSP_MERGE(false, false);
+    }
+#undef BSP_MERGE
+}
+
+}  // namespace bsp
+
+using namespace bsp;
+
+// ------------------------------------------------------------------ the host side --------
+// The visited set while the loop runs: an int32 operand (the next product's mask) and a level per entry.  Its arrays come
+// from the context's result cache, like a product's, because the last V becomes the result object as it stands; the handle
+// does not own them.
+struct BfsVisited {
+    bspgemm_matrix *m = nullptr;
+    int *vals = nullptr;
+};
+
+static inline size_t bfs_bytes_rowptr32(int rows) { return ((size_t)rows + 1) * sizeof(int); }
+
+static void bfs_release(bspgemm_context *ctx, BfsVisited *V)
+{
+    if (!V->m) return;
+    result_release(ctx, V->m->d_row_ptr, bfs_bytes_rowptr32(V->m->rows));
+    result_release(ctx, V->m->d_col_idx, result_bytes_colidx(V->m->nnz));
+    result_release(ctx, V->vals, result_bytes_colidx(V->m->nnz));
+    bspgemm_matrix_free(V->m);                              // (not owned: the handle and its derived tables)
+    V->m = nullptr;
+    V->vals = nullptr;
+}
+
+// the arrays of a visited set of `nnz` entries, nothing written yet
+static bspgemm_status bfs_alloc(bspgemm_context *ctx, int rows, int cols, long long nnz, BfsVisited *V)
+{
+    V->m = new (std::nothrow) bspgemm_matrix{ctx, rows, cols, nnz, nullptr, nullptr, false};
+    if (!V->m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    auto bail = [&](bspgemm_status st) { bfs_release(ctx, V); return st; };
+    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&V->m->d_row_ptr), bfs_bytes_rowptr32(rows)));
+    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&V->m->d_col_idx), result_bytes_colidx(nnz)));
+    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&V->vals), result_bytes_colidx(nnz)));
+    return BSPGEMM_OK;
+}
+
+// out = V u N with the level `level` on N's entries; V and N canonical and disjoint.  No synchronisation unless the
+// context checks (BSPGEMM_OPT_CHECK).
+static bspgemm_status bfs_merge(bspgemm_context *ctx, const BfsVisited &V, const bspgemm_matrix *N, int level, BfsVisited *out)
+{
+    hipStream_t s = ctx->stream;
+    const int rows = V.m->rows;
+    const long long EV = V.m->nnz, EN = N->nnz;
+    if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)(EV > EN ? EV : EN))) return st;
+    unsigned *d_hit = nullptr;
+    if (ctx->check) {
+        if (bspgemm_status st = ensure_tmp(ctx, 4)) return st;
+        d_hit = reinterpret_cast<unsigned *>(ctx->tmp);
+        HIPCHK(hipMemsetAsync(d_hit, 0, sizeof(unsigned), s));
+    }
+    if (bspgemm_status st = bfs_alloc(ctx, rows, V.m->cols, EV + EN, out)) return st;
+    auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bfs_release(ctx, out); return st; };
+    // the two sides' launches follow each other on the stream, so they share tile_row
+    launch_merge_side(V.m->d_row_ptr, V.m->d_col_idx, V.vals, 0, rows, EV, N->d_row_ptr, N->d_col_idx, ctx->tile_row,
+                      out->m->d_col_idx, out->vals, d_hit, s);
+    launch_merge_side(N->d_row_ptr, N->d_col_idx, nullptr, level, rows, EN, V.m->d_row_ptr, V.m->d_col_idx, ctx->tile_row,
+                      out->m->d_col_idx, out->vals, d_hit, s);
+    hipLaunchKernelGGL(k_merge_row_ptr, dim3((unsigned)(((long long)rows + 1 + 255) / 256)), dim3(256), 0, s, V.m->d_row_ptr,
+                       N->d_row_ptr, rows, out->m->d_row_ptr);
+    HIPCHK_B(hipGetLastError());
+    if (d_hit) {
+        unsigned hit = 0;
+        HIPCHK_B(hipMemcpyAsync(&hit, d_hit, sizeof hit, hipMemcpyDeviceToHost, s));
+        HIPCHK_B(hipStreamSynchronize(s));
+        if (hit) return bail(FAIL(BSPGEMM_ERR_HIP, "bspgemm_bfs: the new frontier holds a vertex of the visited set"));
+    }
+    if (bspgemm_status st = ensure_deg8(out->m)) return bail(st);
+    return BSPGEMM_OK;
+}
+
+extern "C" bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix *A, int nsources, const int *sources,
+                                      int max_depth, bspgemm_result **levels, int *depth, int *complete)
+{
+    if (levels) *levels = nullptr;
+    if (depth) *depth = 0;
+    if (complete) *complete = 0;
+    if (!ctx || !A || !sources || !levels) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs: NULL argument");
+    if (nsources < 1) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs: nsources < 1");
+    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs: operand belongs to another context");
+    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs needs a square matrix");
+    const int n = A->rows, S = nsources;
+    for (int i = 0; i < S; i++)
+        if (sources[i] < 0 || sources[i] >= n) {
+            snprintf(g_err, sizeof g_err, "bspgemm_bfs: sources[%d] = %d is outside [0, %d)", i, sources[i], n);
+            return BSPGEMM_ERR_INVALID;
+        }
+    if (bspgemm_status st = use_device(ctx)) return st;
+    hipStream_t s = ctx->stream;
+    const long long full = (long long)S * n;                // nnz(V) when every source has reached every vertex
+
+    BfsVisited V;
+    if (bspgemm_status st = bfs_alloc(ctx, S, n, S, &V)) return st;
+    bspgemm_matrix *Fown = nullptr;                         // the frontier of levels >= 1 (level 0: V0 itself)
+    auto bail = [&](bspgemm_status st) {
+        hipStreamSynchronize(s);
+        bspgemm_matrix_free(Fown);
+        bfs_release(ctx, &V);
+        return st;
+    };
+    hipLaunchKernelGGL(k_bfs_unit_row_ptr, dim3((unsigned)(((long long)S + 1 + 255) / 256)), dim3(256), 0, s, S, V.m->d_row_ptr);
+    HIPCHK_B(hipGetLastError());
+    HIPCHK_B(hipMemcpyAsync(V.m->d_col_idx, sources, (size_t)S * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK_B(hipMemsetAsync(V.vals, 0, (size_t)S * sizeof(int), s));
+    if (bspgemm_status st = ensure_deg8(V.m)) return bail(st);
+    HIPCHK_B(hipStreamSynchronize(s));                      // `sources` is the caller's again
+
+    int d = 0, done = V.m->nnz == full;
+    while (!done) {
+        const bspgemm_matrix *F = Fown ? Fown : V.m;
+        bspgemm_result *N = nullptr;
+        bspgemm_matrix *Nm = nullptr;
+        if (bspgemm_status st = bspgemm_multiply_masked_ex(ctx, F, A, V.m, BSPGEMM_MASK_COMPLEMENT, 0, S, &N)) return bail(st);
+        if (N->nnz == 0) {                                  // nothing new: the search ended by itself
+            bspgemm_result_free(N);
+            done = 1;
+            break;
+        }
+        if (V.m->nnz + N->nnz > INT_MAX) {
+            snprintf(g_err, sizeof g_err, "bspgemm_bfs: %lld reached entries at level %d: more than INT_MAX, not usable as an int32 operand",
+                     V.m->nnz + N->nnz, d + 1);
+            bspgemm_result_free(N);
+            return bail(BSPGEMM_ERR_OVERFLOW);
+        }
+        bspgemm_status st = bspgemm_matrix_from_result(ctx, N, n, &Nm);
+        bspgemm_result_free(N);
+        if (st) return bail(st);
+        BfsVisited next;
+        st = bfs_merge(ctx, V, Nm, d + 1, &next);
+        if (st) {
+            bspgemm_matrix_free(Nm);
+            return bail(st);
+        }
+        bspgemm_matrix_free(Fown);
+        Fown = Nm;
+        bfs_release(ctx, &V);
+        V = next;
+        d++;
+        if (V.m->nnz == full) done = 1;                     // every vertex in every row: no further product
+        else if (max_depth > 0 && d >= max_depth) break;
+    }
+
+    // the last V is the result: its columns and values as they are, its row_ptr widened
+    bspgemm_result *R = new (std::nothrow) bspgemm_result{ctx, S, V.m->nnz, nullptr, V.m->d_col_idx, V.m->nnz};
+    if (!R) return bail(FAIL(BSPGEMM_ERR_ALLOC, "result"));
+    if (hipError_t e = result_alloc(ctx, reinterpret_cast<void **>(&R->d_row_ptr), result_bytes_rowptr(S))) {
+        delete R;
+        snprintf(g_err, sizeof g_err, "bspgemm_bfs: result row_ptr: %s", hipGetErrorString(e));
+        return bail(e == hipErrorOutOfMemory ? BSPGEMM_ERR_ALLOC : BSPGEMM_ERR_HIP);
+    }
+    R->d_values = V.vals;
+    hipLaunchKernelGGL(k_widen_row_ptr, dim3((unsigned)(((long long)S + 1 + 255) / 256)), dim3(256), 0, s, V.m->d_row_ptr, S + 1,
+                       R->d_row_ptr);
+    if (hipError_t e = hipGetLastError()) {
+        result_release(ctx, R->d_row_ptr, result_bytes_rowptr(S));
+        delete R;
+        snprintf(g_err, sizeof g_err, "bspgemm_bfs: k_widen_row_ptr: %s", hipGetErrorString(e));
+        return bail(BSPGEMM_ERR_HIP);
+    }
+    result_release(ctx, V.m->d_row_ptr, bfs_bytes_rowptr32(S));   // (stream-ordered behind the widening, like any freed result)
+    bspgemm_matrix_free(V.m);
+    bspgemm_matrix_free(Fown);
+    if (depth) *depth = d;
+    if (complete) *complete = done;
+    *levels = R;
+    return BSPGEMM_OK;
+}

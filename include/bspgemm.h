@@ -385,6 +385,37 @@ bspgemm_status bspgemm_triangle_count(bspgemm_context *ctx, const bspgemm_matrix
 bspgemm_status bspgemm_ktruss(bspgemm_context *ctx, const bspgemm_matrix *A, int k, int max_iter,
                               bspgemm_matrix **T, int *iterations, int *converged);
 
+/* Multi-source breadth-first search with a level per reached vertex, everything device-resident: the loop the complemented
+ * mask is for.  A is square, row u lists the out-neighbours of u; its rows may be unsorted and hold repeats, as for any
+ * product operand.  sources: a HOST array of nsources >= 1 vertex ids in [0, A.rows); repeats are allowed and give equal rows.
+ *   - *levels is a result object of nsources rows: row s holds the vertices reachable from sources[s], the source itself
+ *     included, ascending and duplicate-free like every result; the int32 value of entry (s, v) is the level of v, the
+ *     number of edges on a shortest path from sources[s] (0 for the source).  It is an ordinary counted result, allocated as
+ *     a product's is: bspgemm_result_download, _download_values, _values_device, _values_sum and _free work on it unchanged,
+ *     bspgemm_matrix_from_result gives the reachability rows, bspgemm_matrix_from_result_where the frontier of level d
+ *     (BSPGEMM_CMP_EQ, d) or the k-hop neighbourhood (BSPGEMM_CMP_LE, k).  It is complete on the context's stream when the
+ *     call returns.
+ *   - The loop: V0 = F0 = the nsources x n operand with the one entry (s, sources[s]) per row, level 0.  Level d = 1, 2, ...:
+ *     N = !V .* (F*A) (bspgemm_multiply_masked_ex with BSPGEMM_MASK_COMPLEMENT over all rows), the next frontier F = N as an
+ *     operand (bspgemm_matrix_from_result), V = V u N with the value d on N's entries.  Cost per level: one complement
+ *     product, one bspgemm_matrix_from_result, one merge, and the frees of what they replace.  The merge adds no
+ *     synchronisation: V and N are disjoint and sorted by construction, so its size is known before it runs and it needs
+ *     no flags, no scan and no read-back -- two entry-parallel launches (a hub row costs what its entries cost) that read
+ *     each operand once and search each entry in the other operand's row, and an O(1)-per-row pass for the row_ptr.
+ *   - max_depth <= 0: no cap.  max_depth > 0: at most that many products; the result then holds exactly the vertices at
+ *     distance <= max_depth.  *depth = the largest level stored.  *complete = 1 when the search ended by itself -- a
+ *     frontier came back empty, or every source had reached every vertex (then no further product runs) -- and 0 when the
+ *     cap ended it.  depth and complete may be NULL.
+ *   - bspgemm_last_stats afterwards describes the last complement product.  The knobs act on the products as always and
+ *     change no result.  With BSPGEMM_OPT_CHECK the merge also verifies that N and V are disjoint (one more
+ *     synchronisation per level) and fails with BSPGEMM_ERR_HIP if they are not.
+ *   - BSPGEMM_ERR_INVALID with *levels = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A, sources
+ *     or levels, nsources < 1, a source out of range (its index is reported), a non-square A, A from another context.
+ *     BSPGEMM_ERR_OVERFLOW: the visited set would pass INT_MAX entries (it is an int32 operand while the loop runs).  On
+ *     every failure path every intermediate is freed and the context stays usable.                                        */
+bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix *A, int nsources, const int *sources,
+                           int max_depth, bspgemm_result **levels, int *depth, int *complete);
+
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
  * an OR-accumulating variant for it): T0 = A or I, T(k+1) = T(k)*T(k) until nnz stops growing
