@@ -57,7 +57,7 @@ EXPORTS = [
     "bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values",
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
-    "bspgemm_bfs",
+    "bspgemm_bfs", "bspgemm_connected_components",
 ]
 
 
@@ -203,6 +203,7 @@ def lib():
     L.bspgemm_triangle_count.argtypes = [VP, VP, C.POINTER(C.c_int64)]
     L.bspgemm_ktruss.argtypes = [VP, VP, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_bfs.argtypes = [VP, VP, C.c_int, VP, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -493,6 +494,15 @@ class Context:
         _chk(lib().bspgemm_bfs(self._h, A._h, int(src.size), C.c_void_p(src.ctypes.data) if src.size else None,
                                int(max_depth), C.byref(r), C.byref(depth), C.byref(complete)), "bspgemm_bfs")
         return Result(self, r), depth.value, bool(complete.value)
+
+    def connected_components(self, A):
+        """bspgemm_connected_components: (P as a Matrix, ncomponents, rounds) -- the weakly connected components of A's
+        graph; P.download()[1] is the label array, label(v) = the smallest vertex id of v's component; device-resident,
+        no product"""
+        m, nc, rounds = C.c_void_p(), C.c_int(), C.c_int()
+        _chk(lib().bspgemm_connected_components(self._h, A._h, C.byref(m), C.byref(nc), C.byref(rounds)),
+             "bspgemm_connected_components")
+        return Matrix(self, m, keep=None), nc.value, rounds.value
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

@@ -1,0 +1,198 @@
+// cc.hip -- connected components with min-vertex labels, everything device-resident: bspgemm_connected_components
+// (include/bspgemm.h).  No product: a label array parent[n] (allocated as the col_idx of the assignment operand P that the
+// call returns, so nothing is copied at the end) and rounds of two kernels until a round writes nothing.
+//     parent[v] = v
+//     round:  k_cc_hook   per stored entry (u, v), v in range and v != u: pu = parent[u], pv = parent[v]; if they differ,
+//                         atomicMin(&parent[max(pu, pv)], min(pu, pv)) at device scope.  Entry-parallel in select's geometry
+//                         (sel_rows.hpp): a workgroup owns kSelTile consecutive entries of A whatever rows they belong to,
+//                         a lane four of them per step (one 16-byte non-temporal load), the tile's window of A.row_ptr is
+//                         staged in LDS -- a hub row costs what its entries cost.  A column outside [0, n) is tested BEFORE
+//                         it indexes parent[], sets the `bad` word and is skipped.
+//             k_cc_jump   per vertex: p = parent[v], kCcJumps times p = parent[p], stored back when it moved; counts the
+//                         vertices with parent[v] == v (exact in the round that ends the loop).
+//             one read-back of {changed, bad, roots} with the round's one synchronisation
+// Invariant: parent[x] <= x at all times (the hook stores min < max, the jump stores an ancestor), so chains strictly
+// decrease and cannot cycle, every value that parent[x] ever held lies in x's component, and so does every hook's pair.
+//
+// Visibility.  The per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs' stores, so a plain load of
+// parent[] inside a kernel may return an older value -- with monotone values an earlier ancestor, which costs rounds and
+// nothing else.  Nothing waits: every loop's trip count is bounded by the thread's own entries or by kCcJumps.  The decision
+// "converged" rests on a round with changed == 0: an atomicMin that lowers nothing and a jump that moves nothing store
+// nothing, so every load of that round returned the value of the kernel boundary before it, the true one.  Then
+// parent[parent[v]] == parent[v] for every v (every tree is a star) and parent[u] == parent[v] for every entry (a root r
+// has parent[r] == r, so two different roots on one entry would have been hooked): one root per component, and by the
+// invariant it is the component's smallest vertex.  Every other round lowers some parent value, so the loop ends; the host
+// caps it at n + 2 rounds all the same and never spins.
+#include "internal.hpp"
+#include "sel_rows.hpp"
+
+namespace bsp {
+
+constexpr int kCcJumps = 2;             // pointer-jumping steps per vertex and round (measured: DESIGN.md 4.13)
+constexpr int kCcThreads = 256;
+
+struct CcFlags {
+    unsigned changed;       // a hook lowered a parent, or a jump moved one
+    unsigned bad;           // a column outside [0, n)
+    int roots;              // vertices with parent[v] == v after the jump
+    unsigned pad;
+};
+
+// P.row_ptr = 0 .. n (k_bfs_unit_row_ptr's job) and parent[v] = v in one pass
+__global__ __launch_bounds__(kCcThreads) void k_cc_init(int n, int *__restrict__ row_ptr, int *__restrict__ parent)
+{
+    const long long r = (long long)blockIdx.x * kCcThreads + threadIdx.x;
+    if (r <= n) row_ptr[r] = (int)r;
+    if (r < n) parent[r] = (int)r;
+}
+
+// parent is read by plain loads and lowered by atomics in the same launch: neither const nor __restrict__
+__global__ __launch_bounds__(kSelThreads) void k_cc_hook(const int *__restrict__ row_ptr, const int *__restrict__ col, int n,
+                                                        long long E, bool vec, const int *__restrict__ tile_row, int *parent,
+                                                        CcFlags *__restrict__ flags)
+{
+    __shared__ int srp[kSelStage + 1];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const SelTileRows tr = sel_stage_tile_rows(row_ptr, n, E, tile_row, srp);
+    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
+    v4i c4[kSelSteps];
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) c4[j] = load4<true>(col, w0 + j * kSelGroup + 4 * lane, E, vec);
+    bool changed = false, bad = false;
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e0 = w0 + j * kSelGroup + 4 * lane;
+        if (e0 >= E) continue;
+        const int c[4] = {c4[j].x, c4[j].y, c4[j].z, c4[j].w};
+        int u = tr.find(tr.rb, (int)e0);                                 // one search per lane and step, then a walk
+        int end = tr.row_end(u);
+        int pu = parent[u];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const long long p = e0 + k;
+            if (p >= E) break;
+            if (p >= end) {
+                u = tr.find(u + 1, (int)p);
+                end = tr.row_end(u);
+                pu = parent[u];
+            }
+            const int v = c[k];
+            if ((unsigned)v >= (unsigned)n) {                            // before v indexes anything
+                bad = true;
+                continue;
+            }
+            if (v == u) continue;
+            const int pv = parent[v];
+            if (pu == pv) continue;
+            const int hi = max(pu, pv), lo = min(pu, pv);                // both in [0, n): parent[x] <= x
+            if (atomicMin(&parent[hi], lo) > lo) changed = true;
+        }
+    }
+    const u64 any_changed = __ballot(changed), any_bad = __ballot(bad);
+    if (lane == 0) {                                                     // one lane per wave
+        if (any_changed) flags->changed = 1u;
+        if (any_bad) flags->bad = 1u;
+    }
+}
+
+// Only thread v stores parent[v] here, and what it stores is an ancestor not above the old value: a racing reader sees the
+// old or the new one, both ancestors of v.
+__global__ __launch_bounds__(kCcThreads) void k_cc_jump(int n, int *parent, CcFlags *__restrict__ flags)
+{
+    __shared__ int wroots[kCcThreads / 64];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const long long v = (long long)blockIdx.x * kCcThreads + threadIdx.x;
+    bool moved = false, root = false;
+    if (v < n) {
+        const int p0 = parent[v];
+        int p = p0;
+#pragma unroll
+        for (int k = 0; k < kCcJumps; k++) p = parent[p];
+        if (p != p0) {
+            parent[v] = p;
+            moved = true;
+        }
+        root = p == (int)v;
+    }
+    const u64 any_moved = __ballot(moved), roots = __ballot(root);
+    if (lane == 0) {
+        if (any_moved) flags->changed = 1u;
+        wroots[w] = __popcll(roots);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+#pragma unroll
+        for (int q = 0; q < kCcThreads / 64; q++) s += wroots[q];
+        if (s) atomicAdd(&flags->roots, s);
+    }
+}
+
+static inline bool cc_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace bsp
+
+using namespace bsp;
+
+extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_matrix **P,
+                                                       int *ncomponents, int *rounds)
+{
+    if (P) *P = nullptr;
+    if (ncomponents) *ncomponents = 0;
+    if (rounds) *rounds = 0;
+    if (!ctx || !A || !P) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components: NULL argument");
+    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components: operand belongs to another context");
+    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components needs a square matrix");
+    if (A->nnz > 0 && (A->rows <= 0 || !A->d_col_idx))
+        return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components: nonzeros without rows");
+    if (A->nnz > INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_connected_components: more than INT_MAX nonzeros");
+    if (bspgemm_status st = use_device(ctx)) return st;
+    hipStream_t s = ctx->stream;
+    const int n = A->rows;
+    const long long E = A->nnz;
+    if (E > 0) {                                            // (before anything is launched: growing them synchronises)
+        if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return st;
+        if (bspgemm_status st = ensure_tmp(ctx, sizeof(CcFlags) / sizeof(int))) return st;
+    }
+    // the assignment operand, laid out like an uploaded one; its col_idx is the label array while the rounds run
+    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, n, n, n, nullptr, nullptr, true};
+    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)n + 1) * sizeof(int)));
+    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)n + 1) * sizeof(int)));
+    int *parent = m->d_col_idx;
+    const dim3 vgrid((unsigned)(((long long)n + 1 + kCcThreads - 1) / kCcThreads)), vblock(kCcThreads);
+    hipLaunchKernelGGL(k_cc_init, vgrid, vblock, 0, s, n, m->d_row_ptr, parent);
+    HIPCHK_B(hipGetLastError());
+    CcFlags h = {0, 0, n, 0};
+    int r = 0;
+    if (E > 0) {
+        CcFlags *d_flags = reinterpret_cast<CcFlags *>(ctx->tmp);
+        launch_select_tile_rows(A->d_row_ptr, n, ctx->tile_row, s);
+        const dim3 egrid((unsigned)((E + kSelTile - 1) / kSelTile)), eblock(kSelThreads);
+        const bool vec = cc_aligned16(A->d_col_idx);
+        const long long cap = (long long)n + 2;             // defensive: every round but the last lowers a parent value
+        for (;;) {
+            if (r >= cap) return bail(FAIL(BSPGEMM_ERR_HIP, "bspgemm_connected_components: did not converge"));
+            r++;
+            HIPCHK_B(hipMemsetAsync(d_flags, 0, sizeof(CcFlags), s));
+            hipLaunchKernelGGL(k_cc_hook, egrid, eblock, 0, s, A->d_row_ptr, A->d_col_idx, n, E, vec, ctx->tile_row, parent,
+                               d_flags);
+            hipLaunchKernelGGL(k_cc_jump, vgrid, vblock, 0, s, n, parent, d_flags);
+            HIPCHK_B(hipGetLastError());
+            HIPCHK_B(hipMemcpyAsync(&h, d_flags, sizeof h, hipMemcpyDeviceToHost, s));
+            HIPCHK_B(hipStreamSynchronize(s));              // the round's one synchronisation
+            if (h.bad) {
+                snprintf(g_err, sizeof g_err, "bspgemm_connected_components: a column index outside [0, %d) (A.cols)", n);
+                return bail(BSPGEMM_ERR_INVALID);
+            }
+            if (!h.changed) break;
+        }
+    }
+    if (bspgemm_status st = ensure_deg8(m)) return bail(st);
+    HIPCHK_B(hipStreamSynchronize(s));
+    if (ncomponents) *ncomponents = h.roots;
+    if (rounds) *rounds = r;
+    *P = m;
+    return BSPGEMM_OK;
+}

@@ -416,6 +416,35 @@ bspgemm_status bspgemm_ktruss(bspgemm_context *ctx, const bspgemm_matrix *A, int
 bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix *A, int nsources, const int *sources,
                            int max_depth, bspgemm_result **levels, int *depth, int *complete);
 
+/* Connected components with min-vertex labels, everything device-resident and without a product.  A is square and its
+ * entries are read as UNDIRECTED edges: the components are the weakly connected components of the directed graph stored in
+ * A (for a symmetric A: its connected components), so no symmetrize is needed and the in-edges that bspgemm_readCOO hands
+ * back give the same answer as the file's orientation.  A's rows may be unsorted and hold repeats and self-loops; any n,
+ * n == 0 and nnz == 0 included.
+ *   - *P is the n x n assignment operand: row v holds exactly one entry, the column label(v) = the smallest vertex id of
+ *     v's component.  P.row_ptr = 0, 1, ..., n and P.col_idx[v] = label(v), so bspgemm_matrix_download gives the label
+ *     array as col_idx; bspgemm_matrix_transpose(P) holds the ascending member list of component c in row c (an empty row
+ *     when c is no label; its row lengths are the component sizes); P^T * A * P by two multiplies is the quotient graph.
+ *     It is an owned operand laid out like an uploaded one (bspgemm_matrix_free), complete on the context's stream when
+ *     the call returns.
+ *   - The labels are the deterministic min-id labelling: bit for bit the same on every run, independent of scheduling.
+ *     *ncomponents = the number of v with label(v) == v, counted on the device.  *rounds = hook launches (below); 0 when
+ *     nnz == 0 or n == 0.  ncomponents and rounds may be NULL.
+ *   - The scheme: a label array parent[] (P.col_idx itself) with parent[x] <= x throughout, and rounds of two kernels.
+ *     The hook is entry-parallel over A.col_idx (a hub row costs what its entries cost): an entry (u, v) with different
+ *     parent[u] and parent[v] lowers the parent of the larger of the two to the smaller by a device-scope atomicMin.  The
+ *     jump replaces every parent[v] by an ancestor a fixed number of steps up.  One read-back of three words per round; the
+ *     loop ends with the first round that wrote nothing.  No kernel waits for another workgroup's store, and the result
+ *     does not depend on when such stores become visible (csrc/cc.hip).  4 * nnz + 4 * (n + 1) + 8 * n bytes per round and
+ *     the gathers of parent[]; a defensive cap of n + 2 rounds (BSPGEMM_ERR_HIP, "did not converge").
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *P = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A or P, a
+ *     non-square A, A from another context, a column outside [0, n) anywhere in A (every column is tested on the device
+ *     before it is used as an index; the context stays usable).  BSPGEMM_ERR_ALLOC: an allocation failed.  Nothing is
+ *     leaked on any failure path.                                                                                         */
+bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A,
+                                            bspgemm_matrix **P, int *ncomponents, int *rounds);
+
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
  * an OR-accumulating variant for it): T0 = A or I, T(k+1) = T(k)*T(k) until nnz stops growing

@@ -1,0 +1,48 @@
+"""SpGEMM_hip_cc, the command-line driver of bspgemm_connected_components: on a Matrix Market file written here entry by
+entry, its line and its --labels file equal what the scipy reference gives; a missing file ends it like the other drivers.
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bspgemm
+import cc_ref
+import gen
+
+pytestmark = pytest.mark.gpu
+CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_cc")
+
+
+def _write_edges(path, rp, ci, n):
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    with open(path, "w") as f:
+        f.write("%%%%MatrixMarket matrix coordinate pattern general\n%d %d %d\n" % (n, n, ci.size))
+        f.write("".join("%d %d\n" % (r + 1, c + 1) for r, c in zip(rows.tolist(), ci.tolist())))
+
+
+def test_cli_matches_the_reference(tmp_path):
+    assert os.path.exists(CLI), "%s is not built" % CLI
+    rp, ci, n = gen.rmat(10, 6, (0.57, 0.19, 0.19, 0.05), 7601)
+    label, count = cc_ref.labels(rp, ci, n)
+    largest = int(np.bincount(label).max())
+    assert 1 < count < n and 1 < largest < n
+    src, out = str(tmp_path / "graph.mtx"), str(tmp_path / "labels.txt")
+    _write_edges(src, rp, ci, n)
+    for extra in ([], ["--labels", out]):
+        r = subprocess.run([CLI, src] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        f = r.stdout.strip().split(",")
+        assert len(f) == 6 and [int(x) for x in f[:4]] == [n, ci.size, count, largest], r.stdout
+        assert 1 <= int(f[4]) <= n + 1 and float(f[5]) > 0, r.stdout
+    assert np.array_equal(np.loadtxt(out, dtype=np.int64), label)
+
+
+def test_cli_usage_and_missing_file(tmp_path):
+    r = subprocess.run([CLI], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1 and r.stdout.startswith("usage: SpGEMM_hip_cc")
+    r = subprocess.run([CLI, str(tmp_path / "graph.mtx"), "--labels"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1 and r.stdout.startswith("usage: SpGEMM_hip_cc")
+    r = subprocess.run([CLI, str(tmp_path / "missing.mtx")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1 and r.stdout == ""
