@@ -27,17 +27,6 @@
 
 namespace bsp {
 
-// first position in [lo, hi) of y whose column is not below c
-__device__ __forceinline__ int merge_lower_bound(const int *__restrict__ y, int lo, int hi, int c)
-{
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (y[mid] < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // VALS: the entries' values come from valsX (the V side), else every entry gets `level` (the N side).  X's columns and
 // values are read once (non-temporal); Y's columns are probed by many lanes and stay temporal.  The destinations
 // p + lb < E + nnz(Y) for consistent row_ptrs: lb <= rpY[rows] = nnz(Y).
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(kSelThreads) void k_merge_disjoint(const int *__res
                 from = rpY[r];
                 yend = rpY[r + 1];
             }
-            from = merge_lower_bound(colY, from, yend, c[k]);            // (an empty row of Y: nothing is read)
+            from = sel_lower_bound(colY, from, yend, c[k]);            // (an empty row of Y: nothing is read)
             if (CHECK && from < yend && colY[from] == c[k]) common = true;
             const long long dst = p + from;
             out_col[dst] = c[k];
@@ -110,8 +99,6 @@ __global__ __launch_bounds__(256) void k_bfs_unit_row_ptr(int rows, int *__restr
     if (r <= rows) row_ptr[r] = r;
 }
 
-static inline bool merge_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // one side of the merge: the nnzX > 0 entries of X (vals: their values, or NULL for the constant `level`) to their places
 // in out_col / out_val.  tile_row: nnzX / kSelTile + 1 ints of scratch; hit: NULL, or the device word of the check.
 static void launch_merge_side(const int *rpX, const int *colX, const int *vals, int level, int rows, long long nnzX,
@@ -120,8 +107,8 @@ static void launch_merge_side(const int *rpX, const int *colX, const int *vals, 
 {
     if (nnzX <= 0) return;
     launch_select_tile_rows(rpX, rows, tile_row, s);
-    const dim3 grid((unsigned)((nnzX + kSelTile - 1) / kSelTile)), block(kSelThreads);
-    const bool vec = merge_aligned16(colX), vecv = vals && merge_aligned16(vals);
+    const dim3 grid(select_tiles(nnzX)), block(kSelThreads);
+    const bool vec = aligned16(colX), vecv = vals && aligned16(vals);
 #define BSP_MERGE(VALS, CHECK)                                                                                            \
     hipLaunchKernelGGL((k_merge_disjoint<VALS, CHECK>), grid, block, 0, s, rpX, colX, vals, level, rows, nnzX, vec, vecv, \
                        tile_row, rpY, colY, out_col, out_val, hit)
@@ -142,7 +129,9 @@ using namespace bsp;
 // ------------------------------------------------------------------ the host side --------
 // The visited set while the loop runs: an int32 operand (the next product's mask) and a level per entry.  Its arrays come
 // from the context's result cache, like a product's, because the last V becomes the result object as it stands; the handle
-// does not own them.
+// does not own them.  That is why it is not built by operand_new / operand_cols (internal.hpp): those hipMalloc arrays
+// that bspgemm_matrix_free frees, these go back to the cache (bfs_release) or on into the result, with a third array
+// (the levels) that an operand does not have.
 struct BfsVisited {
     bspgemm_matrix *m = nullptr;
     int *vals = nullptr;
@@ -194,8 +183,7 @@ static bspgemm_status bfs_merge(bspgemm_context *ctx, const BfsVisited &V, const
                       out->m->d_col_idx, out->vals, d_hit, s);
     launch_merge_side(N->d_row_ptr, N->d_col_idx, nullptr, level, rows, EN, V.m->d_row_ptr, V.m->d_col_idx, ctx->tile_row,
                       out->m->d_col_idx, out->vals, d_hit, s);
-    hipLaunchKernelGGL(k_merge_row_ptr, dim3((unsigned)(((long long)rows + 1 + 255) / 256)), dim3(256), 0, s, V.m->d_row_ptr,
-                       N->d_row_ptr, rows, out->m->d_row_ptr);
+    hipLaunchKernelGGL(k_merge_row_ptr, row_pass_grid(rows), dim3(256), 0, s, V.m->d_row_ptr, N->d_row_ptr, rows, out->m->d_row_ptr);
     HIPCHK_B(hipGetLastError());
     if (d_hit) {
         unsigned hit = 0;
@@ -215,8 +203,7 @@ extern "C" bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix
     if (complete) *complete = 0;
     if (!ctx || !A || !sources || !levels) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs: NULL argument");
     if (nsources < 1) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs: nsources < 1");
-    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs: operand belongs to another context");
-    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_bfs needs a square matrix");
+    if (bspgemm_status st = check_operand(ctx, A, "bspgemm_bfs", NEED_SQUARE)) return st;
     const int n = A->rows, S = nsources;
     for (int i = 0; i < S; i++)
         if (sources[i] < 0 || sources[i] >= n) {
@@ -230,13 +217,16 @@ extern "C" bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix
     BfsVisited V;
     if (bspgemm_status st = bfs_alloc(ctx, S, n, S, &V)) return st;
     bspgemm_matrix *Fown = nullptr;                         // the frontier of levels >= 1 (level 0: V0 itself)
+    bspgemm_result *R = nullptr;                            // the result object, made at the end: shares V's columns and values
     auto bail = [&](bspgemm_status st) {
         hipStreamSynchronize(s);
+        if (R) result_release(ctx, R->d_row_ptr, result_bytes_rowptr(S));
+        delete R;
         bspgemm_matrix_free(Fown);
         bfs_release(ctx, &V);
         return st;
     };
-    hipLaunchKernelGGL(k_bfs_unit_row_ptr, dim3((unsigned)(((long long)S + 1 + 255) / 256)), dim3(256), 0, s, S, V.m->d_row_ptr);
+    hipLaunchKernelGGL(k_bfs_unit_row_ptr, row_pass_grid(S), dim3(256), 0, s, S, V.m->d_row_ptr);
     HIPCHK_B(hipGetLastError());
     HIPCHK_B(hipMemcpyAsync(V.m->d_col_idx, sources, (size_t)S * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK_B(hipMemsetAsync(V.vals, 0, (size_t)S * sizeof(int), s));
@@ -279,22 +269,12 @@ extern "C" bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix
     }
 
     // the last V is the result: its columns and values as they are, its row_ptr widened
-    bspgemm_result *R = new (std::nothrow) bspgemm_result{ctx, S, V.m->nnz, nullptr, V.m->d_col_idx, V.m->nnz};
+    R = new (std::nothrow) bspgemm_result{ctx, S, V.m->nnz, nullptr, V.m->d_col_idx, V.m->nnz};
     if (!R) return bail(FAIL(BSPGEMM_ERR_ALLOC, "result"));
-    if (hipError_t e = result_alloc(ctx, reinterpret_cast<void **>(&R->d_row_ptr), result_bytes_rowptr(S))) {
-        delete R;
-        snprintf(g_err, sizeof g_err, "bspgemm_bfs: result row_ptr: %s", hipGetErrorString(e));
-        return bail(e == hipErrorOutOfMemory ? BSPGEMM_ERR_ALLOC : BSPGEMM_ERR_HIP);
-    }
+    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_row_ptr), result_bytes_rowptr(S)));
     R->d_values = V.vals;
-    hipLaunchKernelGGL(k_widen_row_ptr, dim3((unsigned)(((long long)S + 1 + 255) / 256)), dim3(256), 0, s, V.m->d_row_ptr, S + 1,
-                       R->d_row_ptr);
-    if (hipError_t e = hipGetLastError()) {
-        result_release(ctx, R->d_row_ptr, result_bytes_rowptr(S));
-        delete R;
-        snprintf(g_err, sizeof g_err, "bspgemm_bfs: k_widen_row_ptr: %s", hipGetErrorString(e));
-        return bail(BSPGEMM_ERR_HIP);
-    }
+    hipLaunchKernelGGL(k_widen_row_ptr, row_pass_grid(S), dim3(256), 0, s, V.m->d_row_ptr, S + 1, R->d_row_ptr);
+    HIPCHK_B(hipGetLastError());
     result_release(ctx, V.m->d_row_ptr, bfs_bytes_rowptr32(S));   // (stream-ordered behind the widening, like any freed result)
     bspgemm_matrix_free(V.m);
     bspgemm_matrix_free(Fown);

@@ -128,8 +128,6 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_jump(int n, int *parent, CcFl
     }
 }
 
-static inline bool cc_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace bsp
 
 using namespace bsp;
@@ -141,10 +139,7 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
     if (ncomponents) *ncomponents = 0;
     if (rounds) *rounds = 0;
     if (!ctx || !A || !P) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components: NULL argument");
-    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components: operand belongs to another context");
-    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components needs a square matrix");
-    if (A->nnz > 0 && (A->rows <= 0 || !A->d_col_idx))
-        return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components: nonzeros without rows");
+    if (bspgemm_status st = check_operand(ctx, A, "bspgemm_connected_components", NEED_SQUARE | NEED_ENTRIES_CONSISTENT)) return st;
     if (A->nnz > INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_connected_components: more than INT_MAX nonzeros");
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
@@ -155,11 +150,10 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
         if (bspgemm_status st = ensure_tmp(ctx, sizeof(CcFlags) / sizeof(int))) return st;
     }
     // the assignment operand, laid out like an uploaded one; its col_idx is the label array while the rounds run
-    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, n, n, n, nullptr, nullptr, true};
-    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    bspgemm_matrix *m = nullptr;
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)n + 1) * sizeof(int)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)n + 1) * sizeof(int)));
+    if (bspgemm_status st = operand_new(ctx, n, n, &m)) return bail(st);
+    if (bspgemm_status st = operand_cols(m, n)) return bail(st);
     int *parent = m->d_col_idx;
     const dim3 vgrid((unsigned)(((long long)n + 1 + kCcThreads - 1) / kCcThreads)), vblock(kCcThreads);
     hipLaunchKernelGGL(k_cc_init, vgrid, vblock, 0, s, n, m->d_row_ptr, parent);
@@ -169,8 +163,8 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
     if (E > 0) {
         CcFlags *d_flags = reinterpret_cast<CcFlags *>(ctx->tmp);
         launch_select_tile_rows(A->d_row_ptr, n, ctx->tile_row, s);
-        const dim3 egrid((unsigned)((E + kSelTile - 1) / kSelTile)), eblock(kSelThreads);
-        const bool vec = cc_aligned16(A->d_col_idx);
+        const dim3 egrid(select_tiles(E)), eblock(kSelThreads);
+        const bool vec = aligned16(A->d_col_idx);
         const long long cap = (long long)n + 2;             // defensive: every round but the last lowers a parent value
         for (;;) {
             if (r >= cap) return bail(FAIL(BSPGEMM_ERR_HIP, "bspgemm_connected_components: did not converge"));
@@ -189,7 +183,7 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
             if (!h.changed) break;
         }
     }
-    if (bspgemm_status st = ensure_deg8(m)) return bail(st);
+    if (bspgemm_status st = operand_finish(m, n)) return bail(st);   // one label per vertex
     HIPCHK_B(hipStreamSynchronize(s));
     if (ncomponents) *ncomponents = h.roots;
     if (rounds) *rounds = r;

@@ -1,5 +1,5 @@
 // context.hip -- the handle side of the C ABI (include/bspgemm.h): errors, the per-GPU context and its
-// workspaces, device-resident operands and their derived tables, the cache of freed result buffers,
+// workspaces, device-resident operands, the builder of derived ones and their tables, the cache of freed result buffers,
 // result accessors, statistics.  No CPU compute path exists in this library: without a gfx950 device
 // every compute entry point fails with BSPGEMM_ERR_NO_DEVICE.
 #include "internal.hpp"
@@ -244,6 +244,57 @@ extern "C" bspgemm_status bspgemm_synchronize(bspgemm_context *ctx)
 }
 
 // ------------------------------------------------------------------ operands -------------
+// The three steps of a derived operand (internal.hpp).  Nothing here touches the stream but operand_finish's one launch.
+bspgemm_status operand_new(bspgemm_context *ctx, int rows, int cols, bspgemm_matrix **out)
+{
+    bspgemm_matrix *m = *out = new (std::nothrow) bspgemm_matrix{ctx, rows, cols, 0, nullptr, nullptr, true};
+    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)rows + 1) * sizeof(int)));
+    return BSPGEMM_OK;
+}
+
+bspgemm_status operand_cols(bspgemm_matrix *m, long long cap)
+{
+    // +1 int of slack on col_idx so an empty matrix still has a valid pointer
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)cap + 1) * sizeof(int)));
+    return BSPGEMM_OK;
+}
+
+bspgemm_status operand_finish(bspgemm_matrix *m, long long nnz)
+{
+    m->nnz = nnz;
+    return ensure_deg8(m);
+}
+
+bspgemm_status check_operand(const bspgemm_context *ctx, const bspgemm_matrix *A, const char *who, unsigned flags)
+{
+    const char *what = nullptr;
+    if (A->ctx != ctx) what = ": operand belongs to another context";
+    else if ((flags & NEED_SQUARE) && A->rows != A->cols) what = " needs a square matrix";
+    else if ((flags & NEED_ENTRIES_CONSISTENT) && A->nnz > 0 && (A->rows <= 0 || !A->d_col_idx)) what = ": nonzeros without rows";
+    if (!what) return BSPGEMM_OK;
+    snprintf(g_err, sizeof g_err, "%s%s", who, what);
+    return BSPGEMM_ERR_INVALID;
+}
+
+size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratch *sc)
+{
+    const size_t W = select_words(E);
+    if (W > (size_t)INT_MAX) return 0;
+    auto take = [&](size_t ints) { const size_t o = at; at += (ints + 3) & ~(size_t)3; return o; };
+    const size_t o_flags = take(2 * W), o_pre = take(2 * (W + 1)), o_part = take(2 * (W / 2048 + 4)), o_cnt = take(W);
+    const size_t o_lbs = take(lbs ? W * 64 : 0);
+    if (sc) {
+        sc->flags = reinterpret_cast<unsigned long long *>(tmp + o_flags);
+        sc->pre = reinterpret_cast<long long *>(tmp + o_pre);
+        sc->part = reinterpret_cast<long long *>(tmp + o_part);
+        sc->cnt = tmp + o_cnt;
+        sc->lbs = lbs ? tmp + o_lbs : nullptr;
+        sc->words = (int)W;
+    }
+    return at;
+}
+
 extern "C" bspgemm_status bspgemm_matrix_upload(bspgemm_context *ctx, int rows, int cols,
                                                 const int *row_ptr, const int *col_idx,
                                                 bspgemm_matrix **out)
@@ -254,17 +305,15 @@ extern "C" bspgemm_status bspgemm_matrix_upload(bspgemm_context *ctx, int rows, 
     const long long nnz = (long long)row_ptr[rows] - base;
     if (nnz < 0 || (nnz > 0 && !col_idx)) return FAIL(BSPGEMM_ERR_INVALID, "row_ptr not ascending / col_idx NULL");
     if (bspgemm_status st = use_device(ctx)) return st;
-    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, rows, cols, nnz, nullptr, nullptr, true};
-    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    bspgemm_matrix *m = nullptr;
     auto bail = [&](bspgemm_status st) { bspgemm_matrix_free(m); return st; };   // handle + device arrays
-    // +1 int of slack on col_idx so an empty matrix still has a valid pointer
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)rows + 1) * sizeof(int)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)nnz + 1) * sizeof(int)));
+    if (bspgemm_status st = operand_new(ctx, rows, cols, &m)) return bail(st);
+    if (bspgemm_status st = operand_cols(m, nnz)) return bail(st);
     HIPCHK_B(hipMemcpyAsync(m->d_row_ptr, row_ptr, ((size_t)rows + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     if (nnz > 0)
         HIPCHK_B(hipMemcpyAsync(m->d_col_idx, col_idx + base, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     launch_rebase_i32(m->d_row_ptr, rows + 1, (int)base, ctx->stream);
-    if (bspgemm_status st = ensure_deg8(m)) return bail(st);
+    if (bspgemm_status st = operand_finish(m, nnz)) return bail(st);
     HIPCHK_B(hipStreamSynchronize(ctx->stream));
     *out = m;
     return BSPGEMM_OK;

@@ -1,6 +1,8 @@
 // internal.hpp -- what the translation units behind include/bspgemm.h share: the error macros, the handle
-// structs, the workspace / result-cache helpers (context.hip) that the flows (multiply.hip), the int32 drop-ins
-// (dropin.hip) and the communicator layer (comm.hip) use.  Not installed; nothing here is part of the C ABI.
+// structs, the builder of derived operands and the operand check that every entry point returning an operand uses, the
+// workspace / result-cache helpers (context.hip) that the flows (multiply.hip), the int32 drop-ins (dropin.hip) and the
+// communicator layer (comm.hip) use, the flag scratch of select.hip and setop.hip.  Not installed; nothing here is part
+// of the C ABI.
 #pragma once
 #include "../../include/bspgemm.h"
 #include "kernels.hpp"
@@ -167,6 +169,23 @@ bspgemm_status ensure_deg8(const bspgemm_matrix *m);
 bspgemm_status ensure_blk16(const bspgemm_matrix *m);
 bspgemm_status ensure_pad(const bspgemm_matrix *m);   // before ensure_blk16: the blocked table carries padded bases
 
+// ------------------------------------------------------------------ derived operands (context.hip) ---
+// An operand that the library builds on the device (upload, from_result, select, setop, transpose, ...) owns its two
+// arrays (owned == true) and is built in three steps, each of which the call site places where its launches and its
+// synchronisation want it.  After a failed step *m is NULL or a handle that bspgemm_matrix_free takes, so a caller needs
+// one `bail` that frees m, whichever step failed.
+bspgemm_status operand_new(bspgemm_context *ctx, int rows, int cols, bspgemm_matrix **m);   // handle (nnz 0) + d_row_ptr
+bspgemm_status operand_cols(bspgemm_matrix *m, long long cap);                             // d_col_idx for cap entries
+bspgemm_status operand_finish(bspgemm_matrix *m, long long nnz);                           // nnz, and d_deg8 on the stream
+// sorted duplicate-free copy of X: transposed twice (transpose.hip)
+bspgemm_status operand_canonical(bspgemm_context *ctx, const bspgemm_matrix *X, bspgemm_matrix **out);
+
+// What an entry point asks of an operand of its context, tested in this order: it belongs to ctx, (NEED_SQUARE) rows ==
+// cols, (NEED_ENTRIES_CONSISTENT) an operand with nonzeros has rows and a col_idx.  who: the entry point's name, which the
+// message starts with.  BSPGEMM_ERR_INVALID with the text set, or BSPGEMM_OK.
+enum : unsigned { NEED_SQUARE = 1u, NEED_ENTRIES_CONSISTENT = 2u };
+bspgemm_status check_operand(const bspgemm_context *ctx, const bspgemm_matrix *A, const char *who, unsigned flags);
+
 struct bspgemm_result {
     bspgemm_context *ctx;
     int rows;
@@ -192,6 +211,19 @@ hipError_t result_alloc(bspgemm_context *ctx, void **out, size_t bytes);
 void result_release(bspgemm_context *ctx, void *p, size_t bytes);
 static inline size_t result_bytes_rowptr(int rows) { return ((size_t)rows + 1) * sizeof(long long); }
 static inline size_t result_bytes_colidx(long long nnz) { return ((size_t)nnz + 4) * sizeof(int); }
+
+// Scratch of the flag-word passes over E entries (select.hip, setop.hip), carved from ctx->tmp (kept between calls, like
+// the transpose's): the flag words (one per 64 entries, whole tiles), the int64 scan of their counts, the scan's partials,
+// the counts, and (lbs) an int per entry in whole tiles.
+struct FlagScratch {
+    unsigned long long *flags;
+    long long *pre, *part;
+    int *cnt, *lbs;
+    int words;
+};
+// Lays the scratch of E entries out from int offset `at` of tmp, every array on a 16-byte boundary, and returns the end;
+// 0: more words than the scan's int count takes.  sc NULL: the end alone (what to ask ensure_tmp for: tmp may move).
+size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratch *sc);
 
 // one line on stderr for a failed drop-in ("SpGEMM_hip: <status>: <last error>"), returns the status as int (dropin.hip)
 int dropin_fail(const char *fn, bspgemm_status st);

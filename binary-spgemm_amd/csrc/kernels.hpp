@@ -2,7 +2,7 @@
 // Kernels: prepass.hip (row work, scans, class records), wave_rows.inc (k_wave_rows; one object per (LEVELS, mask mode) pair,
 // dispatched by wave_rows.hip), wave_masked.hip (k_wave_masked), dense_rows.hip (k_dense_rows, k_dense_rows_count,
 // k_rank_rows) over the heavy rows' gather in heavy_gather.hpp, compact.hip (compaction, heavy-row moves),
-// small.hip, transpose.hip, select.hip, setop.hip, bfs.hip (its launches stay in that file).  A family is ONE template kernel with the mask mode as a template parameter.
+// small.hip, transpose.hip, select.hip, setop.hip, bfs.hip, cc.hip (the launches of the last three stay in their files).  A family is ONE template kernel with the mask mode as a template parameter.
 // Tuning constants are compile-time constants, not switches: what was tried against them is in profiles/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -251,7 +251,11 @@ void launch_add_diagonal(const int *Arow, const int *Acol, int n, int *Trow, int
 // A select over nnz entries works in tiles of kSelTile entries and keeps, per 64 entries, one flag word (bit b of word w:
 // entry 64 w + b is kept) and its popcount: select_words(nnz) of each, whole tiles (the words past the last entry are 0).
 constexpr int kSelTile = kRowWorkTile;     // the structural select borrows the flat prepass's tile_row (ensure_tile_rows(nnz))
-inline size_t select_words(long long nnz) { return (size_t)((nnz + kSelTile - 1) / kSelTile) * (kSelTile / 64); }
+inline int select_tiles(long long nnz) { return (int)((nnz + kSelTile - 1) / kSelTile); }   // the grid of an entry-parallel pass
+inline size_t select_words(long long nnz) { return (size_t)select_tiles(nnz) * (kSelTile / 64); }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }   // 16-byte loads are allowed
+// the grid of a row pass: one thread of a 256-thread workgroup per r in [0, rows]
+inline dim3 row_pass_grid(int rows) { return dim3((unsigned)(((long long)rows + 1 + 255) / 256)); }
 // pass 1, structural: entry (r, c) is kept when c < r (op 1, BSPGEMM_SELECT_TRIL), c > r (2, TRIU), c != r (3, OFFDIAG);
 // tile_row: nnz / kSelTile + 1 ints of scratch
 void launch_select_flags_struct(const int *row_ptr, const int *col_idx, int rows, long long nnz, int op, int *tile_row,
@@ -270,22 +274,6 @@ void launch_select_row_ptr(const int *row_ptr32, const long long *row_ptr64, int
                            const unsigned long long *flags, const long long *prefix, int *out, hipStream_t s);
 // *sum (device, zeroed by the caller) += vals[0 .. nnz), exact in 64 bits
 void launch_values_sum(const int *vals, long long nnz, unsigned long long *sum, hipStream_t s);
-
-// ---- set operations on two operands' patterns (setop.hip), in select's tiles, flag words and scan ----
-// pass 1 over operand X against Y (same shape): *err |= (1: a column outside [0, cols), 2: a row not strictly ascending),
-// shifted left by two bits when `second`.  search: bit b of flags[w] = entry 64 w + b of X is also in Y's row (invert: is
-// not), cnt[w] its popcount, and (lbs != NULL, whole tiles of ints) lbs[e] = the position in colY of the first entry of the
-// row that is not below X's column.  Without search only the check runs.  tile_row: nnzX / kSelTile + 1 ints of scratch.
-void launch_setop_flags(const int *rpX, const int *colX, int rows, int cols, long long nnzX, const int *rpY, const int *colY,
-                        bool search, bool invert, bool second, int *tile_row, unsigned long long *flags, int *cnt, int *lbs,
-                        unsigned *err, hipStream_t s);
-// pass 2 of OR (k = 1) and XOR (k = 2) over X: out[e + lbs[e] - k * (common entries before e)] = colX[e] for every entry
-// (all) or every non-common one; flags: the common entries, prefix: the scan of their counts
-void launch_setop_place(const int *colX, long long nnzX, const unsigned long long *flags, const long long *prefix,
-                        const int *lbs, int k, bool all, int *out, hipStream_t s);
-// out[r] = rpA[r] + rpB[r] - k * (common entries of A before rpA[r]), r in [0, rows]
-void launch_setop_row_ptr(const int *rpA, const int *rpB, int rows, long long nnzA, const unsigned long long *flags,
-                          const long long *prefix, int k, int *out, hipStream_t s);
 
 // row_ptr rebasing helper for interior-pointer uploads
 void launch_rebase_i32(int *row_ptr, int n, int base, hipStream_t s);

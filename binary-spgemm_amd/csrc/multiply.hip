@@ -575,15 +575,14 @@ extern "C" bspgemm_status bspgemm_matrix_from_result(bspgemm_context *ctx, const
     *out = nullptr;
     if (C->nnz > INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "product has more than INT_MAX nonzeros: not usable as an int32 operand");
     if (bspgemm_status st = use_device(ctx)) return st;
-    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, C->rows, cols, C->nnz, nullptr, nullptr, true};
-    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    bspgemm_matrix *m = nullptr;
     auto bail = [&](bspgemm_status st) { bspgemm_matrix_free(m); return st; };
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)C->rows + 1) * sizeof(int)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)C->nnz + 1) * sizeof(int)));
+    if (bspgemm_status st = operand_new(ctx, C->rows, cols, &m)) return bail(st);
+    if (bspgemm_status st = operand_cols(m, C->nnz)) return bail(st);
     launch_narrow_row_ptr(C->d_row_ptr, m->d_row_ptr, C->rows + 1, ctx->stream);
     if (C->nnz > 0)
         HIPCHK_B(hipMemcpyAsync(m->d_col_idx, C->d_col_idx, (size_t)C->nnz * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
-    if (bspgemm_status st = ensure_deg8(m)) return bail(st);
+    if (bspgemm_status st = operand_finish(m, C->nnz)) return bail(st);
     HIPCHK_B(hipStreamSynchronize(ctx->stream));
     *out = m;
     return BSPGEMM_OK;
@@ -599,14 +598,13 @@ extern "C" bspgemm_status bspgemm_closure(bspgemm_context *ctx, const bspgemm_ma
     if (A->nnz + (long long)A->rows > INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "A or I exceeds int32 nonzeros");
     if (bspgemm_status st = use_device(ctx)) return st;
     const int n = A->rows;
-    bspgemm_matrix *cur = new (std::nothrow) bspgemm_matrix{ctx, n, n, A->nnz + n, nullptr, nullptr, true};
-    if (!cur) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    bspgemm_matrix *cur = nullptr;                      // T0 = A | I
     {
         auto bail = [&](bspgemm_status st) { bspgemm_matrix_free(cur); return st; };
-        HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&cur->d_row_ptr), ((size_t)n + 1) * sizeof(int)));
-        HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&cur->d_col_idx), ((size_t)cur->nnz + 1) * sizeof(int)));
+        if (bspgemm_status st = operand_new(ctx, n, n, &cur)) return bail(st);
+        if (bspgemm_status st = operand_cols(cur, A->nnz + n)) return bail(st);
         launch_add_diagonal(A->d_row_ptr, A->d_col_idx, n, cur->d_row_ptr, cur->d_col_idx, ctx->stream);
-        if (bspgemm_status st = ensure_deg8(cur)) return bail(st);
+        if (bspgemm_status st = operand_finish(cur, A->nnz + n)) return bail(st);
         HIPCHK_B(hipStreamSynchronize(ctx->stream));
     }
     long long prev_nnz = -1;      // nnz of the deduplicated T(k); unknown for T0 (may hold duplicates)

@@ -1,6 +1,7 @@
-// sel_rows.hpp -- device code that the entry-parallel passes of select.hip and setop.hip share: the tile geometry, the
-// 16-byte entry loads, the DPP join of a lane's four flags into the 64-bit flag word of 64 entries, and the search of an
-// entry's row in the tile's window of row_ptr (staged in LDS; tile_row comes from k_sel_tile_rows).  Device code only.
+// sel_rows.hpp -- device code that the entry-parallel passes of select.hip, setop.hip, bfs.hip and cc.hip share: the tile
+// geometry, the 16-byte entry loads, the DPP join of a lane's four flags into the 64-bit flag word of 64 entries, the search
+// of an entry's row in the tile's window of row_ptr (staged in LDS; tile_row comes from k_sel_tile_rows) and the lower bound
+// of a column in a row of another operand.  Device code only.
 #pragma once
 #include "kernels.hpp"
 #include "wave.hpp"
@@ -68,6 +69,17 @@ __device__ __forceinline__ int sel_row_of(P rp, int lo, int hi, int e)
         const int mid = (lo + hi + 1) >> 1;
         if (rp[mid] <= e) lo = mid;
         else hi = mid - 1;
+    }
+    return lo;
+}
+
+// first position in [lo, hi) of y whose column is not below c
+__device__ __forceinline__ int sel_lower_bound(const int *__restrict__ y, int lo, int hi, int c)
+{
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (y[mid] < c) lo = mid + 1;
+        else hi = mid;
     }
     return lo;
 }

@@ -1,6 +1,7 @@
 // select.hip -- stable filters of CSR entries on the device, the reduction of a counted result's values, and the two loops
 // built on them: bspgemm_matrix_select, bspgemm_matrix_from_result_where, bspgemm_result_values_sum, bspgemm_triangle_count,
-// bspgemm_ktruss (include/bspgemm.h).  The loads, the flag-word join and the row search are in sel_rows.hpp (also setop.hip's).
+// bspgemm_ktruss (include/bspgemm.h).  The loads, the flag-word join and the row search are in sel_rows.hpp (also setop.hip's),
+// the flag scratch and the operand builder in internal.hpp.
 //
 // One design serves the structural select (col against row) and the value select (count against a threshold).  Work is
 // spread over ENTRIES: a workgroup owns kSelTile consecutive entries whatever rows they belong to, so a hub row of 10^5
@@ -180,9 +181,6 @@ __global__ __launch_bounds__(256) void k_values_sum(const int *__restrict__ vals
     if (threadIdx.x == 0) atomicAdd(sum, (unsigned long long)(wsum[0] + wsum[1] + wsum[2] + wsum[3]));
 }
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline int sel_tiles(long long nnz) { return (int)((nnz + kSelTile - 1) / kSelTile); }
-
 void launch_select_tile_rows(const int *row_ptr, int rows, int *tile_row, hipStream_t s)
 {
     hipLaunchKernelGGL(k_sel_tile_rows, dim3((rows + 255) / 256), dim3(256), 0, s, row_ptr, rows, tile_row);
@@ -192,8 +190,8 @@ void launch_select_flags_struct(const int *row_ptr, const int *col_idx, int rows
                                 unsigned long long *flags, int *cnt, hipStream_t s)
 {
     if (nnz <= 0) return;
-    hipLaunchKernelGGL(k_sel_tile_rows, dim3((rows + 255) / 256), dim3(256), 0, s, row_ptr, rows, tile_row);
-    hipLaunchKernelGGL(k_sel_flags_struct, dim3(sel_tiles(nnz)), dim3(kSelThreads), 0, s, row_ptr, col_idx, rows, nnz, op,
+    launch_select_tile_rows(row_ptr, rows, tile_row, s);
+    hipLaunchKernelGGL(k_sel_flags_struct, dim3(select_tiles(nnz)), dim3(kSelThreads), 0, s, row_ptr, col_idx, rows, nnz, op,
                        aligned16(col_idx), tile_row, flags, cnt);
 }
 
@@ -201,7 +199,7 @@ void launch_select_flags_value(const int *vals, long long nnz, int cmp, int thre
                                hipStream_t s)
 {
     if (nnz <= 0) return;
-    hipLaunchKernelGGL(k_sel_flags_value, dim3(sel_tiles(nnz)), dim3(kSelThreads), 0, s, vals, nnz, cmp, threshold,
+    hipLaunchKernelGGL(k_sel_flags_value, dim3(select_tiles(nnz)), dim3(kSelThreads), 0, s, vals, nnz, cmp, threshold,
                        aligned16(vals), flags, cnt);
 }
 
@@ -209,14 +207,14 @@ void launch_select_scatter(const int *src, long long nnz, const unsigned long lo
                            hipStream_t s)
 {
     if (nnz <= 0) return;
-    hipLaunchKernelGGL(k_sel_scatter, dim3(sel_tiles(nnz)), dim3(kSelThreads), 0, s, src, nnz, aligned16(src), flags, prefix, out);
+    hipLaunchKernelGGL(k_sel_scatter, dim3(select_tiles(nnz)), dim3(kSelThreads), 0, s, src, nnz, aligned16(src), flags, prefix, out);
 }
 
 void launch_select_row_ptr(const int *row_ptr32, const long long *row_ptr64, int rows, long long nnz,
                            const unsigned long long *flags, const long long *prefix, int *out, hipStream_t s)
 {
     const long long words = (long long)select_words(nnz);
-    const dim3 grid((unsigned)(((long long)rows + 1 + 255) / 256));
+    const dim3 grid = row_pass_grid(rows);
     if (row_ptr32)
         hipLaunchKernelGGL(k_sel_row_ptr<int>, grid, dim3(256), 0, s, row_ptr32, rows, nnz, words, flags, prefix, out);
     else
@@ -236,85 +234,67 @@ void launch_values_sum(const int *vals, long long nnz, unsigned long long *sum, 
 using namespace bsp;
 
 // ------------------------------------------------------------------ the two selects ------
-// Scratch of a select over E entries, carved from the context's upper-bound workspace (kept, like the transpose's): the
-// flag words, the scan of their counts, the scan's partials, the counts.
-struct SelScratch {
-    unsigned long long *flags;
-    long long *pre, *part;
-    int *cnt;
-    int words;
-};
-
-static bspgemm_status select_scratch(bspgemm_context *ctx, long long E, SelScratch *sc)
+// the flag scratch (internal.hpp) of a select over E entries, at the start of the context's upper-bound workspace
+static bspgemm_status select_scratch(bspgemm_context *ctx, long long E, FlagScratch *sc)
 {
-    const size_t W = select_words(E);
-    if (W > (size_t)INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "select: too many entries for the word scan");
-    const size_t o_pre = 2 * W, o_part = o_pre + 2 * (W + 1), o_cnt = o_part + 2 * (W / 2048 + 4);
-    if (bspgemm_status st = ensure_tmp(ctx, o_cnt + W + 4)) return st;
-    sc->flags = reinterpret_cast<unsigned long long *>(ctx->tmp);
-    sc->pre = reinterpret_cast<long long *>(ctx->tmp + o_pre);
-    sc->part = reinterpret_cast<long long *>(ctx->tmp + o_part);
-    sc->cnt = ctx->tmp + o_cnt;
-    sc->words = (int)W;
+    const size_t ints = flag_scratch_carve(nullptr, 0, E, false, nullptr);
+    if (!ints) return FAIL(BSPGEMM_ERR_OVERFLOW, "select: too many entries for the word scan");
+    if (bspgemm_status st = ensure_tmp(ctx, ints)) return st;
+    flag_scratch_carve(ctx->tmp, 0, E, false, sc);
     return BSPGEMM_OK;
 }
 
-// What both selects do once pass 1 has left the flag words and counts of the E entries of `src`: the scan, the call's one
-// synchronisation (the kept count), the operand's arrays, pass 2 and the row pass.  m: the new operand's handle, rows and
-// cols set; on failure the caller frees it.  The operand is finished as after upload (its byte table of row lengths,
-// nnz + 1 ints of col_idx); it is complete on the context's stream when the call returns.
-static bspgemm_status select_finish(bspgemm_context *ctx, bspgemm_matrix *m, const int *src, long long E, const int *rp32,
-                                    const long long *rp64, const SelScratch &sc, const char *who)
+// What both selects do once pass 1 has left the flag words and counts of the E entries of `src`: the operand's handle and
+// row_ptr, the scan, the call's one synchronisation (the kept count), col_idx, pass 2 and the row pass.  The operand is
+// complete on the context's stream when the call returns; a failed call has freed what it made.
+static bspgemm_status select_finish(bspgemm_context *ctx, int rows, int cols, const int *src, long long E, const int *rp32,
+                                    const long long *rp64, const FlagScratch &sc, const char *who, bspgemm_matrix **out)
 {
     hipStream_t s = ctx->stream;
     long long kept = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)m->rows + 1) * sizeof(int)));
+    bspgemm_matrix *m = nullptr;
+    auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
+    if (bspgemm_status st = operand_new(ctx, rows, cols, &m)) return bail(st);
     if (E > 0) {
         launch_scan_counts(sc.cnt, sc.words, sc.pre, sc.part, nullptr, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&kept, sc.pre + sc.words, sizeof kept, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK_B(hipGetLastError());
+        HIPCHK_B(hipMemcpyAsync(&kept, sc.pre + sc.words, sizeof kept, hipMemcpyDeviceToHost, s));
+        HIPCHK_B(hipStreamSynchronize(s));
         if (kept > INT_MAX) {
             snprintf(g_err, sizeof g_err, "%s: %lld entries kept: more than INT_MAX, not usable as an int32 operand", who, kept);
-            return BSPGEMM_ERR_OVERFLOW;
+            return bail(BSPGEMM_ERR_OVERFLOW);
         }
     }
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)kept + 1) * sizeof(int)));
+    if (bspgemm_status st = operand_cols(m, kept)) return bail(st);
     if (E > 0) {
         launch_select_scatter(src, E, sc.flags, sc.pre, m->d_col_idx, s);
-        launch_select_row_ptr(rp32, rp64, m->rows, E, sc.flags, sc.pre, m->d_row_ptr, s);
+        launch_select_row_ptr(rp32, rp64, rows, E, sc.flags, sc.pre, m->d_row_ptr, s);
     } else {
-        HIPCHK(hipMemsetAsync(m->d_row_ptr, 0, ((size_t)m->rows + 1) * sizeof(int), s));
+        HIPCHK_B(hipMemsetAsync(m->d_row_ptr, 0, ((size_t)rows + 1) * sizeof(int), s));
     }
-    HIPCHK(hipGetLastError());
-    m->nnz = kept;
-    return ensure_deg8(m);
+    HIPCHK_B(hipGetLastError());
+    if (bspgemm_status st = operand_finish(m, kept)) return bail(st);
+    *out = m;
+    return BSPGEMM_OK;
 }
 
 extern "C" bspgemm_status bspgemm_matrix_select(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_select op,
                                                 bspgemm_matrix **out)
 {
+    const char *who = "bspgemm_matrix_select";
     if (out) *out = nullptr;
     if (!ctx || !A || !out) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_select: NULL argument");
-    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_select: operand belongs to another context");
+    if (bspgemm_status st = check_operand(ctx, A, who, 0)) return st;
     if (op != BSPGEMM_SELECT_TRIL && op != BSPGEMM_SELECT_TRIU && op != BSPGEMM_SELECT_OFFDIAG)
         return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_select: unknown select op");
-    if (A->nnz > 0 && (A->rows <= 0 || !A->d_col_idx)) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_select: nonzeros without rows");
+    if (bspgemm_status st = check_operand(ctx, A, who, NEED_ENTRIES_CONSISTENT)) return st;
     if (bspgemm_status st = use_device(ctx)) return st;
     const long long E = A->nnz;
-    SelScratch sc = {};
+    FlagScratch sc = {};
     if (bspgemm_status st = select_scratch(ctx, E, &sc)) return st;
     if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return st;
-    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, A->rows, A->cols, 0, nullptr, nullptr, true};
-    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
     launch_select_flags_struct(A->d_row_ptr, A->d_col_idx, A->rows, E, (int)op, ctx->tile_row, sc.flags, sc.cnt, ctx->stream);
-    if (bspgemm_status st = select_finish(ctx, m, A->d_col_idx, E, A->d_row_ptr, nullptr, sc, "bspgemm_matrix_select")) {
-        hipStreamSynchronize(ctx->stream);
-        bspgemm_matrix_free(m);
-        return st;
-    }
-    *out = m;
-    return BSPGEMM_OK;
+    return select_finish(ctx, A->rows, A->cols, A->d_col_idx, E, A->d_row_ptr, nullptr, sc, who, out);
 }
 
 extern "C" bspgemm_status bspgemm_matrix_from_result_where(bspgemm_context *ctx, const bspgemm_result *C, int cols,
@@ -328,18 +308,10 @@ extern "C" bspgemm_status bspgemm_matrix_from_result_where(bspgemm_context *ctx,
     if (!C->d_values) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_from_result_where: pattern-only result (no values)");
     if (bspgemm_status st = use_device(ctx)) return st;
     const long long E = C->nnz;
-    SelScratch sc = {};
+    FlagScratch sc = {};
     if (bspgemm_status st = select_scratch(ctx, E, &sc)) return st;
-    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, C->rows, cols, 0, nullptr, nullptr, true};
-    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
     launch_select_flags_value(C->d_values, E, (int)cmp, threshold, sc.flags, sc.cnt, ctx->stream);
-    if (bspgemm_status st = select_finish(ctx, m, C->d_col_idx, E, nullptr, C->d_row_ptr, sc, "bspgemm_matrix_from_result_where")) {
-        hipStreamSynchronize(ctx->stream);
-        bspgemm_matrix_free(m);
-        return st;
-    }
-    *out = m;
-    return BSPGEMM_OK;
+    return select_finish(ctx, C->rows, cols, C->d_col_idx, E, nullptr, C->d_row_ptr, sc, "bspgemm_matrix_from_result_where", out);
 }
 
 extern "C" bspgemm_status bspgemm_result_values_sum(bspgemm_context *ctx, const bspgemm_result *C, int64_t *sum)
@@ -361,23 +333,20 @@ extern "C" bspgemm_status bspgemm_result_values_sum(bspgemm_context *ctx, const 
 }
 
 // ------------------------------------------------------------------ triangles, k-truss ---
-// dedup(select(A, op)): the selection with sorted duplicate-free rows (transposed twice)
+// dedup(select(A, op)): the selection with sorted duplicate-free rows
 static bspgemm_status select_dedup(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_select op, bspgemm_matrix **out)
 {
-    bspgemm_matrix *sel = nullptr, *t = nullptr;
+    bspgemm_matrix *sel = nullptr;
     bspgemm_status st = bspgemm_matrix_select(ctx, A, op, &sel);
-    if (!st) st = bspgemm_matrix_transpose(ctx, sel, &t);
+    if (!st) st = operand_canonical(ctx, sel, out);
     bspgemm_matrix_free(sel);
-    if (!st) st = bspgemm_matrix_transpose(ctx, t, out);
-    bspgemm_matrix_free(t);
     return st;
 }
 
 extern "C" bspgemm_status bspgemm_triangle_count(bspgemm_context *ctx, const bspgemm_matrix *A, int64_t *triangles)
 {
     if (!ctx || !A || !triangles) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_triangle_count: NULL argument");
-    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_triangle_count: operand belongs to another context");
-    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_triangle_count needs a square matrix");
+    if (bspgemm_status st = check_operand(ctx, A, "bspgemm_triangle_count", NEED_SQUARE)) return st;
     bspgemm_matrix *L = nullptr;
     bspgemm_result *C = nullptr;
     int64_t sum = 0;
@@ -400,8 +369,7 @@ extern "C" bspgemm_status bspgemm_ktruss(bspgemm_context *ctx, const bspgemm_mat
     if (iterations) *iterations = 0;
     if (converged) *converged = 0;
     if (!ctx || !A || !T) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_ktruss: NULL argument");
-    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_ktruss: operand belongs to another context");
-    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_ktruss needs a square matrix");
+    if (bspgemm_status st = check_operand(ctx, A, "bspgemm_ktruss", NEED_SQUARE)) return st;
     if (k < 2) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_ktruss: k < 2");
     const int n = A->rows;
     bspgemm_matrix *S = nullptr;

@@ -1,9 +1,10 @@
 // setop.hip -- entry-wise set operations on the patterns of two CSR operands, on the device: bspgemm_matrix_setop
 // (A | B, A & B, A \ B, A ^ B), bspgemm_matrix_equal and bspgemm_matrix_symmetrize (include/bspgemm.h).
 //
-// The passes are select.hip's (sel_rows.hpp holds what the two files share): work is spread over ENTRIES, a workgroup owns
-// kSelTile consecutive entries of one operand X whatever rows they belong to, and what is kept is described by 64-bit flag
-// words, their popcounts and one scan.  For operands whose rows are strictly ascending ("canonical"):
+// The passes are select.hip's (sel_rows.hpp holds the device code they share, internal.hpp the flag scratch): work is
+// spread over ENTRIES, a workgroup owns kSelTile consecutive entries of one operand X whatever rows they belong to, and
+// what is kept is described by 64-bit flag words, their popcounts and one scan.  For operands whose rows are strictly
+// ascending ("canonical"):
 //   pass 1  k_set_flags     every lane takes four consecutive entries of X (one 16-byte load) and finds their row like the
 //                           structural select.  It CHECKS them -- 0 <= col < cols, and col[p] > col[p - 1] unless p starts a
 //                           row -- into an error word, and binary-searches each column in the same row of the other operand
@@ -28,17 +29,6 @@ namespace bsp {
 constexpr unsigned kSetErrRange = 1u;    // a column outside [0, cols)
 constexpr unsigned kSetErrOrder = 2u;    // a row that is not strictly ascending
 constexpr int kSetErrShiftB = 2;         // operand B's two bits
-
-// first position in [lo, hi) of y whose column is not below c
-__device__ __forceinline__ int set_lower_bound(const int *__restrict__ y, int lo, int hi, int c)
-{
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (y[mid] < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // pass 1 over operand X.  SEARCH false: the check alone (nothing but *err is written).  The columns are read again by pass
 // 2, so the loads stay temporal.  invert: the flags are the NON-common entries (ANDNOT).  lbs (may be NULL): lb per entry.
@@ -95,7 +85,7 @@ __global__ __launch_bounds__(kSelThreads) void k_set_flags(const int *__restrict
                 if (p > beg && c[k] <= pc) bad |= kSetErrOrder;
                 pc = c[k];
                 if (SEARCH) {
-                    from = set_lower_bound(colY, from, yend, c[k]);
+                    from = sel_lower_bound(colY, from, yend, c[k]);
                     const bool common = from < yend && colY[from] == c[k];
                     if (common != invert) nib |= 1u << k;
                     lb[k] = from;
@@ -158,38 +148,43 @@ __global__ __launch_bounds__(256) void k_set_row_ptr(const int *__restrict__ rpA
     out[r] = (int)(p + rpB[r] - k * common);
 }
 
-static inline bool set_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline int set_tiles(long long nnz) { return (int)((nnz + kSelTile - 1) / kSelTile); }
-
-void launch_setop_flags(const int *rpX, const int *colX, int rows, int cols, long long nnzX, const int *rpY, const int *colY,
-                        bool search, bool invert, bool second, int *tile_row, unsigned long long *flags, int *cnt, int *lbs,
-                        unsigned *err, hipStream_t s)
+// pass 1 over operand X against Y (same shape): *err |= (kSetErrRange: a column outside [0, cols), kSetErrOrder: a row not
+// strictly ascending), shifted left by kSetErrShiftB when `second`.  search: bit b of flags[w] = entry 64 w + b of X is also
+// in Y's row (invert: is not), cnt[w] its popcount, and (lbs != NULL, whole tiles of ints) lbs[e] = the position in colY of
+// the first entry of the row that is not below X's column.  Without search only the check runs.  tile_row: nnzX / kSelTile
+// + 1 ints of scratch.
+static void launch_setop_flags(const int *rpX, const int *colX, int rows, int cols, long long nnzX, const int *rpY,
+                               const int *colY, bool search, bool invert, bool second, int *tile_row,
+                               unsigned long long *flags, int *cnt, int *lbs, unsigned *err, hipStream_t s)
 {
     if (nnzX <= 0) return;
     launch_select_tile_rows(rpX, rows, tile_row, s);
-    const dim3 grid(set_tiles(nnzX)), block(kSelThreads);
+    const dim3 grid(select_tiles(nnzX)), block(kSelThreads);
     const int shift = second ? kSetErrShiftB : 0;
     if (search)
-        hipLaunchKernelGGL(k_set_flags<true>, grid, block, 0, s, rpX, colX, rows, cols, nnzX, set_aligned16(colX), tile_row, rpY,
+        hipLaunchKernelGGL(k_set_flags<true>, grid, block, 0, s, rpX, colX, rows, cols, nnzX, aligned16(colX), tile_row, rpY,
                            colY, invert, shift, flags, cnt, lbs, err);
     else
-        hipLaunchKernelGGL(k_set_flags<false>, grid, block, 0, s, rpX, colX, rows, cols, nnzX, set_aligned16(colX), tile_row, rpY,
+        hipLaunchKernelGGL(k_set_flags<false>, grid, block, 0, s, rpX, colX, rows, cols, nnzX, aligned16(colX), tile_row, rpY,
                            colY, invert, shift, flags, cnt, lbs, err);
 }
 
-void launch_setop_place(const int *colX, long long nnzX, const unsigned long long *flags, const long long *prefix,
-                        const int *lbs, int k, bool all, int *out, hipStream_t s)
+// pass 2 of OR (k = 1) and XOR (k = 2) over X: out[e + lbs[e] - k * (common entries before e)] = colX[e] for every entry
+// (all) or every non-common one; flags: the common entries, prefix: the scan of their counts
+static void launch_setop_place(const int *colX, long long nnzX, const unsigned long long *flags, const long long *prefix,
+                               const int *lbs, int k, bool all, int *out, hipStream_t s)
 {
     if (nnzX <= 0) return;
-    hipLaunchKernelGGL(k_set_place, dim3(set_tiles(nnzX)), dim3(kSelThreads), 0, s, colX, nnzX, set_aligned16(colX), flags,
+    hipLaunchKernelGGL(k_set_place, dim3(select_tiles(nnzX)), dim3(kSelThreads), 0, s, colX, nnzX, aligned16(colX), flags,
                        prefix, lbs, k, all, out);
 }
 
-void launch_setop_row_ptr(const int *rpA, const int *rpB, int rows, long long nnzA, const unsigned long long *flags,
-                          const long long *prefix, int k, int *out, hipStream_t s)
+// out[r] = rpA[r] + rpB[r] - k * (common entries of A before rpA[r]), r in [0, rows]
+static void launch_setop_row_ptr(const int *rpA, const int *rpB, int rows, long long nnzA, const unsigned long long *flags,
+                                 const long long *prefix, int k, int *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_set_row_ptr, dim3((unsigned)(((long long)rows + 1 + 255) / 256)), dim3(256), 0, s, rpA, rpB, rows,
-                       nnzA, (long long)select_words(nnzA), flags, prefix, k, out);
+    hipLaunchKernelGGL(k_set_row_ptr, row_pass_grid(rows), dim3(256), 0, s, rpA, rpB, rows, nnzA,
+                       (long long)select_words(nnzA), flags, prefix, k, out);
 }
 
 }  // namespace bsp
@@ -197,52 +192,6 @@ void launch_setop_row_ptr(const int *rpA, const int *rpB, int rows, long long nn
 using namespace bsp;
 
 // ------------------------------------------------------------------ the host side --------
-// Scratch of one operand's passes, carved from the context's upper-bound workspace (kept, like select's): the flag words,
-// the scan of their counts, the scan's partials, the counts, and (OR, XOR) lb per entry in whole tiles.
-struct SetSide {
-    unsigned long long *flags;
-    long long *pre, *part;
-    int *cnt, *lbs;
-    int words;
-};
-struct SetLayout {
-    size_t o_flags, o_pre, o_part, o_cnt, o_lbs;
-};
-
-// offsets in ints, every array on a 16-byte boundary; returns the end
-static size_t set_layout(size_t at, size_t W, bool lbs, SetLayout *l)
-{
-    auto take = [&](size_t ints) { const size_t o = at; at += (ints + 3) & ~(size_t)3; return o; };
-    l->o_flags = take(2 * W);
-    l->o_pre = take(2 * (W + 1));
-    l->o_part = take(2 * (W / 2048 + 4));
-    l->o_cnt = take(W);
-    l->o_lbs = take(lbs ? W * 64 : 0);
-    return at;
-}
-
-static SetSide set_side(int *tmp, const SetLayout &l, size_t W, bool lbs)
-{
-    SetSide sd;
-    sd.flags = reinterpret_cast<unsigned long long *>(tmp + l.o_flags);
-    sd.pre = reinterpret_cast<long long *>(tmp + l.o_pre);
-    sd.part = reinterpret_cast<long long *>(tmp + l.o_part);
-    sd.cnt = tmp + l.o_cnt;
-    sd.lbs = lbs ? tmp + l.o_lbs : nullptr;
-    sd.words = (int)W;
-    return sd;
-}
-
-// sorted duplicate-free copy of X: transposed twice
-static bspgemm_status set_canonical(bspgemm_context *ctx, const bspgemm_matrix *X, bspgemm_matrix **out)
-{
-    bspgemm_matrix *t = nullptr;
-    bspgemm_status st = bspgemm_matrix_transpose(ctx, X, &t);
-    if (!st) st = bspgemm_matrix_transpose(ctx, t, out);
-    bspgemm_matrix_free(t);
-    return st;
-}
-
 // op: a bspgemm_setop, or 0 for the comparison (*equal).  The arguments are checked by the callers.  canonical: both
 // operands are known to have strictly ascending rows (the second round).
 static bspgemm_status setop_run(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B, int op,
@@ -254,15 +203,17 @@ static bspgemm_status setop_run(bspgemm_context *ctx, const bspgemm_matrix *A, c
     const int rows = A->rows, cols = A->cols;
     const bool both = op == BSPGEMM_SETOP_OR || op == BSPGEMM_SETOP_XOR;      // B contributes entries: both sides are searched
     const int k = op == BSPGEMM_SETOP_XOR ? 2 : 1;
-    const size_t WA = select_words(EA), WB = both ? select_words(EB) : 0;
-    if (WA > (size_t)INT_MAX || WB > (size_t)INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "setop: too many entries for the word scan");
-    SetLayout la, lb;
-    const size_t o_b = set_layout(4, WA, both, &la);                          // the first four ints: the error word
-    const size_t total = set_layout(o_b, WB, both, &lb);
+    // the workspace: the error word (four ints), then the flag scratch of each side (B's is empty unless B is searched)
+    const long long EBs = both ? EB : 0;
+    const size_t o_b = flag_scratch_carve(nullptr, 4, EA, both, nullptr);
+    const size_t total = o_b ? flag_scratch_carve(nullptr, o_b, EBs, both, nullptr) : 0;
+    if (!total) return FAIL(BSPGEMM_ERR_OVERFLOW, "setop: too many entries for the word scan");
     if (bspgemm_status st = ensure_tmp(ctx, total)) return st;
     if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)(EA > EB ? EA : EB))) return st;
     unsigned *d_err = reinterpret_cast<unsigned *>(ctx->tmp);
-    const SetSide sa = set_side(ctx->tmp, la, WA, both), sb = set_side(ctx->tmp, lb, WB, both);
+    FlagScratch sa, sb;
+    flag_scratch_carve(ctx->tmp, 4, EA, both, &sa);
+    flag_scratch_carve(ctx->tmp, o_b, EBs, both, &sb);
 
     // A's flags: its common entries (ANDNOT: the others).  The kernels of the two sides follow each other on the stream,
     // so they share tile_row.
@@ -291,9 +242,9 @@ static bspgemm_status setop_run(bspgemm_context *ctx, const bspgemm_matrix *A, c
         bspgemm_matrix *ca = nullptr, *cb = nullptr;
         bspgemm_status st = BSPGEMM_OK;
         const bool same = A == B;
-        if (same || (err & kSetErrOrder)) st = set_canonical(ctx, A, &ca);
+        if (same || (err & kSetErrOrder)) st = operand_canonical(ctx, A, &ca);
         if (same) cb = ca;
-        else if (!st && (err & (kSetErrOrder << kSetErrShiftB))) st = set_canonical(ctx, B, &cb);
+        else if (!st && (err & (kSetErrOrder << kSetErrShiftB))) st = operand_canonical(ctx, B, &cb);
         if (!st) st = setop_run(ctx, ca ? ca : A, cb ? cb : B, op, out, equal, who, true);
         if (cb != ca) bspgemm_matrix_free(cb);
         bspgemm_matrix_free(ca);
@@ -308,11 +259,10 @@ static bspgemm_status setop_run(bspgemm_context *ctx, const bspgemm_matrix *A, c
         snprintf(g_err, sizeof g_err, "%s: %lld entries in the result: more than INT_MAX, not usable as an int32 operand", who, kept);
         return BSPGEMM_ERR_OVERFLOW;
     }
-    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, rows, cols, 0, nullptr, nullptr, true};
-    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    bspgemm_matrix *m = nullptr;
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)rows + 1) * sizeof(int)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)kept + 1) * sizeof(int)));
+    if (bspgemm_status st = operand_new(ctx, rows, cols, &m)) return bail(st);
+    if (bspgemm_status st = operand_cols(m, kept)) return bail(st);
     if (both ? EA + EB == 0 : EA == 0) {
         HIPCHK_B(hipMemsetAsync(m->d_row_ptr, 0, ((size_t)rows + 1) * sizeof(int), s));
     } else if (both) {
@@ -324,8 +274,7 @@ static bspgemm_status setop_run(bspgemm_context *ctx, const bspgemm_matrix *A, c
         launch_select_row_ptr(A->d_row_ptr, nullptr, rows, EA, sa.flags, sa.pre, m->d_row_ptr, s);
     }
     HIPCHK_B(hipGetLastError());
-    m->nnz = kept;
-    if (bspgemm_status st = ensure_deg8(m)) return bail(st);
+    if (bspgemm_status st = operand_finish(m, kept)) return bail(st);
     *out = m;
     return BSPGEMM_OK;
 }
@@ -333,13 +282,14 @@ static bspgemm_status setop_run(bspgemm_context *ctx, const bspgemm_matrix *A, c
 // what setop and equal ask of their operands; who: the function's name
 static bspgemm_status setop_operands(const bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B, const char *who)
 {
-    const char *what = nullptr;
-    if (A->ctx != ctx || B->ctx != ctx) what = "an operand belongs to another context";
-    else if (A->rows != B->rows || A->cols != B->cols) what = "the operands differ in shape";
-    else if ((A->nnz > 0 && (A->rows <= 0 || !A->d_col_idx)) || (B->nnz > 0 && !B->d_col_idx)) what = "nonzeros without rows";
-    if (!what) return BSPGEMM_OK;
-    snprintf(g_err, sizeof g_err, "%s: %s", who, what);
-    return BSPGEMM_ERR_INVALID;
+    if (bspgemm_status st = check_operand(ctx, A, who, 0)) return st;
+    if (bspgemm_status st = check_operand(ctx, B, who, 0)) return st;
+    if (A->rows != B->rows || A->cols != B->cols) {
+        snprintf(g_err, sizeof g_err, "%s: the operands differ in shape", who);
+        return BSPGEMM_ERR_INVALID;
+    }
+    if (bspgemm_status st = check_operand(ctx, A, who, NEED_ENTRIES_CONSISTENT)) return st;
+    return check_operand(ctx, B, who, NEED_ENTRIES_CONSISTENT);
 }
 
 extern "C" bspgemm_status bspgemm_matrix_setop(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
@@ -368,9 +318,9 @@ extern "C" bspgemm_status bspgemm_matrix_symmetrize(bspgemm_context *ctx, const 
 {
     if (out) *out = nullptr;
     if (!ctx || !A || !out) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize: NULL argument");
-    if (A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize: operand belongs to another context");
+    if (bspgemm_status st = check_operand(ctx, A, "bspgemm_matrix_symmetrize", 0)) return st;
     if (flags & ~BSPGEMM_SYMMETRIZE_DROP_DIAGONAL) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize: unknown flag");
-    if (A->rows != A->cols) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_matrix_symmetrize needs a square matrix");
+    if (bspgemm_status st = check_operand(ctx, A, "bspgemm_matrix_symmetrize", NEED_SQUARE)) return st;
     bspgemm_matrix *off = nullptr, *t = nullptr;
     bspgemm_status st = BSPGEMM_OK;
     if (flags & BSPGEMM_SYMMETRIZE_DROP_DIAGONAL) st = bspgemm_matrix_select(ctx, A, BSPGEMM_SELECT_OFFDIAG, &off);

@@ -1,4 +1,5 @@
-// transpose.hip -- AT = pattern(A)^T on the device (bspgemm_matrix_transpose, include/bspgemm.h).
+// transpose.hip -- AT = pattern(A)^T on the device (bspgemm_matrix_transpose, include/bspgemm.h), and the sorted
+// duplicate-free copy of an operand that two of them make (operand_canonical, internal.hpp).
 //
 // A stable LSD radix sort of the pairs (k = column, i = row) keyed by k alone, then one compaction pass.  A's entries in
 // CSR order are already ordered by i, so a stable sort by k leaves every row of AT in ascending i with duplicate pairs
@@ -303,18 +304,18 @@ using namespace bsp;
 extern "C" bspgemm_status bspgemm_matrix_transpose(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_matrix **AT)
 {
     if (AT) *AT = nullptr;
-    if (!ctx || !A || !AT || A->ctx != ctx) return FAIL(BSPGEMM_ERR_INVALID, "matrix_transpose");
+    if (!ctx || !A || !AT) return FAIL(BSPGEMM_ERR_INVALID, "matrix_transpose");
+    if (bspgemm_status st = check_operand(ctx, A, "matrix_transpose", 0)) return st;
     if (A->nnz > kTrMaxNnz) return FAIL(BSPGEMM_ERR_OVERFLOW, "matrix_transpose: too many nonzeros for the int32 sort");
-    if (A->nnz > 0 && (A->rows <= 0 || !A->d_col_idx)) return FAIL(BSPGEMM_ERR_INVALID, "matrix_transpose: nonzeros without rows");
+    if (bspgemm_status st = check_operand(ctx, A, "matrix_transpose", NEED_ENTRIES_CONSISTENT)) return st;
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
     const int E = (int)A->nnz, rows = A->rows, cols = A->cols;
-    bspgemm_matrix *m = new (std::nothrow) bspgemm_matrix{ctx, cols, rows, 0, nullptr, nullptr, true};
-    if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
+    bspgemm_matrix *m = nullptr;
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
     // col_idx sized for nnz(A): nnz(AT) (duplicates dropped) is known only at the end
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)cols + 1) * sizeof(int)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)E + 1) * sizeof(int)));
+    if (bspgemm_status st = operand_new(ctx, cols, rows, &m)) return bail(st);
+    if (bspgemm_status st = operand_cols(m, E)) return bail(st);
     TrScalars h = {0, 0, 0};
     TrScalars *d_scal = nullptr;
     if (E == 0) {
@@ -369,7 +370,7 @@ extern "C" bspgemm_status bspgemm_matrix_transpose(bspgemm_context *ctx, const b
                            m->d_col_idx, m->d_row_ptr, d_scal);
         HIPCHK_B(hipGetLastError());
     }
-    if (bspgemm_status st = ensure_deg8(m)) return bail(st);
+    if (bspgemm_status st = operand_finish(m, 0)) return bail(st);   // (nnz(AT) comes with the read-back below)
     if (d_scal) HIPCHK_B(hipMemcpyAsync(&h, d_scal, sizeof h, hipMemcpyDeviceToHost, s));
     HIPCHK_B(hipStreamSynchronize(s));                      // the call's one synchronisation: nnz(AT) and the error word
     if (h.err) {
@@ -379,4 +380,13 @@ extern "C" bspgemm_status bspgemm_matrix_transpose(bspgemm_context *ctx, const b
     m->nnz = h.nnz;
     *AT = m;
     return BSPGEMM_OK;
+}
+
+bspgemm_status operand_canonical(bspgemm_context *ctx, const bspgemm_matrix *X, bspgemm_matrix **out)
+{
+    bspgemm_matrix *t = nullptr;
+    bspgemm_status st = bspgemm_matrix_transpose(ctx, X, &t);
+    if (!st) st = bspgemm_matrix_transpose(ctx, t, out);
+    bspgemm_matrix_free(t);
+    return st;
 }

@@ -14,6 +14,7 @@ import pytest
 
 import bspgemm
 import cc_ref
+import empty_ref
 import gen
 
 pytestmark = pytest.mark.gpu
@@ -42,12 +43,13 @@ GRAPHS = {
     "uniform300": lambda: gen.uniform(300, 2, 5404),
     "empty0": lambda: (np.zeros(1, np.int32), np.zeros(0, np.int32), 0),
     "empty1": lambda: (np.zeros(2, np.int32), np.zeros(0, np.int32), 1),
+    "empty4": lambda: (np.zeros(5, np.int32), np.zeros(0, np.int32), 4),
     "empty1000": lambda: (np.zeros(1001, np.int32), np.zeros(0, np.int32), 1000),
     "self_loop": lambda: (np.array([0, 1], np.int32), np.zeros(1, np.int32), 1),
 }
 COMPONENTS = {"path200": 1, "path200_reversed": 1, "path4099_permuted": 1, "cycle200": 1, "star_hub_last": 1,
               "star_hub_middle": 1, "star_leaf_rows": 1, "halves_joined_from_first": 1, "halves_joined_from_second": 1,
-              "rmat12": 1131, "rmat10": 258, "empty0": 0, "empty1": 1, "empty1000": 1000, "self_loop": 1}
+              "rmat12": 1131, "rmat10": 258, "empty0": 0, "empty1": 1, "empty4": 4, "empty1000": 1000, "self_loop": 1}
 
 
 @pytest.fixture(scope="module")
@@ -113,6 +115,37 @@ def test_labels_equal_the_reference(ctx, name):
     label, count, rounds = _run_named(ctx, name)
     if name.startswith("empty"):
         assert np.array_equal(label, np.arange(n)) and count == n
+
+
+@pytest.mark.parametrize("rows,cols", empty_ref.SHAPES, ids=empty_ref.IDS)
+def test_graph_without_edges(ctx, rows, cols):
+    """0 x 0: P is an operand without entries; 4 x 4: P is the identity, and works at once as B and as A of a product;
+    not square: refused, as it always was"""
+    A = ctx.upload(*empty_ref.csr(rows), cols)
+    try:
+        if rows != cols:
+            out = C.c_void_p(0x5A5A)
+            st = bspgemm.lib().bspgemm_connected_components(ctx._h, A._h, C.byref(out), None, None)
+            assert st == ERR_INVALID and not out.value
+            return
+        P, count, rounds = ctx.connected_components(A)
+        assert (count, rounds) == (rows, 0) == (cc_ref.labels(*empty_ref.csr(rows), rows)[1], 0)
+        if rows == 0:
+            empty_ref.check(ctx, P, 0, 0)
+        else:
+            G = empty_ref.gather_all(ctx, rows)
+            eye = empty_ref.diagonal(rows)
+            assert all(np.array_equal(g, e) for g, e in zip(P.download(), eye))
+            for X, x in ((G, G.download()), (P, eye)):
+                R = ctx.multiply(X, P)
+                erp, eci = gen.small_reference(x[0], x[1], eye[0], eye[1])
+                grp, gci = R.download()
+                assert np.array_equal(grp, erp) and np.array_equal(gci, eci)
+                R.free()
+            G.free()
+        P.free()
+    finally:
+        A.free()
 
 
 def test_sizes_that_are_no_multiple_of_the_vertex_tiles(ctx):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import bspgemm
+import empty_ref
 import gen
 from oracle import oracle as O
 
@@ -893,6 +894,25 @@ def test_more_than_int32_output_nonzeros(ctx):
     with pytest.raises(bspgemm.BspgemmError) as e:
         bspgemm.SpGEMM_hip(ci, rp, n, ci, rp, n)
     assert e.value.status == 5          # BSPGEMM_ERR_OVERFLOW
+
+
+@pytest.mark.parametrize("rows,cols", empty_ref.SHAPES + ((4, 4),), ids=empty_ref.IDS + ["4x4_disjoint"])
+def test_product_without_entries_as_an_operand(request, ctx, rows, cols):
+    """bspgemm_matrix_from_result of a product that holds nothing: of operands without entries, and (4 x 4) of operands
+    with one entry each, where the one row of B that A gathers is empty"""
+    if request.node.callspec.id.endswith("disjoint"):
+        a_rp, a_ci = np.array([0, 0, 0, 0, 1], np.int32), np.array([0], np.int32)     # row 3 -> 0
+        b_rp, b_ci = np.array([0, 0, 1, 1, 1], np.int32), np.array([2], np.int32)     # row 1 -> 2: never gathered
+    else:
+        (a_rp, a_ci), (b_rp, b_ci) = empty_ref.csr(rows), empty_ref.csr(cols)
+    erp, eci = O.spgemm(a_rp, a_ci, b_rp, b_ci, cols)
+    assert erp.size == rows + 1 and not erp.any() and eci.size == 0
+    A, B = ctx.upload(a_rp, a_ci, cols), ctx.upload(b_rp, b_ci, cols)
+    P = ctx.multiply(A, B)
+    M = ctx.matrix_from_result(P, cols)
+    empty_ref.check(ctx, M, rows, cols)
+    for h in (M, P, B, A):
+        h.free()
 
 
 def test_device_resident_closure(ctx):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import bspgemm
+import empty_ref
 import gen
 from ktruss_ref import dedup_ref, select_ref, symmetrise, where_ref
 
@@ -104,6 +105,46 @@ def test_select_empty_shapes(ctx):
     assert _same(ctx.select(up, "triu").download(), (rp, ci)) and ctx.select(up, "tril").nnz == 0
     diag.free()
     up.free()
+
+
+@pytest.mark.parametrize("rows,cols", empty_ref.SHAPES, ids=empty_ref.IDS)
+def test_select_of_nothing_is_an_operand(ctx, rows, cols):
+    rp, ci = empty_ref.csr(rows)
+    A = ctx.upload(rp, ci, cols)
+    for op in OPS:
+        S = ctx.select(A, op)
+        assert _same(S.download(), select_ref(rp, ci, op))
+        empty_ref.check(ctx, S, rows, cols)
+        S.free()
+    # by value: the counted product of operands without entries
+    Y = ctx.upload(*empty_ref.csr(cols), cols)
+    Cc = ctx.multiply_masked_count(A, Y, A)
+    assert (Cc.rows, Cc.nnz, Cc.values_sum()) == (rows, 0, 0)
+    for cmp in CMPS:
+        M = ctx.matrix_from_result_where(Cc, cols, cmp, 1)
+        empty_ref.check(ctx, M, rows, cols)
+        M.free()
+    for h in (Cc, Y, A):
+        h.free()
+
+
+def test_select_that_keeps_nothing_is_an_operand(ctx):
+    """a 4 x 4 diagonal: no entry is off it, and no count of D .* (D * D) is above 1"""
+    n = 4
+    rp, ci = empty_ref.diagonal(n)
+    D = ctx.upload(rp, ci, n)
+    for op in OPS:
+        S = ctx.select(D, op)
+        assert _same(S.download(), select_ref(rp, ci, op))
+        empty_ref.check(ctx, S, n, n)
+        S.free()
+    Cc = ctx.multiply_masked_count(D, D, D)
+    assert np.array_equal(Cc.download_values(), np.ones(n, np.int32))
+    M = ctx.matrix_from_result_where(Cc, n, ">", 1)
+    assert _same(M.download(), where_ref(*Cc.download(), Cc.download_values(), ">", 1))
+    empty_ref.check(ctx, M, n, n)
+    for h in (M, Cc, D):
+        h.free()
 
 
 def test_select_operand_sources(ctx):

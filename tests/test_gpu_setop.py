@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import bspgemm
+import empty_ref
 import gen
 import ktruss_ref
 from oracle import oracle as O
@@ -181,6 +182,41 @@ def test_degenerate_shapes(ctx):
     for x, y, what in ((full, full, "1x1 both"), (full, hole, "1x1 A"), (hole, full, "1x1 B"), (hole, hole, "1x1 none")):
         bad += _check(ctx, x, y, 1, 1, what)
     assert not bad, bad
+
+
+@pytest.mark.parametrize("rows,cols", empty_ref.SHAPES, ids=empty_ref.IDS)
+def test_setop_of_nothing_is_an_operand(ctx, rows, cols):
+    e = empty_ref.csr(rows)
+    A, B = ctx.upload(e[0], e[1], cols), ctx.upload(e[0], e[1], cols)
+    for op in OPS:
+        S = ctx.setop(A, B, op)
+        assert _same(S.download(), setop_ref(e[0], e[1], e[0], e[1], rows, cols, op))
+        empty_ref.check(ctx, S, rows, cols)
+        S.free()
+    assert ctx.matrix_equal(A, B)
+    if rows == cols:
+        for drop in (False, True):
+            S = ctx.symmetrize(A, drop_diagonal=drop)
+            empty_ref.check(ctx, S, rows, cols)
+            S.free()
+    A.free()
+    B.free()
+
+
+def test_setop_that_leaves_nothing_is_an_operand(ctx):
+    """4 x 4: A \\ A, A ^ A, and A & B of disjoint patterns"""
+    n = 4
+    a, b = empty_ref.diagonal(n), _from_rows([[1], [2], [3], [0]], n)
+    A, B = ctx.upload(a[0], a[1], n), ctx.upload(b[0], b[1], n)
+    for X, Y, x, y, op in ((A, A, a, a, "andnot"), (A, A, a, a, "xor"), (A, B, a, b, "and"), (B, A, b, a, "and")):
+        S = ctx.setop(X, Y, op)
+        assert _same(S.download(), setop_ref(x[0], x[1], y[0], y[1], n, n, op))
+        empty_ref.check(ctx, S, n, n)
+        S.free()
+    S = ctx.symmetrize(A, drop_diagonal=True)
+    empty_ref.check(ctx, S, n, n)
+    for h in (S, A, B):
+        h.free()
 
 
 # ---------------------------------------------------------------- 6. algebra -----------------------------------------

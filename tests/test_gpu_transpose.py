@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import bspgemm
+import empty_ref
 import gen
 from oracle import oracle as O
 
@@ -97,6 +98,18 @@ def test_shapes(ctx, rows, cols, nnz):
     AT = check(ctx, A, rp, ci, cols)
     ATT = ctx.transpose(AT)
     assert (ATT.rows, ATT.cols) == (rows, cols)
+
+
+@pytest.mark.parametrize("rows,cols", empty_ref.SHAPES, ids=empty_ref.IDS)
+def test_transpose_of_nothing_is_an_operand(ctx, rows, cols):
+    rp, ci = empty_ref.csr(rows)
+    A = ctx.upload(rp, ci, cols)
+    AT = check(ctx, A, rp, ci, cols)
+    empty_ref.check(ctx, AT, cols, rows)
+    ATT = ctx.transpose(AT)
+    empty_ref.check(ctx, ATT, rows, cols)
+    for h in (ATT, AT, A):
+        h.free()
 
 
 @pytest.mark.parametrize("cols", [255, 256, 257, 65535, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 24) + 1])
