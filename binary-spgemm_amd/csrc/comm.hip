@@ -472,7 +472,7 @@ extern "C" int SpGEMM_hip_multi(bspgemm_comm *c, int *Acol, int *Arow, int An, i
         if (!c || !Acol || !Arow || !Bcol || !Brow || !Ccol || !Crow || An < 0 || Bm < 0)
             return FAIL(BSPGEMM_ERR_INVALID, "SpGEMM_hip_multi arguments");
         bspgemm_context *ctx = c->ctx;
-        const int brows = bspgemm_par_max_plus_one(Acol + Arow[0], (long long)Arow[An] - Arow[0]);
+        const int brows = dropin_b_rows(Acol, Arow, 0, An);
         bspgemm_matrix *A = nullptr, *B = nullptr;
         bspgemm_result *C = nullptr;
         int *bounds = static_cast<int *>(malloc(((size_t)c->nranks + 1) * sizeof(int)));
@@ -480,8 +480,7 @@ extern "C" int SpGEMM_hip_multi(bspgemm_comm *c, int *Acol, int *Arow, int An, i
         int64_t *rp64 = nullptr;
         int *dst = nullptr;
         bspgemm_status st = (bounds && shard) ? BSPGEMM_OK : FAIL(BSPGEMM_ERR_ALLOC, "bounds");
-        if (!st) st = bspgemm_matrix_upload(ctx, An, brows, Arow, Acol, &A);
-        if (!st) st = bspgemm_matrix_upload(ctx, brows, Bm, Brow, Bcol, &B);
+        if (!st) st = dropin_upload(ctx, Acol, Arow, 0, An, Bcol, Brow, brows, Bm, false, &A, &B);   // (B in full, never a view)
         if (!st) st = bspgemm_partition_rows(ctx, A, B, c->nranks, bounds);
         if (!st) st = bspgemm_multiply(ctx, A, B, bounds[c->rank], bounds[c->rank + 1], &C);
         // from here on the ranks act together: nobody enters a collective unless everybody does
@@ -509,7 +508,7 @@ extern "C" int SpGEMM_hip_multi(bspgemm_comm *c, int *Acol, int *Arow, int An, i
             if (hipMemcpy(rp64, d_global, ((size_t)An + 1) * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess)
                 st = FAIL(BSPGEMM_ERR_HIP, "row_ptr to host");
             else {
-                for (int i = 0; i <= An; i++) Crow[i] = (int)rp64[i];
+                dropin_crow(rp64, An, Crow);
                 *Ccol = dst;
                 dst = nullptr;
             }

@@ -1,8 +1,9 @@
 // internal.hpp -- what the translation units behind include/bspgemm.h share: the error macros, the handle
 // structs, the builder of derived operands and the operand check that every entry point returning an operand uses, the
-// workspace / result-cache helpers (context.hip) that the flows (multiply.hip), the int32 drop-ins (dropin.hip) and the
-// communicator layer (comm.hip) use, the flag scratch of select.hip and setop.hip.  Not installed; nothing here is part
-// of the C ABI.
+// workspace / result-cache helpers (context.hip) that the flows (multiply.hip), the int32 drop-ins (dropin.hip: dropin_run in
+// stages -- check and bound, operands, multiply, destination, download, hand-over -- over the early destination that
+// early_dest.hpp owns) and the communicator layer (comm.hip) use, the drop-ins' host steps that SpGEMM_hip_multi repeats, the
+// flag scratch of select.hip and setop.hip.  Not installed; nothing here is part of the C ABI.
 #pragma once
 #include "../../include/bspgemm.h"
 #include "kernels.hpp"
@@ -225,5 +226,20 @@ struct FlagScratch {
 // 0: more words than the scan's int count takes.  sc NULL: the end alone (what to ask ensure_tmp for: tmp may move).
 size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratch *sc);
 
-// one line on stderr for a failed drop-in ("SpGEMM_hip: <status>: <last error>"), returns the status as int (dropin.hip)
+// ------------------------------------------------------------------ drop-in host steps (dropin.hip) ---
+// one line on stderr for a failed drop-in ("SpGEMM_hip: <status>: <last error>"), returns the status as int
 int dropin_fail(const char *fn, bspgemm_status st);
+// B's row count is implicit in the reference (never passed): 1 + the largest column that A's rows [r0, r1) use
+static inline int dropin_b_rows(const int *Acol, const int *Arow, int r0, int r1)
+{
+    return bspgemm_par_max_plus_one(Acol + Arow[r0], (long long)Arow[r1] - Arow[r0]);
+}
+// A's rows [r0, r1) and B (brows x Bm) onto the device; view_ok: B = A through the same host arrays becomes a view of A's
+// device copy.  On failure the caller frees whatever *A and *B hold.
+bspgemm_status dropin_upload(bspgemm_context *ctx, const int *Acol, const int *Arow, int r0, int r1, const int *Bcol,
+                             const int *Brow, int brows, int Bm, bool view_ok, bspgemm_matrix **A, bspgemm_matrix **B);
+// the int64 row_ptr of a result that fits the int32 interface (nnz <= INT_MAX was checked) into the caller's Crow
+static inline void dropin_crow(const int64_t *rp64, int rows, int *Crow)
+{
+    for (int i = 0; i <= rows; i++) Crow[i] = (int)rp64[i];
+}

@@ -175,6 +175,23 @@ def test_host_c_under_address_and_ub_sanitizers(tmp_path):
     assert "host_asan ok" in r.stdout and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr
 
 
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_early_destination_under_sanitizers(san):
+    """csrc/early_dest.hpp, the object that owns the drop-ins' early destination (block, helper thread, pin flags), with
+    counting pin stubs and 64 KiB pieces (oracle/early_dest_main.cpp): consumed piece by piece and released, stopped early and
+    destroyed, pins refused, no hooks, never started, release(0) -- once under -fsanitize=address,undefined (with the leak
+    check) and once under -fsanitize=thread; any report or failed check ends the program with a non-zero status."""
+    import subprocess
+    exe = os.path.join(ROOT, "oracle", "asan", "early_dest_" + san)
+    if not os.path.exists(exe):
+        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "asan"], check=True, stdout=subprocess.DEVNULL)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
+               TSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "early_dest ok" in r.stdout and "ERROR" not in r.stderr and "WARNING" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+
+
 def test_powerlaw_generator_hits_the_requested_mean_degree():
     """the generator drew deg_i columns per row ONCE and let duplicates collapse (mean 52 for a requested
     64 at BASELINE config 5); rows are now topped up to deg_i DISTINCT columns"""
