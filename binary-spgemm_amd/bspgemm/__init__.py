@@ -57,7 +57,7 @@ EXPORTS = [
     "bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values",
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
-    "bspgemm_bfs", "bspgemm_connected_components",
+    "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
 ]
 
 
@@ -204,6 +204,8 @@ def lib():
     L.bspgemm_ktruss.argtypes = [VP, VP, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_bfs.argtypes = [VP, VP, C.c_int, VP, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_core_numbers.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_kcore.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -503,6 +505,21 @@ class Context:
         _chk(lib().bspgemm_connected_components(self._h, A._h, C.byref(m), C.byref(nc), C.byref(rounds)),
              "bspgemm_connected_components")
         return Matrix(self, m, keep=None), nc.value, rounds.value
+
+    def core_numbers(self, A):
+        """bspgemm_core_numbers: (cores as a Result, degeneracy, rounds) -- row v of the result holds the one entry (v, v),
+        Result.download_values()[v] is the core number of v in the simple undirected graph of A's entries; device-resident
+        level-synchronous peeling, no product; rounds = peel launches"""
+        r, top, rounds = C.c_void_p(), C.c_int(), C.c_int()
+        _chk(lib().bspgemm_core_numbers(self._h, A._h, C.byref(r), C.byref(top), C.byref(rounds)), "bspgemm_core_numbers")
+        return Result(self, r), top.value, rounds.value
+
+    def kcore(self, A, k):
+        """bspgemm_kcore: (T as a Matrix, degeneracy) -- the subgraph of A's simple undirected graph induced by the vertices
+        of core number >= k, symmetric with sorted rows and no diagonal; empty for k > degeneracy"""
+        m, top = C.c_void_p(), C.c_int()
+        _chk(lib().bspgemm_kcore(self._h, A._h, int(k), C.byref(m), C.byref(top)), "bspgemm_kcore")
+        return Matrix(self, m, keep=None), top.value
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

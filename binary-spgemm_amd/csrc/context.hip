@@ -183,6 +183,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     if (const char *e = getenv("BSPGEMM_SHARED_SLOTS")) { const int v = atoi(e); ctx->shared_slots = v < 0 ? -1 : (v > kSharedSlotsMax ? kSharedSlotsMax : v); }
     ctx->debug_alloc = getenv("BSPGEMM_DEBUG_ALLOC") != nullptr;
     ctx->dropin_timing = getenv("BSPGEMM_DROPIN_TIMING") != nullptr;
+    ctx->kcore_timing = getenv("BSPGEMM_KCORE_TIMING") != nullptr;
     if (ctx->debug_alloc)
         fprintf(stderr, "[bspgemm] device %d: %s, %zu MiB, %d CUs; result cache budget %zu MiB\n", device,
                 prop.gcnArchName, (size_t)(prop.totalGlobalMem >> 20), prop.multiProcessorCount, ctx->cache_budget >> 20);

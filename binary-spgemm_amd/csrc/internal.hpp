@@ -133,6 +133,7 @@ struct bspgemm_context {
     int shared_slots = -1;              // BSPGEMM_SHARED_SLOTS / BSPGEMM_OPT_SHARED_SLOTS: -1 per class (wave_shared_max), 0 off, k: up to k shared slots in every class
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
+    bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
 };
 
 extern "C" int bspgemm_par_max_plus_one(const int *idx, long long n);              // host/par_copy.c

@@ -1,0 +1,99 @@
+/*
+ * spgemm_hip_kcore.c -- k-core decomposition of a graph, everything resident on the GPU (include/bspgemm.h:
+ * bspgemm_core_numbers, bspgemm_kcore), beside the closure, k-truss, BFS and components drivers.
+ *
+ *     SpGEMM_hip_kcore  file.mtx  [--numbers out.txt]  [--k K --out core.mtx]
+ *
+ * The file's entries are read as undirected edges, so the transpose that the loader hands back (readCOO,
+ * final/utils.c:47-81) is used as it is: the call symmetrizes its operand.
+ * Prints one line  n,nnz,degeneracy,top,rounds,ms  -- the largest core number, the number of vertices that have it
+ * (counted on the host from the downloaded values), the peel launches the call took and its wall time, the operand already
+ * on the device.
+ * --numbers writes one core number per line, line v that of vertex v (0-based).
+ * --k K --out writes the K-core (bspgemm_kcore: the subgraph induced by the vertices of core number >= K, both directions
+ * of every edge) with bspgemm_write_mtx, such that the loader reconstructs exactly that operand.
+ */
+#include "../../include/bspgemm.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#define CHECK(st, what)                                                                         \
+    do {                                                                                        \
+        bspgemm_status s_ = (st);                                                               \
+        if (s_ != BSPGEMM_OK) {                                                                 \
+            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
+            exit(1);                                                                            \
+        }                                                                                       \
+    } while (0)
+
+static void usage(void)
+{
+    printf("usage: SpGEMM_hip_kcore  path-to-matrix  [--numbers out.txt]  [--k K --out path-to-core]\n");
+    exit(1);
+}
+
+int main(int argc, char **argv)
+{
+    const char *numbers_path = NULL, *out_path = NULL, *k_arg = NULL;
+    if (argc < 2) usage();
+    for (int i = 2; i < argc; i += 2) {
+        if (i + 1 >= argc) usage();
+        if (strcmp(argv[i], "--numbers") == 0) numbers_path = argv[i + 1];
+        else if (strcmp(argv[i], "--k") == 0) k_arg = argv[i + 1];
+        else if (strcmp(argv[i], "--out") == 0) out_path = argv[i + 1];
+        else usage();
+    }
+    if ((k_arg == NULL) != (out_path == NULL)) usage();
+    uint32_t *Arow, *Acol, M, N, nnz;
+    bspgemm_status st = bspgemm_readCOO(argv[1], &Arow, &Acol, &M, &N, &nnz);
+    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
+    if (st != BSPGEMM_OK) exit(1);
+    if (M != N) { fprintf(stderr, "k-core needs a square matrix (%ux%u)\n", M, N); exit(1); }
+    const char *devenv = getenv("BSPGEMM_DEVICE");
+    bspgemm_context *ctx;
+    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    bspgemm_matrix *A;
+    bspgemm_result *R;
+    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
+    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    int degeneracy = 0, rounds = 0;
+    CHECK(bspgemm_core_numbers(ctx, A, &R, &degeneracy, &rounds), "bspgemm_core_numbers");
+    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    int *core = malloc(((size_t)M + 1) * sizeof(int));
+    if (!core) exit(1);
+    CHECK(bspgemm_result_download_values(ctx, R, core), "download");
+    int top = 0;
+    for (uint32_t v = 0; v < M; v++) top += core[v] == degeneracy;
+    if (numbers_path) {
+        FILE *f = fopen(numbers_path, "w");
+        if (!f) { fprintf(stderr, "cannot write %s\n", numbers_path); exit(1); }
+        for (uint32_t v = 0; v < M; v++) fprintf(f, "%d\n", core[v]);
+        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", numbers_path); exit(1); }
+    }
+    printf("%u,%u,%d,%d,%d,%.3f\n", M, nnz, degeneracy, top, rounds, ms);
+    if (out_path) {
+        bspgemm_matrix *T;
+        CHECK(bspgemm_kcore(ctx, A, atoi(k_arg), &T, NULL), "bspgemm_kcore");
+        const long long tn = bspgemm_matrix_nnz(T);
+        int *rp = malloc(((size_t)M + 1) * sizeof(int));
+        int *ci = malloc((size_t)(tn > 0 ? tn : 1) * sizeof(int));
+        if (!rp || !ci) exit(1);
+        CHECK(bspgemm_matrix_download(ctx, T, rp, ci), "download");
+        CHECK(bspgemm_write_mtx(out_path, (int)M, (int)M, rp, ci), "write");
+        free(rp); free(ci);
+        bspgemm_matrix_free(T);
+    }
+    free(core);
+    bspgemm_result_free(R);
+    bspgemm_matrix_free(A);
+    bspgemm_destroy(ctx);
+    free(Arow); free(Acol);
+    return 0;
+}

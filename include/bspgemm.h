@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -444,6 +444,53 @@ bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix *A, int ns
  *     leaked on any failure path.                                                                                         */
 bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A,
                                             bspgemm_matrix **P, int *ncomponents, int *rounds);
+
+/* k-core decomposition: the core number of every vertex, everything device-resident and without a product.  A is square and
+ * its entries are read as UNDIRECTED edges, as bspgemm_connected_components reads them.  The graph is
+ * S = bspgemm_matrix_symmetrize(A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL), computed inside the call and freed on every path, so
+ * unsorted rows, repeats, self-loops, one-direction storage and the in-edges that bspgemm_readCOO hands back all give the
+ * same answer; no flag skips it.  Any n, n == 0 and nnz == 0 included.
+ *   - *cores is a counted result of n rows, allocated as a product's is: row v holds exactly one entry, (v, v), whose int32
+ *     value is core(v) = the largest k such that v belongs to a subgraph of S in which every vertex has degree >= k; 0 for an
+ *     isolated vertex.  bspgemm_result_download, _download_values, _values_device, _values_sum and _free work on it
+ *     unchanged; bspgemm_matrix_from_result gives the identity, bspgemm_matrix_from_result_where(cores, n, BSPGEMM_CMP_GE, k)
+ *     the diagonal selector D_k of the k-core's vertices and BSPGEMM_CMP_EQ that of the k-shell.  n == 0: a result without
+ *     rows.  It is complete on the context's stream when the call returns.
+ *   - Core numbers are unique: the result is bit for bit the same on every run, independent of scheduling.
+ *     *degeneracy = the largest core number, 0 for n == 0 or a graph without edges.  *rounds = peel launches (below), 0 when
+ *     S has no entries.  degeneracy and rounds may be NULL.
+ *   - The scheme is level-synchronous peeling on residual degrees deg[] (from S.row_ptr), the result's values as core[]
+ *     (-1 = unassigned) and two frontier lists; deg, the lists and four counters live in the context's workspace, about
+ *     3 n ints.  Level k: a vertex-parallel scan gives every unassigned v with deg[v] <= k the core number k and appends it
+ *     to the frontier (one atomic per wave), and reduces the smallest deg of the vertices it leaves -- exact, no degree
+ *     changes in that launch; an empty frontier jumps k to that minimum.  A peel launch gives one wave to every frontier
+ *     vertex, its lanes striding over the vertex's row of S: each neighbour's deg is lowered by a device-scope atomicSub, and
+ *     the one decrement that returns k + 1 assigns k and appends the neighbour to the other list.  Peel launches swap the
+ *     two lists until one comes back empty, then k + 1.  Decisions rest only on atomic return values and on values from
+ *     before the launch; no kernel waits for another workgroup, and the result does not depend on when stores become
+ *     visible (csrc/kcore.hip).
+ *   - Cost: one synchronisation (4 to 16 bytes read back) per scan and per peel launch -- a path of n vertices takes n / 2
+ *     peel launches -- at most two scans per distinct core value, every stored entry of S walked once with at most one
+ *     atomic.  A frontier vertex's row is walked by ONE wave, 64 entries per step: a hub row in the frontier is a serial
+ *     tail, not the "a hub costs what its entries cost" geometry of the entry-parallel passes.  Defensive caps of n peel
+ *     launches and 2 n + 2 scans (BSPGEMM_ERR_HIP, "did not converge").
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *cores = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A or cores,
+ *     a non-square A, A from another context.  Otherwise the errors of bspgemm_matrix_symmetrize: BSPGEMM_ERR_INVALID for a
+ *     column outside [0, n) anywhere in A (its transpose tests every column on the device; the context stays usable),
+ *     BSPGEMM_ERR_OVERFLOW for more than INT_MAX entries in S, BSPGEMM_ERR_ALLOC.  Nothing is leaked on any path.           */
+bspgemm_status bspgemm_core_numbers(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_result **cores, int *degeneracy, int *rounds);
+
+/* The k-core as an operand: T = the subgraph of S (above) induced by {v : core(v) >= k}, n x n, symmetric, rows sorted and
+ * duplicate-free, no diagonal; the vertex-side companion of bspgemm_ktruss and the usual filter in front of it.  Composed of
+ * public calls on the core numbers: D_k = bspgemm_matrix_from_result_where(cores, n, BSPGEMM_CMP_GE, k), then D_k * S * D_k
+ * by two bspgemm_multiply calls with bspgemm_matrix_from_result between them; every intermediate is freed on every path.
+ *   - k == 0: T = S.  k > degeneracy: T is the empty n x n operand (D_k itself) and no product runs.
+ *   - *degeneracy as bspgemm_core_numbers gives it; may be NULL.  bspgemm_last_stats afterwards describes the last product
+ *     that ran.  T is an owned operand (bspgemm_matrix_free), usable in every product.
+ *   - BSPGEMM_ERR_INVALID with *T = NULL: k < 0, a NULL ctx, A or T, a non-square A, A from another context; otherwise the
+ *     errors of bspgemm_core_numbers and of the calls above.                                                            */
+bspgemm_status bspgemm_kcore(bspgemm_context *ctx, const bspgemm_matrix *A, int k, bspgemm_matrix **T, int *degeneracy);
 
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
