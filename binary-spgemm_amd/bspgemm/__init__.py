@@ -58,6 +58,7 @@ EXPORTS = [
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
+    "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
 
 
@@ -224,6 +225,10 @@ def lib():
     L.SpGEMM_hip_masked.argtypes = [_I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, _I32P, _I32P, IPP, _I32P,
                                     C.POINTER(C.c_int)]
     L.bspgemm_dropin_set_device.argtypes = [C.c_int]
+    L.bspgemm_debug_fail_alloc.argtypes = [C.c_int]
+    L.bspgemm_debug_fail_alloc.restype = None
+    L.bspgemm_debug_alloc_state.argtypes = [_I64P]
+    L.bspgemm_debug_alloc_state.restype = None
     L.bspgemm_comm_unique_id.argtypes = [C.c_char_p]
     L.bspgemm_comm_create.argtypes = [VP, C.c_char_p, C.c_int, C.c_int, PVP]
     L.bspgemm_comm_destroy.argtypes = [VP]
@@ -331,6 +336,19 @@ def gen_rmat(scale, edge_factor=16, abc=(0.30, 0.25, 0.25), seed=1):
 
 def gen_powerlaw(n, mean_degree, alpha=2.1, max_degree=0, seed=1):
     return _gen(lib().bspgemm_gen_powerlaw, n, n, mean_degree, alpha, max_degree, seed)
+
+
+# ------------------------------------------------------------------ test hooks -------------
+def debug_fail_alloc(nth):
+    """bspgemm_debug_fail_alloc: the nth device allocation from now (1 = the next) fails, once; 0 disarms"""
+    lib().bspgemm_debug_fail_alloc(int(nth))
+
+
+def debug_alloc_state():
+    """bspgemm_debug_alloc_state: (requests so far, live allocations, live bytes, injected failures fired so far)"""
+    out = np.zeros(4, dtype=np.int64)
+    lib().bspgemm_debug_alloc_state(out)
+    return tuple(int(v) for v in out)
 
 
 # ------------------------------------------------------------------ native handle API -----

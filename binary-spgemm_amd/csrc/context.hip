@@ -4,6 +4,9 @@
 // every compute entry point fails with BSPGEMM_ERR_NO_DEVICE.
 #include "internal.hpp"
 
+#include <mutex>
+#include <unordered_map>
+
 using namespace bsp;
 
 // ------------------------------------------------------------------ errors ---------------
@@ -28,13 +31,93 @@ extern "C" const char *bspgemm_status_string(bspgemm_status s)
     return "unknown status";
 }
 
+// ------------------------------------------------------------------ device memory -------
+// The one gate for device memory (internal.hpp: dev_alloc / dev_free): every array the library keeps on a GPU is allocated
+// and freed here, so that the live set can be counted and the n-th request can be made to fail (include/bspgemm.h, "test
+// hooks").  Process-wide and locked: contexts of several threads share it.  Off the timed path: a steady-state multiply
+// allocates nothing (kept workspaces, result cache).  The state is never destroyed: the drop-in context may free after exit().
+namespace {
+struct DevGate {
+    std::mutex mu;
+    std::unordered_map<void *, size_t> live;
+    long long requests = 0, live_bytes = 0, fired = 0, countdown = 0;
+};
+DevGate &dev_gate()
+{
+    static DevGate *g = new DevGate();
+    return *g;
+}
+}  // namespace
+
+hipError_t dev_alloc_bytes(void **p, size_t bytes)
+{
+    DevGate &g = dev_gate();
+    *p = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g.mu);
+        g.requests++;
+        if (g.countdown > 0 && --g.countdown == 0) {        // the injected failure: no HIP call, no sticky HIP error
+            g.fired++;
+            return hipErrorOutOfMemory;
+        }
+    }
+    void *q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return e;
+    if (q) {
+        std::lock_guard<std::mutex> lk(g.mu);
+        g.live[q] = bytes;
+        g.live_bytes += (long long)bytes;
+    }
+    *p = q;
+    return hipSuccess;
+}
+
+hipError_t dev_free(void *p)
+{
+    if (!p) return hipSuccess;
+    DevGate &g = dev_gate();
+    {
+        std::lock_guard<std::mutex> lk(g.mu);
+        auto it = g.live.find(p);
+        if (it != g.live.end()) {
+            g.live_bytes -= (long long)it->second;
+            g.live.erase(it);
+        }
+    }
+    return hipFree(p);
+}
+
+extern "C" void bspgemm_debug_fail_alloc(int nth)
+{
+    DevGate &g = dev_gate();
+    std::lock_guard<std::mutex> lk(g.mu);
+    g.countdown = nth > 0 ? nth : 0;
+}
+
+extern "C" void bspgemm_debug_alloc_state(int64_t out[4])
+{
+    if (!out) return;
+    DevGate &g = dev_gate();
+    std::lock_guard<std::mutex> lk(g.mu);
+    out[0] = g.requests;
+    out[1] = (int64_t)g.live.size();
+    out[2] = g.live_bytes;
+    out[3] = g.fired;
+}
+
 
 bspgemm_status ensure_deg8(const bspgemm_matrix *m)
 {
     if (m->d_deg8) return BSPGEMM_OK;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_deg8), (size_t)m->rows + 1));
+    HIPCHK(dev_alloc(&m->d_deg8, (size_t)m->rows + 1));
     launch_deg8(m->d_row_ptr, m->rows, m->d_deg8, m->ctx->stream);
-    HIPCHK(hipGetLastError());
+    if (hipError_t e = hipGetLastError()) {                // (an unbuilt table must not pass for a built one)
+        hipStreamSynchronize(m->ctx->stream);
+        dev_free(m->d_deg8);
+        m->d_deg8 = nullptr;
+        HIPCHK(e);
+    }
     return BSPGEMM_OK;
 }
 
@@ -56,26 +139,27 @@ bspgemm_status ensure_pad(const bspgemm_matrix *m)
     const size_t rows = (size_t)m->rows;
     int *plen = nullptr;
     long long *pp64 = nullptr, *partials = nullptr;
-    auto drop = [&] { hipFree(plen); hipFree(pp64); hipFree(partials); };
+    auto drop = [&] { dev_free(plen); dev_free(pp64); dev_free(partials); };
     auto bail = [&](bspgemm_status st) {
         hipStreamSynchronize(s);
         drop();
-        hipFree(m->d_col_pad); hipFree(m->d_row_ptr_pad); hipFree(m->d_ext);
+        dev_free(m->d_col_pad); dev_free(m->d_row_ptr_pad); dev_free(m->d_ext);
         m->d_col_pad = nullptr; m->d_row_ptr_pad = nullptr; m->d_ext = nullptr;
+        if (st != BSPGEMM_OK) m->pad_state = 0;                // a failed build decides nothing: the next use as B tries again
         return st;
     };
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&plen), rows * sizeof(int)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&pp64), (rows + 1) * sizeof(long long)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&partials), (rows / 2048 + 4) * sizeof(long long)));
+    HIPCHK_B(dev_alloc(&plen, rows * sizeof(int)));
+    HIPCHK_B(dev_alloc(&pp64, (rows + 1) * sizeof(long long)));
+    HIPCHK_B(dev_alloc(&partials, (rows / 2048 + 4) * sizeof(long long)));
     launch_pad_lengths(m->d_row_ptr, m->rows, plen, s);
     launch_scan_counts(plen, m->rows, pp64, partials, nullptr, s);
     long long total = 0;
     HIPCHK_B(hipMemcpyAsync(&total, pp64 + rows, sizeof(long long), hipMemcpyDeviceToHost, s));
     HIPCHK_B(hipStreamSynchronize(s));
     if (total > 0x7fffffffll - 64 || (force < 0 && total > 2 * m->nnz)) { drop(); return BSPGEMM_OK; }   // (stays "not for this operand")
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->d_col_pad), ((size_t)total + 64) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr_pad), (rows + 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->d_ext), rows * sizeof(int2));
+    hipError_t e = dev_alloc(&m->d_col_pad, ((size_t)total + 64) * sizeof(int));
+    if (e == hipSuccess) e = dev_alloc(&m->d_row_ptr_pad, (rows + 1) * sizeof(int));
+    if (e == hipSuccess) e = dev_alloc(&m->d_ext, rows * sizeof(int2));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         if (force == 1) { snprintf(g_err, sizeof g_err, "padded copy of col_idx: %s", hipGetErrorString(e)); return bail(BSPGEMM_ERR_ALLOC); }
@@ -109,14 +193,22 @@ bspgemm_status ensure_blk16(const bspgemm_matrix *m)
     const int force = m->ctx->rw_blk;                              // 0 never, 1 always, -1 decide per operand
     if (force == 0 || (force < 0 && m->rows < (1 << 21))) return BSPGEMM_OK;
     const size_t ints = (size_t)4 * (((size_t)m->rows + 15) / 16 + 1);   // 16-byte entries (hipMalloc aligns them), one spare
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_blk16), (ints + 4) * sizeof(int)));
+    hipStream_t s = m->ctx->stream;
+    auto bail = [&](bspgemm_status st) {                           // a failed build decides nothing: the next use as B tries again
+        hipStreamSynchronize(s);
+        dev_free(m->d_blk16);
+        m->d_blk16 = nullptr;
+        m->blk16_state = 0;
+        return st;
+    };
+    HIPCHK_B(dev_alloc(&m->d_blk16, (ints + 4) * sizeof(int)));
     unsigned long long *d_clamped = reinterpret_cast<unsigned long long *>(m->d_blk16 + ints);
-    HIPCHK(hipMemsetAsync(d_clamped, 0, sizeof(unsigned long long), m->ctx->stream));
-    launch_blk16(m->d_row_ptr, m->pad_state == 1 ? m->d_row_ptr_pad : nullptr, m->rows, m->d_blk16, d_clamped, m->ctx->stream);
-    HIPCHK(hipGetLastError());
+    HIPCHK_B(hipMemsetAsync(d_clamped, 0, sizeof(unsigned long long), s));
+    launch_blk16(m->d_row_ptr, m->pad_state == 1 ? m->d_row_ptr_pad : nullptr, m->rows, m->d_blk16, d_clamped, s);
+    HIPCHK_B(hipGetLastError());
     unsigned long long clamped = 0;
-    HIPCHK(hipMemcpyAsync(&clamped, d_clamped, sizeof(clamped), hipMemcpyDeviceToHost, m->ctx->stream));
-    HIPCHK(hipStreamSynchronize(m->ctx->stream));
+    HIPCHK_B(hipMemcpyAsync(&clamped, d_clamped, sizeof(clamped), hipMemcpyDeviceToHost, s));
+    HIPCHK_B(hipStreamSynchronize(s));
     if (force == 1 || clamped * 4ull <= (unsigned long long)m->nnz) m->blk16_state = 1;
     return BSPGEMM_OK;
 }
@@ -157,12 +249,12 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     HIPCHK_B(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     ctx->own_stream = true;
     HIPCHK_B(hipHostMalloc(reinterpret_cast<void **>(&ctx->h), sizeof(HostScalars), hipHostMallocDefault));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_prep), sizeof(PrepScalars)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_small), sizeof(SmallScalars)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_small_tiles), sizeof(SmallTiles)));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->d_err), 64));
+    HIPCHK_B(dev_alloc(&ctx->d_prep, sizeof(PrepScalars)));
+    HIPCHK_B(dev_alloc(&ctx->d_small, sizeof(SmallScalars)));
+    HIPCHK_B(dev_alloc(&ctx->d_small_tiles, sizeof(SmallTiles)));
+    HIPCHK_B(dev_alloc(&ctx->d_err, 64));
     HIPCHK_B(hipMemset(ctx->d_err, 0, 64));
-    HIPCHK_B(hipMalloc(reinterpret_cast<void **>(&ctx->bin_count), kNumBins * sizeof(int)));
+    HIPCHK_B(dev_alloc(&ctx->bin_count, kNumBins * sizeof(int)));
     for (auto &sl : ctx->slots) {
         for (auto &e : sl.ev) HIPCHK_B(hipEventCreate(&e));
         for (auto &ph : sl.ev_cls) for (auto &c : ph) for (auto &e : c) HIPCHK_B(hipEventCreate(&e));
@@ -196,25 +288,25 @@ extern "C" void bspgemm_destroy(bspgemm_context *ctx)
     if (!ctx) return;
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->F); hipFree(ctx->Fprefix); hipFree(ctx->partials);
-    hipFree(ctx->cnt); hipFree(ctx->bin_tiles); hipFree(ctx->bin_count); hipFree(ctx->tmp); hipFree(ctx->tmpv);
-    hipFree(ctx->rec); hipFree(ctx->recpre); hipFree(ctx->ab); hipFree(ctx->tile_row); hipFree(ctx->Fmask); hipFree(ctx->hpartials);
-    hipFree(ctx->hub_rec); hipFree(ctx->hub_pre);
+    dev_free(ctx->F); dev_free(ctx->Fprefix); dev_free(ctx->partials);
+    dev_free(ctx->cnt); dev_free(ctx->bin_tiles); dev_free(ctx->bin_count); dev_free(ctx->tmp); dev_free(ctx->tmpv);
+    dev_free(ctx->rec); dev_free(ctx->recpre); dev_free(ctx->ab); dev_free(ctx->tile_row); dev_free(ctx->Fmask); dev_free(ctx->hpartials);
+    dev_free(ctx->hub_rec); dev_free(ctx->hub_pre);
     if (ctx->h) hipHostFree(ctx->h);
-    hipFree(ctx->d_prep);
-    hipFree(ctx->d_err);
-    hipFree(ctx->d_small);
-    hipFree(ctx->d_small_tiles);
-    hipFree(ctx->chunk_row);
+    dev_free(ctx->d_prep);
+    dev_free(ctx->d_err);
+    dev_free(ctx->d_small);
+    dev_free(ctx->d_small_tiles);
+    dev_free(ctx->chunk_row);
     for (auto &sl : ctx->slots) {
         for (auto &e : sl.ev) if (e) hipEventDestroy(e);
         for (auto &ph : sl.ev_cls) for (auto &c : ph) for (auto &e : c) if (e) hipEventDestroy(e);
     }
-    for (auto &c : ctx->cache) if (c.p) hipFree(c.p);
+    for (auto &c : ctx->cache) if (c.p) dev_free(c.p);
     if (ctx->stream_b) { hipStreamSynchronize(ctx->stream_b); hipStreamDestroy(ctx->stream_b); }
     if (ctx->stream_c) { hipStreamSynchronize(ctx->stream_c); hipStreamDestroy(ctx->stream_c); }
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    hipFree(ctx->stitch_partials);
+    dev_free(ctx->stitch_partials);
     for (auto &t : ctx->ev_tile) for (auto &e : t) if (e) hipEventDestroy(e);
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -250,14 +342,14 @@ bspgemm_status operand_new(bspgemm_context *ctx, int rows, int cols, bspgemm_mat
 {
     bspgemm_matrix *m = *out = new (std::nothrow) bspgemm_matrix{ctx, rows, cols, 0, nullptr, nullptr, true};
     if (!m) return FAIL(BSPGEMM_ERR_ALLOC, "matrix");
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_row_ptr), ((size_t)rows + 1) * sizeof(int)));
+    HIPCHK(dev_alloc(&m->d_row_ptr, ((size_t)rows + 1) * sizeof(int)));
     return BSPGEMM_OK;
 }
 
 bspgemm_status operand_cols(bspgemm_matrix *m, long long cap)
 {
     // +1 int of slack on col_idx so an empty matrix still has a valid pointer
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_col_idx), ((size_t)cap + 1) * sizeof(int)));
+    HIPCHK(dev_alloc(&m->d_col_idx, ((size_t)cap + 1) * sizeof(int)));
     return BSPGEMM_OK;
 }
 
@@ -338,14 +430,14 @@ extern "C" void bspgemm_matrix_free(bspgemm_matrix *m)
     if (!m) return;
     hipSetDevice(m->ctx->device);
     if (m->owned) {
-        hipFree(m->d_row_ptr);
-        hipFree(m->d_col_idx);
+        dev_free(m->d_row_ptr);
+        dev_free(m->d_col_idx);
     }
-    hipFree(m->d_deg8);
-    hipFree(m->d_blk16);
-    hipFree(m->d_col_pad);
-    hipFree(m->d_row_ptr_pad);
-    hipFree(m->d_ext);
+    dev_free(m->d_deg8);
+    dev_free(m->d_blk16);
+    dev_free(m->d_col_pad);
+    dev_free(m->d_row_ptr_pad);
+    dev_free(m->d_ext);
     delete m;
 }
 extern "C" bspgemm_status bspgemm_matrix_download(bspgemm_context *ctx, const bspgemm_matrix *m, int *row_ptr, int *col_idx)
@@ -365,11 +457,11 @@ extern "C" bspgemm_status bspgemm_matrix_invalidate(bspgemm_matrix *m)
     if (!m) return FAIL(BSPGEMM_ERR_INVALID, "matrix is NULL");
     if (bspgemm_status st = use_device(m->ctx)) return st;
     HIPCHK(hipStreamSynchronize(m->ctx->stream));          // a multiply may still be reading the tables
-    hipFree(m->d_deg8);
-    hipFree(m->d_blk16);
-    hipFree(m->d_col_pad);
-    hipFree(m->d_row_ptr_pad);
-    hipFree(m->d_ext);
+    dev_free(m->d_deg8);
+    dev_free(m->d_blk16);
+    dev_free(m->d_col_pad);
+    dev_free(m->d_row_ptr_pad);
+    dev_free(m->d_ext);
     m->d_deg8 = nullptr;
     m->d_blk16 = nullptr;
     m->blk16_state = 0;
@@ -396,27 +488,26 @@ bspgemm_status ensure_rows(bspgemm_context *ctx, size_t rows)
 {
     if (rows <= ctx->rows_cap) return BSPGEMM_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->F); hipFree(ctx->Fprefix); hipFree(ctx->partials); hipFree(ctx->cnt); hipFree(ctx->bin_tiles);
-    hipFree(ctx->rec); hipFree(ctx->recpre); hipFree(ctx->Fmask); hipFree(ctx->hpartials);
+    dev_free(ctx->F); dev_free(ctx->Fprefix); dev_free(ctx->partials); dev_free(ctx->cnt); dev_free(ctx->bin_tiles);
+    dev_free(ctx->rec); dev_free(ctx->recpre); dev_free(ctx->Fmask); dev_free(ctx->hpartials);
     ctx->F = ctx->Fprefix = ctx->partials = ctx->recpre = ctx->Fmask = ctx->hpartials = nullptr;
     ctx->cnt = ctx->bin_tiles = nullptr;
     ctx->rec = nullptr;
     ctx->rows_cap = 0;
     const size_t cap = rows + rows / 8 + 64;
     const size_t tiles = cap / 2048 + 2;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->F), cap * sizeof(long long)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->Fmask), cap * sizeof(long long)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->Fprefix), (cap + 1) * sizeof(long long)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->partials), (tiles + 1) * sizeof(long long)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->hpartials), (tiles + 1) * sizeof(long long)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->cnt), cap * sizeof(int)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->bin_tiles), (tiles + 1) * kNumBins * sizeof(int)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->rec), cap * sizeof(RowRec)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->recpre), cap * sizeof(long long)));
-    if (!ctx->hub_rec) {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->hub_rec), kHeavySortMax * sizeof(RowRec)));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->hub_pre), kHeavySortMax * sizeof(long long)));
-    }
+    HIPCHK(dev_alloc(&ctx->F, cap * sizeof(long long)));
+    HIPCHK(dev_alloc(&ctx->Fmask, cap * sizeof(long long)));
+    HIPCHK(dev_alloc(&ctx->Fprefix, (cap + 1) * sizeof(long long)));
+    HIPCHK(dev_alloc(&ctx->partials, (tiles + 1) * sizeof(long long)));
+    HIPCHK(dev_alloc(&ctx->hpartials, (tiles + 1) * sizeof(long long)));
+    HIPCHK(dev_alloc(&ctx->cnt, cap * sizeof(int)));
+    HIPCHK(dev_alloc(&ctx->bin_tiles, (tiles + 1) * kNumBins * sizeof(int)));
+    HIPCHK(dev_alloc(&ctx->rec, cap * sizeof(RowRec)));
+    HIPCHK(dev_alloc(&ctx->recpre, cap * sizeof(long long)));
+    // (each on its own: a call that got hub_rec and failed on hub_pre must not leave hub_pre NULL for good)
+    if (!ctx->hub_rec) HIPCHK(dev_alloc(&ctx->hub_rec, kHeavySortMax * sizeof(RowRec)));
+    if (!ctx->hub_pre) HIPCHK(dev_alloc(&ctx->hub_pre, kHeavySortMax * sizeof(long long)));
     ctx->rows_cap = cap;
     return BSPGEMM_OK;
 }
@@ -425,11 +516,11 @@ bspgemm_status ensure_ab(bspgemm_context *ctx, size_t pairs)
 {
     if (pairs <= ctx->ab_cap) return BSPGEMM_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->ab);
+    dev_free(ctx->ab);
     ctx->ab = nullptr;
     ctx->ab_cap = 0;
     const size_t cap = pairs + pairs / 16 + 64;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->ab), cap * sizeof(int2)));
+    HIPCHK(dev_alloc(&ctx->ab, cap * sizeof(int2)));
     ctx->ab_cap = cap;
     return BSPGEMM_OK;
 }
@@ -440,11 +531,11 @@ bspgemm_status ensure_tile_rows(bspgemm_context *ctx, size_t items)
     const size_t need = items / kRowWorkTile + 2;
     if (need <= ctx->tile_row_cap) return BSPGEMM_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->tile_row);
+    dev_free(ctx->tile_row);
     ctx->tile_row = nullptr;
     ctx->tile_row_cap = 0;
     const size_t cap = need + need / 16 + 64;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->tile_row), cap * sizeof(int)));
+    HIPCHK(dev_alloc(&ctx->tile_row, cap * sizeof(int)));
     ctx->tile_row_cap = cap;
     return BSPGEMM_OK;
 }
@@ -453,15 +544,15 @@ bspgemm_status ensure_tmp(bspgemm_context *ctx, size_t ints)
 {
     if (ints <= ctx->tmp_cap) return BSPGEMM_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->tmp);
+    dev_free(ctx->tmp);
     ctx->tmp = nullptr;
     ctx->tmp_cap = 0;
     const size_t cap = ints + ints / 16 + 1024;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->tmp), cap * sizeof(int));
+    hipError_t e = dev_alloc(&ctx->tmp, cap * sizeof(int));
     if (e == hipErrorOutOfMemory) {                     // the cache of freed results may hold what is missing
-        for (auto &c : ctx->cache) if (c.p) { hipFree(c.p); c.p = nullptr; }
+        for (auto &c : ctx->cache) if (c.p) { dev_free(c.p); c.p = nullptr; }
         (void)hipGetLastError();
-        e = hipMalloc(reinterpret_cast<void **>(&ctx->tmp), cap * sizeof(int));
+        e = dev_alloc(&ctx->tmp, cap * sizeof(int));
     }
     HIPCHK(e);
     ctx->tmp_cap = cap;
@@ -473,15 +564,15 @@ bspgemm_status ensure_tmpv(bspgemm_context *ctx, size_t ints)
 {
     if (ints <= ctx->tmpv_cap) return BSPGEMM_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->tmpv);
+    dev_free(ctx->tmpv);
     ctx->tmpv = nullptr;
     ctx->tmpv_cap = 0;
     const size_t cap = ints + ints / 16 + 1024;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->tmpv), cap * sizeof(int));
+    hipError_t e = dev_alloc(&ctx->tmpv, cap * sizeof(int));
     if (e == hipErrorOutOfMemory) {                     // the cache of freed results may hold what is missing
-        for (auto &c : ctx->cache) if (c.p) { hipFree(c.p); c.p = nullptr; }
+        for (auto &c : ctx->cache) if (c.p) { dev_free(c.p); c.p = nullptr; }
         (void)hipGetLastError();
-        e = hipMalloc(reinterpret_cast<void **>(&ctx->tmpv), cap * sizeof(int));
+        e = dev_alloc(&ctx->tmpv, cap * sizeof(int));
     }
     HIPCHK(e);
     ctx->tmpv_cap = cap;
@@ -492,11 +583,11 @@ bspgemm_status ensure_chunk_rows(bspgemm_context *ctx, size_t entries)
 {
     if (entries <= ctx->chunk_cap) return BSPGEMM_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->chunk_row);
+    dev_free(ctx->chunk_row);
     ctx->chunk_row = nullptr;
     ctx->chunk_cap = 0;
     const size_t cap = entries + entries / 16 + 64;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->chunk_row), cap * sizeof(int)));
+    HIPCHK(dev_alloc(&ctx->chunk_row, cap * sizeof(int)));
     ctx->chunk_cap = cap;
     return BSPGEMM_OK;
 }
@@ -525,7 +616,7 @@ hipError_t result_alloc(bspgemm_context *ctx, void **out, size_t bytes)
     }
     const bool dbg = ctx->debug_alloc;
     const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = hipMalloc(out, bytes);
+    hipError_t e = dev_alloc(out, bytes);
     if (dbg) {
         fprintf(stderr, "[bspgemm] hipMalloc(%zu) %.3f ms; cache:", bytes,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -533,9 +624,9 @@ hipError_t result_alloc(bspgemm_context *ctx, void **out, size_t bytes)
         fprintf(stderr, "\n");
     }
     if (e == hipErrorOutOfMemory) {                     // drop the cache and retry once
-        for (auto &c : ctx->cache) if (c.p) { hipFree(c.p); c.p = nullptr; }
+        for (auto &c : ctx->cache) if (c.p) { dev_free(c.p); c.p = nullptr; }
         (void)hipGetLastError();
-        e = hipMalloc(out, bytes);
+        e = dev_alloc(out, bytes);
     }
     return e;
 }
@@ -556,10 +647,10 @@ void result_release(bspgemm_context *ctx, void *p, size_t bytes)
             if (ctx->cache[i].p && (small < 0 || ctx->cache[i].bytes < ctx->cache[small].bytes)) small = i;
         if (small < 0) break;
         held -= ctx->cache[small].bytes;
-        hipFree(ctx->cache[small].p);
+        dev_free(ctx->cache[small].p);
         ctx->cache[small].p = nullptr;
     }
-    if (bytes > ctx->cache_budget) { hipFree(p); return; }
+    if (bytes > ctx->cache_budget) { dev_free(p); return; }
     int slot = -1;
     for (int i = 0; i < 8; i++)
         if (!ctx->cache[i].p) { slot = i; break; }
@@ -567,8 +658,8 @@ void result_release(bspgemm_context *ctx, void *p, size_t bytes)
         slot = 0;
         for (int i = 1; i < 8; i++)
             if (ctx->cache[i].bytes < ctx->cache[slot].bytes) slot = i;
-        if (ctx->cache[slot].bytes >= bytes) { hipFree(p); return; }
-        hipFree(ctx->cache[slot].p);
+        if (ctx->cache[slot].bytes >= bytes) { dev_free(p); return; }
+        dev_free(ctx->cache[slot].p);
     }
     ctx->cache[slot].p = p;
     ctx->cache[slot].bytes = bytes;

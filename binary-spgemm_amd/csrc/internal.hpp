@@ -48,6 +48,15 @@ static inline bspgemm_status fail(bspgemm_status st, const char *what, const cha
         }                                                                                  \
     } while (0)
 
+// ------------------------------------------------------------------ device memory (context.hip) ---
+// The one gate for device memory: every allocation and release of a device array outside comm.hip (which has hooks of its
+// own) goes through this pair -- the workspaces, the operands and their tables, the result buffers and their cache.  It
+// counts the live allocations and can fail the n-th request (bspgemm_debug_fail_alloc, include/bspgemm.h).  A failed
+// request leaves *p NULL.  Pinned (hipHostMalloc) and host memory (new, malloc) stay outside.
+hipError_t dev_alloc_bytes(void **p, size_t bytes);
+template <class T> static inline hipError_t dev_alloc(T **p, size_t bytes) { return dev_alloc_bytes(reinterpret_cast<void **>(p), bytes); }
+hipError_t dev_free(void *p);                           // NULL: nothing
+
 // ------------------------------------------------------------------ objects --------------
 using bsp::kNumBins;
 using bsp::PrepScalars;

@@ -553,10 +553,10 @@ extern "C" bspgemm_status bspgemm_lengths_to_row_ptr(bspgemm_context *ctx, const
     // own scan scratch: this may run on another stream than a multiply that is using ctx->partials
     const size_t need = (size_t)width / 2048 + 2;
     if (need > ctx->stitch_partials_cap) {
-        if (ctx->stitch_partials) HIPCHK(hipFree(ctx->stitch_partials));
+        if (ctx->stitch_partials) HIPCHK(dev_free(ctx->stitch_partials));
         ctx->stitch_partials = nullptr;
         ctx->stitch_partials_cap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&ctx->stitch_partials), need * sizeof(long long)));
+        HIPCHK(dev_alloc(&ctx->stitch_partials, need * sizeof(long long)));
         ctx->stitch_partials_cap = need;
     }
     long long *out = reinterpret_cast<long long *>(d_row_ptr);

@@ -676,6 +676,23 @@ int SpGEMM_hip_multi(bspgemm_comm *comm, int *Acol, int *Arow, int An,
                      int *Bcol, int *Brow, int Bm,
                      int **Ccol, int *Crow, int tBlock);
 
+/* ---------------------------------------------------------------- test hooks ----------
+ * Every device allocation of the library outside the communicator layer (which has bspgemm_comm_inject_failure) passes
+ * one gate: the workspaces of a context, the operands and their derived tables, the result buffers and the cache of
+ * freed ones.  A result buffer taken from that cache is no allocation and does not pass it.  Pinned and host memory
+ * (hipHostMalloc, new, malloc) stay outside.  The gate's state is process-wide and safe to touch from several threads.
+ *
+ * test hook (one-shot): the `nth` request from now (1 = the next) fails with hipErrorOutOfMemory without calling hipMalloc
+ * and leaves its pointer NULL; 0 disarms.  The entry point that made the request returns BSPGEMM_ERR_ALLOC as documented
+ * for it -- or succeeds where a fallback is documented: BSPGEMM_FLOW_AUTO runs the exact flow, an optional table is left
+ * out, and the retry that follows dropping the result cache is a new request, which may succeed.  The hook leaves no sticky
+ * HIP error behind, so what the library does to clear one after a real out-of-memory condition is not exercised by it.    */
+void           bspgemm_debug_fail_alloc(int nth);
+/* out = {requests so far, live allocations, live bytes, injected failures fired so far}, counted since the process
+ * started.  Live: handed out by the gate and not yet freed, buffers held by a context's result cache included; all zero
+ * before the first context exists.  Equal live counts before bspgemm_create and after bspgemm_destroy: nothing leaked.  */
+void           bspgemm_debug_alloc_state(int64_t out[4]);
+
 /* ---------------------------------------------------------------- host utilities (C) --
  * Plain C, no GPU needed.                                                                    */
 

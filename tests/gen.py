@@ -121,6 +121,20 @@ def tiny_b_heavy(nnzb, b_cols=(7, 0, 10, 3, 4), nrep=5000):
     return a_rp, a_ci, b_rp, b_ci
 
 
+def mixed_class_rows(nrows=200, inner=512, ncols=4096, seed=41):
+    """a small product that still reaches every row kind of the general flows: B is inner x ncols with 20 draws per row; of
+    A's nrows rows every fourth is empty, the others cycle through 1, 5, 12 and 40 entries (about 20, 100, 240 and 800
+    products: four one-wave classes), and row 21 has 150 (about 3000 products: a heavy row).  (a_rp, a_ci, b_rp, b_ci)."""
+    rng = np.random.default_rng(seed)
+    b_rp, b_ci = uniform_rect(inner, ncols, 20, seed + 1)
+    deg = np.array([0, 1, 5, 12, 0, 40, 1, 5] * (nrows // 8 + 1))[:nrows]
+    deg[21] = 150
+    rows = np.repeat(np.arange(nrows), deg)
+    cols = rng.integers(0, inner, size=rows.size)
+    a_rp, a_ci = _csr_from_pairs(rows, cols, nrows)
+    return a_rp, a_ci, b_rp, b_ci
+
+
 WAVE_CHUNKS = (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32)   # csrc/kernels.hpp kWaveChunks
 WAVE_CAPS = [64 * c for c in WAVE_CHUNKS]
 

@@ -26,6 +26,34 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert sorted(bspgemm.EXPORTS) == declared, "python binding list out of sync with the header"
 
 
+def test_alloc_test_hooks_are_declared_and_idle_before_any_context():
+    """the two test hooks of the device-memory gate: declared with these argument lists, exported, bound, and in a process
+    that has created no context the gate has seen nothing (requests, live allocations, live bytes, injected failures)"""
+    import subprocess
+    import sys
+    text = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "bspgemm.h")).read())
+    assert "void bspgemm_debug_fail_alloc(int nth);" in text
+    assert "void bspgemm_debug_alloc_state(int64_t out[4]);" in text
+    L = bspgemm.lib()
+    for name in ("bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state"):
+        assert name in bspgemm.EXPORTS and hasattr(L, name)
+    assert L.bspgemm_debug_fail_alloc.restype is None and L.bspgemm_debug_alloc_state.restype is None
+    state = bspgemm.debug_alloc_state()
+    assert len(state) == 4 and all(v >= 0 for v in state) and state[3] <= state[0]
+    code = ("import ctypes\n"
+            "L = ctypes.CDLL(%r)\n"
+            "out = (ctypes.c_int64 * 4)(7, 7, 7, 7)\n"
+            "L.bspgemm_debug_alloc_state(out)\n"
+            "assert list(out) == [0, 0, 0, 0], list(out)\n"
+            "L.bspgemm_debug_fail_alloc(3)\n"                   # arming allocates nothing and fires nothing
+            "L.bspgemm_debug_fail_alloc(0)\n"
+            "L.bspgemm_debug_alloc_state(out)\n"
+            "assert list(out) == [0, 0, 0, 0], list(out)\n"
+            "print('idle')\n") % bspgemm.LIB_PATH
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "idle" in r.stdout, r.stdout + r.stderr
+
+
 def test_header_cites_the_reference_interfaces():
     text = open(os.path.join(ROOT, "include", "bspgemm.h")).read()
     for cite in ("final/SpGEMM_mpi_omp.c:71-74", "final/SpGEMM_mpi_omp.c:15-18", "final/utils.c:47-81",
