@@ -19,8 +19,13 @@
 // under the mask): one more blocked scan gives the level-0 words' popcount prefix, so every distinct mask column has a rank
 // and an LDS counter (CAP per wave, cleared over the row's distinct columns only).  A hit adds one to its counter instead of
 // setting a kept bit; the read-out walks the mask row in rank order and emits the columns whose counter is non-zero, the
-// counts going to vals at the same offsets as the columns in tmp.  One template kernel, COUNT a template constant: each
-// instance compiles to the instructions of the separate kernel it replaced (tools/isa_diff.py).
+// counts going to vals at the same offsets as the columns in tmp.  One template kernel, COUNT a template constant: the Count
+// instances compile to the instructions of the separate kernel they replaced (tools/isa_diff.py); the Keep instances did
+// too until they took the Count instances' guard on the mask's columns (step 1: one more compare per mask column).
+//
+// The mask may have any number of columns (include/bspgemm.h).  Its entries beyond the topw top words that B's columns use
+// are dropped in step 1, in every instance, before anything is indexed with them; those from B.cols up to there go into the
+// structure like any other, and no product lands on them.
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -112,7 +117,7 @@ void k_wave_masked(const int2 *__restrict__ ab, const int *__restrict__ Bcol, in
 
         // ---- 1. rank bitmap of the mask row (all levels stay alive) ----------------------
         int mcol[CHUNKS], rank[CHUNKS];
-        bool live[CHUNKS];                                         // COUNT: the lane's column of chunk c is a mask column
+        bool live[CHUNKS];                                         // the lane's column of chunk c is a mask column that counts
 #pragma unroll
         for (int c = 0; c < CHUNKS; c++) {
             const int p = c * 64 + lane;
@@ -120,9 +125,10 @@ void k_wave_masked(const int2 *__restrict__ ab, const int *__restrict__ Bcol, in
         }
 #pragma unroll
         for (int c = 0; c < CHUNKS; c++) {
-            // COUNT: a mask column beyond the top bitmap (at or above B.cols) is dropped here -- its top word would lie
-            // outside s_top, and no product can land on it
-            const bool ok = c * 64 + lane < mlen && (!COUNT || ((u32)mcol[c] >> (5 * LEVELS)) < (u32)topw);
+            // every instance: a mask column whose top word is not one of the topw words that B's columns use (a column at
+            // or above topw * 32^LEVELS >= B.cols; compared unsigned: one with the sign bit too) is dropped here -- its top
+            // word may lie outside s_top, and no product can land on it
+            const bool ok = c * 64 + lane < mlen && ((u32)mcol[c] >> (5 * LEVELS)) < (u32)topw;
             const u32 cc = ok ? (u32)mcol[c] : 0u;
             mcol[c] = (int)cc;
             const u32 tw = cc >> (5 * LEVELS);
@@ -143,7 +149,8 @@ void k_wave_masked(const int2 *__restrict__ ab, const int *__restrict__ Bcol, in
                 unsigned short *Spre = preB;                       // only level 1 needs ranks
 #pragma unroll
                 for (int c = 0; c < CHUNKS; c++) {
-                    const bool ok = c * 64 + lane < mlen && (!COUNT || live[c]);
+                    const bool ok = c * 64 + lane < mlen && live[c];   // (live: within the top bitmap; written as the
+                                                                         // Count instances always had it: they compile as before)
                     const u32 cc = (u32)mcol[c];
                     const u32 x = P[rank[c]];
                     const int pre = Ppre[rank[c]];

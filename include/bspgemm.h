@@ -204,7 +204,17 @@ int            bspgemm_matrix_uses_blocked_table(const bspgemm_matrix *m);
 int            bspgemm_matrix_uses_padded_rows(const bspgemm_matrix *m);
 
 /* C = F .* (A*B), complement convention of SpGEMM_masked (final/SpGEMM_mpi_omp.c:232-288):
- * a column k is admitted to row i only if (i,k) is in F's pattern.                           */
+ * a column k is admitted to row i only if (i,k) is in F's pattern.
+ *   - F is indexed by ABSOLUTE row: F.rows >= row_end and F in ctx, else BSPGEMM_ERR_INVALID with *C = NULL.
+ *   - F may have any number of columns, fewer or more than B.cols.  Entries of F at or above B.cols (read as
+ *     unsigned: a negative entry too) have no effect: no product can land on them, and no kernel indexes
+ *     anything with them.  (The reference indexes a flag array of Bm entries with them; the drop-in
+ *     SpGEMM_hip_masked takes them like this call.)
+ *   - F's rows may be unsorted and hold repeats; C's rows are ascending and duplicate-free all the same.
+ *   - Rows are binned and placed by the mask row's length AS STORED (|C_i| <= |F_i|): repeats and entries at or
+ *     above B.cols count towards the class of a row (bspgemm_stats.rows_per_bin, bin_cap).  A row without
+ *     products is in class 0, a row of more than 8192 products in a heavy class whatever its mask.
+ *   - Flow: always upper-bound placement + compaction (no small path, no EXACT flow).                          */
 bspgemm_status bspgemm_multiply_masked(bspgemm_context *ctx,
                                        const bspgemm_matrix *A, const bspgemm_matrix *B,
                                        const bspgemm_matrix *F,

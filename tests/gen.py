@@ -228,9 +228,11 @@ def _mid_rank_caps(cols):
     return mid_cap, rank_cap
 
 
-def row_bins(F, cols):
-    """capacity class of every row as csrc/prepass.hip bin_of places it (BSPGEMM_RANK_ROWS at its default)"""
-    mid_cap, rank_cap = _mid_rank_caps(cols)
+def row_bins(F, cols, rank_cap=None):
+    """capacity class of every row as csrc/prepass.hip bin_of places it (BSPGEMM_RANK_ROWS at its default; rank_cap = 0:
+    without the rank class, as the masked products bin their rows)"""
+    mid_cap, default_rank_cap = _mid_rank_caps(cols)
+    rank_cap = default_rank_cap if rank_cap is None else rank_cap
     F = np.asarray(F, np.int64)
     b = np.zeros(F.size, np.int64)
     wave = (F > 0) & (F <= 2048)
@@ -245,10 +247,24 @@ def expected_bins(F, cols):
     return np.bincount(row_bins(F, cols), minlength=NUM_BINS).tolist()
 
 
-def expected_bin_caps(cols):
-    """bspgemm_stats.bin_cap (csrc/context.hip)"""
-    mid_cap, rank_cap = _mid_rank_caps(cols)
+def expected_bin_caps(cols, rank_cap=None):
+    """bspgemm_stats.bin_cap (csrc/context.hip); rank_cap = 0: of the masked products, which have no rank class"""
+    mid_cap, default_rank_cap = _mid_rank_caps(cols)
+    rank_cap = default_rank_cap if rank_cap is None else rank_cap
     return [0] + WAVE_CAPS + [max(rank_cap, 2048), mid_cap, 0x7fffffff]
+
+
+MASK_WAVE_MAX_PRODUCTS = 8192   # csrc/wave_masked.hip kMaskWaveMaxProducts: rows with more go to the window kernel
+
+
+def masked_row_bins(products, mask_len, cols):
+    """capacity class of every row of the masked products C = F .* (A*B) (csrc/wave_masked.hip k_mask_lengths, then bin_of
+    without the rank class): by the mask row's length AS STORED (repeats and columns at or above B.cols count), 0 for a
+    row without products, and a heavy class for a row of more than 8192 products whatever its mask"""
+    F = np.asarray(products, np.int64)
+    m = np.where(F > 0, np.asarray(mask_len, np.int64), 0)
+    m = np.where((m > 0) & (m <= WAVE_CAPS[-1]) & (F > MASK_WAVE_MAX_PRODUCTS), WAVE_CAPS[-1] + 1, m)
+    return row_bins(m, cols, rank_cap=0)
 
 
 def wave_levels(cols):
@@ -913,3 +929,170 @@ def small_range_case():
     t[5], t[300], t[37], t[69], t[101], t[357] = 600, 600, 17, 16, 2, 33
     t[[40, 110]], t[[41, 111]] = 0, -1
     return _small_case(t, "pairs", "mixed", 6000, 2602, ranges=SMALL_RANGES)
+
+
+# ---- masks with columns at or above B.cols: tests/test_gpu_masked.py, checked without a GPU by tests/test_masked_shapes.py ----
+INT_MAX = 2**31 - 1
+MASK_CAPS = (64, 128, 256, 512, 768, 1024, 2048)    # mask-row capacities of k_wave_masked (wave_masked.hip launch_mask_levels)
+# the three depths of k_wave_masked and both sides of each depth boundary
+MASK_ONE_WAVE_COLS = (1000, 8192, 8193, 100_000, 1 << 18, (1 << 18) + 1, 5_000_000, 1 << 23)
+MASK_WINDOW_COLS = (300_001, 700_001, (1 << 23) + 1)  # one window, two windows, every row on the window kernel (17 windows)
+MASK_KEEP_WINDOW = 1 << 19                          # columns per window of the Keep window kernel: two bitmaps share 128 KiB
+MASK_KINDS = ("mixed", "beyond only", "one in range")
+
+
+def mask_levels(cols):
+    """LEVELS of k_wave_masked for `cols` columns (kernels.hpp levels_for_cols); 0: above 2^23, the window kernel only"""
+    return next((lv for lv in (1, 2, 3) if cols <= 256 << (5 * lv)), 0)
+
+
+def mask_cap_of_len(m):
+    """the capacity of the k_wave_masked instance that takes a mask row of m entries (1 .. 2048)"""
+    return MASK_CAPS[int(np.searchsorted(np.array(MASK_CAPS), m, side="left"))]
+
+
+def mask_window(cols):
+    """columns per window of the Keep window kernel (dense_rows.hip launch_dense_impl)"""
+    return min(-(-cols // 64) * 64, MASK_KEEP_WINDOW)
+
+
+def mask_alias_spans(cols):
+    """the distances at which a mask column at or above B.cols would land on a product column in a kernel that truncated
+    or wrapped its index: the reach of the top bitmap, 256 * 32^LEVELS (k_wave_masked), and the window (k_dense_rows)"""
+    L = mask_levels(cols)
+    return ([256 << (5 * L)] if L else []) + [mask_window(cols)]
+
+
+def masked_reference(want, f_rp, f_ci, r0=0, r1=None):
+    """rows [r0, r1) of `want` (the product, (row_ptr, col_idx) with sorted duplicate-free rows) restricted to F's entries,
+    F indexed by absolute row: (row_ptr int64 slice-local, col_idx int32).  F's columns are compared as they are stored, so
+    F may hold any column, repeats and unsorted rows."""
+    rp, ci = np.asarray(want[0], np.int64), np.asarray(want[1])
+    r1 = rp.size - 1 if r1 is None else r1
+    f_rp = np.asarray(f_rp, np.int64)
+    rows = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(rp[r0:r1 + 1]))
+    kc = (rows << 32) | ci[rp[r0]:rp[r1]].astype(np.int64)
+    frow = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(f_rp[r0:r1 + 1]))
+    kf = (frow << 32) | np.asarray(f_ci[f_rp[r0]:f_rp[r1]], np.int64)
+    keep = np.isin(kc, kf)
+    counts = np.bincount((kc[keep] >> 32) - r0, minlength=r1 - r0)
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), ci[rp[r0]:rp[r1]][keep].astype(np.int32)
+
+
+def _beyond_columns(rng, cols, absent, top):
+    """mask columns at or above `cols` (and at most `top`) that must change nothing, the telling ones first: B.cols itself;
+    for every alias span S: S itself, a column of [B.cols, S) and p + k * S (k = 1, 2, 3) for product columns p of the row
+    that are NOT in the mask; the next window edge and a column below it; p + 2^30; `top`"""
+    spans = mask_alias_spans(cols)
+    W = mask_window(cols)
+    edge = -(-cols // W) * W
+    out = [cols]
+    ps = [int(p) for p in absent[:2]]
+    for S in spans:
+        out.append(S)
+        if S > cols:
+            out.append(int(rng.integers(cols, S)))
+        out += [p + k * S for p in ps[:1] for k in (1, 2, 3)]
+    out.append(edge)
+    if edge > cols:
+        out.append(int(rng.integers(cols, edge)))
+    out += [p + k * S for S in spans for p in ps[1:] for k in (1, 2, 3)]
+    out += [p + (1 << 30) for p in ps]
+    out.append(top)
+    return np.array([c for c in out if cols <= c <= top], np.int64)
+
+
+def _mask_row(rng, prod, n_in, noise, length, cols, top):
+    """one mask row: n_in of the row's product columns `prod`, `noise` random columns of [0, cols), the columns of
+    _beyond_columns, some entries twice, and random columns at or above `cols` up to exactly `length` entries (None: no
+    filling); shuffled.  The product columns go first when `length` is short."""
+    pick = rng.permutation(prod)[:n_in]
+    inr = np.concatenate([pick, rng.integers(0, cols, size=noise)]) if noise else pick
+    bey = _beyond_columns(rng, cols, np.setdiff1d(prod, inr), top)
+    if length is None:
+        row = np.concatenate([inr, bey])
+        row = np.concatenate([row, row[rng.integers(0, row.size, size=min(5, row.size))]])
+        return rng.permutation(row)
+    inr = inr[:length]
+    bey = bey[:length - inr.size]
+    row = np.concatenate([inr, bey])
+    nrep = min(length - row.size, 5, length // 8)
+    fill = length - row.size - nrep
+    S = mask_alias_spans(cols)[0]
+    near = fill // 2 if S > cols else 0                  # half of the filling within the top bitmap / the last window
+    parts = [row, row[rng.integers(0, row.size, size=nrep)] if nrep else row[:0],
+             rng.integers(cols, max(S, cols + 1), size=near), rng.integers(cols, top, size=fill - near)]
+    return rng.permutation(np.concatenate(parts))
+
+
+def _case(a_rp, a_ci, b_rp, b_ci, cols, rows, kinds, top):
+    f_rp = np.concatenate([[0], np.cumsum([r.size for r in rows])])
+    f_ci = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    assert f_ci.min() >= 0 and f_ci.max() <= top <= INT_MAX
+    i32 = lambda x: np.ascontiguousarray(x, np.int32)
+    return dict(a_rp=i32(a_rp), a_ci=i32(a_ci), b_rp=i32(b_rp), b_ci=i32(b_ci), ncols=cols, f_rp=i32(f_rp), f_ci=i32(f_ci),
+                kinds=np.array(kinds), top=top, products=row_products(a_rp, a_ci, b_rp, 0, len(rows)))
+
+
+def masked_one_wave_case(cols, top=INT_MAX, nrows=2000):
+    """A (nrows x 500, 6 entries per row, every 97th row empty), B (500 x cols, 1 to 39 entries per row: no row has more
+    than 8192 products) and a mask F whose rows hold columns at and far above B.cols (_beyond_columns) up to `top`.
+    Row i is of capacity MASK_CAPS[i % 7]; within a capacity the rows take the lengths (bottom, top, between) and the
+    kinds MASK_KINDS in turn: mixed = a random half of the row's product columns, three columns of [0, cols) and the columns
+    beyond; beyond only = no column below B.cols (an empty output row); one in range = one product column and else
+    columns beyond.  Returns the operands, f_rp / f_ci, kinds (per row), products (per row), top."""
+    rng = np.random.default_rng(7100 + cols % 9973)
+    a_rp, a_ci = uniform_rect(nrows, 500, 6, seed=1901)
+    ar = np.repeat(np.arange(nrows), np.diff(a_rp))
+    a_rp, a_ci = _csr_from_pairs(ar[ar % 97 != 5], a_ci[ar % 97 != 5], nrows)
+    lens = rng.integers(1, 40, size=500)
+    b_cols = rng.integers(0, cols, size=int(lens.sum()))
+    b_cols[::53], b_cols[7::53] = cols - 1, 0              # the last column and column 0 among the products
+    b_rp, b_ci = _csr_from_pairs(np.repeat(np.arange(500), lens), b_cols, 500)
+    p_rp, p_ci = small_reference(a_rp, a_ci, b_rp, b_ci)
+    rows, kinds = [], []
+    for i in range(nrows):
+        g, j = i % 7, i // 7
+        lo, hi = (MASK_CAPS[g - 1] + 1 if g else 1), MASK_CAPS[g]
+        length = (lo, hi, int(rng.integers(lo, hi + 1)))[j % 3]
+        kind = MASK_KINDS[(j // 3) % 3]
+        prod = p_ci[p_rp[i]:p_rp[i + 1]].astype(np.int64)
+        n_in, noise = {"mixed": ((prod.size + 1) // 2, 3), "beyond only": (0, 0), "one in range": (1, 0)}[kind]
+        rows.append(_mask_row(rng, prod, n_in, noise, length, cols, top))
+        kinds.append(kind)
+    return _case(a_rp, a_ci, b_rp, b_ci, cols, rows, kinds, top)
+
+
+MASK_WINDOW_KINDS = ("half", "short", "beyond only, long", "half, filled long")
+
+
+def masked_window_case(cols, top=INT_MAX, nrows=402):
+    """A (nrows x 300) and B (300 x cols, 100 to 299 entries per row, unsorted with repeats, a fifth of them in the last
+    3000 columns) for the Keep window kernel.  Rows 0 and 1 of A draw every B row (about 60 000 products), the others 1 to
+    60 of them (up to 12 000 products).  Masks, MASK_WINDOW_KINDS in turn from row 2 on: half = a random half of the row's
+    product columns (row 0 too: far more than 2048); short = at most 100 of them (row 1 too: a short mask on a row of more
+    than 8192 products); beyond only, long = 2100 columns at or above B.cols; half, filled long = half of the product
+    columns and columns beyond up to 2049 entries or more.  Every row also holds _beyond_columns, up to `top`."""
+    rng = np.random.default_rng(7300 + cols % 9973)
+    nb = 300
+    lens = rng.integers(100, 300, size=nb)
+    b_rows = np.repeat(np.arange(nb), lens)
+    b_cols = np.where(rng.random(b_rows.size) < 0.2, rng.integers(max(0, cols - 3000), cols, size=b_rows.size),
+                      rng.integers(0, cols, size=b_rows.size))
+    b_cols[::97], b_cols[7::97] = cols - 1, 0              # the last column and column 0 among the products
+    b_rp, b_ci = _csr_from_pairs(b_rows, b_cols, nb, dedup=False, sort=False)
+    a_rows = [np.concatenate([np.arange(nb), rng.integers(0, nb, size=50)]) for _ in range(2)]
+    a_rows += [rng.integers(0, nb, size=int(rng.integers(1, 61))) for _ in range(nrows - 2)]
+    a_rp = np.concatenate([[0], np.cumsum([r.size for r in a_rows])])
+    a_ci = np.concatenate(a_rows)
+    p_rp, p_ci = small_reference(a_rp, a_ci, b_rp, b_ci)
+    rows, kinds = [], []
+    for i in range(nrows):
+        kind = MASK_WINDOW_KINDS[(0, 1)[i] if i < 2 else i % 4]
+        prod = p_ci[p_rp[i]:p_rp[i + 1]].astype(np.int64)
+        half = (prod.size + 1) // 2
+        n_in, noise, length = {"half": (half, 3, None), "short": (min(half, 100), 3, None), "beyond only, long": (0, 0, 2100),
+                               "half, filled long": (half, 3, max(2049, half + 40))}[kind]
+        rows.append(_mask_row(rng, prod, n_in, noise, length, cols, top))
+        kinds.append(kind)
+    return _case(a_rp, a_ci, b_rp, b_ci, cols, rows, kinds, top)

@@ -227,25 +227,49 @@ def test_complement_shape(ctx, name):
         ctx.set_option("small_path", -1)
         ctx.set_flow("auto")
         assert st_mul["rows_per_bin"] == bins, (st_mul["rows_per_bin"], bins)
-        # masked(F) and complemented(F) split the product (F within B's columns: the masked product's domain)
-        f_rp, f_ci = random_mask(rng, R, cols, want, beyond=0)
-        Fm = ctx.upload(f_rp, f_ci, cols)
-        try:
-            comp, _ = _run(ctx, A, B, Fm)
-            kept, _ = _run(ctx, A, B, Fm, complement=False)
-        finally:
-            Fm.free()
-        kk, kc = _keys(*kept), _keys(*comp)
-        if _diff(comp, complement_ref(want, f_rp, f_ci)):
-            failures.append("in-range mask: %s" % _diff(comp, complement_ref(want, f_rp, f_ci)))
-        if np.intersect1d(kk, kc).size:
-            failures.append("masked and complemented product share entries")
-        if not np.array_equal(np.union1d(kk, kc), _keys(*want)):
-            failures.append("masked and complemented product do not make up the product")
+        # masked(F) and complemented(F) split the product: for a mask within B's columns, for one whose extra columns start
+        # where the one-wave masked kernel's top bitmap ends, and (below) for the random mask with columns up to B.cols + 1000
+        top = 256 << (5 * gen.mask_levels(cols)) if gen.mask_levels(cols) else cols
+        f_in = random_mask(rng, R, cols, want, beyond=0)
+        far_rows = rng.integers(0, R, size=3 * R)
+        far_cols = np.concatenate([np.full(R, top), rng.integers(top, min(4 * top, gen.INT_MAX), size=R),
+                                   rng.integers(top, gen.INT_MAX, size=R)])
+        all_rows = np.concatenate([np.repeat(np.arange(R, dtype=np.int64), np.diff(f_in[0])), far_rows])
+        perm = rng.permutation(all_rows.size)
+        f_far = gen._csr_from_pairs(all_rows[perm], np.concatenate([f_in[1].astype(np.int64), far_cols])[perm], R,
+                                    dedup=False, sort=False)      # (the in-range mask's entries and the far columns)
+        wk = _keys(*want)
+
+        def split(sname, f_rp, f_ci, comp, kept):
+            """comp = the product minus F, kept = the product within F, and the two results themselves are disjoint and make up
+            the product (one np.isin for both references, one sort for the identity)"""
+            inside = np.isin(wk, _keys(f_rp, f_ci))
+            for what, got, sel in (("", comp, ~inside), (", masked product", kept, inside)):
+                counts = np.bincount((wk[sel] >> 32).astype(np.int64), minlength=R)
+                bad = _diff(got, (np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), np.asarray(want[1])[sel]))
+                if bad:
+                    failures.append("%s mask%s: %s" % (sname, what, bad))
+            both = np.sort(np.concatenate([_keys(*kept), _keys(*comp)]))
+            if np.any(both[1:] == both[:-1]):
+                failures.append("%s mask: masked and complemented product share entries" % sname)
+            elif not np.array_equal(both, wk):
+                failures.append("%s mask: masked and complemented product do not make up the product" % sname)
+
+        for sname, (f_rp, f_ci), fcols in (("in-range", f_in, cols),
+                                           ("beyond the top bitmap", f_far, gen.INT_MAX)):
+            Fm = ctx.upload(f_rp, f_ci, fcols)
+            try:
+                comp, _ = _run(ctx, A, B, Fm)
+                kept, _ = _run(ctx, A, B, Fm, complement=False)
+            finally:
+                Fm.free()
+            split(sname, f_rp, f_ci, comp, kept)
         for mname, (f_rp, f_ci) in masks.items():
             Fm = ctx.upload(f_rp, f_ci, cols + 1000)
             try:
                 got, st = _run(ctx, A, B, Fm)
+                if mname == "random":                       # (columns up to B.cols + 1000: the split once more)
+                    split(mname, f_rp, f_ci, got, _run(ctx, A, B, Fm, complement=False)[0])
                 exp = complement_ref(want, f_rp, f_ci)
                 if mname == "empty":
                     exp = (want[0].astype(np.int64), want[1])
@@ -331,7 +355,7 @@ def test_complement_knobs_and_ranges(ctx, name):
 def test_complement_errors_and_flags_zero(ctx):
     rp, ci, n = gen.uniform(700, 6, 5301)
     A = ctx.upload(rp, ci, n)
-    # (within B's columns: the masked product and its oracle, which flags columns in an array of n entries, are compared below)
+    # (within B's columns: the masked ORACLE, which flags columns in an array of n entries, is compared below)
     f_rp, f_ci = random_mask(np.random.default_rng(5), n, n, O.spgemm(rp, ci, rp, ci, n), beyond=0)
     Fm = ctx.upload(f_rp, f_ci, n)
     short = ctx.upload(rp[:301], ci[:rp[300]], n)

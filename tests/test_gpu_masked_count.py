@@ -4,9 +4,9 @@ arguments, the values with the reference count -- A1 @ B1 with a 1 per stored en
 pattern(F) within [0, B.cols).  The reference is cross-checked against scipy on the small shapes.
 
 Every shape runs with a random mask (unsorted rows, repeats, columns beyond B's), the same within B's columns, F = A,
-F = pattern(A*B) (each row's counts then sum to its product count) and an empty mask.  Where F lies within B's columns (the
-masked product's domain) the pattern and rows_per_bin must equal the masked product's, so the counting twin of every class
-ran.  Then counts above 16 bits, the int32 refusal, ranges and knobs, graph identities (triangles, support), errors and
+F = pattern(A*B) (each row's counts then sum to its product count) and an empty mask.  For every mask the pattern and
+rows_per_bin must equal the masked product's on the same arguments, so the counting twin of every class ran.  Then counts
+above 16 bits, the int32 refusal, ranges and knobs, graph identities (triangles, support), errors and
 the result object.
 """
 import ctypes as C
@@ -302,17 +302,14 @@ def test_count_shape(ctx, name):
         prod = expand(s["a_rp"], s["a_ci"], s["b_rp"], s["b_ci"])
         for mname, (f_rp, f_ci) in masks.items():
             Fm = ctx.upload(f_rp, f_ci, cols + 1000)
-            # (the masked product itself is compared where F lies within B's columns, its domain)
-            in_range = f_ci.size == 0 or int(f_ci.max()) < cols
             try:
                 got, st = _count(ctx, A, B, Fm)
-                if in_range:
-                    ref, st_m = _masked(ctx, A, B, Fm)
+                ref, st_m = _masked(ctx, A, B, Fm)
             finally:
                 Fm.free()
-            if in_range and _diff(got[:2], ref):
+            if _diff(got[:2], ref):
                 failures.append("mask %s: pattern differs from the masked product: %s" % (mname, _diff(got[:2], ref)))
-            if in_range and (st["rows_per_bin"] != st_m["rows_per_bin"] or st["bin_cap"] != st_m["bin_cap"]):
+            if st["rows_per_bin"] != st_m["rows_per_bin"] or st["bin_cap"] != st_m["bin_cap"]:
                 failures.append("mask %s: classes %s, masked product %s" % (mname, st["rows_per_bin"], st_m["rows_per_bin"]))
             path = {k: st[k] for k in ("flow", "small_path", "products", "nnz_c")}
             if path != dict(flow=1, small_path=0, products=int(prefix[-1]), nnz_c=int(got[1].size)):
@@ -391,12 +388,16 @@ def test_one_wave_mask_columns_beyond_the_top_bitmap(ctx, cols):
     Fm = ctx.upload(f_rp, f_ci, (1 << 30) + 1)
     try:
         got, st = _count(ctx, A, B, Fm)
+        kept, st_m = _masked(ctx, A, B, Fm)
     finally:
         for h in (A, B, Fm):
             h.free()
     assert sum(st["rows_per_bin"][1:17]) > 0 and not any(st["rows_per_bin"][17:]), st["rows_per_bin"]
     bad = _diff(got, count_ref(a_rp, a_ci, b_rp, b_ci, f_rp, f_ci, cols, prod=(uk, cnt)))
     assert bad is None, bad
+    # the masked product on the same arguments: the same pattern from the same classes
+    assert _diff(kept, got[:2]) is None, "masked product: %s" % _diff(kept, got[:2])
+    assert st_m["rows_per_bin"] == st["rows_per_bin"] and st_m["bin_cap"] == st["bin_cap"]
 
 
 # ---------------------------------------------------------------- counts above 16 bits, the int32 refusal -----------
