@@ -58,6 +58,7 @@ EXPORTS = [
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
+    "bspgemm_strongly_connected_components",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
 
@@ -207,6 +208,7 @@ def lib():
     L.bspgemm_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_core_numbers.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_kcore.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
+    L.bspgemm_strongly_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -538,6 +540,16 @@ class Context:
         m, top = C.c_void_p(), C.c_int()
         _chk(lib().bspgemm_kcore(self._h, A._h, int(k), C.byref(m), C.byref(top)), "bspgemm_kcore")
         return Matrix(self, m, keep=None), top.value
+
+    def strongly_connected_components(self, A):
+        """bspgemm_strongly_connected_components: (P as a Matrix, ncomponents, rounds, sweeps) -- the strongly connected
+        components of the directed graph whose row u lists u's out-neighbours; P.download()[1] is the label array,
+        label(v) = the smallest vertex id of v's component; device-resident trimming and min-colour propagation, no product
+        and no transpose; rounds = colouring rounds, sweeps = entry-parallel launches"""
+        m, nc, rounds, sweeps = C.c_void_p(), C.c_int(), C.c_int(), C.c_int()
+        _chk(lib().bspgemm_strongly_connected_components(self._h, A._h, C.byref(m), C.byref(nc), C.byref(rounds),
+                                                         C.byref(sweeps)), "bspgemm_strongly_connected_components")
+        return Matrix(self, m, keep=None), nc.value, rounds.value, sweeps.value
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

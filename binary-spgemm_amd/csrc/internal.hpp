@@ -143,6 +143,7 @@ struct bspgemm_context {
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
     bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
+    bool scc_timing = false;            // BSPGEMM_SCC_TIMING: trim / forward / backward launch counts and times of the strong components on stderr
 };
 
 extern "C" int bspgemm_par_max_plus_one(const int *idx, long long n);              // host/par_copy.c

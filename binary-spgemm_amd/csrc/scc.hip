@@ -1,0 +1,400 @@
+// scc.hip -- strongly connected components with min-vertex labels, everything device-resident:
+// bspgemm_strongly_connected_components (include/bspgemm.h).  No product and no transpose: trimming plus min-colour
+// propagation (Orzan's colouring, the "Multistep" family) on A alone, row u = the out-neighbours of u.  State:
+//     label[n]    -1 = unassigned ("alive"); the col_idx of the assignment operand P that the call returns, so nothing is
+//                 copied at the end
+//     color[n], has_out[n], has_in[n] and a block of eight counters                                          (workspace)
+// Self-loops (u == v) are skipped everywhere.  Three entry-parallel sweeps in select's geometry (sel_rows.hpp, as k_cc_hook:
+// a workgroup owns kSelTile consecutive entries of A whatever rows they belong to, a lane four of them per step by one
+// 16-byte non-temporal load, the tile's window of A.row_ptr staged in LDS -- a hub row costs what its entries cost) and three
+// vertex-parallel passes:
+//     trim     repeat until a pass removes nothing:
+//                k_scc_mark   per entry (u, v) with both ends alive: has_out[u] = 1, has_in[v] = 1 (plain stores of the
+//                             same value, no atomics).  label[] is only read in this launch, so the marks are those of the
+//                             launch boundary and the sequence of trim passes is deterministic.
+//                k_scc_trim   per vertex: an alive v that lacks either mark is an SCC by itself, label[v] = v; counts the
+//                             removals and the vertices that stay alive, clears the marks and leaves color[v] = v for the
+//                             vertices that stay alive and -1 for everybody else -- the start of a colouring round.
+//     a colouring round on what is left:
+//       forward  repeat until a repetition changes nothing:
+//                k_scc_forward  per entry (u, v) with color[u] >= 0 and color[u] < color[v]: atomicMin(&color[v], color[u])
+//                               at device scope (-1 marks a vertex that is not alive: it neither gives nor takes a colour)
+//                k_scc_jump     per vertex: kSccJumps times color[v] = color[color[v]], stored when it moved
+//       k_scc_roots  the alive v with color[v] == v: label[v] = v
+//       backward repeat until a sweep stores nothing:
+//                k_scc_backward per entry (u, v) with color[u] == color[v] >= 0, label[v] >= 0 and label[u] < 0:
+//                               label[u] = color[u] (a plain store, every racer writes the same value)
+//     every vertex labelled in the round drops out; trim again, then the next round.
+//
+// Why the labels are the minima.  color[v] = c always means "c is alive and reaches v" (c == v at the start; an entry
+// (u, v) hands v a colour that reaches u; the jump hands v a colour that reaches color[v]), and color[v] <= v.  At the forward
+// fixpoint color[u] >= color[v] over every entry between alive vertices, so color[v] is the SMALLEST alive vertex that
+// reaches v: the smallest such a has color[a] == a (a colour below a would reach a and so v) and hands a down the path to v.
+// A root r (color[r] == r) has no smaller ancestor, so it is the minimum of its SCC, and SCC(r) is exactly the vertices of
+// colour r that reach r -- what the backward sweeps collect: they walk entries against their direction from r and never
+// leave colour r, and every vertex of SCC(r) has colour r and a path to r inside it.  A labelled v with color[v] >= 0 was
+// labelled in this round, with color[v]; the dead vertices of earlier rounds have color -1.  The smallest alive vertex is
+// always a root, so a round removes at least one whole SCC; removing whole SCCs leaves the others intact, so starting the
+// colours again on the remainder is correct.  A trimmed vertex has no alive in- or no alive out-neighbour apart from itself,
+// so it lies on no cycle through alive vertices: an SCC by itself.  Every step's outcome is a unique fixpoint: the labels,
+// the number of rounds and the number of trim passes are the same on every run.
+//
+// Visibility.  The per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs' stores, so a plain load of
+// color[] or label[] inside a launch that changes them may return an older value.  color[] only ever falls inside a round
+// and label[] only goes from -1 to its final value: a stale colour is an earlier ancestor of the same vertex, a stale label
+// is "not yet"; either costs sweeps and nothing else.  Every "converged" decision rests on a repetition that stored nothing:
+// an atomicMin that lowers nothing, a jump that moves nothing and a backward sweep without a store leave memory as it was,
+// so every load of that repetition returned the values of the kernel boundary before it, the true ones.  The marks are read
+// by the next launch only.  No kernel waits for another workgroup: every loop is bounded by the thread's own entries or by
+// kSccJumps.
+//
+// Cost.  Every sweep is one launch that reads all of A, and every repetition ends in one synchronisation with a read-back of
+// 32 bytes.  A directed path of n vertices takes about n / 2 trim passes, a cycle of n vertices n backward sweeps (its
+// forward sweeps are cut to about log n by the jump), a descending chain of k small SCCs k rounds.  The
+// host caps every inner loop at n + 2 repetitions and the rounds at n and never spins.
+#include "internal.hpp"
+#include "sel_rows.hpp"
+
+namespace bsp {
+
+constexpr int kSccJumps = 1;            // pointer-jumping steps per vertex and forward repetition; 0: no jump launch
+constexpr int kSccThreads = 256;
+
+struct SccFlags {
+    // zeroed in front of every repetition (the first 16 bytes of the workspace)
+    unsigned changed;       // a forward sweep lowered a colour, a jump moved one, a backward sweep stored a label
+    unsigned bad;           // a column outside [0, n)
+    int removed;            // vertices that this trim pass labelled
+    int alive;              // vertices that this trim pass left unassigned
+    // zeroed once
+    int components;         // vertices with label[v] == v so far: the trimmed ones and the roots
+    int pad[3];
+};
+constexpr size_t kSccFlagInts = sizeof(SccFlags) / sizeof(int);
+
+// P.row_ptr = 0 .. n, label = fill (-1, or v itself for a graph without entries: every vertex is an SCC), no marks
+__global__ __launch_bounds__(kSccThreads) void k_scc_init(int n, int *__restrict__ row_ptr, int *__restrict__ label, bool alive,
+                                                         int *__restrict__ has_out, int *__restrict__ has_in,
+                                                         SccFlags *__restrict__ flags)
+{
+    const long long r = (long long)blockIdx.x * kSccThreads + threadIdx.x;
+    if (r <= n) row_ptr[r] = (int)r;
+    if (r < n) {
+        label[r] = alive ? -1 : (int)r;
+        if (alive) has_out[r] = has_in[r] = 0;
+    }
+    if (alive && r == 0) *flags = SccFlags{};
+}
+
+// The walk that the three sweeps share: op.row(u) when the lane enters row u, op.edge(u, v) for every stored entry (u, v)
+// with v in [0, n) and v != u.  A column outside [0, n) is tested BEFORE it reaches op, sets the `bad` word and is skipped.
+// op.changed ends up in the `changed` word.  Called by every thread of the workgroup.
+template <typename Op>
+__device__ __forceinline__ void scc_sweep(const int *__restrict__ row_ptr, const int *__restrict__ col, int n, long long E,
+                                          bool vec, const int *__restrict__ tile_row, SccFlags *__restrict__ flags, Op &op)
+{
+    __shared__ int srp[kSelStage + 1];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const SelTileRows tr = sel_stage_tile_rows(row_ptr, n, E, tile_row, srp);
+    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
+    v4i c4[kSelSteps];
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) c4[j] = load4<true>(col, w0 + j * kSelGroup + 4 * lane, E, vec);
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e0 = w0 + j * kSelGroup + 4 * lane;
+        if (e0 >= E) continue;
+        const int c[4] = {c4[j].x, c4[j].y, c4[j].z, c4[j].w};
+        int u = tr.find(tr.rb, (int)e0);                                 // one search per lane and step, then a walk
+        int end = tr.row_end(u);
+        op.row(u);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const long long p = e0 + k;
+            if (p >= E) break;
+            if (p >= end) {
+                u = tr.find(u + 1, (int)p);
+                end = tr.row_end(u);
+                op.row(u);
+            }
+            const int v = c[k];
+            if ((unsigned)v >= (unsigned)n) {                            // before v indexes anything
+                bad = true;
+                continue;
+            }
+            if (v != u) op.edge(u, v);
+        }
+    }
+    const u64 any_changed = __ballot(op.changed), any_bad = __ballot(bad);
+    if (lane == 0) {                                                     // one lane per wave
+        if (any_changed) flags->changed = 1u;
+        if (any_bad) flags->bad = 1u;
+    }
+}
+
+// label[] is only read here: the marks are those of the launch boundary
+struct SccMark {
+    const int *__restrict__ label;
+    int *__restrict__ has_out, *__restrict__ has_in;
+    bool changed, alive_u;
+    __device__ __forceinline__ void row(int u) { alive_u = label[u] < 0; }
+    __device__ __forceinline__ void edge(int u, int v)
+    {
+        if (alive_u && label[v] < 0) {
+            has_out[u] = 1;
+            has_in[v] = 1;
+        }
+    }
+};
+
+// color is read by plain loads and lowered by atomics in the same launch: neither const nor __restrict__
+struct SccForward {
+    int *color;
+    bool changed;
+    int cu;
+    __device__ __forceinline__ void row(int u) { cu = color[u]; }
+    __device__ __forceinline__ void edge(int, int v)
+    {
+        if (cu >= 0 && color[v] > cu && atomicMin(&color[v], cu) > cu) changed = true;   // (-1 > cu never holds)
+    }
+};
+
+// label is read by plain loads and stored in the same launch: neither const nor __restrict__
+struct SccBackward {
+    const int *__restrict__ color;
+    int *label;
+    bool changed, open;
+    int cu;
+    __device__ __forceinline__ void row(int u)
+    {
+        open = label[u] < 0;                                             // alive, so color[u] >= 0
+        cu = color[u];
+    }
+    __device__ __forceinline__ void edge(int u, int v)
+    {
+        if (open && color[v] == cu && label[v] >= 0) {
+            label[u] = cu;
+            open = false;
+            changed = true;
+        }
+    }
+};
+
+__global__ __launch_bounds__(kSelThreads) void k_scc_mark(const int *__restrict__ row_ptr, const int *__restrict__ col, int n,
+                                                         long long E, bool vec, const int *__restrict__ tile_row,
+                                                         const int *__restrict__ label, int *__restrict__ has_out,
+                                                         int *__restrict__ has_in, SccFlags *__restrict__ flags)
+{
+    SccMark op = {label, has_out, has_in, false, false};
+    scc_sweep(row_ptr, col, n, E, vec, tile_row, flags, op);
+}
+
+__global__ __launch_bounds__(kSelThreads) void k_scc_forward(const int *__restrict__ row_ptr, const int *__restrict__ col, int n,
+                                                            long long E, bool vec, const int *__restrict__ tile_row, int *color,
+                                                            SccFlags *__restrict__ flags)
+{
+    SccForward op = {color, false, -1};
+    scc_sweep(row_ptr, col, n, E, vec, tile_row, flags, op);
+}
+
+__global__ __launch_bounds__(kSelThreads) void k_scc_backward(const int *__restrict__ row_ptr, const int *__restrict__ col, int n,
+                                                             long long E, bool vec, const int *__restrict__ tile_row,
+                                                             const int *__restrict__ color, int *label,
+                                                             SccFlags *__restrict__ flags)
+{
+    SccBackward op = {color, label, false, false, -1};
+    scc_sweep(row_ptr, col, n, E, vec, tile_row, flags, op);
+}
+
+// the workgroup's count of `x` added to *word (and *also, unless NULL) by one atomic each; called by every thread
+__device__ __forceinline__ void scc_block_add(bool x, int *word, int *also, int *wsum)
+{
+    const u64 m = __ballot(x);
+    if (lane_id() == 0) wsum[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+#pragma unroll
+        for (int q = 0; q < kSccThreads / 64; q++) s += wsum[q];
+        if (s) atomicAdd(word, s);
+        if (s && also) atomicAdd(also, s);
+    }
+    __syncthreads();                                                     // (wsum is free again)
+}
+
+// Only thread v touches label[v], color[v] and the marks of v here.
+__global__ __launch_bounds__(kSccThreads) void k_scc_trim(int n, int *__restrict__ label, int *__restrict__ color,
+                                                         int *__restrict__ has_out, int *__restrict__ has_in, SccFlags *flags)
+{
+    __shared__ int wsum[kSccThreads / 64];
+    const long long v = (long long)blockIdx.x * kSccThreads + threadIdx.x;
+    bool removed = false, stays = false;
+    if (v < n) {
+        if (label[v] < 0) {
+            removed = !(has_out[v] && has_in[v]);
+            stays = !removed;
+            if (removed) label[v] = (int)v;
+        }
+        color[v] = stays ? (int)v : -1;
+        has_out[v] = has_in[v] = 0;
+    }
+    scc_block_add(removed, &flags->removed, &flags->components, wsum);
+    scc_block_add(stays, &flags->alive, nullptr, wsum);
+}
+
+// Only thread v stores color[v] here, and what it stores is an ancestor of v not above the old value: a racing reader sees
+// the old or the new one.  A colour is the id of a vertex that was alive when the round began, so color[c] >= 0.
+__global__ __launch_bounds__(kSccThreads) void k_scc_jump(int n, int *color, SccFlags *__restrict__ flags)
+{
+    const long long v = (long long)blockIdx.x * kSccThreads + threadIdx.x;
+    bool moved = false;
+    if (v < n) {
+        const int c0 = color[v];
+        if (c0 >= 0) {
+            int c = c0;
+#pragma unroll
+            for (int k = 0; k < kSccJumps; k++) c = color[c];
+            if (c != c0) {
+                color[v] = c;
+                moved = true;
+            }
+        }
+    }
+    if (__ballot(moved) && lane_id() == 0) flags->changed = 1u;
+}
+
+__global__ __launch_bounds__(kSccThreads) void k_scc_roots(int n, const int *__restrict__ color, int *__restrict__ label,
+                                                          SccFlags *flags)
+{
+    __shared__ int wsum[kSccThreads / 64];
+    const long long v = (long long)blockIdx.x * kSccThreads + threadIdx.x;
+    const bool root = v < n && color[v] == (int)v;                       // (color >= 0: alive when the round began)
+    if (root) label[v] = (int)v;
+    scc_block_add(root, &flags->components, nullptr, wsum);
+}
+
+}  // namespace bsp
+
+using namespace bsp;
+
+extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_matrix **P,
+                                                                int *ncomponents, int *rounds, int *sweeps)
+{
+    static const char who[] = "bspgemm_strongly_connected_components";
+    if (P) *P = nullptr;
+    if (ncomponents) *ncomponents = 0;
+    if (rounds) *rounds = 0;
+    if (sweeps) *sweeps = 0;
+    if (!ctx || !A || !P) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_strongly_connected_components: NULL argument");
+    if (bspgemm_status st = check_operand(ctx, A, who, NEED_SQUARE | NEED_ENTRIES_CONSISTENT)) return st;
+    if (A->nnz > INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_strongly_connected_components: more than INT_MAX nonzeros");
+    if (bspgemm_status st = use_device(ctx)) return st;
+    hipStream_t s = ctx->stream;
+    const int n = A->rows;
+    const long long E = A->nnz;
+    const bool edges = E > 0;
+    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
+    if (edges) {                                            // (before anything is launched: growing them synchronises)
+        if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return st;
+        if (bspgemm_status st = ensure_tmp(ctx, kSccFlagInts + 3 * n4)) return st;
+    }
+    // BSPGEMM_SCC_TIMING: host clocks around the repetitions, each of which ends synchronised anyway
+    const bool timed = ctx->scc_timing;
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    const clk::time_point t_call = clk::now();
+    double ms_trim = 0, ms_fwd = 0, ms_bwd = 0;
+    // the assignment operand, laid out like an uploaded one; its col_idx is the label array while the rounds run
+    bspgemm_matrix *m = nullptr;
+    auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
+    auto stuck = [&]() { return bail(FAIL(BSPGEMM_ERR_HIP, "bspgemm_strongly_connected_components: did not converge")); };
+    if (bspgemm_status st = operand_new(ctx, n, n, &m)) return bail(st);
+    if (bspgemm_status st = operand_cols(m, n)) return bail(st);
+    int *label = m->d_col_idx;
+    SccFlags *d_flags = nullptr;
+    int *color = nullptr, *has_out = nullptr, *has_in = nullptr;
+    if (edges) {
+        d_flags = reinterpret_cast<SccFlags *>(ctx->tmp);
+        color = ctx->tmp + kSccFlagInts;
+        has_out = color + n4;
+        has_in = color + 2 * n4;
+    }
+    const dim3 vgrid((unsigned)(((long long)n + 1 + kSccThreads - 1) / kSccThreads)), vblock(kSccThreads);
+    hipLaunchKernelGGL(k_scc_init, vgrid, vblock, 0, s, n, m->d_row_ptr, label, edges, has_out, has_in, d_flags);
+    HIPCHK_B(hipGetLastError());
+    SccFlags h = {};
+    h.components = n;                                       // without entries every vertex is an SCC
+    int r = 0;
+    long long trims = 0, fwd = 0, bwd = 0;
+    if (edges) {
+        launch_select_tile_rows(A->d_row_ptr, n, ctx->tile_row, s);
+        const dim3 egrid(select_tiles(E)), eblock(kSelThreads);
+        const bool vec = aligned16(A->d_col_idx);
+        const long long cap = (long long)n + 2;             // defensive: every repetition but the last changes a vertex
+        // the read-back that ends a repetition: its one synchronisation
+        auto fetch = [&]() -> hipError_t {
+            if (hipError_t e = hipGetLastError()) return e;
+            if (hipError_t e = hipMemcpyAsync(&h, d_flags, sizeof h, hipMemcpyDeviceToHost, s)) return e;
+            return hipStreamSynchronize(s);
+        };
+        auto reset = [&]() { return hipMemsetAsync(d_flags, 0, 4 * sizeof(int), s); };
+        for (;;) {
+            // trim to the fixpoint; the last pass leaves color[] ready for the round
+            clk::time_point t = clk::now();
+            for (long long it = 0;; it++) {
+                if (it >= cap) return stuck();
+                trims++;
+                HIPCHK_B(reset());
+                hipLaunchKernelGGL(k_scc_mark, egrid, eblock, 0, s, A->d_row_ptr, A->d_col_idx, n, E, vec, ctx->tile_row, label,
+                                   has_out, has_in, d_flags);
+                hipLaunchKernelGGL(k_scc_trim, vgrid, vblock, 0, s, n, label, color, has_out, has_in, d_flags);
+                HIPCHK_B(fetch());
+                if (h.bad) {
+                    snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) (A.cols)", who, n);
+                    return bail(BSPGEMM_ERR_INVALID);
+                }
+                if (h.removed == 0 || h.alive == 0) break;
+            }
+            if (timed) ms_trim += ms_since(t);
+            if (h.alive == 0) break;
+            if (r >= n) return stuck();                     // (a round labels at least one vertex)
+            r++;
+            t = clk::now();
+            for (long long it = 0;; it++) {
+                if (it >= cap) return stuck();
+                fwd++;
+                HIPCHK_B(reset());
+                hipLaunchKernelGGL(k_scc_forward, egrid, eblock, 0, s, A->d_row_ptr, A->d_col_idx, n, E, vec, ctx->tile_row, color,
+                                   d_flags);
+                if (kSccJumps > 0) hipLaunchKernelGGL(k_scc_jump, vgrid, vblock, 0, s, n, color, d_flags);
+                HIPCHK_B(fetch());
+                if (!h.changed) break;
+            }
+            if (timed) ms_fwd += ms_since(t);
+            t = clk::now();
+            hipLaunchKernelGGL(k_scc_roots, vgrid, vblock, 0, s, n, color, label, d_flags);
+            for (long long it = 0;; it++) {
+                if (it >= cap) return stuck();
+                bwd++;
+                HIPCHK_B(reset());
+                hipLaunchKernelGGL(k_scc_backward, egrid, eblock, 0, s, A->d_row_ptr, A->d_col_idx, n, E, vec, ctx->tile_row, color,
+                                   label, d_flags);
+                HIPCHK_B(fetch());
+                if (!h.changed) break;
+            }
+            if (timed) ms_bwd += ms_since(t);
+        }
+    }
+    if (bspgemm_status st = operand_finish(m, n)) return bail(st);   // one label per vertex
+    HIPCHK_B(hipStreamSynchronize(s));
+    if (timed)
+        fprintf(stderr, "[bspgemm] %s: n %d nnz %lld components %d rounds %d | total %.3f ms = %lld trim passes %.3f + %lld forward "
+                        "sweeps %.3f + %lld backward sweeps %.3f + rest\n",
+                who, n, E, h.components, r, ms_since(t_call), trims, ms_trim, fwd, ms_fwd, bwd, ms_bwd);
+    if (ncomponents) *ncomponents = h.components;
+    if (rounds) *rounds = r;
+    if (sweeps) *sweeps = (int)(trims + fwd + bwd > INT_MAX ? INT_MAX : trims + fwd + bwd);
+    *P = m;
+    return BSPGEMM_OK;
+}

@@ -1,0 +1,77 @@
+/*
+ * spgemm_hip_scc.c -- strongly connected components of a directed graph, everything resident on the GPU
+ * (include/bspgemm.h: bspgemm_strongly_connected_components), beside the connected-components and k-core drivers.
+ *
+ *     SpGEMM_hip_scc  file.mtx  [--labels out.txt]
+ *
+ * The transpose that the loader hands back (readCOO, final/utils.c:47-81) is used as it is: a graph and its transpose
+ * have the same strongly connected components.
+ * Prints one line  n,nnz,components,largest,rounds,sweeps,ms  -- the number of components, the size of the largest one
+ * (counted on the host from the downloaded labels), the colouring rounds and the entry-parallel launches the call took
+ * and its wall time, the operand already on the device.
+ * --labels writes one label per line, line v the smallest vertex id (0-based) of v's component.
+ */
+#include "../../include/bspgemm.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#define CHECK(st, what)                                                                         \
+    do {                                                                                        \
+        bspgemm_status s_ = (st);                                                               \
+        if (s_ != BSPGEMM_OK) {                                                                 \
+            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
+            exit(1);                                                                            \
+        }                                                                                       \
+    } while (0)
+
+int main(int argc, char **argv)
+{
+    const char *labels_path = NULL;
+    if (argc == 4 && strcmp(argv[2], "--labels") == 0) labels_path = argv[3];
+    if (argc != 2 && !labels_path) {
+        printf("usage: SpGEMM_hip_scc  path-to-matrix  [--labels out.txt]\n");
+        exit(1);
+    }
+    uint32_t *Arow, *Acol, M, N, nnz;
+    bspgemm_status st = bspgemm_readCOO(argv[1], &Arow, &Acol, &M, &N, &nnz);
+    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
+    if (st != BSPGEMM_OK) exit(1);
+    if (M != N) { fprintf(stderr, "scc needs a square matrix (%ux%u)\n", M, N); exit(1); }
+    const char *devenv = getenv("BSPGEMM_DEVICE");
+    bspgemm_context *ctx;
+    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    bspgemm_matrix *A, *P;
+    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
+    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    int components = 0, rounds = 0, sweeps = 0;
+    CHECK(bspgemm_strongly_connected_components(ctx, A, &P, &components, &rounds, &sweeps),
+          "bspgemm_strongly_connected_components");
+    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    int *label = malloc(((size_t)M + 1) * sizeof(int));
+    int *size = calloc((size_t)M + 1, sizeof(int));
+    if (!label || !size) exit(1);
+    CHECK(bspgemm_matrix_download(ctx, P, NULL, label), "download");
+    int largest = 0;
+    for (uint32_t v = 0; v < M; v++)
+        if (++size[label[v]] > largest) largest = size[label[v]];
+    if (labels_path) {
+        FILE *f = fopen(labels_path, "w");
+        if (!f) { fprintf(stderr, "cannot write %s\n", labels_path); exit(1); }
+        for (uint32_t v = 0; v < M; v++) fprintf(f, "%d\n", label[v]);
+        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", labels_path); exit(1); }
+    }
+    printf("%u,%u,%d,%d,%d,%d,%.3f\n", M, nnz, components, largest, rounds, sweeps, ms);
+    free(label); free(size);
+    bspgemm_matrix_free(P);
+    bspgemm_matrix_free(A);
+    bspgemm_destroy(ctx);
+    free(Arow); free(Acol);
+    return 0;
+}

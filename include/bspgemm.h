@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -501,6 +501,43 @@ bspgemm_status bspgemm_core_numbers(bspgemm_context *ctx, const bspgemm_matrix *
  *   - BSPGEMM_ERR_INVALID with *T = NULL: k < 0, a NULL ctx, A or T, a non-square A, A from another context; otherwise the
  *     errors of bspgemm_core_numbers and of the calls above.                                                            */
 bspgemm_status bspgemm_kcore(bspgemm_context *ctx, const bspgemm_matrix *A, int k, bspgemm_matrix **T, int *degeneracy);
+
+/* Strongly connected components with min-vertex labels, everything device-resident, without a product and without a
+ * transpose.  A is square and row u lists the OUT-neighbours of u; two vertices share a component when each reaches the
+ * other.  SCCs are invariant under transposition, so the in-edges that bspgemm_readCOO hands back give the same labels as
+ * the file's orientation and no bspgemm_matrix_transpose is needed.  A's rows may be unsorted and hold repeats and
+ * self-loops (a self-loop is ignored: a vertex is always in its own component); any n, n == 0 and nnz == 0 included.
+ *   - *P is the n x n assignment operand, exactly as bspgemm_connected_components returns it: P.row_ptr = 0, 1, ..., n and
+ *     P.col_idx[v] = label(v) = the smallest vertex id of v's strongly connected component.  bspgemm_matrix_transpose(P)
+ *     holds the ascending member list of component c in row c; P^T * A * P by two multiplies is the condensation, a DAG
+ *     apart from its diagonal.  It is an owned operand laid out like an uploaded one (bspgemm_matrix_free), usable in
+ *     every product, transpose and select, complete on the context's stream when the call returns.
+ *   - The labels are bit for bit the same on every run, independent of scheduling.  *ncomponents = the number of v with
+ *     label(v) == v, counted on the device.  *rounds = colouring rounds (below): deterministic, 0 when trimming alone
+ *     assigns every vertex (a DAG, nnz == 0, n == 0).  *sweeps = entry-parallel launches in total: it depends on scheduling
+ *     and is only bounded (by the caps below); at least 1 when nnz > 0.  ncomponents, rounds and sweeps may be NULL.
+ *   - The scheme is trimming plus min-colour propagation (Orzan's colouring, the "Multistep" family), on label[] (P.col_idx
+ *     itself, -1 = unassigned) and, in the context's workspace, color[n], two mark arrays of n ints and eight counters.
+ *     Trim: an entry-parallel sweep marks has_out[u] and has_in[v] for every entry (u, v), u != v, whose ends are both
+ *     unassigned (plain stores); a vertex pass gives every unassigned v that lacks a mark label(v) = v; repeated until a
+ *     pass removes nothing.  A colouring round on the rest: color[v] = v; forward sweeps lower color[v] to color[u] over
+ *     every entry (u, v) by a device-scope atomicMin, each followed by one pointer jump color[v] = color[color[v]], until
+ *     nothing changes -- color[v] is then the smallest vertex that reaches v; the vertices with color[v] == v are the
+ *     minima of their components and get label(v) = v; backward sweeps give u the label color[u] over every entry (u, v)
+ *     with color[u] == color[v] and v labelled, until a sweep stores nothing.  Trim again, next round.  No kernel waits
+ *     for another workgroup's store, and the result does not depend on when such stores become visible (csrc/scc.hip).
+ *   - Cost: every sweep is one launch that reads all of A (4 * nnz bytes, the tile's window of row_ptr and the gathers of
+ *     the per-vertex arrays) and every repetition ends in one synchronisation with 32 bytes read back.  A directed path of
+ *     n vertices takes about n / 2 trim passes, a directed cycle of n vertices n backward sweeps, a chain of k small
+ *     components whose ids descend along the edges k rounds.  Defensive caps of n + 2 repetitions of every inner loop and
+ *     n rounds (BSPGEMM_ERR_HIP, "did not converge").
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *P = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A or P, a
+ *     non-square A, A from another context, a column outside [0, n) anywhere in A (every column is tested on the device
+ *     before it is used as an index; the context stays usable).  BSPGEMM_ERR_OVERFLOW: more than INT_MAX entries.
+ *     BSPGEMM_ERR_ALLOC: an allocation failed.  Nothing is leaked on any failure path.                                    */
+bspgemm_status bspgemm_strongly_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A,
+                                                     bspgemm_matrix **P, int *ncomponents, int *rounds, int *sweeps);
 
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
