@@ -27,9 +27,38 @@
 
 namespace bsp {
 
-// VALS: the entries' values come from valsX (the V side), else every entry gets `level` (the N side).  X's columns and
-// values are read once (non-temporal); Y's columns are probed by many lanes and stay temporal.  The destinations
-// p + lb < E + nnz(Y) for consistent row_ptrs: lb <= rpY[rows] = nnz(Y).
+// One side of the merge as an op of sel_walk_entries (sel_rows.hpp).  VALS: the entries' values come from valsX (the V
+// side), else every entry gets `level` (the N side).  X's columns and values are read once (non-temporal); Y's columns are
+// probed by many lanes and stay temporal.  The destinations p + lb < E + nnz(Y) for consistent row_ptrs: lb <= rpY[rows] =
+// nnz(Y).
+template <bool VALS, bool CHECK>
+struct MergeDisjoint {
+    const int *__restrict__ valsX, *__restrict__ rpY, *__restrict__ colY;
+    int *__restrict__ out_col, *__restrict__ out_val;
+    int level;
+    long long E;
+    bool vecv, common;
+    int from, yend;                                                      // what is left of Y's row: X ascends, so does lb
+    v4i x[kSelSteps];
+    __device__ __forceinline__ void load(int j, long long e)
+    {
+        if (VALS) x[j] = load4<true>(valsX, e, E, vecv);
+    }
+    __device__ __forceinline__ void row(int r)
+    {
+        from = rpY[r];
+        yend = rpY[r + 1];
+    }
+    __device__ __forceinline__ void entry(int, long long p, int c, int s)
+    {
+        from = sel_lower_bound(colY, from, yend, c);                     // (an empty row of Y: nothing is read)
+        if (CHECK && from < yend && colY[from] == c) common = true;
+        const long long dst = p + from;
+        out_col[dst] = c;
+        out_val[dst] = VALS ? x[s >> 2][s & 3] : level;
+    }
+};
+
 template <bool VALS, bool CHECK>
 __global__ __launch_bounds__(kSelThreads) void k_merge_disjoint(const int *__restrict__ rpX, const int *__restrict__ colX,
                                                                const int *__restrict__ valsX, int level, int rows, long long E,
@@ -38,45 +67,9 @@ __global__ __launch_bounds__(kSelThreads) void k_merge_disjoint(const int *__res
                                                                int *__restrict__ out_col, int *__restrict__ out_val,
                                                                unsigned *__restrict__ hit)
 {
-    __shared__ int srp[kSelStage + 1];
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    const SelTileRows tr = sel_stage_tile_rows(rpX, rows, E, tile_row, srp);
-    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
-    v4i v[kSelSteps], x[kSelSteps];
-#pragma unroll
-    for (int j = 0; j < kSelSteps; j++) {
-        const long long e = w0 + j * kSelGroup + 4 * lane;
-        v[j] = load4<true>(colX, e, E, vec);
-        if (VALS) x[j] = load4<true>(valsX, e, E, vecv);
-    }
-    bool common = false;
-#pragma unroll
-    for (int j = 0; j < kSelSteps; j++) {
-        const long long e0 = w0 + j * kSelGroup + 4 * lane;
-        if (e0 >= E) continue;
-        const int c[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-        const int val[4] = {VALS ? x[j].x : level, VALS ? x[j].y : level, VALS ? x[j].z : level, VALS ? x[j].w : level};
-        int r = tr.find(tr.rb, (int)e0);                                 // one search per lane and step, then a walk
-        int end = tr.row_end(r);
-        int from = rpY[r], yend = rpY[r + 1];                            // what is left of Y's row: X ascends, so does lb
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const long long p = e0 + k;
-            if (p >= E) break;
-            if (p >= end) {
-                r = tr.find(r + 1, (int)p);
-                end = tr.row_end(r);
-                from = rpY[r];
-                yend = rpY[r + 1];
-            }
-            from = sel_lower_bound(colY, from, yend, c[k]);            // (an empty row of Y: nothing is read)
-            if (CHECK && from < yend && colY[from] == c[k]) common = true;
-            const long long dst = p + from;
-            out_col[dst] = c[k];
-            out_val[dst] = val[k];
-        }
-    }
-    if (CHECK && common) atomicOr(hit, 1u);
+    MergeDisjoint<VALS, CHECK> op = {valsX, rpY, colY, out_col, out_val, level, E, vecv, false, 0, 0, {}};
+    sel_walk_entries<true>(rpX, colX, rows, E, vec, tile_row, op);
+    if (CHECK && op.common) atomicOr(hit, 1u);
 }
 
 __global__ __launch_bounds__(256) void k_merge_row_ptr(const int *__restrict__ rpV, const int *__restrict__ rpN, int rows,

@@ -31,9 +31,7 @@ namespace bsp {
 constexpr int kCcJumps = 2;             // pointer-jumping steps per vertex and round (measured: DESIGN.md 4.13)
 constexpr int kCcThreads = 256;
 
-struct CcFlags {
-    unsigned changed;       // a hook lowered a parent, or a jump moved one
-    unsigned bad;           // a column outside [0, n)
+struct CcFlags : SweepFlags {   // changed: a hook lowered a parent, or a jump moved one
     int roots;              // vertices with parent[v] == v after the jump
     unsigned pad;
 };
@@ -46,53 +44,28 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_init(int n, int *__restrict__
     if (r < n) parent[r] = (int)r;
 }
 
+// The hook as an op of sel_sweep_graph (sel_rows.hpp), which walks the entries, tests the columns and skips self-loops.
 // parent is read by plain loads and lowered by atomics in the same launch: neither const nor __restrict__
+struct CcHook {
+    int *parent;
+    bool changed;
+    int pu;
+    __device__ __forceinline__ void row(int u) { pu = parent[u]; }
+    __device__ __forceinline__ void edge(int, int v)
+    {
+        const int pv = parent[v];
+        if (pu == pv) return;
+        const int hi = max(pu, pv), lo = min(pu, pv);                    // both in [0, n): parent[x] <= x
+        if (atomicMin(&parent[hi], lo) > lo) changed = true;
+    }
+};
+
 __global__ __launch_bounds__(kSelThreads) void k_cc_hook(const int *__restrict__ row_ptr, const int *__restrict__ col, int n,
                                                         long long E, bool vec, const int *__restrict__ tile_row, int *parent,
                                                         CcFlags *__restrict__ flags)
 {
-    __shared__ int srp[kSelStage + 1];
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    const SelTileRows tr = sel_stage_tile_rows(row_ptr, n, E, tile_row, srp);
-    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
-    v4i c4[kSelSteps];
-#pragma unroll
-    for (int j = 0; j < kSelSteps; j++) c4[j] = load4<true>(col, w0 + j * kSelGroup + 4 * lane, E, vec);
-    bool changed = false, bad = false;
-#pragma unroll
-    for (int j = 0; j < kSelSteps; j++) {
-        const long long e0 = w0 + j * kSelGroup + 4 * lane;
-        if (e0 >= E) continue;
-        const int c[4] = {c4[j].x, c4[j].y, c4[j].z, c4[j].w};
-        int u = tr.find(tr.rb, (int)e0);                                 // one search per lane and step, then a walk
-        int end = tr.row_end(u);
-        int pu = parent[u];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const long long p = e0 + k;
-            if (p >= E) break;
-            if (p >= end) {
-                u = tr.find(u + 1, (int)p);
-                end = tr.row_end(u);
-                pu = parent[u];
-            }
-            const int v = c[k];
-            if ((unsigned)v >= (unsigned)n) {                            // before v indexes anything
-                bad = true;
-                continue;
-            }
-            if (v == u) continue;
-            const int pv = parent[v];
-            if (pu == pv) continue;
-            const int hi = max(pu, pv), lo = min(pu, pv);                // both in [0, n): parent[x] <= x
-            if (atomicMin(&parent[hi], lo) > lo) changed = true;
-        }
-    }
-    const u64 any_changed = __ballot(changed), any_bad = __ballot(bad);
-    if (lane == 0) {                                                     // one lane per wave
-        if (any_changed) flags->changed = 1u;
-        if (any_bad) flags->bad = 1u;
-    }
+    CcHook op = {parent, false, -1};
+    sel_sweep_graph(row_ptr, col, n, E, vec, tile_row, flags, op);
 }
 
 // Only thread v stores parent[v] here, and what it stores is an ancestor not above the old value: a racing reader sees the
@@ -100,7 +73,6 @@ __global__ __launch_bounds__(kSelThreads) void k_cc_hook(const int *__restrict__
 __global__ __launch_bounds__(kCcThreads) void k_cc_jump(int n, int *parent, CcFlags *__restrict__ flags)
 {
     __shared__ int wroots[kCcThreads / 64];
-    const int lane = lane_id(), w = threadIdx.x >> 6;
     const long long v = (long long)blockIdx.x * kCcThreads + threadIdx.x;
     bool moved = false, root = false;
     if (v < n) {
@@ -114,18 +86,8 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_jump(int n, int *parent, CcFl
         }
         root = p == (int)v;
     }
-    const u64 any_moved = __ballot(moved), roots = __ballot(root);
-    if (lane == 0) {
-        if (any_moved) flags->changed = 1u;
-        wroots[w] = __popcll(roots);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int q = 0; q < kCcThreads / 64; q++) s += wroots[q];
-        if (s) atomicAdd(&flags->roots, s);
-    }
+    if (__ballot(moved) && lane_id() == 0) flags->changed = 1u;
+    block_add<kCcThreads>(root, &flags->roots, nullptr, wroots);
 }
 
 }  // namespace bsp
@@ -135,12 +97,12 @@ using namespace bsp;
 extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_matrix **P,
                                                        int *ncomponents, int *rounds)
 {
+    static const char who[] = "bspgemm_connected_components";
     if (P) *P = nullptr;
     if (ncomponents) *ncomponents = 0;
     if (rounds) *rounds = 0;
     if (!ctx || !A || !P) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_connected_components: NULL argument");
-    if (bspgemm_status st = check_operand(ctx, A, "bspgemm_connected_components", NEED_SQUARE | NEED_ENTRIES_CONSISTENT)) return st;
-    if (A->nnz > INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_connected_components: more than INT_MAX nonzeros");
+    if (bspgemm_status st = check_graph_operand(ctx, A, who, NEED_SQUARE | NEED_ENTRIES_CONSISTENT)) return st;
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
     const int n = A->rows;
@@ -149,16 +111,15 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
         if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return st;
         if (bspgemm_status st = ensure_tmp(ctx, sizeof(CcFlags) / sizeof(int))) return st;
     }
-    // the assignment operand, laid out like an uploaded one; its col_idx is the label array while the rounds run
-    bspgemm_matrix *m = nullptr;
+    bspgemm_matrix *m = nullptr;                            // the assignment operand: its col_idx is parent[]
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
-    if (bspgemm_status st = operand_new(ctx, n, n, &m)) return bail(st);
-    if (bspgemm_status st = operand_cols(m, n)) return bail(st);
+    if (bspgemm_status st = assignment_operand(ctx, n, &m)) return bail(st);
     int *parent = m->d_col_idx;
-    const dim3 vgrid((unsigned)(((long long)n + 1 + kCcThreads - 1) / kCcThreads)), vblock(kCcThreads);
+    const dim3 vgrid = vertex_grid(n, kCcThreads), vblock(kCcThreads);
     hipLaunchKernelGGL(k_cc_init, vgrid, vblock, 0, s, n, m->d_row_ptr, parent);
     HIPCHK_B(hipGetLastError());
-    CcFlags h = {0, 0, n, 0};
+    CcFlags h = {};
+    h.roots = n;                                            // without entries every vertex is a component
     int r = 0;
     if (E > 0) {
         CcFlags *d_flags = reinterpret_cast<CcFlags *>(ctx->tmp);
@@ -167,19 +128,14 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
         const bool vec = aligned16(A->d_col_idx);
         const long long cap = (long long)n + 2;             // defensive: every round but the last lowers a parent value
         for (;;) {
-            if (r >= cap) return bail(FAIL(BSPGEMM_ERR_HIP, "bspgemm_connected_components: did not converge"));
+            if (r >= cap) return bail(fail_stuck(who));
             r++;
-            HIPCHK_B(hipMemsetAsync(d_flags, 0, sizeof(CcFlags), s));
+            HIPCHK_B(round_reset(d_flags, sizeof(CcFlags), s));
             hipLaunchKernelGGL(k_cc_hook, egrid, eblock, 0, s, A->d_row_ptr, A->d_col_idx, n, E, vec, ctx->tile_row, parent,
                                d_flags);
             hipLaunchKernelGGL(k_cc_jump, vgrid, vblock, 0, s, n, parent, d_flags);
-            HIPCHK_B(hipGetLastError());
-            HIPCHK_B(hipMemcpyAsync(&h, d_flags, sizeof h, hipMemcpyDeviceToHost, s));
-            HIPCHK_B(hipStreamSynchronize(s));              // the round's one synchronisation
-            if (h.bad) {
-                snprintf(g_err, sizeof g_err, "bspgemm_connected_components: a column index outside [0, %d) (A.cols)", n);
-                return bail(BSPGEMM_ERR_INVALID);
-            }
+            HIPCHK_B(round_fetch(&h, d_flags, sizeof h, s));   // the round's one synchronisation
+            if (h.bad) return bail(fail_bad_column(who, n));
             if (!h.changed) break;
         }
     }

@@ -3,7 +3,7 @@
 // workspace / result-cache helpers (context.hip) that the flows (multiply.hip), the int32 drop-ins (dropin.hip: dropin_run in
 // stages -- check and bound, operands, multiply, destination, download, hand-over -- over the early destination that
 // early_dest.hpp owns) and the communicator layer (comm.hip) use, the drop-ins' host steps that SpGEMM_hip_multi repeats, the
-// flag scratch of select.hip and setop.hip.  Not installed; nothing here is part of the C ABI.
+// flag scratch of select.hip and setop.hip, the host helpers of the round-based algorithms (cc.hip, scc.hip, kcore.hip).  Not installed; nothing here is part of the C ABI.
 #pragma once
 #include "../../include/bspgemm.h"
 #include "kernels.hpp"
@@ -236,6 +236,53 @@ struct FlagScratch {
 // Lays the scratch of E entries out from int offset `at` of tmp, every array on a 16-byte boundary, and returns the end;
 // 0: more words than the scan's int count takes.  sc NULL: the end alone (what to ask ensure_tmp for: tmp may move).
 size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratch *sc);
+
+// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip) ---
+// What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
+// each algorithm's own.  who: the entry point's name, which every message starts with.
+// the graph operand: check_operand with `flags`, then an entry count that an int32 entry index cannot hold
+static inline bspgemm_status check_graph_operand(const bspgemm_context *ctx, const bspgemm_matrix *A, const char *who, unsigned flags)
+{
+    if (bspgemm_status st = check_operand(ctx, A, who, flags)) return st;
+    if (A->nnz <= INT_MAX) return BSPGEMM_OK;
+    char what[128];
+    snprintf(what, sizeof what, "%s: more than INT_MAX nonzeros", who);
+    return FAIL(BSPGEMM_ERR_OVERFLOW, what);
+}
+// the assignment operand of n vertices, laid out like an uploaded one: row v holds one entry, and its col_idx is the label
+// array while the rounds run, so nothing is copied at the end (operand_finish(m, n) completes it).  After a failure *m is
+// NULL or a handle that bspgemm_matrix_free takes.
+static inline bspgemm_status assignment_operand(bspgemm_context *ctx, int n, bspgemm_matrix **m)
+{
+    if (bspgemm_status st = operand_new(ctx, n, n, m)) return st;
+    return operand_cols(*m, n);
+}
+// the grid of a pass with one thread per vertex and one more (row_ptr has n + 1 words)
+static inline dim3 vertex_grid(int n, int threads) { return dim3((unsigned)(((long long)n + 1 + threads - 1) / threads)); }
+// A repetition: zero the leading `bytes` of the device flag block, launch, read the block back -- its one synchronisation.
+static inline hipError_t round_reset(void *d_flags, size_t bytes, hipStream_t s) { return hipMemsetAsync(d_flags, 0, bytes, s); }
+static inline hipError_t round_fetch(void *h, const void *d_flags, size_t bytes, hipStream_t s)
+{
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = hipMemcpyAsync(h, d_flags, bytes, hipMemcpyDeviceToHost, s)) return e;
+    return hipStreamSynchronize(s);
+}
+static inline bspgemm_status fail_bad_column(const char *who, int n)
+{
+    snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) (A.cols)", who, n);
+    return BSPGEMM_ERR_INVALID;
+}
+static inline bspgemm_status fail_stuck(const char *who)
+{
+    snprintf(g_err, sizeof g_err, "%s: did not converge", who);
+    return BSPGEMM_ERR_HIP;
+}
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING)
+using host_clock = std::chrono::steady_clock;
+static inline double ms_since(host_clock::time_point t)
+{
+    return std::chrono::duration<double, std::milli>(host_clock::now() - t).count();
+}
 
 // ------------------------------------------------------------------ drop-in host steps (dropin.hip) ---
 // one line on stderr for a failed drop-in ("SpGEMM_hip: <status>: <last error>"), returns the status as int

@@ -145,11 +145,9 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
     // BSPGEMM_KCORE_TIMING: host clocks around the stages; a launch is then synchronised before its read-back is issued, so
     // that the two are told apart
     const bool timed = ctx->kcore_timing;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     double ms_sym = 0, ms_scan = 0, ms_peel = 0, ms_peel_max = 0, ms_back = 0;
     int peel_max_size = 0, peel_max_k = 0;
-    const clk::time_point t_call = clk::now();
+    const host_clock::time_point t_call = host_clock::now();
     bspgemm_matrix *S = nullptr;
     if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &S)) return st;
     if (timed) {
@@ -170,10 +168,7 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
         bspgemm_matrix_free(S);
         return st;
     };
-    auto stuck = [&]() {
-        snprintf(g_err, sizeof g_err, "%s: did not converge", who);
-        return bail(BSPGEMM_ERR_HIP);
-    };
+    auto stuck = [&]() { return bail(fail_stuck(who)); };
     // deg, the two lists and the counters (before anything is launched: growing the workspace synchronises)
     const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
     if (edges)
@@ -193,7 +188,7 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
         list[0] = deg + n4;
         list[1] = deg + 2 * n4;
     }
-    const dim3 vgrid((unsigned)(((long long)n + 1 + kKcThreads - 1) / kKcThreads)), block(kKcThreads);
+    const dim3 vgrid = vertex_grid(n, kKcThreads), block(kKcThreads);
     // without edges every vertex is isolated: core 0, nothing to peel
     hipLaunchKernelGGL(k_kcore_init, vgrid, block, 0, s, n, edges ? S->d_row_ptr : nullptr, deg, core, R->d_row_ptr,
                        R->d_col_idx, edges ? -1 : 0);
@@ -206,14 +201,14 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
         while (assigned < n) {
             if (++scans > scan_cap) return stuck();
             KcFlags h = {};
-            HIPCHK_B(hipMemsetAsync(d_flags, 0, sizeof(KcFlags), s));
-            clk::time_point t = clk::now();
+            HIPCHK_B(round_reset(d_flags, sizeof(KcFlags), s));
+            host_clock::time_point t = host_clock::now();
             hipLaunchKernelGGL(k_kcore_scan, vgrid, block, 0, s, n, k, deg, core, list[0], d_flags);
             HIPCHK_B(hipGetLastError());
             if (timed) {
                 HIPCHK_B(hipStreamSynchronize(s));
                 ms_scan += ms_since(t);
-                t = clk::now();
+                t = host_clock::now();
             }
             HIPCHK_B(hipMemcpyAsync(&h, d_flags, sizeof h, hipMemcpyDeviceToHost, s));
             HIPCHK_B(hipStreamSynchronize(s));
@@ -231,7 +226,7 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
                 peels++;
                 assigned += fsize;
                 const dim3 pgrid((unsigned)(((long long)fsize + kKcWaves - 1) / kKcWaves));
-                t = clk::now();
+                t = host_clock::now();
                 hipLaunchKernelGGL(k_kcore_peel, pgrid, block, 0, s, n, k, fsize, list[cur], S->d_row_ptr, S->d_col_idx, deg, core,
                                    list[cur ^ 1], &d_flags->size[cur ^ 1], &d_flags->size[cur]);
                 HIPCHK_B(hipGetLastError());
@@ -244,7 +239,7 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
                         peel_max_size = fsize;
                         peel_max_k = k;
                     }
-                    t = clk::now();
+                    t = host_clock::now();
                 }
                 HIPCHK_B(hipMemcpyAsync(&fsize, &d_flags->size[cur ^ 1], sizeof fsize, hipMemcpyDeviceToHost, s));
                 HIPCHK_B(hipStreamSynchronize(s));          // the launch's one synchronisation

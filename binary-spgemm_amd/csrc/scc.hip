@@ -60,10 +60,9 @@ namespace bsp {
 constexpr int kSccJumps = 1;            // pointer-jumping steps per vertex and forward repetition; 0: no jump launch
 constexpr int kSccThreads = 256;
 
-struct SccFlags {
-    // zeroed in front of every repetition (the first 16 bytes of the workspace)
-    unsigned changed;       // a forward sweep lowered a colour, a jump moved one, a backward sweep stored a label
-    unsigned bad;           // a column outside [0, n)
+struct SccFlags : SweepFlags {
+    // SweepFlags (changed: a forward sweep lowered a colour, a jump moved one, a backward sweep stored a label) and the next
+    // two are zeroed in front of every repetition: the first 16 bytes of the workspace
     int removed;            // vertices that this trim pass labelled
     int alive;              // vertices that this trim pass left unassigned
     // zeroed once
@@ -86,53 +85,7 @@ __global__ __launch_bounds__(kSccThreads) void k_scc_init(int n, int *__restrict
     if (alive && r == 0) *flags = SccFlags{};
 }
 
-// The walk that the three sweeps share: op.row(u) when the lane enters row u, op.edge(u, v) for every stored entry (u, v)
-// with v in [0, n) and v != u.  A column outside [0, n) is tested BEFORE it reaches op, sets the `bad` word and is skipped.
-// op.changed ends up in the `changed` word.  Called by every thread of the workgroup.
-template <typename Op>
-__device__ __forceinline__ void scc_sweep(const int *__restrict__ row_ptr, const int *__restrict__ col, int n, long long E,
-                                          bool vec, const int *__restrict__ tile_row, SccFlags *__restrict__ flags, Op &op)
-{
-    __shared__ int srp[kSelStage + 1];
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    const SelTileRows tr = sel_stage_tile_rows(row_ptr, n, E, tile_row, srp);
-    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
-    v4i c4[kSelSteps];
-#pragma unroll
-    for (int j = 0; j < kSelSteps; j++) c4[j] = load4<true>(col, w0 + j * kSelGroup + 4 * lane, E, vec);
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < kSelSteps; j++) {
-        const long long e0 = w0 + j * kSelGroup + 4 * lane;
-        if (e0 >= E) continue;
-        const int c[4] = {c4[j].x, c4[j].y, c4[j].z, c4[j].w};
-        int u = tr.find(tr.rb, (int)e0);                                 // one search per lane and step, then a walk
-        int end = tr.row_end(u);
-        op.row(u);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const long long p = e0 + k;
-            if (p >= E) break;
-            if (p >= end) {
-                u = tr.find(u + 1, (int)p);
-                end = tr.row_end(u);
-                op.row(u);
-            }
-            const int v = c[k];
-            if ((unsigned)v >= (unsigned)n) {                            // before v indexes anything
-                bad = true;
-                continue;
-            }
-            if (v != u) op.edge(u, v);
-        }
-    }
-    const u64 any_changed = __ballot(op.changed), any_bad = __ballot(bad);
-    if (lane == 0) {                                                     // one lane per wave
-        if (any_changed) flags->changed = 1u;
-        if (any_bad) flags->bad = 1u;
-    }
-}
-
+// The three sweeps: ops of sel_sweep_graph (sel_rows.hpp), which walks the entries, tests the columns and skips self-loops.
 // label[] is only read here: the marks are those of the launch boundary
 struct SccMark {
     const int *__restrict__ label;
@@ -187,7 +140,7 @@ __global__ __launch_bounds__(kSelThreads) void k_scc_mark(const int *__restrict_
                                                          int *__restrict__ has_in, SccFlags *__restrict__ flags)
 {
     SccMark op = {label, has_out, has_in, false, false};
-    scc_sweep(row_ptr, col, n, E, vec, tile_row, flags, op);
+    sel_sweep_graph(row_ptr, col, n, E, vec, tile_row, flags, op);
 }
 
 __global__ __launch_bounds__(kSelThreads) void k_scc_forward(const int *__restrict__ row_ptr, const int *__restrict__ col, int n,
@@ -195,7 +148,7 @@ __global__ __launch_bounds__(kSelThreads) void k_scc_forward(const int *__restri
                                                             SccFlags *__restrict__ flags)
 {
     SccForward op = {color, false, -1};
-    scc_sweep(row_ptr, col, n, E, vec, tile_row, flags, op);
+    sel_sweep_graph(row_ptr, col, n, E, vec, tile_row, flags, op);
 }
 
 __global__ __launch_bounds__(kSelThreads) void k_scc_backward(const int *__restrict__ row_ptr, const int *__restrict__ col, int n,
@@ -204,23 +157,7 @@ __global__ __launch_bounds__(kSelThreads) void k_scc_backward(const int *__restr
                                                              SccFlags *__restrict__ flags)
 {
     SccBackward op = {color, label, false, false, -1};
-    scc_sweep(row_ptr, col, n, E, vec, tile_row, flags, op);
-}
-
-// the workgroup's count of `x` added to *word (and *also, unless NULL) by one atomic each; called by every thread
-__device__ __forceinline__ void scc_block_add(bool x, int *word, int *also, int *wsum)
-{
-    const u64 m = __ballot(x);
-    if (lane_id() == 0) wsum[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int q = 0; q < kSccThreads / 64; q++) s += wsum[q];
-        if (s) atomicAdd(word, s);
-        if (s && also) atomicAdd(also, s);
-    }
-    __syncthreads();                                                     // (wsum is free again)
+    sel_sweep_graph(row_ptr, col, n, E, vec, tile_row, flags, op);
 }
 
 // Only thread v touches label[v], color[v] and the marks of v here.
@@ -239,8 +176,8 @@ __global__ __launch_bounds__(kSccThreads) void k_scc_trim(int n, int *__restrict
         color[v] = stays ? (int)v : -1;
         has_out[v] = has_in[v] = 0;
     }
-    scc_block_add(removed, &flags->removed, &flags->components, wsum);
-    scc_block_add(stays, &flags->alive, nullptr, wsum);
+    block_add<kSccThreads>(removed, &flags->removed, &flags->components, wsum);
+    block_add<kSccThreads>(stays, &flags->alive, nullptr, wsum);
 }
 
 // Only thread v stores color[v] here, and what it stores is an ancestor of v not above the old value: a racing reader sees
@@ -271,7 +208,7 @@ __global__ __launch_bounds__(kSccThreads) void k_scc_roots(int n, const int *__r
     const long long v = (long long)blockIdx.x * kSccThreads + threadIdx.x;
     const bool root = v < n && color[v] == (int)v;                       // (color >= 0: alive when the round began)
     if (root) label[v] = (int)v;
-    scc_block_add(root, &flags->components, nullptr, wsum);
+    block_add<kSccThreads>(root, &flags->components, nullptr, wsum);
 }
 
 }  // namespace bsp
@@ -287,8 +224,7 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
     if (rounds) *rounds = 0;
     if (sweeps) *sweeps = 0;
     if (!ctx || !A || !P) return FAIL(BSPGEMM_ERR_INVALID, "bspgemm_strongly_connected_components: NULL argument");
-    if (bspgemm_status st = check_operand(ctx, A, who, NEED_SQUARE | NEED_ENTRIES_CONSISTENT)) return st;
-    if (A->nnz > INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_strongly_connected_components: more than INT_MAX nonzeros");
+    if (bspgemm_status st = check_graph_operand(ctx, A, who, NEED_SQUARE | NEED_ENTRIES_CONSISTENT)) return st;
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
     const int n = A->rows;
@@ -301,16 +237,12 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
     }
     // BSPGEMM_SCC_TIMING: host clocks around the repetitions, each of which ends synchronised anyway
     const bool timed = ctx->scc_timing;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-    const clk::time_point t_call = clk::now();
+    const host_clock::time_point t_call = host_clock::now();
     double ms_trim = 0, ms_fwd = 0, ms_bwd = 0;
-    // the assignment operand, laid out like an uploaded one; its col_idx is the label array while the rounds run
-    bspgemm_matrix *m = nullptr;
+    bspgemm_matrix *m = nullptr;                            // the assignment operand: its col_idx is label[]
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
-    auto stuck = [&]() { return bail(FAIL(BSPGEMM_ERR_HIP, "bspgemm_strongly_connected_components: did not converge")); };
-    if (bspgemm_status st = operand_new(ctx, n, n, &m)) return bail(st);
-    if (bspgemm_status st = operand_cols(m, n)) return bail(st);
+    auto stuck = [&]() { return bail(fail_stuck(who)); };
+    if (bspgemm_status st = assignment_operand(ctx, n, &m)) return bail(st);
     int *label = m->d_col_idx;
     SccFlags *d_flags = nullptr;
     int *color = nullptr, *has_out = nullptr, *has_in = nullptr;
@@ -320,7 +252,7 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
         has_out = color + n4;
         has_in = color + 2 * n4;
     }
-    const dim3 vgrid((unsigned)(((long long)n + 1 + kSccThreads - 1) / kSccThreads)), vblock(kSccThreads);
+    const dim3 vgrid = vertex_grid(n, kSccThreads), vblock(kSccThreads);
     hipLaunchKernelGGL(k_scc_init, vgrid, vblock, 0, s, n, m->d_row_ptr, label, edges, has_out, has_in, d_flags);
     HIPCHK_B(hipGetLastError());
     SccFlags h = {};
@@ -332,16 +264,12 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
         const dim3 egrid(select_tiles(E)), eblock(kSelThreads);
         const bool vec = aligned16(A->d_col_idx);
         const long long cap = (long long)n + 2;             // defensive: every repetition but the last changes a vertex
-        // the read-back that ends a repetition: its one synchronisation
-        auto fetch = [&]() -> hipError_t {
-            if (hipError_t e = hipGetLastError()) return e;
-            if (hipError_t e = hipMemcpyAsync(&h, d_flags, sizeof h, hipMemcpyDeviceToHost, s)) return e;
-            return hipStreamSynchronize(s);
-        };
-        auto reset = [&]() { return hipMemsetAsync(d_flags, 0, 4 * sizeof(int), s); };
+        // a repetition zeroes the block's first four words and ends in the read-back of all of it: its one synchronisation
+        auto reset = [&]() { return round_reset(d_flags, 4 * sizeof(int), s); };
+        auto fetch = [&]() { return round_fetch(&h, d_flags, sizeof h, s); };
         for (;;) {
             // trim to the fixpoint; the last pass leaves color[] ready for the round
-            clk::time_point t = clk::now();
+            host_clock::time_point t = host_clock::now();
             for (long long it = 0;; it++) {
                 if (it >= cap) return stuck();
                 trims++;
@@ -350,17 +278,14 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
                                    has_out, has_in, d_flags);
                 hipLaunchKernelGGL(k_scc_trim, vgrid, vblock, 0, s, n, label, color, has_out, has_in, d_flags);
                 HIPCHK_B(fetch());
-                if (h.bad) {
-                    snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) (A.cols)", who, n);
-                    return bail(BSPGEMM_ERR_INVALID);
-                }
+                if (h.bad) return bail(fail_bad_column(who, n));
                 if (h.removed == 0 || h.alive == 0) break;
             }
             if (timed) ms_trim += ms_since(t);
             if (h.alive == 0) break;
             if (r >= n) return stuck();                     // (a round labels at least one vertex)
             r++;
-            t = clk::now();
+            t = host_clock::now();
             for (long long it = 0;; it++) {
                 if (it >= cap) return stuck();
                 fwd++;
@@ -372,7 +297,7 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
                 if (!h.changed) break;
             }
             if (timed) ms_fwd += ms_since(t);
-            t = clk::now();
+            t = host_clock::now();
             hipLaunchKernelGGL(k_scc_roots, vgrid, vblock, 0, s, n, color, label, d_flags);
             for (long long it = 0;; it++) {
                 if (it >= cap) return stuck();

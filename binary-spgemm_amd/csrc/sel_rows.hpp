@@ -1,7 +1,14 @@
-// sel_rows.hpp -- device code that the entry-parallel passes of select.hip, setop.hip, bfs.hip and cc.hip share: the tile
-// geometry, the 16-byte entry loads, the DPP join of a lane's four flags into the 64-bit flag word of 64 entries, the search
-// of an entry's row in the tile's window of row_ptr (staged in LDS; tile_row comes from k_sel_tile_rows) and the lower bound
-// of a column in a row of another operand.  Device code only.
+// sel_rows.hpp -- device code that the entry-parallel passes share: the tile geometry, the 16-byte entry loads, the DPP join
+// of a lane's four flags into the 64-bit flag word of 64 entries, the search of an entry's row in the tile's window of
+// row_ptr (staged in LDS; tile_row comes from k_sel_tile_rows), the lower bound of a column in a row of another operand,
+// and the walk itself.  Who uses what:
+//     sel_walk_entries   the walk over a tile's entries with an op (load / row / entry): k_merge_disjoint (bfs.hip)
+//     sel_sweep_graph    the same walk behind the graph adapter (range check, self-loop skip, changed / bad words) with
+//                        an op (row / edge): k_cc_hook (cc.hip), k_scc_mark, k_scc_forward, k_scc_backward (scc.hip)
+//     SelTileRows alone  k_set_flags (setop.hip): it also needs row_begin, the column in front of the lane's four and a
+//                        flag word for the steps past E, so it keeps its own loop
+//     the pieces         k_sel_flags_struct (select.hip) spells the staging out in its body, see SelTileRows
+// Device code only.
 #pragma once
 #include "kernels.hpp"
 #include "wave.hpp"
@@ -120,6 +127,90 @@ __device__ __forceinline__ SelTileRows sel_stage_tile_rows(const int *__restrict
         for (int q = threadIdx.x; q <= t.span; q += kSelThreads) srp[q] = row_ptr[t.rb + q];
     __syncthreads();
     return t;
+}
+
+// The entry-parallel walk.  A workgroup owns the kSelTile consecutive entries of tile blockIdx.x whatever rows they belong
+// to, a wave kSelWaveSpan of them, a lane four per step by one 16-byte load of `col` (NT: non-temporal), all kSelSteps
+// loads in flight before the first is used; the tile's window of row_ptr is staged in LDS -- a hub row costs what its
+// entries cost.  One row search per lane and step, then a walk of the four entries that searches again when the row ends.
+//     op.load(j, e)          before the walk, beside the column load of step j (entries e .. e + 3, e possibly past E):
+//                            where an op issues 16-byte loads of its own
+//     op.row(r)              whenever the lane enters row r
+//     op.entry(r, p, c, s)   entry p of row r with column c; s = 4 * j + k, the lane's s-th entry (a constant once the loops
+//                            are unrolled: it indexes what op.load fetched)
+// Called by every thread of the workgroup (it holds the staging barrier); the grid is ceil(E / kSelTile).
+template <bool NT, typename Op>
+__device__ __forceinline__ void sel_walk_entries(const int *__restrict__ row_ptr, const int *__restrict__ col, int rows,
+                                                 long long E, bool vec, const int *__restrict__ tile_row, Op &op)
+{
+    __shared__ int srp[kSelStage + 1];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const SelTileRows tr = sel_stage_tile_rows(row_ptr, rows, E, tile_row, srp);
+    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
+    v4i c4[kSelSteps];
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e = w0 + j * kSelGroup + 4 * lane;
+        c4[j] = load4<NT>(col, e, E, vec);
+        op.load(j, e);
+    }
+#pragma unroll
+    for (int j = 0; j < kSelSteps; j++) {
+        const long long e0 = w0 + j * kSelGroup + 4 * lane;
+        if (e0 >= E) continue;
+        const int c[4] = {c4[j].x, c4[j].y, c4[j].z, c4[j].w};
+        int r = tr.find(tr.rb, (int)e0);                                 // one search per lane and step, then a walk
+        int end = tr.row_end(r);
+        op.row(r);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const long long p = e0 + k;
+            if (p >= E) break;
+            if (p >= end) {
+                r = tr.find(r + 1, (int)p);
+                end = tr.row_end(r);
+                op.row(r);
+            }
+            op.entry(r, p, c[k], 4 * j + k);
+        }
+    }
+}
+
+// The two words that every graph sweep reports, at the head of the algorithm's flag block (CcFlags, SccFlags)
+struct SweepFlags {
+    unsigned changed;       // op.changed of any lane
+    unsigned bad;           // a column outside [0, n)
+};
+
+// The walk over the entries of a graph (n x n): op.row(u) when the lane enters row u, op.edge(u, v) for every stored entry
+// (u, v) with v in [0, n) and v != u.  A column outside [0, n) is tested BEFORE it reaches op, sets the `bad` word and is
+// skipped.  op.changed ends up in the `changed` word.  Called by every thread of the workgroup.
+template <typename Op>
+struct SelGraphWalk {
+    Op &op;
+    int n;
+    bool bad;
+    __device__ __forceinline__ void load(int, long long) {}
+    __device__ __forceinline__ void row(int u) { op.row(u); }
+    __device__ __forceinline__ void entry(int u, long long, int v, int)
+    {
+        if ((unsigned)v >= (unsigned)n) bad = true;                      // before v indexes anything
+        else if (v != u) op.edge(u, v);
+    }
+};
+
+template <typename Op>
+__device__ __forceinline__ void sel_sweep_graph(const int *__restrict__ row_ptr, const int *__restrict__ col, int n, long long E,
+                                                bool vec, const int *__restrict__ tile_row, SweepFlags *__restrict__ flags,
+                                                Op &op)
+{
+    SelGraphWalk<Op> g = {op, n, false};
+    sel_walk_entries<true>(row_ptr, col, n, E, vec, tile_row, g);
+    const u64 any_changed = __ballot(op.changed), any_bad = __ballot(g.bad);
+    if (lane_id() == 0) {                                                // one lane per wave
+        if (any_changed) flags->changed = 1u;
+        if (any_bad) flags->bad = 1u;
+    }
 }
 
 }  // namespace bsp

@@ -113,4 +113,22 @@ __device__ __forceinline__ void clear_blocked(u32 *P, int lane)
     for (int k = 0; k < W; k++) P[lane * W + k] = 0u;
 }
 
+// the workgroup's count of `x` added to *word (and *also, unless NULL) by one atomic each; wsum: THREADS / 64 ints of LDS.
+// Called by every thread of the workgroup (THREADS of them).
+template <int THREADS>
+__device__ __forceinline__ void block_add(bool x, int *word, int *also, int *wsum)
+{
+    const u64 m = __ballot(x);
+    if (lane_id() == 0) wsum[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+#pragma unroll
+        for (int q = 0; q < THREADS / 64; q++) s += wsum[q];
+        if (s) atomicAdd(word, s);
+        if (s && also) atomicAdd(also, s);
+    }
+    __syncthreads();                                                     // (wsum is free again)
+}
+
 }  // namespace bsp

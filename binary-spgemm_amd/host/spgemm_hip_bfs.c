@@ -12,23 +12,9 @@
  * from it (itself included), the largest level among them and the sum of their levels -- and then one line
  * n,nnz,nsources,depth,complete,ms.  ms: wall time of bspgemm_bfs, the operand already on the device.
  */
-#include "../../include/bspgemm.h"
-
+#include "cli_common.h"
 #include <errno.h>
 #include <limits.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-
-#define CHECK(st, what)                                                                         \
-    do {                                                                                        \
-        bspgemm_status s_ = (st);                                                               \
-        if (s_ != BSPGEMM_OK) {                                                                 \
-            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
-            exit(1);                                                                            \
-        }                                                                                       \
-    } while (0)
 
 int main(int argc, char **argv)
 {
@@ -50,26 +36,20 @@ int main(int argc, char **argv)
         sources[i] = (int)v;
     }
     uint32_t *Arow, *Acol, M, N, nnz;
-    bspgemm_status st = bspgemm_readCOO(argv[1], &Arow, &Acol, &M, &N, &nnz);
-    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
-    if (st != BSPGEMM_OK) exit(1);
-    if (M != N) { fprintf(stderr, "bfs needs a square matrix (%ux%u)\n", M, N); exit(1); }
-    const char *devenv = getenv("BSPGEMM_DEVICE");
-    bspgemm_context *ctx;
-    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
+    cli_need_square("bfs", M, N);
+    bspgemm_context *ctx = cli_context(0);
     bspgemm_matrix *At, *A;
     CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &At), "upload");
     CHECK(bspgemm_matrix_transpose(ctx, At, &A), "bspgemm_matrix_transpose");
     bspgemm_matrix_free(At);
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
+    const struct timespec t0 = cli_now();
     bspgemm_result *L;
     int depth = 0, complete = 0;
     CHECK(bspgemm_bfs(ctx, A, S, sources, 0, &L, &depth, &complete), "bspgemm_bfs");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    const double ms = cli_ms(t0, cli_now());
     const long long total = bspgemm_result_nnz(L);
     int64_t *rp = malloc(((size_t)S + 1) * sizeof(int64_t));
     int *lv = malloc((size_t)(total > 0 ? total : 1) * sizeof(int));

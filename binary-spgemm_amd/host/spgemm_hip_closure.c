@@ -9,20 +9,7 @@
  * input (readCOO, final/utils.c:47-81: transposed in memory; the closure of the transpose is the
  * transpose of the closure, and the writer transposes back).
  */
-#include "../../include/bspgemm.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-#include <time.h>
-
-#define CHECK(st, what)                                                                         \
-    do {                                                                                        \
-        bspgemm_status s_ = (st);                                                               \
-        if (s_ != BSPGEMM_OK) {                                                                 \
-            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
-            exit(1);                                                                            \
-        }                                                                                       \
-    } while (0)
+#include "cli_common.h"
 
 int main(int argc, char **argv)
 {
@@ -31,22 +18,16 @@ int main(int argc, char **argv)
         exit(1);
     }
     uint32_t *Arow, *Acol, M, N, nnz;
-    bspgemm_status st = bspgemm_readCOO(argv[1], &Arow, &Acol, &M, &N, &nnz);
-    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
-    if (st != BSPGEMM_OK) exit(1);
-    if (M != N) { fprintf(stderr, "closure needs a square matrix (%ux%u)\n", M, N); exit(1); }
-    const char *devenv = getenv("BSPGEMM_DEVICE");
-    bspgemm_context *ctx;
-    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
+    cli_need_square("closure", M, N);
+    bspgemm_context *ctx = cli_context(0);
     bspgemm_matrix *A;
     CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
+    const struct timespec t0 = cli_now();
     bspgemm_result *T;
     int products = 0;
     CHECK(bspgemm_closure(ctx, A, 64, &T, &products), "bspgemm_closure");
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    const double secs = (double)(t1.tv_sec - t0.tv_sec) + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-9;
+    const double secs = cli_ms(t0, cli_now()) * 1e-3;
     printf("%s,%u,%u,%d,%lld,%lf\n", argv[1], M, nnz, products, (long long)bspgemm_result_nnz(T), secs);
     if (argc == 3) {
         const long long tn = bspgemm_result_nnz(T);

@@ -13,21 +13,7 @@
  * --k K --out writes the K-core (bspgemm_kcore: the subgraph induced by the vertices of core number >= K, both directions
  * of every edge) with bspgemm_write_mtx, such that the loader reconstructs exactly that operand.
  */
-#include "../../include/bspgemm.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-
-#define CHECK(st, what)                                                                         \
-    do {                                                                                        \
-        bspgemm_status s_ = (st);                                                               \
-        if (s_ != BSPGEMM_OK) {                                                                 \
-            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
-            exit(1);                                                                            \
-        }                                                                                       \
-    } while (0)
+#include "cli_common.h"
 
 static void usage(void)
 {
@@ -48,35 +34,24 @@ int main(int argc, char **argv)
     }
     if ((k_arg == NULL) != (out_path == NULL)) usage();
     uint32_t *Arow, *Acol, M, N, nnz;
-    bspgemm_status st = bspgemm_readCOO(argv[1], &Arow, &Acol, &M, &N, &nnz);
-    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
-    if (st != BSPGEMM_OK) exit(1);
-    if (M != N) { fprintf(stderr, "k-core needs a square matrix (%ux%u)\n", M, N); exit(1); }
-    const char *devenv = getenv("BSPGEMM_DEVICE");
-    bspgemm_context *ctx;
-    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
+    cli_need_square("k-core", M, N);
+    bspgemm_context *ctx = cli_context(0);
     bspgemm_matrix *A;
     bspgemm_result *R;
     CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
+    const struct timespec t0 = cli_now();
     int degeneracy = 0, rounds = 0;
     CHECK(bspgemm_core_numbers(ctx, A, &R, &degeneracy, &rounds), "bspgemm_core_numbers");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    const double ms = cli_ms(t0, cli_now());
     int *core = malloc(((size_t)M + 1) * sizeof(int));
     if (!core) exit(1);
     CHECK(bspgemm_result_download_values(ctx, R, core), "download");
     int top = 0;
     for (uint32_t v = 0; v < M; v++) top += core[v] == degeneracy;
-    if (numbers_path) {
-        FILE *f = fopen(numbers_path, "w");
-        if (!f) { fprintf(stderr, "cannot write %s\n", numbers_path); exit(1); }
-        for (uint32_t v = 0; v < M; v++) fprintf(f, "%d\n", core[v]);
-        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", numbers_path); exit(1); }
-    }
+    if (numbers_path) cli_write_ints(numbers_path, core, M);
     printf("%u,%u,%d,%d,%d,%.3f\n", M, nnz, degeneracy, top, rounds, ms);
     if (out_path) {
         bspgemm_matrix *T;

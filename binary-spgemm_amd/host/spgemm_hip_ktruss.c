@@ -14,21 +14,7 @@
  * graph; nnz stays the loader's count.
  * ms: wall time of the triangle count and the k-truss together, operands already on the device.
  */
-#include "../../include/bspgemm.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-
-#define CHECK(st, what)                                                                         \
-    do {                                                                                        \
-        bspgemm_status s_ = (st);                                                               \
-        if (s_ != BSPGEMM_OK) {                                                                 \
-            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
-            exit(1);                                                                            \
-        }                                                                                       \
-    } while (0)
+#include "cli_common.h"
 
 int main(int argc, char **argv)
 {
@@ -43,13 +29,9 @@ int main(int argc, char **argv)
     }
     const int k = atoi(argv[2]);
     uint32_t *Arow, *Acol, M, N, nnz;
-    bspgemm_status st = bspgemm_readCOO_ex(argv[1], BSPGEMM_READ_EXPAND_SYMMETRIC, &Arow, &Acol, &M, &N, &nnz);
-    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
-    if (st != BSPGEMM_OK) exit(1);
-    if (M != N) { fprintf(stderr, "k-truss needs a square matrix (%ux%u)\n", M, N); exit(1); }
-    const char *devenv = getenv("BSPGEMM_DEVICE");
-    bspgemm_context *ctx;
-    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    cli_load(argv[1], BSPGEMM_READ_EXPAND_SYMMETRIC, &Arow, &Acol, &M, &N, &nnz);
+    cli_need_square("k-truss", M, N);
+    bspgemm_context *ctx = cli_context(0);
     bspgemm_matrix *A, *T;
     CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
     if (symmetrize) {
@@ -59,15 +41,13 @@ int main(int argc, char **argv)
         A = U;
         CHECK(bspgemm_synchronize(ctx), "synchronize");
     }
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
+    const struct timespec t0 = cli_now();
     int64_t triangles = 0;
     int iterations = 0, converged = 0;
     CHECK(bspgemm_triangle_count(ctx, A, &triangles), "bspgemm_triangle_count");
     CHECK(bspgemm_ktruss(ctx, A, k, 0, &T, &iterations, &converged), "bspgemm_ktruss");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    const double ms = cli_ms(t0, cli_now());
     const long long tn = bspgemm_matrix_nnz(T);
     printf("%u,%u,%lld,%d,%lld,%d,%d,%.3f\n", M, nnz, (long long)triangles, k, tn, iterations, converged, ms);
     if (argc == 4) {

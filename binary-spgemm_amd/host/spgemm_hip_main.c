@@ -29,37 +29,16 @@
  * mpi_transport.h); col_idx stays on the GPUs.
  * BSPGEMM_EXPAND_SYMMETRIC=1 in the environment loads symmetric files expanded (opt-in, f2).
  */
-#include "../../include/bspgemm.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
+#include "cli_common.h"
 #ifdef BSPGEMM_WITH_MPI
 #include "mpi_transport.h"
 #endif
-
-static double now_s(void)
-{
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);                       /* tictoc, final/utils.c:104-113 */
-    return (double)t.tv_sec + (double)t.tv_nsec * 1e-9;
-}
 
 static int cmp_double(const void *a, const void *b)
 {
     const double x = *(const double *)a, y = *(const double *)b;
     return (x > y) - (x < y);
 }
-
-#define CHECK(st, what)                                                                         \
-    do {                                                                                        \
-        bspgemm_status s_ = (st);                                                               \
-        if (s_ != BSPGEMM_OK) {                                                                 \
-            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
-            exit(1);                                                                            \
-        }                                                                                       \
-    } while (0)
 
 int main(int argc, char **argv)
 {
@@ -85,16 +64,10 @@ int main(int argc, char **argv)
     const char *sym = getenv("BSPGEMM_EXPAND_SYMMETRIC");
     const unsigned rflags = (sym && sym[0] == '1') ? BSPGEMM_READ_EXPAND_SYMMETRIC : 0u;
     uint32_t *Arow, *Acol, An, Am, Annz;
-    bspgemm_status st = bspgemm_readCOO_ex(argv[1], rflags, &Arow, &Acol, &An, &Am, &Annz);   /* An = M, Am = N */
-    /* the reference prints for a bad banner only (utils.c:56-59); fopen and size-line failures
-     * exit(1) silently (:54-55, :60-61) */
-    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
-    if (st != BSPGEMM_OK) exit(1);
+    cli_load(argv[1], rflags, &Arow, &Acol, &An, &Am, &Annz);   /* An = M, Am = N */
 
     const int ndev = bspgemm_device_count();
-    const char *devenv = getenv("BSPGEMM_DEVICE");
-    bspgemm_context *ctx;
-    CHECK(bspgemm_create(devenv ? atoi(devenv) : (ndev > 0 ? rank % ndev : 0), &ctx), "bspgemm_create");
+    bspgemm_context *ctx = cli_context(ndev > 0 ? rank % ndev : 0);
 
     /* in-memory (transposed) shapes: loaded(X) has X.N rows and X.M columns */
     const int a_rows = (int)Am, a_cols = (int)An;
@@ -103,9 +76,7 @@ int main(int argc, char **argv)
     int c_cols = a_cols;
     if (argc >= 6 && strcmp(argv[5], "-") != 0) {
         uint32_t *Brow, *Bcol, Bn, Bm, Bnnz;
-        st = bspgemm_readCOO_ex(argv[5], rflags, &Brow, &Bcol, &Bn, &Bm, &Bnnz);
-        if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
-        if (st != BSPGEMM_OK) exit(1);
+        cli_load(argv[5], rflags, &Brow, &Bcol, &Bn, &Bm, &Bnnz);
         if ((int)Bn != a_rows) { fprintf(stderr, "inner dimensions differ: A is %ux%u, B is %ux%u\n", An, Am, Bn, Bm); exit(1); }
         CHECK(bspgemm_matrix_upload(ctx, (int)Bm, (int)Bn, (const int *)Brow, (const int *)Bcol, &L), "upload B");
         free(Brow); free(Bcol);
@@ -122,7 +93,7 @@ int main(int argc, char **argv)
     const int64_t *d_row_ptr_global = NULL;   /* stitched C.row_ptr, device, owned by comm */
     int64_t *shard_nnz = malloc((size_t)numtasks * sizeof(int64_t));
     int used_rccl = 0;
-    if (numtasks > 1) CHECK(mpi_make_comm(ctx, rank, numtasks, devenv ? 1 : ndev, &comm, &used_rccl), "communicator");
+    if (numtasks > 1) CHECK(mpi_make_comm(ctx, rank, numtasks, getenv("BSPGEMM_DEVICE") ? 1 : ndev, &comm, &used_rccl), "communicator");
 #endif
 
     double *alltimes = malloc((size_t)times * sizeof(double));
@@ -136,7 +107,7 @@ int main(int argc, char **argv)
 #ifdef BSPGEMM_WITH_MPI
         MPI_Barrier(MPI_COMM_WORLD);                                     /* :319 */
 #endif
-        const double t0 = now_s();                                       /* tic :320 */
+        const struct timespec t0 = cli_now();                            /* tic :320 (tictoc, final/utils.c:104-113) */
         bspgemm_result *C;
         CHECK(bspgemm_multiply(ctx, Lhs, A, r0, r1, &C), "bspgemm_multiply");
         long long local_nnz = bspgemm_result_nnz(C);
@@ -148,14 +119,14 @@ int main(int argc, char **argv)
             for (int r = 0; r < numtasks; r++) nnzC += shard_nnz[r];
         }
 #endif
-        alltimes[i] = now_s() - t0;                                      /* toc :324 */
+        alltimes[i] = cli_ms(t0, cli_now()) * 1e-3;                      /* toc :324 */
         timesum += alltimes[i];
         bspgemm_last_stats(ctx, &stats);
         /* end-to-end: bring this rank's shard of C to the host as well */
         int *hcol = malloc((size_t)(local_nnz > 0 ? local_nnz : 1) * sizeof(int));
         if (hcol) {
             CHECK(bspgemm_result_download(ctx, C, hrow, hcol), "download");
-            const double e2e = now_s() - t0;
+            const double e2e = cli_ms(t0, cli_now()) * 1e-3;
             if (e2e < e2e_fastest) e2e_fastest = e2e;
             if (argc == 7 && i == times - 1 && numtasks == 1)            /* f2: C in the file's orientation */
                 CHECK(bspgemm_write_result_mtx(argv[6], c_rows, c_cols, hrow, hcol), "write C");

@@ -11,21 +11,7 @@
  * and its wall time, the operand already on the device.
  * --labels writes one label per line, line v the smallest vertex id (0-based) of v's component.
  */
-#include "../../include/bspgemm.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-
-#define CHECK(st, what)                                                                         \
-    do {                                                                                        \
-        bspgemm_status s_ = (st);                                                               \
-        if (s_ != BSPGEMM_OK) {                                                                 \
-            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
-            exit(1);                                                                            \
-        }                                                                                       \
-    } while (0)
+#include "cli_common.h"
 
 int main(int argc, char **argv)
 {
@@ -36,24 +22,18 @@ int main(int argc, char **argv)
         exit(1);
     }
     uint32_t *Arow, *Acol, M, N, nnz;
-    bspgemm_status st = bspgemm_readCOO(argv[1], &Arow, &Acol, &M, &N, &nnz);
-    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");
-    if (st != BSPGEMM_OK) exit(1);
-    if (M != N) { fprintf(stderr, "scc needs a square matrix (%ux%u)\n", M, N); exit(1); }
-    const char *devenv = getenv("BSPGEMM_DEVICE");
-    bspgemm_context *ctx;
-    CHECK(bspgemm_create(devenv ? atoi(devenv) : 0, &ctx), "bspgemm_create");
+    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
+    cli_need_square("scc", M, N);
+    bspgemm_context *ctx = cli_context(0);
     bspgemm_matrix *A, *P;
     CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
+    const struct timespec t0 = cli_now();
     int components = 0, rounds = 0, sweeps = 0;
     CHECK(bspgemm_strongly_connected_components(ctx, A, &P, &components, &rounds, &sweeps),
           "bspgemm_strongly_connected_components");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    const double ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+    const double ms = cli_ms(t0, cli_now());
     int *label = malloc(((size_t)M + 1) * sizeof(int));
     int *size = calloc((size_t)M + 1, sizeof(int));
     if (!label || !size) exit(1);
@@ -61,12 +41,7 @@ int main(int argc, char **argv)
     int largest = 0;
     for (uint32_t v = 0; v < M; v++)
         if (++size[label[v]] > largest) largest = size[label[v]];
-    if (labels_path) {
-        FILE *f = fopen(labels_path, "w");
-        if (!f) { fprintf(stderr, "cannot write %s\n", labels_path); exit(1); }
-        for (uint32_t v = 0; v < M; v++) fprintf(f, "%d\n", label[v]);
-        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", labels_path); exit(1); }
-    }
+    if (labels_path) cli_write_ints(labels_path, label, M);
     printf("%u,%u,%d,%d,%d,%d,%.3f\n", M, nnz, components, largest, rounds, sweeps, ms);
     free(label); free(size);
     bspgemm_matrix_free(P);

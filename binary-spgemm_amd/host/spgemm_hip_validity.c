@@ -23,23 +23,10 @@
  * Both runs are GPU runs: this binary checks decomposition invariance like the reference's; the
  * CPU-vs-GPU parity lives in tests/.
  */
-#include "../../include/bspgemm.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "cli_common.h"
 #ifdef BSPGEMM_WITH_MPI
 #include "mpi_transport.h"
 #endif
-
-#define CHECK(st, what)                                                                         \
-    do {                                                                                        \
-        bspgemm_status s_ = (st);                                                               \
-        if (s_ != BSPGEMM_OK) {                                                                 \
-            fprintf(stderr, "%s: %s: %s\n", what, bspgemm_status_string(s_), bspgemm_last_error()); \
-            exit(1);                                                                            \
-        }                                                                                       \
-    } while (0)
 
 int main(int argc, char **argv)
 {
@@ -58,15 +45,12 @@ int main(int argc, char **argv)
     }
     int tBlock = atoi(argv[2]);
     uint32_t *Arow, *Acol, An, Am, Annz;
-    bspgemm_status st = bspgemm_readCOO(argv[1], &Arow, &Acol, &An, &Am, &Annz);
-    if (st == BSPGEMM_ERR_FORMAT) printf("Could not process Matrix Market banner.\n");   /* utils.c:56-59; :54,:60 are silent */
-    if (st != BSPGEMM_OK) exit(1);
+    cli_load(argv[1], 0, &Arow, &Acol, &An, &Am, &Annz);
     const int n = (int)An;
     if (tBlock <= 0 || tBlock > n) tBlock = n > 0 ? n : 1;
 
     const int ndev = bspgemm_device_count();
-    const char *devenv = getenv("BSPGEMM_DEVICE");
-    const int device = devenv ? atoi(devenv) : (ndev > 0 ? rank % ndev : 0);
+    const int device = cli_device(ndev > 0 ? rank % ndev : 0);
     bspgemm_dropin_set_device(device);
     bspgemm_context *ctx;
     CHECK(bspgemm_create(device, &ctx), "bspgemm_create");
@@ -76,7 +60,7 @@ int main(int argc, char **argv)
 #ifdef BSPGEMM_WITH_MPI
     bspgemm_comm *comm = NULL;
     int used_rccl = 0;
-    CHECK(mpi_make_comm(ctx, rank, numtasks, devenv ? 1 : ndev, &comm, &used_rccl), "communicator");
+    CHECK(mpi_make_comm(ctx, rank, numtasks, getenv("BSPGEMM_DEVICE") ? 1 : ndev, &comm, &used_rccl), "communicator");
     if (SpGEMM_hip_multi(comm, (int *)Acol, (int *)Arow, n, (int *)Acol, (int *)Arow, n, &nCcol, nCrow, tBlock) != 0)
         ok = 0;                                                          /* :331 */
     int all_ok = 0;
