@@ -1096,3 +1096,690 @@ def masked_window_case(cols, top=INT_MAX, nrows=402):
         rows.append(_mask_row(rng, prod, n_in, noise, length, cols, top))
         kinds.append(kind)
     return _case(a_rp, a_ci, b_rp, b_ci, cols, rows, kinds, top)
+
+
+# ---- the heavy rows (csrc/dense_rows.hip over csrc/heavy_gather.hpp): constants, host model, shapes -------------------------
+# tests/test_gpu_heavy_rows.py; every constant mirrors the kernels' by name
+HEAVY_SHAPES = {512: (512, 8, 4),       # dense_rows.hip kDenseThreadsMid, kDenseQuadsPerThreadMid, kDenseInFlightMid (= kRankThreads, kRankQPT, kRankInFlight)
+                1024: (1024, 16, 8)}    # dense_rows.hip kDenseThreadsBig, kDenseQuadsPerThreadBig, kDenseInFlightBig (Keep, Count too)
+HEAVY_WINDOW_WORDS = {512: 4096, 1024: 16384, "keep": 8192}    # dense_rows.hip kMidMaxWords, kDenseMaxWords, launch_dense_impl max_words (two bitmaps)
+RANK_SPAN = 1 << 20                     # dense_rows.hip kRankSpan
+RANK_CAP = 6144                         # kernels.hpp kRankCap
+RANK_THREADS = 512                      # dense_rows.hip kRankThreads
+READOUT_STEP_WORDS, READOUT_WPL = 256, 4    # dense_rows.hip k_dense_rows kStepWords, kWpl
+DENSE_WORD_BITS = 12                    # dense_rows.hip kDenseWordBits
+COUNT_MAX_COLS, COUNT_SLOTS = 1 << 18, 20480    # dense_rows.hip kCountMaxCols, kCountSlots
+HEAVY_MIN = 2048                        # kernels.hpp kMaxWaveCap: rows with more products are heavy
+HEAVY_POPS = (1, 2, 3, 11, 12, 13, 63, 64)      # word popcounts around the pair store's tail and kDenseWordBits
+HEAVY_MODES = ("none", "keep", "drop", "insert", "count")
+HEAVY_LEFTS = ("1", "q", "q+1", "2q", "2q+1", "3q", "3q+1", "step")
+
+
+def heavy_tile(shape):
+    """(tile, step, quarter step) in quads of a thread shape (heavy_gather.hpp kTileQ, kInFlight * kThreads, the thresholds)"""
+    T, qpt, fl = shape
+    return T * qpt, T * fl, T * fl // 4
+
+
+def heavy_window_geometry(cols, threads, keep=False):
+    """(wwords, nwin, wpw) of k_dense_rows: launch_dense_impl's words per window, the windows, the words per wave"""
+    cap = HEAVY_WINDOW_WORDS["keep" if keep else threads]
+    wwords = max(1, min(-(-cols // 64), cap))
+    nwin = -(-cols // (64 * wwords))
+    wpw = -(-(-(-wwords // (threads // 64))) // READOUT_STEP_WORDS) * READOUT_STEP_WORDS
+    return wwords, nwin, wpw
+
+
+def _row_entries(b_rp, b_ci, src):
+    """the products of one A row in gather order: (columns, source index, B position) per entry"""
+    s, L = b_rp[src], b_rp[src + 1] - b_rp[src]
+    tot = int(L.sum())
+    sid = np.repeat(np.arange(src.size), L)
+    pos = np.repeat(s - (np.cumsum(L) - L), L) + np.arange(tot)
+    return np.asarray(b_ci, np.int64)[pos], sid, pos
+
+
+def heavy_gather_plan(L, shape):
+    """gather_sweep's decisions for a row whose sources have the lengths L: batches (sources, nonempty, QB, tiles of
+    (nqt, left, nu, starts)), kept, and the cells the plan reaches as strings"""
+    T, qpt, fl = shape
+    tile, step, q = heavy_tile(shape)
+    L = np.asarray(L, np.int64)
+    nq_all = -(-L // 4)
+    names = {1: "1", q: "q", q + 1: "q+1", 2 * q: "2q", 2 * q + 1: "2q+1", 3 * q: "3q", 3 * q + 1: "3q+1", step: "step"}
+    batches, cells = [], set()
+    nb = -(-L.size // T)
+    for j in range(nb):
+        n = nq_all[j * T:(j + 1) * T]
+        QB = int(n.sum())
+        ex = np.cumsum(n) - n
+        st, ln = ex[n > 0], n[n > 0]
+        tiles = []
+        for T0 in range(0, QB, tile):
+            nqt = min(QB - T0, tile)
+            left = nqt - (nqt - 1) // step * step
+            nu = fl if left > 3 * q else 3 * fl // 4 if left > 2 * q else fl // 2 if left > q else fl // 4
+            starts = int(((st >= T0) & (st < T0 + tile)).sum())
+            tiles.append(dict(nqt=nqt, left=left, nu=nu, starts=starts))
+            cells.add("g:nu=%d/4" % (4 * nu // fl))
+            if left in names:
+                cells.add("g:left=" + names[left])
+            if starts == 0:
+                cells.add("g:tile without a start")
+        batches.append(dict(sources=int(n.size), nonempty=int((n > 0).sum()), QB=QB, tiles=tiles))
+        if QB == 0 and nb > 1:
+            cells.add("g:empty batch " + ("first" if j == 0 else "last" if j == nb - 1 else "middle"))
+        if ((st % tile == 0) & (st > 0)).any():
+            cells.add("g:start on quad 0 of a later tile")
+        if (st % tile == tile - 1).any():
+            cells.add("g:start on the last quad of a tile")
+        if (st // tile != (st + ln - 1) // tile).any():
+            cells.add("g:source crosses a tile boundary")
+        if len(tiles) > 1:
+            cells.add("g:several tiles")
+    if nb > 1:
+        cells.add("g:several batches")
+    QBl = batches[-1]["QB"] if batches else 0
+    kept = L.size <= T and 0 < QBl <= tile
+    for k in range(1, 9):
+        if (L == k).any():
+            cells.add("g:len%d" % k)
+    if L.size == T and QBl == tile:
+        cells.add("g:T sources, QB == tile")
+    if L.size == T + 1:
+        cells.add("g:T+1 sources")
+    if nb == 1 and QBl == tile + 1:
+        cells.add("g:QB == tile+1")
+    return dict(batches=batches, kept=bool(kept), QB=QBl, cells=cells)
+
+
+def _quad_cells(c, sid, pos, b_rp, src, nnz_b):
+    """cells of the quads' content: lanes as the kernel lays them (the last quad of a source ends at the source's end, a quad
+    never starts before B.col_idx), word order inside a quad; returns (cells, lane of every entry)"""
+    cells = set()
+    s = b_rp[src][sid]
+    e = b_rp[src + 1][sid]
+    p = pos - s
+    qs = s + 4 * (p // 4)
+    b = np.maximum(np.minimum(qs, e - 4), 0)
+    lane = pos - b
+    nqs = -(-(b_rp[src + 1] - b_rp[src]) // 4)
+    quad = np.repeat(np.cumsum(nqs) - nqs, b_rp[src + 1] - b_rp[src]) + p // 4
+    nquads = int(nqs.sum())
+    w = np.full((nquads, 4), -1, np.int64)
+    w[quad, lane] = c >> 5
+    v = w >= 0
+    for k in range(3):
+        if (v[:, k] & v[:, k + 1] & (w[:, k + 1] < w[:, k])).any():
+            cells.add("g:words not ascending")
+    for i, j in ((0, 2), (1, 3), (0, 3)):
+        if (v[:, i] & v[:, j] & (w[:, i] == w[:, j]) & (w[:, i + 1] != w[:, i])).any():
+            cells.add("g:equal words apart")
+    if (e[pos == e - 1] == nnz_b).any():
+        cells.add("g:quad ends at nnzB")
+    if (np.minimum(qs, e - 4) < 0).any():
+        cells.add("g:quad clamped to 0")
+    return cells, lane
+
+
+def heavy_readout(out, cols, threads, keep=False):
+    """the window read-out of k_dense_rows for the output row `out` (sorted distinct columns): windows and the empty ones,
+    wave_words (every wave's word range [wbeg, wend), empty for the waves of `idle`), per step the outputs and stage_cap, cells"""
+    wwords, nwin, wpw = heavy_window_geometry(cols, threads, keep)
+    waves = threads // 64
+    W = 64 * wwords
+    cells = set()
+    pc = np.bincount(out >> 6, minlength=nwin * wwords).reshape(nwin, wwords)
+    idle = [k for k in range(waves) if k * wpw >= wwords]
+    if idle:
+        cells.add("r:idle waves")
+    w0 = np.arange(0, wwords, READOUT_STEP_WORDS)
+    width = np.minimum(READOUT_STEP_WORDS, wwords - w0)          # (waves start on multiples of the step)
+    cap = 2 * width
+    tot = np.add.reduceat(pc, w0, axis=1)
+    empty_win = tot.sum(axis=1) == 0
+    if empty_win.any():
+        cells.add("r:empty window")
+    if (~empty_win).sum() > 1:
+        cells.add("r:several windows with outputs")
+    staged = (tot > 0) & (tot <= cap)
+    direct = tot > cap
+    tail = np.broadcast_to(width < READOUT_STEP_WORDS, tot.shape)
+    for name, f in (("r:step skipped", (tot == 0) & ~empty_win[:, None]), ("r:step staged", staged & ~tail), ("r:step direct", direct & ~tail),
+                    ("r:outputs == 1", tot == 1), ("r:outputs == stage_cap", (tot == cap) & ~tail), ("r:outputs == stage_cap+1", (tot == cap + 1) & ~tail),
+                    ("r:full step", tot == 64 * width), ("r:tail staged", staged & tail), ("r:tail direct", direct & tail),
+                    ("r:tail outputs == stage_cap", (tot == cap) & tail), ("r:tail outputs == stage_cap+1", (tot == cap + 1) & tail),
+                    ("r:tail skipped", (tot == 0) & tail & ~empty_win[:, None])):
+        if f.any():
+            cells.add(name)
+    dmask = np.repeat(direct, width, axis=1)
+    dp = pc[dmask]
+    for k in HEAVY_POPS:
+        if (dp == k).any():
+            cells.add("r:direct pop %d" % k)
+    have = set(out[np.isin(out, np.concatenate([np.arange(1, nwin) * W + d for d in (-1, 0, 1)] + [[cols - 1]]))].tolist()) if out.size else set()
+    for k in range(1, nwin):
+        for d, name in ((-1, "below"), (0, "at"), (1, "above")):
+            if k * W + d < cols:
+                cells.add("r:column %s a boundary %s" % (name, "set" if k * W + d in have else "clear"))
+    if cols - 1 in have:
+        cells.add("r:last column")
+        if cols % W == 1 and nwin > 1:
+            cells.add("r:last window of one column")
+    return dict(wwords=wwords, nwin=nwin, wpw=wpw, idle=idle, wave_words=[(min(k * wpw, wwords), min((k + 1) * wpw, wwords)) for k in range(waves)],
+                tail=int(width[-1]) if width[-1] < READOUT_STEP_WORDS else 0,
+                empty_windows=np.flatnonzero(empty_win).tolist(), step_total=tot, stage_cap=cap, cells=cells)
+
+
+def heavy_count_windows(fcols, prod, cols):
+    """the windows of k_dense_rows_count for a row with the distinct in-range mask columns `fcols` (sorted): a list of
+    (lo, W, what) with what in skipped / narrowed / swept, and the cells"""
+    out, cells = [], set()
+    lo, W = 0, COUNT_MAX_COLS
+    swept = 0
+    while lo < cols:
+        W = min(W, cols - lo)
+        nd = int(np.searchsorted(fcols, lo + W) - np.searchsorted(fcols, lo))
+        if nd == 0:
+            out.append((lo, W, "skipped"))
+            cells.add("c:window skipped")
+            lo += W
+            W = min(2 * W, COUNT_MAX_COLS)
+            continue
+        if nd > COUNT_SLOTS:
+            out.append((lo, W, "narrowed"))
+            cells.add("c:window narrowed")
+            Wn = W >> 1
+            while Wn > COUNT_SLOTS and Wn * nd > COUNT_SLOTS * W:
+                Wn >>= 1
+            W = Wn & ~31
+            continue
+        out.append((lo, W, "swept"))
+        if swept == 0 and lo > 0:
+            cells.add("c:first sweep in a later window")
+        swept += 1
+        np_ = int(np.searchsorted(prod, lo + W) - np.searchsorted(prod, lo))
+        cells.add("c:swept window " + ("with products" if np_ else "without a product"))
+        lo += W
+        if nd <= COUNT_SLOTS // 2:
+            W = min(2 * W, COUNT_MAX_COLS)
+    return out, swept, cells
+
+
+def heavy_rank(prod, dcols, cols, mode):
+    """k_rank_rows for a row with the distinct product columns `prod` and D's distinct in-range columns `dcols` (Insert)"""
+    cells = set()
+    span = min(cols, RANK_SPAN)
+    topw = -(-(-(-span // 1024)) // RANK_THREADS) * RANK_THREADS
+    nspans = -(-cols // RANK_SPAN)
+    cells.add("k:topw %d" % topw)
+    spans = []
+    for sp in range(nspans):
+        lo = sp * RANK_SPAN
+        p = prod[(prod >= lo) & (prod < lo + RANK_SPAN)] - lo
+        d = dcols[(dcols >= lo) & (dcols < lo + RANK_SPAN)] - lo if mode == "insert" else prod[:0]
+        allc = np.union1d(p, d)
+        slots = np.unique(allc >> 5)
+        nslots = int(slots.size)
+        spt = min(max(-(-nslots // RANK_THREADS), 1), RANK_CAP // RANK_THREADS)
+        spans.append(dict(nslots=nslots, spt=spt, products=int(p.size)))
+        if nslots:
+            cells.add("k:spt %d" % spt)
+            first = np.arange(0, nslots, spt)[:RANK_THREADS]        # the first slot of every thread that owns one
+            tw = slots >> 5
+            firsts = np.flatnonzero(np.concatenate([[True], tw[1:] != tw[:-1]]))
+            if not np.isin(first, firsts).all():
+                cells.add("k:skip > 0")
+            if (np.diff(np.append(firsts, nslots)) == 32).any():
+                cells.add("k:full top word")
+            if (np.bincount(np.searchsorted(slots, allc >> 5)) == 32).any():
+                cells.add("k:full slot")
+        if p.size == 0:
+            cells.add("k:span without a product" + (", D reaches it" if d.size else ""))
+    if nspans > 1 and cols % RANK_SPAN == 1 and cols - 1 in set(prod[-1:].tolist()):
+        cells.add("k:last span of one column")
+    return dict(topw=topw, spans=spans, cells=cells)
+
+
+def heavy_model(a_rp, a_ci, b_rp, b_ci, cols, mode, r0, r1, f=None):
+    """What the heavy-row kernels decide for the product over rows [r0, r1), from the operands alone (numpy, no GPU).
+    mode: none | keep | drop | insert | count; f = (f_rp, f_ci): the mask, or D.  Returns dict(F, bins, rows): rows maps every
+    heavy row to dict(kernel, shape, plan, out, cells) -- kernel one of rank / rank spans / win512 / win1024 / keep / count,
+    plan from heavy_gather_plan, cells the set of every cell of the issue's lists that the row reaches (strings)."""
+    assert mode in HEAVY_MODES and (f is not None or mode == "none")
+    a_rp, b_rp = np.asarray(a_rp, np.int64), np.asarray(b_rp, np.int64)
+    a_ci = np.asarray(a_ci, np.int64)
+    F = row_products(a_rp, a_ci, b_rp, r0, r1)
+    flen = np.diff(np.asarray(f[0], np.int64))[r0:r1] if f is not None else np.zeros(r1 - r0, np.int64)
+    if mode in ("keep", "count"):
+        bins = masked_row_bins(F, flen, cols)
+    else:
+        bins = row_bins(F + flen if mode == "insert" else F, cols)
+    nnz_b = int(b_rp[-1])
+    rows = {}
+    for i in np.flatnonzero(bins > 16) + r0:
+        b = int(bins[i - r0])
+        if mode in ("keep", "count"):
+            kernel, threads = mode, 1024
+        elif b == RANK_BIN:
+            kernel, threads = ("rank spans" if cols > RANK_SPAN else "rank"), 512
+        else:
+            kernel, threads = ("win512", 512) if b == MID_BIN else ("win1024", 1024)
+        shape = HEAVY_SHAPES[threads]
+        src = a_ci[a_rp[i]:a_rp[i + 1]]
+        L = b_rp[src + 1] - b_rp[src]
+        plan = heavy_gather_plan(L, shape)
+        cells = set(plan["cells"])
+        c, sid, pos = _row_entries(b_rp, b_ci, src)
+        qc, lane = _quad_cells(c, sid, pos, b_rp, src, nnz_b)
+        cells |= qc
+        if (src == 0).any() and 1 <= b_rp[1] - b_rp[0] <= 3:
+            cells.add("g:B row 0 of 1-3 entries")
+        if ((src == b_rp.size - 2) & (L > 0)).any():
+            cells.add("g:B's last row")
+        prod = np.unique(c)
+        fc = np.asarray(f[1][f[0][i]:f[0][i + 1]], np.int64) if f is not None else prod[:0]
+        fin = np.unique(fc[(fc >= 0) & (fc < cols)])
+        out = {"none": prod, "drop": np.setdiff1d(prod, fin), "insert": np.union1d(prod, fin)}.get(mode, np.intersect1d(prod, fin))
+        r = dict(row=int(i), F=int(F[i - r0]), bin=b, kernel=kernel, shape=shape, plan=plan, out=out)
+        later = False
+        if kernel.startswith("rank"):
+            r["rank"] = heavy_rank(prod, fin, cols, mode)
+            cells |= r["rank"]["cells"]
+            r["held"] = kernel == "rank" and plan["kept"] and plan["QB"] <= shape[0] * shape[2]
+            later = not r["held"]
+            cells.add("g:held" if r["held"] else "g:not held")
+            W = RANK_SPAN
+        elif kernel == "count":
+            r["windows"], swept, cc = heavy_count_windows(fin, prod, cols)
+            cells |= cc
+            later = swept > 1
+            W = COUNT_MAX_COLS
+        else:
+            r["readout"] = heavy_readout(out, cols, threads, kernel == "keep")
+            cells |= r["readout"]["cells"]
+            later = r["readout"]["nwin"] > 1
+            W = 64 * r["readout"]["wwords"]
+        cells.add("g:plan kept" if plan["kept"] else "g:plan not kept")
+        if plan["kept"] and later:
+            cells.add("g:plan kept and used")
+        if mode != "none" and kernel != "count":
+            nw = -(-cols // W)
+            pw = np.bincount(prod // W, minlength=nw) > 0
+            if (fc >= cols).any():
+                cells.add("f:column at or beyond cols")
+            if fin.size and (~pw[fin // W]).any():
+                cells.add("f:column in a window without a product")
+            if fin.size and pw[fin // W].any():
+                cells.add("f:column in a window with products")
+            if np.intersect1d(prod, fin).size:
+                cells.add("f:column that is a product")
+            if mode == "drop" and not kernel.startswith("rank"):
+                l0 = np.bincount(c[lane == 0] // W, minlength=nw) > 0
+                hit = np.bincount(np.intersect1d(prod, fin) // W, minlength=nw) > 0
+                if (pw & ~l0 & hit).any():
+                    cells.add("f:dropped product in a window fed by lanes 1-3 only")
+        if mode == "count" and (fc >= cols).any():
+            cells.add("f:column at or beyond cols")
+        r["later_sweep"] = bool(later)
+        r["cells"] = cells
+        rows[int(i)] = r
+    return dict(F=F, bins=bins, rows=rows, flen=flen)
+
+
+# ---- shapes that drive the heavy-row kernels into their edges: heavy_gather_case, heavy_readout_case, heavy_masks ------------
+ROW0, EMPTY, LAST = -1, -2, -3          # the shared B rows in a row's source list (_heavy_assemble)
+HEAVY_COLS = (6000, (1 << 18) + 1, (1 << 20) + 1, 3 * (1 << 20) + 777)
+_READOUT_CYCLE = ("one", "cap", "zero", "cap+1", "pops", "noise", "zero", "full", "one", "zero")
+READOUT_VARIANTS = len(_READOUT_CYCLE)
+
+
+def _heavy_columns(rng, cols, n, lo=0, hi=None):
+    """n product columns of [lo, hi) in gather order: distinct while they fit, then one in fifty overwritten by another; unsorted"""
+    hi = cols if hi is None else hi
+    c = _strata(rng, 1, n, lo, hi)[0] if n <= hi - lo else lo + np.arange(n, dtype=np.int64) % (hi - lo)
+    c = rng.permutation(c)
+    if n >= 50:
+        c[rng.integers(0, n, size=n // 50)] = c[rng.integers(0, n, size=n // 50)]
+    return c
+
+
+def _gather_sources(rng, cols, nsrc, QB, fmin=0, fmax=None, shared=True):
+    """the sources of one A row as _heavy_assemble takes them: `nsrc` sources of exactly `QB` quads in all (a quad: four
+    entries of one B row or its remainder), fmin <= products <= fmax.  With `shared` (and room): B row 0 first (two
+    entries, one quad), the shared empty B row in the middle and B's last row (five entries, two quads) last.  Lengths
+    1 .. 8 are present where the row has sources of one and two quads; sources beyond the quads are empty B rows."""
+    fixed = shared and nsrc >= 8 and QB >= 8
+    m, Q, Ff = (nsrc - 3, QB - 3, 7) if fixed else (nsrc, QB, 0)
+    nq = np.zeros(m, np.int64)
+    ne = min(m, Q)
+    nq[:ne] = 1
+    if Q > ne:
+        nq[:ne] += rng.multinomial(Q - ne, np.full(ne, 1.0 / ne))
+    r = rng.integers(0, 4, size=m)                          # entries the last quad of the source lacks
+    r[nq == 0] = 0
+    for k in (1, 2):
+        idx = np.flatnonzero(nq == k)[:4]
+        r[idx] = np.array([3, 2, 1, 0])[:idx.size]
+    F = Ff + 4 * int(nq.sum()) - int(r.sum())
+    fmax = max(F, fmin) if fmax is None else fmax
+    if not fmin <= F <= fmax:
+        up = F > fmax                                       # more entries lacking, or fewer
+        need = F - fmax if up else fmin - F
+        order = rng.permutation(np.flatnonzero(nq > 0))
+        room = 3 - r[order] if up else r[order]
+        cum = np.cumsum(room)
+        k = int(np.searchsorted(cum, need))
+        assert k < order.size, "no row of %d sources and %d quads has %d .. %d products" % (nsrc, QB, fmin, fmax)
+        r[order[:k + 1]] = 3 if up else 0
+        r[order[k]] += -(int(cum[k]) - need) if up else int(cum[k]) - need
+    L = (4 * nq - r)[rng.permutation(m)]
+    assert fmin <= Ff + int(L.sum()) <= fmax and int((-(-L // 4)).sum()) == Q
+    src = np.split(_heavy_columns(rng, cols, int(L.sum())), np.cumsum(L)[:-1])
+    return [ROW0] + src[:m // 2] + [EMPTY] + src[m // 2:] + [LAST] if fixed else src
+
+
+def _quad_sources(rng, cols, quads):
+    """sources of exactly the given quad counts (full quads), in this order"""
+    L = 4 * np.asarray(quads, np.int64)
+    return np.split(_heavy_columns(rng, cols, int(L.sum())), np.cumsum(L)[:-1])
+
+
+def _heavy_assemble(cols, rows, names, **kw):
+    """A and B from per-row source lists.  A source is an int array (a B row of its own: any order, repeats, empty), ROW0 /
+    EMPTY / LAST (the shared B rows: row 0 = {cols - 1, 0}, row 1 empty, B's last row of five entries around the last
+    column) or ("again", k): source k of the same row once more (a repeated column of A)."""
+    b_lens, b_cols = [2, 0], [np.array([cols - 1, 0], np.int64)]
+    lists = []
+    for srcs in rows:
+        ids = []
+        for s in srcs:
+            if isinstance(s, tuple):
+                ids.append(ids[s[1]])
+            elif isinstance(s, (int, np.integer)):
+                ids.append({ROW0: 0, EMPTY: 1, LAST: -1}[int(s)])
+            else:
+                ids.append(len(b_lens))
+                b_lens.append(s.size)
+                b_cols.append(np.asarray(s, np.int64))
+        lists.append(np.array(ids, np.int64))
+    last = len(b_lens)
+    b_lens.append(5)
+    b_cols.append(np.array([cols - 1, min(1, cols - 1), cols - 1, min(64, cols - 1), cols // 2], np.int64))
+    a_ci = np.concatenate(lists)
+    a_ci[a_ci == -1] = last
+    a_rp = np.concatenate([[0], np.cumsum([x.size for x in lists])])
+    b_rp = np.concatenate([[0], np.cumsum(b_lens)])
+    b_ci = np.concatenate(b_cols)
+    assert b_ci.min() >= 0 and b_ci.max() < cols and b_rp[-1] < 2**31
+    i32 = lambda x: np.ascontiguousarray(x, np.int32)
+    return dict(a_rp=i32(a_rp), a_ci=i32(a_ci), b_rp=i32(b_rp), b_ci=i32(b_ci), ncols=cols, names=list(names), **kw)
+
+
+def _light_rows(rng, cols):
+    return [[_heavy_columns(rng, cols, 10)], [EMPTY, EMPTY], [], [ROW0, _heavy_columns(rng, cols, 100)]]
+
+
+def heavy_gather_case(cols, seed):
+    """A and B for the gather of the heavy rows (heavy_gather.hpp gather_sweep): per thread shape rows of exact (sources, QB):
+    QB mod step in {1, q, q+1, 2q, 2q+1, 3q, 3q+1, 0}; exactly `threads` sources with QB == tile, threads + 1 sources,
+    QB == tile + 1; batches without a non-empty source first, in the middle and last; sources that start on the last quad
+    of a tile, on quad 0 of the next, that cross a tile boundary; one B row of 2 * tile quads behind a one-quad source, so that
+    a whole tile has no start.  Every row's sources are B rows of its own, unsorted with repeats, among them B row 0 (two
+    entries), empty B rows and B's last row.  The products of every row fit the class the row is meant for at this column
+    count (gen.heavy_model is the authority on where it lands); two more rows lie in the last class."""
+    rng = np.random.default_rng(seed)
+    mid_cap, rank_cap = _mid_rank_caps(cols)
+    rows, names = [], []
+
+    def add(name, srcs):
+        rows.append(srcs)
+        names.append(name)
+
+    G = lambda *a, **k: _gather_sources(rng, cols, *a, **k)
+    empty_batch = lambda T: [EMPTY] * T
+    # ---- the rank class (512, 8, 4): at most 6144 products; D of heavy_masks adds up to 16 (Insert bins by F_i + |D_i|)
+    if rank_cap:
+        lo, hi = HEAVY_MIN + 1, rank_cap - 16
+        for QB, nsrc in ((513, 20), (1024, 200), (1025, 300), (1536, 400), (1537, 512), (800, 513), (1900, 512)):
+            add("rank QB %d, %d sources" % (QB, nsrc), G(nsrc, QB, lo, hi, shared=QB > 513))   # (513 quads with B row 0: 2047 products)
+        add("rank, batches of 512, 1, 0, 700 quads", G(512, 512, shared=False) + G(512, 1, shared=False) + empty_batch(512) + G(300, 700, 700, 2800))
+        add("rank, empty batch first", empty_batch(512) + G(300, 900, lo, hi))
+        add("rank, empty batch last", G(512, 1000, lo, hi) + empty_batch(512))
+        add("rank, 6000 one-entry sources", [c for c in _heavy_columns(rng, cols, 6000).reshape(-1, 1)])
+    # ---- the 512-thread window shape: above the rank class, at most mid_cap products
+    T, (tile, step, q) = 512, heavy_tile(HEAVY_SHAPES[512])
+    lo, hi = max(rank_cap, HEAVY_MIN) + 1, mid_cap
+    for r in (1, q, q + 1, 2 * q, 2 * q + 1, 3 * q, 3 * q + 1, step):
+        add("win512 QB step + %d" % r, G(300, step + r, lo, hi))
+    add("win512 %d sources, QB == tile" % T, G(T, tile, lo, hi))
+    add("win512 %d sources" % (T + 1), G(T + 1, tile, lo, hi))
+    add("win512 QB == tile + 1", G(400, tile + 1, lo, hi))
+    add("win512, empty batch first", empty_batch(T) + G(300, 2500, lo, hi))
+    add("win512, empty batch in the middle", G(T, 1200, shared=False) + empty_batch(T) + G(300, 1300, lo - 4800, hi - 4800))
+    add("win512, empty batch last", G(T, 2400, lo, hi) + empty_batch(T))
+    add("win512, tile-boundary sources", _quad_sources(rng, cols, [tile - 1, 1, 2, 3, tile + 90, 7]))
+    add("win512, a tile without a start", [ROW0] + _quad_sources(rng, cols, [2 * tile, 5]) + [LAST])
+    # ---- the 1024-thread shape: Keep and Count at any size, None / Drop / Insert above mid_cap
+    T, (tile, step, q) = 1024, heavy_tile(HEAVY_SHAPES[1024])
+    k = mid_cap // (4 * step) + 1
+    k = k if k <= 4 else 2                                  # (above that the rows would cost millions of products: Keep and Count only)
+    lo = mid_cap + 1 if 4 * step * k > mid_cap else HEAVY_MIN + 1
+    for r in (1, q, q + 1, 2 * q, 2 * q + 1, 3 * q, 3 * q + 1, step):
+        add("win1024 QB %d steps + %d" % (k, r), G(700, k * step + r, min(lo, 4 * (k * step + r) - 2200)))
+    add("win1024 %d sources, QB == tile" % T, G(T, tile, 4 * tile, shared=False))
+    add("win1024 %d sources" % (T + 1), G(T + 1, tile, 4 * tile - 3000))
+    add("win1024 QB == tile + 1", G(600, tile + 1, 4 * tile - 1000))
+    add("win1024, empty batches first, in the middle and last",
+        empty_batch(T) + G(T, 9000, shared=False) + empty_batch(T) + G(500, 8000) + empty_batch(T))
+    add("win1024, tile-boundary sources", _quad_sources(rng, cols, [tile - 1, 1, 2, 3, tile + 90, 7]))
+    add("win1024, a tile without a start", [ROW0] + _quad_sources(rng, cols, [2 * tile, 5]) + [LAST])
+    for j in range(2):                                      # the last class holds at least two rows: the hub-row ordering runs
+        s = G(1500, mid_cap // 4 + 900, mid_cap + 1)
+        add("hub row %d" % j, s + [("again", 3), ("again", 4)])
+    for srcs in _lane_rows(rng, cols):
+        add("lane row", srcs)
+    mid = len(rows) // 2
+    light = _light_rows(rng, cols)
+    rows[mid:mid] = light
+    names[mid:mid] = ["light"] * len(light)
+    # `late` rows (heavy_masks): the rows that keep their plan get a mask without a column below 2^18 -- Count's first product
+    # sweep, which builds the plan, then happens in a later window
+    return _heavy_assemble(cols, rows, names, lane_rows=[i for i, n in enumerate(names) if n == "lane row"],
+                           late_rows=[i for i, n in enumerate(names) if "QB == tile" in n] if cols > COUNT_MAX_COLS else [])
+
+
+def _pick(rng, lo, hi, n, have):
+    """n distinct columns of [lo, hi), those of `have` among them"""
+    pool = np.setdiff1d(np.arange(lo, hi, dtype=np.int64), have)
+    return np.concatenate([have, rng.permutation(pool)[:n - have.size]])
+
+
+def _pops_step(rng, lo, nfull, width):
+    """the columns of a direct step: one word of each popcount of HEAVY_POPS (as many as the step has whole words, the
+    fullest first), two columns in every other whole word: more than stage_cap = 2 * width outputs"""
+    if nfull == 0:
+        return np.zeros(0, np.int64)
+    words = rng.permutation(nfull)
+    pops = sorted(HEAVY_POPS, reverse=True)[:nfull]
+    out = [lo + 64 * int(w) + rng.permutation(64)[:p] for w, p in zip(words, pops)]
+    out += [lo + 64 * int(w) + rng.permutation(64)[:2] for w in words[len(pops):]]
+    c = np.concatenate(out)
+    return c if c.size > 2 * width else c[:0]
+
+
+def _readout_output(rng, cols, threads, keep, variant, budget):
+    """(S, X): the output row S prescribed per read-out step of the window shape (`threads`, keep) at `cols` columns, and noise
+    columns X in steps of their own.  Step t takes the kind _READOUT_CYCLE[(t + variant) % 10]: no output, one, exactly
+    stage_cap, stage_cap + 1, a full step, a direct step with words of every popcount of HEAVY_POPS, noise; in random
+    order while the budget of distinct columns lasts.  Even variants set the three columns around every window boundary and
+    the last column; odd variants set none of them and leave every fourth window empty."""
+    wwords, nwin, _ = heavy_window_geometry(cols, threads, keep)
+    W = 64 * wwords
+    nsteps = -(-wwords // READOUT_STEP_WORDS)
+    pre = np.zeros(0, np.int64)
+    if variant % 2 == 0:
+        pre = np.concatenate([np.arange(1, nwin) * W + d for d in (-1, 0, 1)] + [[cols - 1]]).astype(np.int64)
+        pre = np.unique(pre[(pre >= 0) & (pre < cols)])
+    S, X, spent, placed = [pre], [], pre.size, np.zeros(pre.size, bool)
+    for t in rng.permutation(nwin * nsteps):
+        win, st = divmod(int(t), nsteps)
+        w0 = st * READOUT_STEP_WORDS
+        width = min(READOUT_STEP_WORDS, wwords - w0)
+        lo = win * W + 64 * w0
+        hi = min(lo + 64 * width, cols)
+        if hi <= lo or (nwin > 1 and variant % 2 == 1 and (win + variant // 2) % 4 == 3):
+            continue
+        have = pre[(pre >= lo) & (pre < hi)]
+        kind = _READOUT_CYCLE[(int(t) + variant) % READOUT_VARIANTS]
+        if kind == "pops":
+            c = _pops_step(rng, lo, (hi - lo) // 64, width)
+        else:
+            n = {"zero": 0, "one": 1, "cap": 2 * width, "cap+1": 2 * width + 1, "full": 64 * width, "noise": min(40, hi - lo)}[kind]
+            if n > hi - lo or n < have.size:
+                continue
+            c = _pick(rng, lo, hi, n, have)
+        if spent + c.size > budget:
+            continue
+        spent += c.size
+        (X if kind == "noise" else S).append(c)
+    return np.unique(np.concatenate(S)), np.unique(np.concatenate(X)) if X else pre[:0]
+
+
+def _sources_from_output(rng, cols_out, F):
+    """sources whose products are exactly the columns `cols_out`, F of them (repeats fill up), unsorted, in B rows of mixed lengths"""
+    c = rng.permutation(cols_out[np.arange(F) % cols_out.size])
+    nsrc = max(2, min(200, F // 40))
+    L = rng.multinomial(F - nsrc, np.full(nsrc, 1.0 / nsrc)) + 1
+    L[0] += L[1] - 1                                        # one long source, one of one entry
+    L[1] = 1
+    src = np.split(c, np.cumsum(L)[:-1])
+    return src[:nsrc // 2] + [EMPTY] + src[nsrc // 2:] + [("again", 2)]
+
+
+def _rank_output(rng, cols, nslots, variant):
+    """the product columns of a rank row: `nslots` 32-column words in span `variant % spans` (a whole 1024-column top word
+    among them, whole 32-column slots, 2100 products or nslots + 50), and in the other spans five columns each or none"""
+    nspans = -(-cols // RANK_SPAN)
+    sp = variant % nspans
+    lo = sp * RANK_SPAN
+    hi = min(lo + RANK_SPAN, cols)
+    if hi - lo < 32 * nslots + 2048:                        # (a last span of a few columns: take the first)
+        sp, lo, hi = 0, 0, min(RANK_SPAN, cols)
+    nw = (hi - lo) // 32
+    g = int(rng.integers(0, nw // 32)) * 32
+    words = np.concatenate([np.arange(g, g + 32), rng.permutation(np.setdiff1d(np.arange(nw), np.arange(g, g + 32)))[:nslots - 32]])
+    bits = np.ones(nslots, np.int64)
+    extra = max(2100, nslots + 50) - nslots
+    nfull = min(extra // 31, nslots - 1)
+    bits[:nfull] = 32
+    bits[nfull] += min(extra - 31 * nfull, 30)
+    bits = rng.permutation(bits)
+    out = [lo + 32 * int(w) + rng.permutation(32)[:b] for w, b in zip(words, bits)]
+    if (variant // nspans) % 2 == 0:
+        for s in range(nspans):
+            if s != sp:
+                s_lo, s_hi = s * RANK_SPAN, min((s + 1) * RANK_SPAN, cols)
+                out.append(np.unique(np.concatenate([rng.integers(s_lo, s_hi, size=5), [s_hi - 1, s_lo]])))
+    return np.unique(np.concatenate(out))
+
+
+RANK_SLOT_TARGETS = (70, 400, 900, 1300, 2000, 2500, 3000, 3500, 4000, 4500, 5000, 5500, 6000)   # spt 1, 1, 2 .. 12
+
+
+def heavy_readout_case(cols, seed):
+    """A and B whose heavy rows have their OUTPUT prescribed: per window shape (512 threads, 1024 threads, Keep's windows)
+    READOUT_VARIANTS rows from _readout_output, sized into the class that takes the shape at this column count (repeats fill
+    the products up); and rank rows of RANK_SLOT_TARGETS slots (_rank_output) where the class exists.  `sx` maps a row to
+    its (S, X), `made_for` to the shape it was built for: heavy_masks gives Keep's rows the mask S, the others X."""
+    rng = np.random.default_rng(seed)
+    mid_cap, rank_cap = _mid_rank_caps(cols)
+    rows, names, sx, made_for, variant = [], [], {}, {}, {}
+    lo512 = max(rank_cap, HEAVY_MIN) + 1
+    plans = [("win512", 512, False, READOUT_VARIANTS, lo512 + 40, mid_cap - 1000),
+             ("win1024", 1024, False, READOUT_VARIANTS if mid_cap < 200000 else 4, mid_cap + 1, mid_cap + 30000),
+             ("keep", 1024, True, READOUT_VARIANTS, HEAVY_MIN + 40, 60000)]
+    for name, threads, keep, nvar, fmin, fmax in plans:
+        for v in range(nvar):
+            S, X = _readout_output(rng, cols, threads, keep, v, fmax - 100)
+            if S.size + X.size == 0:                        # (one step in all, and its turn is "no output": a heavy row has one)
+                S = np.array([cols // 3], np.int64)
+            out = np.union1d(S, X)
+            sx[len(rows)], made_for[len(rows)], variant[len(rows)] = (S, X), name, v
+            rows.append(_sources_from_output(rng, out, max(fmin, out.size + 30)))
+            names.append("%s variant %d" % (name, v))
+    if rank_cap:
+        for v, ns in enumerate(RANK_SLOT_TARGETS):
+            rows.append(_sources_from_output(rng, _rank_output(rng, cols, ns, v), max(2100, ns + 50) + 20))
+            names.append("rank %d slots" % ns)
+    mid = len(rows) // 2
+    light = _light_rows(rng, cols)
+    rows[mid:mid] = light
+    names[mid:mid] = ["light"] * len(light)
+    shift = lambda d: {(i if i < mid else i + len(light)): x for i, x in d.items()}
+    return _heavy_assemble(cols, rows, names, sx=shift(sx), made_for=shift(made_for), variant=shift(variant))
+
+
+def _lane_rows(rng, cols):
+    """two rows for Drop whose windows above the first receive products in lanes 1 to 3 of their quads only: every B row is
+    whole quads whose first entry lies below 2^18 (2^20 for the row of the 1024-thread shape) and whose others lie above"""
+    mid_cap, rank_cap = _mid_rank_caps(cols)
+    out = []
+    for W, F in ((1 << 18, max(rank_cap, HEAVY_MIN) + 2000), (1 << 20, mid_cap + 2000)):
+        if cols <= W + 64 or (W == 1 << 18 and F > mid_cap):
+            continue
+        n = -(-F // 4)
+        quad = np.stack([_heavy_columns(rng, cols, n, 0, W)] + [_heavy_columns(rng, cols, n, W, cols) for _ in range(3)], axis=1)
+        out.append(np.split(quad.ravel(), [4 * (n // 3), 4 * (n // 2)]))
+    return out
+
+
+def heavy_masks(s, seed):
+    """The mask F (f_rp, f_ci: Keep, Drop, Count) and D (d_rp, d_ci: Insert) of a heavy case, from its product pattern.
+    F's row: the row's product columns X (rows with `sx` made for Keep: S; the others half of the products; lane rows: the
+    products from 2^18 on; `late` rows, for Count: none below 2^18), one column in a window without a product per window
+    width (2^18, 2^19, 2^20), columns at and beyond B.cols, some entries twice, and -- rows of at most 8192 products and
+    every other row -- columns at or beyond B.cols up to 2100 stored entries, so that Keep and Count send the row to the window kernels.
+    D's row: at most 16 entries: three products, a column per empty window, the last column, columns beyond, one twice."""
+    rng = np.random.default_rng(seed)
+    cols = s["ncols"]
+    a_rp, b_rp = s["a_rp"].astype(np.int64), s["b_rp"].astype(np.int64)
+    R = a_rp.size - 1
+    F = row_products(a_rp, s["a_ci"], b_rp, 0, R)
+    frows, drows = [], []
+    for i in range(R):
+        prod = np.unique(_row_entries(b_rp, s["b_ci"], s["a_ci"][a_rp[i]:a_rp[i + 1]].astype(np.int64))[0])
+        if F[i] <= HEAVY_MIN:
+            frows.append(prod[:3])
+            drows.append(np.array([cols - 1, cols], np.int64))
+            continue
+        if i in s.get("sx", {}):
+            inr = s["sx"][i][0] if s["made_for"][i] == "keep" else s["sx"][i][1]
+        elif i in s.get("lane_rows", ()):
+            inr = prod[prod >= (1 << 18)]
+        else:
+            inr = rng.permutation(prod)[:(prod.size + 1) // 2]
+        if i in s.get("late_rows", ()):
+            inr = inr[inr >= COUNT_MAX_COLS]
+        empties = []
+        for W in (1 << 18, 1 << 19, 1 << 20):
+            nw = -(-cols // W)
+            free = np.flatnonzero(np.bincount(prod // W, minlength=nw) == 0)
+            if free.size:
+                w = int(free[rng.integers(0, free.size)])
+                empties.append(int(rng.integers(w * W, min((w + 1) * W, cols))))
+        beyond = np.array([cols, cols + 1, cols + (1 << 18), INT_MAX - 1], np.int64)
+        row = np.concatenate([inr, np.array(empties, np.int64), beyond])
+        row = np.concatenate([row, row[rng.integers(0, row.size, size=5)]])
+        if (F[i] <= MASK_WAVE_MAX_PRODUCTS or i % 2 == 0) and row.size < 2100:
+            row = np.concatenate([row, rng.integers(cols, INT_MAX, size=2100 - row.size)])
+        frows.append(rng.permutation(row))
+        d = np.concatenate([rng.permutation(prod)[:3], np.array(empties, np.int64), [cols - 1, cols, cols + 7, INT_MAX - 1]])
+        if s.get("variant", {}).get(i, 0) % 2 == 1:         # (the odd variants keep their prescribed output under Insert)
+            d = np.concatenate([rng.permutation(prod)[:3], [cols, cols + 7, INT_MAX - 1]])
+        drows.append(rng.permutation(np.concatenate([d, d[:1]])))
+    out = dict(s)
+    for key, rws in (("f", frows), ("d", drows)):
+        out[key + "_rp"] = np.concatenate([[0], np.cumsum([r.size for r in rws])]).astype(np.int32)
+        out[key + "_ci"] = np.concatenate(rws).astype(np.int32)
+    return out
