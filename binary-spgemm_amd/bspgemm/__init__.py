@@ -58,7 +58,7 @@ EXPORTS = [
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
-    "bspgemm_strongly_connected_components",
+    "bspgemm_strongly_connected_components", "bspgemm_graph_coloring",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
 
@@ -209,6 +209,7 @@ def lib():
     L.bspgemm_core_numbers.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_kcore.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
     L.bspgemm_strongly_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_graph_coloring.argtypes = [VP, VP, C.c_int, C.c_uint, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -550,6 +551,20 @@ class Context:
         _chk(lib().bspgemm_strongly_connected_components(self._h, A._h, C.byref(m), C.byref(nc), C.byref(rounds),
                                                          C.byref(sweeps)), "bspgemm_strongly_connected_components")
         return Matrix(self, m, keep=None), nc.value, rounds.value, sweeps.value
+
+    COLOR_ORDERS = {"natural": 1, "random": 2, "largest": 3, "largest_first": 3}
+
+    def graph_coloring(self, A, order="random", seed=0):
+        """bspgemm_graph_coloring: (P as a Matrix, ncolors, rounds) -- the greedy colouring of the simple undirected graph
+        of A's entries; P.download()[1] is the colour array, colour(v) = what sequential first fit gives in the order of
+        the keys that include/bspgemm.h defines for order ("natural", "random", "largest") and seed; class 0 is a maximal
+        independent set; device-resident Jones-Plassmann sweep, no product; rounds = frontier launches"""
+        if order not in self.COLOR_ORDERS:
+            raise ValueError("order must be one of %s" % sorted(self.COLOR_ORDERS))
+        m, nc, rounds = C.c_void_p(), C.c_int(), C.c_int()
+        _chk(lib().bspgemm_graph_coloring(self._h, A._h, self.COLOR_ORDERS[order], int(seed) & 0xFFFFFFFF, C.byref(m),
+                                          C.byref(nc), C.byref(rounds)), "bspgemm_graph_coloring")
+        return Matrix(self, m, keep=None), nc.value, rounds.value
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

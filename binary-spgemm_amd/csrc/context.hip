@@ -277,6 +277,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     ctx->dropin_timing = getenv("BSPGEMM_DROPIN_TIMING") != nullptr;
     ctx->kcore_timing = getenv("BSPGEMM_KCORE_TIMING") != nullptr;
     ctx->scc_timing = getenv("BSPGEMM_SCC_TIMING") != nullptr;
+    ctx->color_timing = getenv("BSPGEMM_COLOR_TIMING") != nullptr;
     if (ctx->debug_alloc)
         fprintf(stderr, "[bspgemm] device %d: %s, %zu MiB, %d CUs; result cache budget %zu MiB\n", device,
                 prop.gcnArchName, (size_t)(prop.totalGlobalMem >> 20), prop.multiProcessorCount, ctx->cache_budget >> 20);

@@ -144,6 +144,7 @@ struct bspgemm_context {
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
     bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
     bool scc_timing = false;            // BSPGEMM_SCC_TIMING: trim / forward / backward launch counts and times of the strong components on stderr
+    bool color_timing = false;          // BSPGEMM_COLOR_TIMING: stage times of the graph colouring on stderr (it then synchronises twice per launch)
 };
 
 extern "C" int bspgemm_par_max_plus_one(const int *idx, long long n);              // host/par_copy.c
@@ -236,6 +237,10 @@ struct FlagScratch {
 // Lays the scratch of E entries out from int offset `at` of tmp, every array on a 16-byte boundary, and returns the end;
 // 0: more words than the scan's int count takes.  sc NULL: the end alone (what to ask ensure_tmp for: tmp may move).
 size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratch *sc);
+// ints of the workspace that a transpose of E entries with `cols` columns takes (transpose.hip; 0: none, or E is refused),
+// and the most that bspgemm_matrix_symmetrize of an n x n operand of E entries takes over all its stages (setop.hip)
+size_t transpose_workspace_ints(long long E, int cols);
+size_t symmetrize_workspace_ints(long long E, int n);
 
 // ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip) ---
 // What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
@@ -277,7 +282,7 @@ static inline bspgemm_status fail_stuck(const char *who)
     snprintf(g_err, sizeof g_err, "%s: did not converge", who);
     return BSPGEMM_ERR_HIP;
 }
-// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING)
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING)
 using host_clock = std::chrono::steady_clock;
 static inline double ms_since(host_clock::time_point t)
 {

@@ -313,6 +313,18 @@ extern "C" bspgemm_status bspgemm_matrix_equal(bspgemm_context *ctx, const bspge
     return BSPGEMM_OK;
 }
 
+// What bspgemm_matrix_symmetrize below asks of the context's upper-bound workspace at most, for an n x n operand of E
+// entries: the select's flag scratch, the transposes (of the operand, and of both sides when rows turn out unsorted) and
+// the union's two flag scratches, each of at most E entries and each monotone in its entry count.  A caller that carves
+// state of its own from the workspace afterwards grows it once, to the larger of the two, instead of stage by stage.
+size_t symmetrize_workspace_ints(long long E, int n)
+{
+    size_t ints = flag_scratch_carve(nullptr, 0, E, false, nullptr);
+    ints = std::max(ints, transpose_workspace_ints(E, n));
+    const size_t o_b = flag_scratch_carve(nullptr, 4, E, true, nullptr);
+    return std::max(ints, o_b ? flag_scratch_carve(nullptr, o_b, E, true, nullptr) : 0);
+}
+
 extern "C" bspgemm_status bspgemm_matrix_symmetrize(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags,
                                                     bspgemm_matrix **out)
 {

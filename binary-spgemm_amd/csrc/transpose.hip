@@ -301,6 +301,36 @@ __global__ __launch_bounds__(kTrThreads) void k_tr_dedup_write(const int *__rest
 
 using namespace bsp;
 
+// The sort's passes and where its arrays lie in the context's upper-bound workspace (ints): key and value arrays (two of
+// each when there are two or more passes), the counts, their int64 scan, the scan's partials, the read-back scalars.
+struct TrLayout {
+    int bits, passes, ntiles, H;            // bits(cols - 1), radix passes, tiles of kTrTile entries, (digit, tile) counts
+    size_t E4, o_hist, o_pre, o_part, o_scal, total;
+};
+
+static TrLayout tr_layout(int E, int cols)
+{
+    TrLayout l;
+    l.bits = 0;
+    while (l.bits < 31 && (1ll << l.bits) < (long long)cols) l.bits++;
+    l.passes = l.bits <= kDigitBits ? 1 : (l.bits + kDigitBits - 1) / kDigitBits;
+    l.ntiles = (E + kTrTile - 1) / kTrTile;
+    l.H = kRadix * l.ntiles;
+    l.E4 = ((size_t)E + 63) & ~(size_t)63;
+    const size_t nbuf = l.passes > 1 ? 2 : 1;
+    l.o_hist = 2 * nbuf * l.E4;
+    l.o_pre = l.o_hist + (((size_t)l.H + 1) & ~(size_t)1);
+    l.o_part = l.o_pre + 2 * ((size_t)l.H + 1);
+    l.o_scal = l.o_part + 2 * ((size_t)l.H / 2048 + 4);
+    l.total = l.o_scal + 4;
+    return l;
+}
+
+size_t transpose_workspace_ints(long long E, int cols)
+{
+    return E > 0 && E <= kTrMaxNnz ? tr_layout((int)E, cols).total : 0;
+}
+
 extern "C" bspgemm_status bspgemm_matrix_transpose(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_matrix **AT)
 {
     if (AT) *AT = nullptr;
@@ -321,20 +351,10 @@ extern "C" bspgemm_status bspgemm_matrix_transpose(bspgemm_context *ctx, const b
     if (E == 0) {
         HIPCHK_B(hipMemsetAsync(m->d_row_ptr, 0, ((size_t)cols + 1) * sizeof(int), s));
     } else {
-        int bits = 0;
-        while (bits < 31 && (1ll << bits) < (long long)cols) bits++;            // bits(cols - 1)
-        const int passes = bits <= kDigitBits ? 1 : (bits + kDigitBits - 1) / kDigitBits;
-        const int ntiles = (E + kTrTile - 1) / kTrTile;
-        const int H = kRadix * ntiles;                                          // (digit, tile) counts
-        // workspace (ints, the context's upper-bound workspace): key and value arrays (two of each when there are two or
-        // more passes), the counts, their int64 scan, the scan's partials, the read-back scalars
-        const size_t E4 = ((size_t)E + 63) & ~(size_t)63;
-        const size_t nbuf = passes > 1 ? 2 : 1;
-        const size_t o_hist = 2 * nbuf * E4;
-        const size_t o_pre = o_hist + (((size_t)H + 1) & ~(size_t)1);
-        const size_t o_part = o_pre + 2 * ((size_t)H + 1);
-        const size_t o_scal = o_part + 2 * ((size_t)H / 2048 + 4);
-        if (bspgemm_status st = ensure_tmp(ctx, o_scal + 4)) return bail(st);
+        const TrLayout lay = tr_layout(E, cols);
+        const int bits = lay.bits, passes = lay.passes, ntiles = lay.ntiles, H = lay.H;
+        const size_t E4 = lay.E4, o_hist = lay.o_hist, o_pre = lay.o_pre, o_part = lay.o_part, o_scal = lay.o_scal;
+        if (bspgemm_status st = ensure_tmp(ctx, lay.total)) return bail(st);
         int *ws = ctx->tmp;
         int *kb[2] = {ws, ws + 2 * E4}, *vb[2] = {ws + E4, ws + 3 * E4};
         int *hist = ws + o_hist;

@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -538,6 +538,58 @@ bspgemm_status bspgemm_kcore(bspgemm_context *ctx, const bspgemm_matrix *A, int 
  *     BSPGEMM_ERR_ALLOC: an allocation failed.  Nothing is leaked on any failure path.                                    */
 bspgemm_status bspgemm_strongly_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A,
                                                      bspgemm_matrix **P, int *ncomponents, int *rounds, int *sweeps);
+
+/* Greedy graph colouring with deterministic colours, everything device-resident and without a product: a partition of
+ * the vertices into independent sets, whose first class is a maximal independent set.  A is square and its entries are
+ * read as undirected edges exactly as bspgemm_core_numbers reads them: the graph is S = bspgemm_matrix_symmetrize(A,
+ * BSPGEMM_SYMMETRIZE_DROP_DIAGONAL), computed inside the call and freed on every path, so unsorted rows, repeats,
+ * self-loops, one-direction storage and the in-edges that bspgemm_readCOO hands back all give the same answer; any n,
+ * n == 0 and nnz == 0 included.
+ *   - The order.  Every vertex has a 64-bit key, key(v) = (hi << 32) | lo, and u PRECEDES v when (key(u), u) < (key(v), v)
+ *     lexicographically.  With mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (all in
+ *     uint32):
+ *         BSPGEMM_COLOR_NATURAL        hi = 0, lo = v                             (seed is ignored)
+ *         BSPGEMM_COLOR_RANDOM         hi = 0, lo = mix32((uint32)v ^ seed)
+ *         BSPGEMM_COLOR_LARGEST_FIRST  hi = 0x7fffffff - deg_S(v), lo as for RANDOM
+ *     The formula is part of the contract: the result is defined by it.
+ *   - The result.  colour(v) is what sequential first fit gives when it visits the vertices in that order: the smallest
+ *     colour >= 0 that no preceding neighbour of v has.  That is unique, so every run gives the same bits, independent of
+ *     scheduling.  It follows that adjacent vertices differ in colour, that a vertex of colour c has a neighbour of every
+ *     colour below c, that class 0 is the lexicographically first maximal independent set of the order, and that
+ *     *ncolors <= maxdeg(S) + 1.
+ *   - *P is the n x n assignment operand, exactly as bspgemm_connected_components returns it: P.row_ptr = 0, 1, ..., n and
+ *     P.col_idx[v] = colour(v).  bspgemm_matrix_transpose(P) holds the ascending member list of class c in row c -- row 0
+ *     is the maximal independent set -- and P^T * S * P by two multiplies is the class-adjacency matrix, whose diagonal is
+ *     empty.  It is an owned operand laid out like an uploaded one (bspgemm_matrix_free), usable in every product,
+ *     transpose and select, complete on the context's stream when the call returns.
+ *   - *ncolors = 1 + the largest colour, reduced on the device: 0 for n == 0, 1 when S has no entries.  *rounds = frontier
+ *     launches (below) = the number of vertices on the longest chain of strictly ascending (key, id) along edges of S:
+ *     deterministic, 0 when S has no entries.  ncolors and rounds may be NULL.
+ *   - The scheme is a Jones-Plassmann sweep with first fit, a level-synchronous peeling of the priority DAG, on colour[]
+ *     (P.col_idx itself, -1 = uncoloured) and, in the context's workspace, key[n], cnt[n] (preceding neighbours not yet
+ *     coloured), two frontier lists and four counters, about 5 n ints.  An entry-parallel pass over S counts cnt[]; the
+ *     vertices with cnt == 0 seed the frontier (one atomic per wave).  A launch gives one wave to every frontier vertex u,
+ *     its lanes striding over u's row of S: the colour of a preceding neighbour is marked in the wave's LDS bitmap of 2048
+ *     colours, cnt of a following neighbour is lowered by a device-scope atomicSub and the one decrement that returns 1
+ *     appends that neighbour to the other list; the first free bit is u's colour (a full window of 2048 moves the window
+ *     up and walks the row again for the colours alone).  Launches swap the two lists until one comes back empty.  Every
+ *     preceding neighbour of a frontier vertex was coloured by an EARLIER launch; decisions rest only on atomic return
+ *     values and on values from before the launch; no kernel waits for another workgroup (csrc/color.hip).
+ *   - Cost: one synchronisation (4 bytes read back) per launch -- a path stored in ascending order takes n launches under
+ *     NATURAL -- every stored entry of S walked twice with one atomic each at most.  A frontier vertex's row is walked by
+ *     ONE wave, 64 entries per step and once per window pass: a hub row in the frontier is a serial tail, not the "a hub
+ *     costs what its entries cost" geometry of the counting pass.  Defensive cap of n launches (BSPGEMM_ERR_HIP, "did not
+ *     converge").
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *P = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A or P, an
+ *     unknown order, a non-square A, A from another context.  Otherwise the errors of bspgemm_matrix_symmetrize:
+ *     BSPGEMM_ERR_INVALID for a column outside [0, n) anywhere in A (its transpose tests every column on the device; the
+ *     context stays usable), BSPGEMM_ERR_OVERFLOW for more than INT_MAX entries in S, BSPGEMM_ERR_ALLOC.  Nothing is leaked
+ *     on any path.                                                                                                         */
+typedef enum bspgemm_color_order { BSPGEMM_COLOR_NATURAL = 1, BSPGEMM_COLOR_RANDOM = 2,
+                                   BSPGEMM_COLOR_LARGEST_FIRST = 3 } bspgemm_color_order;
+bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_color_order order,
+                                      unsigned seed, bspgemm_matrix **P, int *ncolors, int *rounds);
 
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
