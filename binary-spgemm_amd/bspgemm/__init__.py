@@ -59,6 +59,7 @@ EXPORTS = [
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
     "bspgemm_strongly_connected_components", "bspgemm_graph_coloring",
+    "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
 
@@ -79,7 +80,16 @@ SETOPS = {"or": 1, "and": 2, "andnot": 3, "xor": 4}                             
 SYMMETRIZE_DROP_DIAGONAL = 1                                                             # BSPGEMM_SYMMETRIZE_DROP_DIAGONAL
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
-           "shared_slots": 6}    # bspgemm_option
+           "shared_slots": 6, "dot_light": 7}    # bspgemm_option
+SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
+
+
+class DotInfo(C.Structure):
+    """bspgemm_dot_info"""
+    _fields_ = [("entries", C.c_int64), ("heavy_entries", C.c_int64), ("kept", C.c_int64), ("canonicalised", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -204,6 +214,9 @@ def lib():
     L.bspgemm_result_values_sum.argtypes = [VP, VP, C.POINTER(C.c_int64)]
     L.bspgemm_triangle_count.argtypes = [VP, VP, C.POINTER(C.c_int64)]
     L.bspgemm_ktruss.argtypes = [VP, VP, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_multiply_masked_dot.argtypes = [VP, VP, VP, VP, C.c_uint, PVP, C.POINTER(DotInfo)]
+    L.bspgemm_triangle_count_ex.argtypes = [VP, VP, C.c_int, C.POINTER(C.c_int64)]
+    L.bspgemm_ktruss_ex.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_bfs.argtypes = [VP, VP, C.c_int, VP, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_core_numbers.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -391,7 +404,7 @@ class Context:
 
     def set_option(self, name, value):
         """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
-        "shared_slots" -1/0/k"""
+        "shared_slots" -1/0/k, "dot_light" T >= 0"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):
@@ -495,17 +508,34 @@ class Context:
              "matrix_symmetrize")
         return Matrix(self, m, keep=None)
 
-    def triangle_count(self, A):
-        """bspgemm_triangle_count: triangles of the undirected graph of A's strictly lower triangle, device-resident"""
+    def multiply_masked_dot(self, A, B, F):
+        """C = F .* (A * B^T) with counts (bspgemm_multiply_masked_dot): C_ij = |A_i n B_j| for every entry (i, j) of F, one
+        sorted-row intersection per mask entry.  Returns (Result, info dict: entries, heavy_entries, kept, canonicalised)."""
+        r, info = C.c_void_p(), DotInfo()
+        _chk(lib().bspgemm_multiply_masked_dot(self._h, A._h, B._h, F._h, 0, C.byref(r), C.byref(info)),
+             "bspgemm_multiply_masked_dot")
+        return Result(self, r), info.as_dict()
+
+    def triangle_count(self, A, method="product"):
+        """bspgemm_triangle_count: triangles of the undirected graph of A's strictly lower triangle, device-resident;
+        method "product" (default) | "dot" (bspgemm_triangle_count_ex): how the support is counted"""
         t = C.c_int64()
-        _chk(lib().bspgemm_triangle_count(self._h, A._h, C.byref(t)), "triangle_count")
+        if method == "product":
+            _chk(lib().bspgemm_triangle_count(self._h, A._h, C.byref(t)), "triangle_count")
+        else:
+            _chk(lib().bspgemm_triangle_count_ex(self._h, A._h, SUPPORT_METHODS[method], C.byref(t)), "triangle_count_ex")
         return t.value
 
-    def ktruss(self, A, k, max_iter=0):
+    def ktruss(self, A, k, max_iter=0, method="product"):
         """bspgemm_ktruss: (T as a Matrix, counted products computed, converged) -- the maximal subgraph in which every
-        edge lies in at least k - 2 triangles, by repeated counted products and on-device selects; max_iter <= 0: no cap"""
+        edge lies in at least k - 2 triangles, by repeated counted products and on-device selects; max_iter <= 0: no cap;
+        method "product" (default) | "dot" (bspgemm_ktruss_ex): how a step counts the support"""
         m, it, conv = C.c_void_p(), C.c_int(), C.c_int()
-        _chk(lib().bspgemm_ktruss(self._h, A._h, int(k), int(max_iter), C.byref(m), C.byref(it), C.byref(conv)), "ktruss")
+        if method == "product":
+            _chk(lib().bspgemm_ktruss(self._h, A._h, int(k), int(max_iter), C.byref(m), C.byref(it), C.byref(conv)), "ktruss")
+        else:
+            _chk(lib().bspgemm_ktruss_ex(self._h, A._h, int(k), int(max_iter), SUPPORT_METHODS[method], C.byref(m),
+                                         C.byref(it), C.byref(conv)), "ktruss_ex")
         return Matrix(self, m, keep=None), it.value, bool(conv.value)
 
     def bfs(self, A, sources, max_depth=0):

@@ -740,6 +740,10 @@ extern "C" bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_optio
         if (value < -1) return FAIL(BSPGEMM_ERR_INVALID, "shared slots: -1, 0 or a count");
         ctx->shared_slots = value > kSharedSlotsMax ? kSharedSlotsMax : value;
         return BSPGEMM_OK;
+    case BSPGEMM_OPT_DOT_LIGHT:
+        if (value < 0) return FAIL(BSPGEMM_ERR_INVALID, "dot light: 0 or a row length");
+        ctx->dot_light = value;
+        return BSPGEMM_OK;
     }
     return FAIL(BSPGEMM_ERR_INVALID, "unknown option");
 }
@@ -754,6 +758,7 @@ extern "C" int bspgemm_get_option(const bspgemm_context *ctx, bspgemm_option opt
     case BSPGEMM_OPT_SMALL_PATH: return ctx->small;
     case BSPGEMM_OPT_PADDED_ROWS: return ctx->pad_rows;
     case BSPGEMM_OPT_SHARED_SLOTS: return ctx->shared_slots;
+    case BSPGEMM_OPT_DOT_LIGHT: return ctx->dot_light;
     }
     return INT_MIN;
 }

@@ -140,6 +140,7 @@ struct bspgemm_context {
     int pad_rows = 0;                   // BSPGEMM_PAD_ROWS / BSPGEMM_OPT_PADDED_ROWS: 0 never (default), 1 always, -1 per operand: gather from a padded copy of B.col_idx
     int small = -1;                     // BSPGEMM_SMALL / BSPGEMM_OPT_SMALL_PATH: -1 automatic, 0 never, 1 whenever the product fits
     int shared_slots = -1;              // BSPGEMM_SHARED_SLOTS / BSPGEMM_OPT_SHARED_SLOTS: -1 per class (wave_shared_max), 0 off, k: up to k shared slots in every class
+    int dot_light = 32;                 // BSPGEMM_OPT_DOT_LIGHT: the longest shorter row that one lane of k_dot_count intersects by itself (dot.hip)
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
     bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
@@ -192,6 +193,10 @@ bspgemm_status operand_cols(bspgemm_matrix *m, long long cap);                  
 bspgemm_status operand_finish(bspgemm_matrix *m, long long nnz);                           // nnz, and d_deg8 on the stream
 // sorted duplicate-free copy of X: transposed twice (transpose.hip)
 bspgemm_status operand_canonical(bspgemm_context *ctx, const bspgemm_matrix *X, bspgemm_matrix **out);
+
+// dedup(select(X, op)): the selection with sorted duplicate-free rows, the first step of the triangle count and the
+// k-truss under either method (select.hip)
+bspgemm_status select_dedup(bspgemm_context *ctx, const bspgemm_matrix *X, bspgemm_select op, bspgemm_matrix **out);
 
 // What an entry point asks of an operand of its context, tested in this order: it belongs to ctx, (NEED_SQUARE) rows ==
 // cols, (NEED_ENTRIES_CONSISTENT) an operand with nonzeros has rows and a col_idx.  who: the entry point's name, which the

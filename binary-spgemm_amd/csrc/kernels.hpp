@@ -2,7 +2,7 @@
 // Kernels: prepass.hip (row work, scans, class records), wave_rows.inc (k_wave_rows; one object per (LEVELS, mask mode) pair,
 // dispatched by wave_rows.hip), wave_masked.hip (k_wave_masked), dense_rows.hip (k_dense_rows, k_dense_rows_count,
 // k_rank_rows) over the heavy rows' gather in heavy_gather.hpp, compact.hip (compaction, heavy-row moves),
-// small.hip, transpose.hip, select.hip, setop.hip, bfs.hip, cc.hip, kcore.hip (the launches of the last four stay in their files).  A family is ONE template kernel with the mask mode as a template parameter.
+// small.hip, transpose.hip, select.hip, setop.hip, bfs.hip, cc.hip, kcore.hip, dot.hip (the launches of the last five stay in their files).  A family is ONE template kernel with the mask mode as a template parameter.
 // Tuning constants are compile-time constants, not switches: what was tried against them is in profiles/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -274,6 +274,14 @@ void launch_select_row_ptr(const int *row_ptr32, const long long *row_ptr64, int
                            const unsigned long long *flags, const long long *prefix, int *out, hipStream_t s);
 // *sum (device, zeroed by the caller) += vals[0 .. nnz), exact in 64 bits
 void launch_values_sum(const int *vals, long long nnz, unsigned long long *sum, hipStream_t s);
+
+// ---- the canonical-form check of setop.hip, alone (k_set_flags<false>; also dot.hip's) ----------------------------
+constexpr unsigned kSetErrRange = 1u;      // a column outside [0, cols)
+constexpr unsigned kSetErrOrder = 2u;      // a row that is not strictly ascending
+// *err |= (kSetErrRange | kSetErrOrder as found in the operand) << err_shift; nothing else is written.  tile_row: nnz /
+// kSelTile + 1 ints of scratch
+void launch_canonical_check(const int *row_ptr, const int *col_idx, int rows, int cols, long long nnz, int err_shift,
+                            int *tile_row, unsigned *err, hipStream_t s);
 
 // row_ptr rebasing helper for interior-pointer uploads
 void launch_rebase_i32(int *row_ptr, int n, int base, hipStream_t s);

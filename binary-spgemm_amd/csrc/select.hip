@@ -333,8 +333,8 @@ extern "C" bspgemm_status bspgemm_result_values_sum(bspgemm_context *ctx, const 
 }
 
 // ------------------------------------------------------------------ triangles, k-truss ---
-// dedup(select(A, op)): the selection with sorted duplicate-free rows
-static bspgemm_status select_dedup(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_select op, bspgemm_matrix **out)
+// dedup(select(A, op)): the selection with sorted duplicate-free rows (internal.hpp: also dot.hip's loops)
+bspgemm_status select_dedup(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_select op, bspgemm_matrix **out)
 {
     bspgemm_matrix *sel = nullptr;
     bspgemm_status st = bspgemm_matrix_select(ctx, A, op, &sel);

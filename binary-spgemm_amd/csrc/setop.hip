@@ -26,9 +26,7 @@
 
 namespace bsp {
 
-constexpr unsigned kSetErrRange = 1u;    // a column outside [0, cols)
-constexpr unsigned kSetErrOrder = 2u;    // a row that is not strictly ascending
-constexpr int kSetErrShiftB = 2;         // operand B's two bits
+constexpr int kSetErrShiftB = 2;         // operand B's two bits (kSetErrRange, kSetErrOrder: kernels.hpp)
 
 // pass 1 over operand X.  SEARCH false: the check alone (nothing but *err is written).  The columns are read again by pass
 // 2, so the loads stay temporal.  invert: the flags are the NON-common entries (ANDNOT).  lbs (may be NULL): lb per entry.
@@ -167,6 +165,17 @@ static void launch_setop_flags(const int *rpX, const int *colX, int rows, int co
     else
         hipLaunchKernelGGL(k_set_flags<false>, grid, block, 0, s, rpX, colX, rows, cols, nnzX, aligned16(colX), tile_row, rpY,
                            colY, invert, shift, flags, cnt, lbs, err);
+}
+
+// the check alone over one operand (kernels.hpp): k_set_flags<false>, the instance that setop's second side launches
+void launch_canonical_check(const int *row_ptr, const int *col_idx, int rows, int cols, long long nnz, int err_shift,
+                            int *tile_row, unsigned *err, hipStream_t s)
+{
+    if (nnz <= 0) return;
+    launch_select_tile_rows(row_ptr, rows, tile_row, s);
+    hipLaunchKernelGGL(k_set_flags<false>, dim3(select_tiles(nnz)), dim3(kSelThreads), 0, s, row_ptr, col_idx, rows, cols, nnz,
+                       aligned16(col_idx), tile_row, (const int *)nullptr, (const int *)nullptr, false, err_shift,
+                       (u64 *)nullptr, (int *)nullptr, (int *)nullptr, err);
 }
 
 // pass 2 of OR (k = 1) and XOR (k = 2) over X: out[e + lbs[e] - k * (common entries before e)] = colX[e] for every entry

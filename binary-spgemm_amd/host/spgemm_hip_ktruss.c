@@ -3,8 +3,10 @@
  * applications the counting masked product was added for (include/bspgemm.h: bspgemm_triangle_count, bspgemm_ktruss),
  * beside the closure driver (spgemm_hip_closure.c).
  *
- *     SpGEMM_hip_ktruss  [--symmetrize]  file.mtx  k  [out.mtx]
+ *     SpGEMM_hip_ktruss  [--symmetrize]  [--dot]  file.mtx  k  [out.mtx]
  *
+ * --dot: both the count and the truss take their support from bspgemm_multiply_masked_dot (BSPGEMM_SUPPORT_DOT of
+ * bspgemm_triangle_count_ex / bspgemm_ktruss_ex) instead of the counting product; the output is the same but for ms.
  * Prints one CSV line: n,nnz,triangles,k,truss_nnz,iterations,converged,ms.  file.mtx is read with
  * BSPGEMM_READ_EXPAND_SYMMETRIC, so a file that stores one triangle of a symmetric matrix gives the whole graph (nnz is the
  * expanded count); the loader hands back the transpose of the file's matrix (readCOO, final/utils.c:47-81), which for a
@@ -18,13 +20,17 @@
 
 int main(int argc, char **argv)
 {
-    const int symmetrize = argc > 1 && strcmp(argv[1], "--symmetrize") == 0;
-    if (symmetrize) {
+    int symmetrize = 0;
+    bspgemm_support_method method = BSPGEMM_SUPPORT_PRODUCT;
+    while (argc > 1 && strncmp(argv[1], "--", 2) == 0) {     /* the options, in any order */
+        if (strcmp(argv[1], "--symmetrize") == 0) symmetrize = 1;
+        else if (strcmp(argv[1], "--dot") == 0) method = BSPGEMM_SUPPORT_DOT;
+        else break;
         argv++;
         argc--;
     }
     if (argc != 3 && argc != 4) {
-        printf("usage: SpGEMM_hip_ktruss  path-to-matrix  k  [path-to-truss]\n");
+        printf("usage: SpGEMM_hip_ktruss  [--symmetrize]  [--dot]  path-to-matrix  k  [path-to-truss]\n");
         exit(1);
     }
     const int k = atoi(argv[2]);
@@ -44,8 +50,8 @@ int main(int argc, char **argv)
     const struct timespec t0 = cli_now();
     int64_t triangles = 0;
     int iterations = 0, converged = 0;
-    CHECK(bspgemm_triangle_count(ctx, A, &triangles), "bspgemm_triangle_count");
-    CHECK(bspgemm_ktruss(ctx, A, k, 0, &T, &iterations, &converged), "bspgemm_ktruss");
+    CHECK(bspgemm_triangle_count_ex(ctx, A, method, &triangles), "bspgemm_triangle_count");
+    CHECK(bspgemm_ktruss_ex(ctx, A, k, 0, method, &T, &iterations, &converged), "bspgemm_ktruss");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
     const double ms = cli_ms(t0, cli_now());
     const long long tn = bspgemm_matrix_nnz(T);

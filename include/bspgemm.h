@@ -185,14 +185,19 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  *   SHARED_SLOTS     -1 per capacity class (default), 0 off, k: k in every class (at most 16): the one-wave kernel emits a
  *                    row that has up to that many products more than 32-column slots -- a row whose products sit alone in
  *                    their slots but for a few -- from its columns alone, without building the slots' masks (env
- *                    BSPGEMM_SHARED_SLOTS).  Read at every multiply.  */
+ *                    BSPGEMM_SHARED_SLOTS).  Read at every multiply.
+ *   DOT_LIGHT        T >= 0 (default 32): bspgemm_multiply_masked_dot intersects a mask entry whose shorter row has at most T
+ *                    entries by one lane, a longer one by a whole wave.  0: every entry with two non-empty rows goes to the
+ *                    wave kernel; a very large value: none does (bspgemm_dot_info.heavy_entries says how many did).  Read
+ *                    at every call.  */
 typedef enum bspgemm_option {
     BSPGEMM_OPT_CLASS_STREAMS   = 1,
     BSPGEMM_OPT_BLOCKED_EXTENTS = 2,
     BSPGEMM_OPT_CHECK           = 3,
     BSPGEMM_OPT_SMALL_PATH      = 4,
     BSPGEMM_OPT_PADDED_ROWS     = 5,
-    BSPGEMM_OPT_SHARED_SLOTS    = 6
+    BSPGEMM_OPT_SHARED_SLOTS    = 6,
+    BSPGEMM_OPT_DOT_LIGHT       = 7
 } bspgemm_option;
 bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_option opt, int value);
 /* current value of a knob (INT32_MIN for an unknown option or a NULL context) */
@@ -394,6 +399,63 @@ bspgemm_status bspgemm_triangle_count(bspgemm_context *ctx, const bspgemm_matrix
  *   - BSPGEMM_ERR_INVALID with *T = NULL: k < 2, a non-square A, a NULL argument, A from another context.               */
 bspgemm_status bspgemm_ktruss(bspgemm_context *ctx, const bspgemm_matrix *A, int k, int max_iter,
                               bspgemm_matrix **T, int *iterations, int *converged);
+
+/* C = F .* (A * B^T) with counts, the masked DOT product: every mask entry (i, j) gets one intersection of two sorted rows,
+ *     C_ij = | pattern(A_i) n pattern(B_j) |   for (i, j) in pattern(F) with 0 <= j < B.rows, stored only where C_ij > 0.
+ * The second algorithm of a masked SpGEMM beside the row-wise product of bspgemm_multiply_masked_count: its cost follows
+ * the MASK, sum over (i, j) in F of min(|A_i|, |B_j|) searches of log max(|A_i|, |B_j|) steps, not the product count, and
+ * B's ROWS are intersected as they are stored -- no transpose when the caller holds them already (L with L for triangles,
+ * a symmetric S with itself for the k-truss).
+ *   - C has A.rows rows; all of them are computed (no row range).  Its rows are ascending and duplicate-free, its row_ptr
+ *     is int64, its values int32.  It is an ordinary counted result, allocated as a product's is: bspgemm_result_download,
+ *     _download_values, _values_device, _values_sum and _free work on it unchanged, bspgemm_matrix_from_result and
+ *     bspgemm_matrix_from_result_where take it.  It is complete on the context's stream when the call returns.
+ *   - For duplicate-free A and B the result is bit for bit that of bspgemm_multiply_masked_count(ctx, A, transpose(B), F,
+ *     0, A.rows, &C): row_ptr, col_idx and values.  Counts are taken on PATTERNS: repeats in A, B or F count once (the
+ *     counting product counts them as stored).  A == B == F as one handle is allowed.
+ *   - Columns of F at or above B.rows (tested unsigned, before they index anything) have no effect.  Columns of A and B
+ *     are only compared, never used as an index.
+ *   - flags: reserved, must be 0.  info (may be NULL): what ran, below; zeroed on failure.
+ *   - Runs on the context's stream with ONE synchronisation when the three operands have sorted duplicate-free rows --
+ *     every product, transpose and from_result* has, and select preserves them: the read-back of the checks' error word,
+ *     the wave kernel's entry count and nnz(C).  The kernels check that form together with the columns' range, each
+ *     distinct handle once; an operand that fails it is first transposed twice (bspgemm_matrix_transpose, with its
+ *     synchronisations and workspace), the passes run again and the operand's bit is set in info.canonicalised.
+ *   - The mask is walked entry-parallel (a hub row of F costs what its entries cost).  An entry whose shorter row has at
+ *     most T = BSPGEMM_OPT_DOT_LIGHT entries is intersected by one lane; a longer one by ONE wave, 64 elements of the
+ *     shorter row per step: a hub-hub mask entry is a serial tail of min(|A_i|, |B_j|) / 64 steps of log-deep searches.
+ *     One entry is never split across waves.  T changes no result.  Scratch, in the context's workspace (kept, like the
+ *     select's): 12 bytes per entry of F (a count and the wave kernel's list) and the select's 12 bytes per 64 entries
+ *     with its scan.  It does not touch the multiply statistics.
+ *   - BSPGEMM_ERR_INVALID with *C = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A, B, F or C;
+ *     flags != 0; an operand of another context; A.cols != B.cols; F.rows != A.rows; a column of F outside [0, F.cols),
+ *     or of A or B outside [0, cols) (the check reports them, as bspgemm_matrix_setop does).  BSPGEMM_ERR_ALLOC: an
+ *     allocation failed; nothing is leaked and the context stays usable.                                                */
+typedef struct bspgemm_dot_info {
+    int64_t entries;        /* nnz of the (canonical) mask that was walked                                          */
+    int64_t heavy_entries;  /* of them, handled by the one-wave-per-entry kernel                                    */
+    int64_t kept;           /* nnz(C)                                                                               */
+    int     canonicalised;  /* bit 0 / 1 / 2: A / B / F had to be brought to sorted duplicate-free form first       */
+} bspgemm_dot_info;
+bspgemm_status bspgemm_multiply_masked_dot(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *B,
+                                           const bspgemm_matrix *F, unsigned flags, bspgemm_result **C,
+                                           bspgemm_dot_info *info);
+
+/* bspgemm_triangle_count and bspgemm_ktruss with the way the support is counted as an argument.  BSPGEMM_SUPPORT_PRODUCT
+ * is the function without _ex, called through.  BSPGEMM_SUPPORT_DOT counts with bspgemm_multiply_masked_dot:
+ *   - triangles: L as there, *triangles = sum(masked_dot(L, L, L)) -- a triangle i > j > k is the entry (i, j) of L together
+ *     with k in L_i n L_j, so rows of L meet rows of L and nothing is transposed;
+ *   - k-truss: S0 as there; whether S0 equals its transpose is decided once (bspgemm_matrix_transpose,
+ *     bspgemm_matrix_equal); a step is C = masked_dot(S, S, S) for a symmetric S0 (S then stays symmetric: the support of
+ *     (i, j) is that of (j, i)), else masked_dot(S, transpose(S), S), followed by the same filter and the same stopping
+ *     rules.  T, *iterations and *converged equal bspgemm_ktruss's for every A, symmetric or not.
+ * Composed of public calls; every intermediate is freed on every path.  The errors of the functions without _ex, and
+ * BSPGEMM_ERR_INVALID for an unknown method.  Which method is faster depends on the graph: DESIGN.md 4.17.               */
+typedef enum bspgemm_support_method { BSPGEMM_SUPPORT_PRODUCT = 0, BSPGEMM_SUPPORT_DOT = 1 } bspgemm_support_method;
+bspgemm_status bspgemm_triangle_count_ex(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_support_method method,
+                                         int64_t *triangles);
+bspgemm_status bspgemm_ktruss_ex(bspgemm_context *ctx, const bspgemm_matrix *A, int k, int max_iter,
+                                 bspgemm_support_method method, bspgemm_matrix **T, int *iterations, int *converged);
 
 /* Multi-source breadth-first search with a level per reached vertex, everything device-resident: the loop the complemented
  * mask is for.  A is square, row u lists the out-neighbours of u; its rows may be unsorted and hold repeats, as for any
