@@ -59,7 +59,7 @@ EXPORTS = [
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
     "bspgemm_strongly_connected_components", "bspgemm_graph_coloring",
-    "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex",
+    "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
 
@@ -80,13 +80,24 @@ SETOPS = {"or": 1, "and": 2, "andnot": 3, "xor": 4}                             
 SYMMETRIZE_DROP_DIAGONAL = 1                                                             # BSPGEMM_SYMMETRIZE_DROP_DIAGONAL
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
-           "shared_slots": 6, "dot_light": 7}    # bspgemm_option
+           "shared_slots": 6, "dot_light": 7, "bfs_alpha": 8, "bfs_beta": 9, "bfs_push_lanes": 10}    # bspgemm_option
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
+BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
 
 
 class DotInfo(C.Structure):
     """bspgemm_dot_info"""
     _fields_ = [("entries", C.c_int64), ("heavy_entries", C.c_int64), ("kept", C.c_int64), ("canonicalised", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class BfsTreeInfo(C.Structure):
+    """bspgemm_bfs_tree_info"""
+    _fields_ = [("reached", C.c_int64), ("edges_pushed", C.c_int64), ("pull_mask", C.c_uint64), ("depth", C.c_int),
+                ("complete", C.c_int), ("push_levels", C.c_int), ("pull_levels", C.c_int), ("transposed", C.c_int),
+                ("canonicalised", C.c_int)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -218,6 +229,7 @@ def lib():
     L.bspgemm_triangle_count_ex.argtypes = [VP, VP, C.c_int, C.POINTER(C.c_int64)]
     L.bspgemm_ktruss_ex.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_bfs.argtypes = [VP, VP, C.c_int, VP, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_bfs_tree.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, PVP, C.POINTER(BfsTreeInfo)]
     L.bspgemm_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_core_numbers.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_kcore.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
@@ -404,7 +416,7 @@ class Context:
 
     def set_option(self, name, value):
         """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
-        "shared_slots" -1/0/k, "dot_light" T >= 0"""
+        "shared_slots" -1/0/k, "dot_light" T >= 0, "bfs_alpha" >= 1, "bfs_beta" >= 1, "bfs_push_lanes" 0/4/16/64"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):
@@ -547,6 +559,18 @@ class Context:
         _chk(lib().bspgemm_bfs(self._h, A._h, int(src.size), C.c_void_p(src.ctypes.data) if src.size else None,
                                int(max_depth), C.byref(r), C.byref(depth), C.byref(complete)), "bspgemm_bfs")
         return Result(self, r), depth.value, bool(complete.value)
+
+    def bfs_tree(self, A, AT=None, source=0, direction="auto", max_depth=0):
+        """bspgemm_bfs_tree: (tree as a Result, info dict) -- single-source direction-optimising BFS; row v of the result
+        holds the one entry (v, parent(v)) with the value level(v) for every vertex reachable from `source` along A's
+        out-edges, parent = the smallest vertex one level up, the source its own parent at level 0.  AT: the transpose of A
+        (A itself for a symmetric canonical A), or None: the call transposes when it first pulls.  direction "auto" | "push"
+        | "pull"; max_depth <= 0: no cap.  info: reached, edges_pushed, pull_mask, depth, complete, push_levels,
+        pull_levels, transposed, canonicalised"""
+        r, info = C.c_void_p(), BfsTreeInfo()
+        _chk(lib().bspgemm_bfs_tree(self._h, A._h, AT._h if AT is not None else None, int(source), BFS_DIRECTIONS[direction],
+                                    int(max_depth), C.byref(r), C.byref(info)), "bspgemm_bfs_tree")
+        return Result(self, r), info.as_dict()
 
     def connected_components(self, A):
         """bspgemm_connected_components: (P as a Matrix, ncomponents, rounds) -- the weakly connected components of A's

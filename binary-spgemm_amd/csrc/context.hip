@@ -278,6 +278,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     ctx->kcore_timing = getenv("BSPGEMM_KCORE_TIMING") != nullptr;
     ctx->scc_timing = getenv("BSPGEMM_SCC_TIMING") != nullptr;
     ctx->color_timing = getenv("BSPGEMM_COLOR_TIMING") != nullptr;
+    ctx->bfs_tree_timing = getenv("BSPGEMM_BFS_TREE_TIMING") != nullptr;
     if (ctx->debug_alloc)
         fprintf(stderr, "[bspgemm] device %d: %s, %zu MiB, %d CUs; result cache budget %zu MiB\n", device,
                 prop.gcnArchName, (size_t)(prop.totalGlobalMem >> 20), prop.multiProcessorCount, ctx->cache_budget >> 20);
@@ -744,6 +745,18 @@ extern "C" bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_optio
         if (value < 0) return FAIL(BSPGEMM_ERR_INVALID, "dot light: 0 or a row length");
         ctx->dot_light = value;
         return BSPGEMM_OK;
+    case BSPGEMM_OPT_BFS_ALPHA:
+        if (value < 1) return FAIL(BSPGEMM_ERR_INVALID, "bfs alpha: 1 or more");
+        ctx->bfs_alpha = value;
+        return BSPGEMM_OK;
+    case BSPGEMM_OPT_BFS_BETA:
+        if (value < 1) return FAIL(BSPGEMM_ERR_INVALID, "bfs beta: 1 or more");
+        ctx->bfs_beta = value;
+        return BSPGEMM_OK;
+    case BSPGEMM_OPT_BFS_PUSH_LANES:
+        if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "bfs push lanes: 0, 4, 16 or 64");
+        ctx->bfs_push_lanes = value;
+        return BSPGEMM_OK;
     }
     return FAIL(BSPGEMM_ERR_INVALID, "unknown option");
 }
@@ -759,6 +772,9 @@ extern "C" int bspgemm_get_option(const bspgemm_context *ctx, bspgemm_option opt
     case BSPGEMM_OPT_PADDED_ROWS: return ctx->pad_rows;
     case BSPGEMM_OPT_SHARED_SLOTS: return ctx->shared_slots;
     case BSPGEMM_OPT_DOT_LIGHT: return ctx->dot_light;
+    case BSPGEMM_OPT_BFS_ALPHA: return ctx->bfs_alpha;
+    case BSPGEMM_OPT_BFS_BETA: return ctx->bfs_beta;
+    case BSPGEMM_OPT_BFS_PUSH_LANES: return ctx->bfs_push_lanes;
     }
     return INT_MIN;
 }

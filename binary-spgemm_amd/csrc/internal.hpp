@@ -141,10 +141,13 @@ struct bspgemm_context {
     int small = -1;                     // BSPGEMM_SMALL / BSPGEMM_OPT_SMALL_PATH: -1 automatic, 0 never, 1 whenever the product fits
     int shared_slots = -1;              // BSPGEMM_SHARED_SLOTS / BSPGEMM_OPT_SHARED_SLOTS: -1 per class (wave_shared_max), 0 off, k: up to k shared slots in every class
     int dot_light = 32;                 // BSPGEMM_OPT_DOT_LIGHT: the longest shorter row that one lane of k_dot_count intersects by itself (dot.hip)
+    int bfs_alpha = 15, bfs_beta = 18;  // BSPGEMM_OPT_BFS_ALPHA / _BETA: the direction rule of bspgemm_bfs_tree under AUTO (bfs_tree.hip)
+    int bfs_push_lanes = 0;             // BSPGEMM_OPT_BFS_PUSH_LANES: 0 per level from the frontier's mean out-degree, or 4, 16, 64 lanes per frontier vertex
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
     bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
     bool scc_timing = false;            // BSPGEMM_SCC_TIMING: trim / forward / backward launch counts and times of the strong components on stderr
+    bool bfs_tree_timing = false;       // BSPGEMM_BFS_TREE_TIMING: stage times of the single-source search on stderr (it then synchronises twice per launch)
     bool color_timing = false;          // BSPGEMM_COLOR_TIMING: stage times of the graph colouring on stderr (it then synchronises twice per launch)
 };
 
@@ -247,7 +250,7 @@ size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratc
 size_t transpose_workspace_ints(long long E, int cols);
 size_t symmetrize_workspace_ints(long long E, int n);
 
-// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip) ---
+// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip) ---
 // What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
 // each algorithm's own.  who: the entry point's name, which every message starts with.
 // the graph operand: check_operand with `flags`, then an entry count that an int32 entry index cannot hold
@@ -287,7 +290,7 @@ static inline bspgemm_status fail_stuck(const char *who)
     snprintf(g_err, sizeof g_err, "%s: did not converge", who);
     return BSPGEMM_ERR_HIP;
 }
-// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING)
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING)
 using host_clock = std::chrono::steady_clock;
 static inline double ms_since(host_clock::time_point t)
 {

@@ -2,7 +2,7 @@
 // Kernels: prepass.hip (row work, scans, class records), wave_rows.inc (k_wave_rows; one object per (LEVELS, mask mode) pair,
 // dispatched by wave_rows.hip), wave_masked.hip (k_wave_masked), dense_rows.hip (k_dense_rows, k_dense_rows_count,
 // k_rank_rows) over the heavy rows' gather in heavy_gather.hpp, compact.hip (compaction, heavy-row moves),
-// small.hip, transpose.hip, select.hip, setop.hip, bfs.hip, cc.hip, kcore.hip, dot.hip (the launches of the last five stay in their files).  A family is ONE template kernel with the mask mode as a template parameter.
+// small.hip, transpose.hip, select.hip, setop.hip, bfs.hip, cc.hip, kcore.hip, dot.hip, bfs_tree.hip (the launches of the last six stay in their files).  A family is ONE template kernel with the mask mode as a template parameter.
 // Tuning constants are compile-time constants, not switches: what was tried against them is in profiles/.
 #pragma once
 #include <hip/hip_runtime.h>

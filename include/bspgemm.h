@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -189,7 +189,9 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  *   DOT_LIGHT        T >= 0 (default 32): bspgemm_multiply_masked_dot intersects a mask entry whose shorter row has at most T
  *                    entries by one lane, a longer one by a whole wave.  0: every entry with two non-empty rows goes to the
  *                    wave kernel; a very large value: none does (bspgemm_dot_info.heavy_entries says how many did).  Read
- *                    at every call.  */
+ *                    at every call.
+ *   BFS_ALPHA, BFS_BETA (>= 1; defaults 15 and 18) and BFS_PUSH_LANES (0 automatic, or 4, 16, 64): the direction rule and the
+ *                    lanes per frontier vertex of bspgemm_bfs_tree, described there.  Read at every call.  */
 typedef enum bspgemm_option {
     BSPGEMM_OPT_CLASS_STREAMS   = 1,
     BSPGEMM_OPT_BLOCKED_EXTENTS = 2,
@@ -197,7 +199,10 @@ typedef enum bspgemm_option {
     BSPGEMM_OPT_SMALL_PATH      = 4,
     BSPGEMM_OPT_PADDED_ROWS     = 5,
     BSPGEMM_OPT_SHARED_SLOTS    = 6,
-    BSPGEMM_OPT_DOT_LIGHT       = 7
+    BSPGEMM_OPT_DOT_LIGHT       = 7,
+    BSPGEMM_OPT_BFS_ALPHA       = 8,
+    BSPGEMM_OPT_BFS_BETA        = 9,
+    BSPGEMM_OPT_BFS_PUSH_LANES  = 10
 } bspgemm_option;
 bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_option opt, int value);
 /* current value of a knob (INT32_MIN for an unknown option or a NULL context) */
@@ -487,6 +492,62 @@ bspgemm_status bspgemm_ktruss_ex(bspgemm_context *ctx, const bspgemm_matrix *A, 
  *     every failure path every intermediate is freed and the context stays usable.                                        */
 bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix *A, int nsources, const int *sources,
                            int max_depth, bspgemm_result **levels, int *depth, int *complete);
+
+/* Single-source direction-optimising breadth-first search that returns the BFS tree (parents and levels, the Graph500
+ * search kernel), everything device-resident and without a product (csrc/bfs_tree.hip).  A is square, row u
+ * lists the out-neighbours of u, as for bspgemm_bfs; its rows may be unsorted and hold repeats and self-loops, and it may come
+ * from any source of operands.  AT is the transpose of A as bspgemm_matrix_transpose returns it (in-edge rows, ascending and
+ * duplicate-free); for a symmetric canonical A the same handle may be passed as AT.  AT == NULL under AUTO or PULL: the call
+ * transposes A itself before the first pull launch and frees that transpose on every path (info.transposed).  Under PUSH, AT
+ * is ignored and may be NULL.  The library does not check that AT really is the transpose of A: one that is not gives some
+ * result, memory-safely.  Its sorted duplicate-free form IS checked, with the check of bspgemm_multiply_masked_dot; an AT that
+ * fails it is canonicalised the way that call does it (transposed twice) and info.canonicalised is set.
+ *   - *tree is an ordinary counted result of n rows.  Row v of a reached vertex holds exactly one entry: column parent(v)
+ *     with the value level(v); the source's row holds (source, source) with the value 0, the Graph500 convention.  Rows of
+ *     unreached vertices are empty.  bspgemm_result_download, _download_values, _values_device, _values_sum and _free work on
+ *     it unchanged; bspgemm_matrix_from_result gives the tree as a child -> parent operand, whose transpose lists every
+ *     vertex's children, and bspgemm_matrix_from_result_where(BSPGEMM_CMP_EQ, d) the vertices of level d with their parents.
+ *   - level(v) is the shortest-path distance from the source.  parent(v) is the SMALLEST u with level(u) == level(v) - 1 and
+ *     (u, v) stored in A.  Both are unique, so the result is bit for bit the same on every run, for every `direction` and for
+ *     every value of the knobs below: this equality is what the tests rest on.
+ *   - max_depth as in bspgemm_bfs: <= 0 no cap, else at most that many levels; info.complete = 1 when an empty frontier ended
+ *     the search, 0 when the cap did.
+ *   - The scheme: level[], parent[], two frontier lists and a counter block in the context's workspace (about 4 n ints, grown
+ *     once, before anything is launched).  Level d is ONE launch over the frontier (the vertices of level d - 1; n_f of them
+ *     with m_f stored out-edges, both known to the host) and one read-back.  A push launch walks the frontier's rows of A with
+ *     W lanes per vertex and claims a neighbour with a device-scope atomicMin on parent[]; a pull launch scans the in-row of
+ *     every unreached vertex for its first member of level d - 1.  Both keep all the arrays, so changing direction costs
+ *     nothing.  No kernel waits for another workgroup.
+ *   - The direction under AUTO, in 64-bit integers, decided before every level from what the host knows: m_u = nnz(A) minus
+ *     the out-degrees of every vertex reached so far (frontier included), alpha and beta the options below.  The search
+ *     starts in PUSH.  In PUSH it switches to PULL when  m_f * alpha > m_u  and  n_f > the previous level's n_f  (0 before
+ *     level 1; without the growth clause the rule flips back to pull on the shrinking tail).  In PULL it switches to PUSH
+ *     when  n_f * beta < n.  A host model of this rule predicts info.pull_mask exactly (tests/bfs_tree_ref.py).
+ *   - Options, read at every call, none changes a result: BSPGEMM_OPT_BFS_ALPHA (>= 1, default 15), BSPGEMM_OPT_BFS_BETA
+ *     (>= 1, default 18), BSPGEMM_OPT_BFS_PUSH_LANES (W: 0 = per level, the smallest of 4, 16, 64 at or above m_f / n_f; or 4,
+ *     16 or 64 for every push launch).  Environment BSPGEMM_BFS_TREE_TIMING=1 (read in bspgemm_create): the stage split of
+ *     every call on stderr (transpose, push launches, pull launches, read-backs, read-out, the longest launch with its level
+ *     and frontier size); it then synchronises twice per launch.
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *tree = NULL, *info zeroed and bspgemm_last_error naming the function and the cause: a NULL
+ *     ctx, A or tree (info may be NULL), an unknown direction, a non-square A, source outside [0, n) (which covers n == 0),
+ *     an AT of another shape than n x n, an operand of another context, a column of A or AT outside [0, n) (every column is
+ *     tested on the device before it indexes anything; the context stays usable).  BSPGEMM_ERR_OVERFLOW: more than INT_MAX
+ *     entries in A or AT.  BSPGEMM_ERR_ALLOC: an allocation failed.  Nothing is leaked on any failure path.                */
+typedef enum bspgemm_bfs_direction { BSPGEMM_BFS_AUTO = 0, BSPGEMM_BFS_PUSH = 1, BSPGEMM_BFS_PULL = 2 } bspgemm_bfs_direction;
+typedef struct bspgemm_bfs_tree_info {
+    int64_t  reached;        /* nnz of the result: vertices reached, the source included                    */
+    int64_t  edges_pushed;   /* entries of A walked by the push launches (the sum of their m_f)             */
+    uint64_t pull_mask;      /* bit d-1 set: level d was produced by a pull launch (levels above 64: none)  */
+    int      depth;          /* largest level stored                                                        */
+    int      complete;       /* 1: an empty frontier ended the search; 0: max_depth did                     */
+    int      push_levels, pull_levels;   /* launches of each kind; their sum = levels attempted             */
+    int      transposed;     /* 1: AT was NULL and the call computed (and freed) the transpose itself       */
+    int      canonicalised;  /* 1: the AT passed in had unsorted rows or repeats and was brought to form    */
+} bspgemm_bfs_tree_info;
+bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *AT, int source,
+                                bspgemm_bfs_direction direction, int max_depth, bspgemm_result **tree,
+                                bspgemm_bfs_tree_info *info);
 
 /* Connected components with min-vertex labels, everything device-resident and without a product.  A is square and its
  * entries are read as UNDIRECTED edges: the components are the weakly connected components of the directed graph stored in
