@@ -6,6 +6,10 @@ Cases: every operand of the golden fixtures; rectangular and degenerate shapes; 
 boundaries with entries in the last column; a hub column in every row, a full row, unsorted rows with duplicates; the
 operand sources (interior upload, wrapped torch tensors, a product); the involution; transposed operands in products,
 masked products and the closure; out-of-range columns; the stats ring; and Graph500-skew scale 20.
+
+The kernel edges -- tile and thread tails, the staged and unstaged row_ptr window of the first pass, duplicate runs
+across threads, waves and tiles, the narrow / wide fills of empty rows -- are pinned one by one in
+tests/test_gpu_transpose_edges.py, with the reference (ref_transpose) and a host model in tests/transpose_ref.py.
 """
 import glob
 import os
@@ -17,6 +21,7 @@ import bspgemm
 import empty_ref
 import gen
 from oracle import oracle as O
+from transpose_ref import ref_transpose
 
 pytestmark = pytest.mark.gpu
 ERR_INVALID = 1
@@ -28,21 +33,6 @@ def ctx():
     c = bspgemm.Context(0)
     yield c
     c.close()
-
-
-def ref_transpose(rp, ci, cols):
-    """(row_ptr int32[cols+1], col_idx int32) of pattern(A)^T"""
-    rp = np.asarray(rp, np.int64)
-    ci = np.asarray(ci, np.int64)[rp[0]:rp[-1]]
-    rows = np.repeat(np.arange(rp.size - 1, dtype=np.int64), np.diff(rp))
-    o = np.lexsort((rows, ci))
-    k, i = ci[o], rows[o]
-    keep = np.ones(k.size, bool)
-    keep[1:] = (k[1:] != k[:-1]) | (i[1:] != i[:-1])
-    k, i = k[keep], i[keep]
-    out = np.zeros(cols + 1, np.int64)
-    out[1:] = np.cumsum(np.bincount(k, minlength=cols))
-    return out.astype(np.int32), i.astype(np.int32)
 
 
 def check(ctx, A, rp, ci, cols):
