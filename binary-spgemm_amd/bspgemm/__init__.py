@@ -58,7 +58,7 @@ EXPORTS = [
     "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
-    "bspgemm_strongly_connected_components", "bspgemm_graph_coloring",
+    "bspgemm_strongly_connected_components", "bspgemm_graph_coloring", "bspgemm_label_propagation",
     "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
@@ -80,7 +80,8 @@ SETOPS = {"or": 1, "and": 2, "andnot": 3, "xor": 4}                             
 SYMMETRIZE_DROP_DIAGONAL = 1                                                             # BSPGEMM_SYMMETRIZE_DROP_DIAGONAL
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
-           "shared_slots": 6, "dot_light": 7, "bfs_alpha": 8, "bfs_beta": 9, "bfs_push_lanes": 10}    # bspgemm_option
+           "shared_slots": 6, "dot_light": 7, "bfs_alpha": 8, "bfs_beta": 9, "bfs_push_lanes": 10,
+           "lp_min_class": 11}                                                                           # bspgemm_option
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
 BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
 
@@ -101,6 +102,17 @@ class BfsTreeInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class LpInfo(C.Structure):
+    """bspgemm_lp_info"""
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("communities", C.c_int), ("changed", C.c_int),
+                ("class_vertices", C.c_int64 * 4)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:4]}
+        d["class_vertices"] = [int(x) for x in self.class_vertices]
+        return d
 
 
 class Stats(C.Structure):
@@ -235,6 +247,7 @@ def lib():
     L.bspgemm_kcore.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
     L.bspgemm_strongly_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_graph_coloring.argtypes = [VP, VP, C.c_int, C.c_uint, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bspgemm_label_propagation.argtypes = [VP, VP, VP, C.c_int, PVP, C.POINTER(LpInfo)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -416,7 +429,8 @@ class Context:
 
     def set_option(self, name, value):
         """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
-        "shared_slots" -1/0/k, "dot_light" T >= 0, "bfs_alpha" >= 1, "bfs_beta" >= 1, "bfs_push_lanes" 0/4/16/64"""
+        "shared_slots" -1/0/k, "dot_light" T >= 0, "bfs_alpha" >= 1, "bfs_beta" >= 1, "bfs_push_lanes" 0/4/16/64,
+        "lp_min_class" 0..3"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):
@@ -619,6 +633,21 @@ class Context:
         _chk(lib().bspgemm_graph_coloring(self._h, A._h, self.COLOR_ORDERS[order], int(seed) & 0xFFFFFFFF, C.byref(m),
                                           C.byref(nc), C.byref(rounds)), "bspgemm_graph_coloring")
         return Matrix(self, m, keep=None), nc.value, rounds.value
+
+    def label_propagation(self, A, max_iter=10, initial=None):
+        """bspgemm_label_propagation: (P as a Matrix, info dict) -- community detection by synchronous label propagation on
+        the simple undirected graph of A's entries; P.download()[1] is the label array after max_iter iterations (or at the
+        first iteration that changes nothing): every vertex takes the most frequent label among its neighbours, ties to the
+        smallest.  initial: n host ints in [0, n), or None for label(v) = v.  info: iterations, converged, communities,
+        changed, class_vertices"""
+        if initial is not None:
+            initial = np.ascontiguousarray(initial, dtype=np.int32)
+            if initial.shape != (A.rows,):
+                raise ValueError("initial must hold one label per vertex")
+        m, info = C.c_void_p(), LpInfo()
+        _chk(lib().bspgemm_label_propagation(self._h, A._h, initial.ctypes.data if initial is not None else None, int(max_iter),
+                                             C.byref(m), C.byref(info)), "bspgemm_label_propagation")
+        return Matrix(self, m, keep=None), info.as_dict()
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

@@ -279,6 +279,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     ctx->scc_timing = getenv("BSPGEMM_SCC_TIMING") != nullptr;
     ctx->color_timing = getenv("BSPGEMM_COLOR_TIMING") != nullptr;
     ctx->bfs_tree_timing = getenv("BSPGEMM_BFS_TREE_TIMING") != nullptr;
+    ctx->lp_timing = getenv("BSPGEMM_LP_TIMING") != nullptr;
     if (ctx->debug_alloc)
         fprintf(stderr, "[bspgemm] device %d: %s, %zu MiB, %d CUs; result cache budget %zu MiB\n", device,
                 prop.gcnArchName, (size_t)(prop.totalGlobalMem >> 20), prop.multiProcessorCount, ctx->cache_budget >> 20);
@@ -757,6 +758,10 @@ extern "C" bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_optio
         if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "bfs push lanes: 0, 4, 16 or 64");
         ctx->bfs_push_lanes = value;
         return BSPGEMM_OK;
+    case BSPGEMM_OPT_LP_MIN_CLASS:
+        if (value < 0 || value > 3) return FAIL(BSPGEMM_ERR_INVALID, "lp min class: 0..3");
+        ctx->lp_min_class = value;
+        return BSPGEMM_OK;
     }
     return FAIL(BSPGEMM_ERR_INVALID, "unknown option");
 }
@@ -775,6 +780,7 @@ extern "C" int bspgemm_get_option(const bspgemm_context *ctx, bspgemm_option opt
     case BSPGEMM_OPT_BFS_ALPHA: return ctx->bfs_alpha;
     case BSPGEMM_OPT_BFS_BETA: return ctx->bfs_beta;
     case BSPGEMM_OPT_BFS_PUSH_LANES: return ctx->bfs_push_lanes;
+    case BSPGEMM_OPT_LP_MIN_CLASS: return ctx->lp_min_class;
     }
     return INT_MIN;
 }

@@ -143,12 +143,14 @@ struct bspgemm_context {
     int dot_light = 32;                 // BSPGEMM_OPT_DOT_LIGHT: the longest shorter row that one lane of k_dot_count intersects by itself (dot.hip)
     int bfs_alpha = 15, bfs_beta = 18;  // BSPGEMM_OPT_BFS_ALPHA / _BETA: the direction rule of bspgemm_bfs_tree under AUTO (bfs_tree.hip)
     int bfs_push_lanes = 0;             // BSPGEMM_OPT_BFS_PUSH_LANES: 0 per level from the frontier's mean out-degree, or 4, 16, 64 lanes per frontier vertex
+    int lp_min_class = 0;               // BSPGEMM_OPT_LP_MIN_CLASS: 0 .. 3, the smallest degree class of bspgemm_label_propagation (lp.hip)
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
     bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
     bool scc_timing = false;            // BSPGEMM_SCC_TIMING: trim / forward / backward launch counts and times of the strong components on stderr
     bool bfs_tree_timing = false;       // BSPGEMM_BFS_TREE_TIMING: stage times of the single-source search on stderr (it then synchronises twice per launch)
     bool color_timing = false;          // BSPGEMM_COLOR_TIMING: stage times of the graph colouring on stderr (it then synchronises twice per launch)
+    bool lp_timing = false;             // BSPGEMM_LP_TIMING: stage times of the label propagation on stderr (it then synchronises twice per iteration)
 };
 
 extern "C" int bspgemm_par_max_plus_one(const int *idx, long long n);              // host/par_copy.c
@@ -250,7 +252,7 @@ size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratc
 size_t transpose_workspace_ints(long long E, int cols);
 size_t symmetrize_workspace_ints(long long E, int n);
 
-// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip) ---
+// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip) ---
 // What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
 // each algorithm's own.  who: the entry point's name, which every message starts with.
 // the graph operand: check_operand with `flags`, then an entry count that an int32 entry index cannot hold
@@ -290,7 +292,7 @@ static inline bspgemm_status fail_stuck(const char *who)
     snprintf(g_err, sizeof g_err, "%s: did not converge", who);
     return BSPGEMM_ERR_HIP;
 }
-// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING)
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING)
 using host_clock = std::chrono::steady_clock;
 static inline double ms_since(host_clock::time_point t)
 {

@@ -1,0 +1,66 @@
+/*
+ * spgemm_hip_cdlp.c -- community detection by synchronous label propagation on an undirected graph, everything resident
+ * on the GPU (include/bspgemm.h: bspgemm_label_propagation), beside the connected-components, k-core and colouring drivers.
+ *
+ *     SpGEMM_hip_cdlp  file.mtx  [--iterations K]  [--labels out.txt]
+ *
+ * The transpose that the loader hands back (readCOO, final/utils.c:47-81) is used as it is: the call reads the entries as
+ * undirected edges.  Every vertex starts with its own id as its label; K defaults to 10 (LDBC Graphalytics' choice).
+ * Prints one line  n,nnz,communities,largest_community,iterations,converged,ms  -- the number of distinct labels, the size
+ * of the largest community (counted on the host from the downloaded labels), the iterations the call ran, whether the last
+ * of them changed nothing, and the call's wall time, the operand already on the device.
+ * --labels writes one label per line, line v the label (a 0-based vertex id) of vertex v.
+ */
+#include "cli_common.h"
+
+static void usage(void)
+{
+    printf("usage: SpGEMM_hip_cdlp  path-to-matrix  [--iterations K]  [--labels out.txt]\n");
+    exit(1);
+}
+
+int main(int argc, char **argv)
+{
+    const char *labels_path = NULL;
+    int iterations = 10;
+    if (argc < 2 || argc % 2 != 0) usage();
+    for (int i = 2; i < argc; i += 2) {
+        if (strcmp(argv[i], "--iterations") == 0) {
+            char *end;
+            const long k = strtol(argv[i + 1], &end, 0);
+            if (end == argv[i + 1] || *end || k < 0 || k > 0x7fffffffL) usage();
+            iterations = (int)k;
+        } else if (strcmp(argv[i], "--labels") == 0) {
+            labels_path = argv[i + 1];
+        } else {
+            usage();
+        }
+    }
+    uint32_t *Arow, *Acol, M, N, nnz;
+    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
+    cli_need_square("label propagation", M, N);
+    bspgemm_context *ctx = cli_context(0);
+    bspgemm_matrix *A, *P;
+    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
+    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    const struct timespec t0 = cli_now();
+    bspgemm_lp_info info;
+    CHECK(bspgemm_label_propagation(ctx, A, NULL, iterations, &P, &info), "bspgemm_label_propagation");
+    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    const double ms = cli_ms(t0, cli_now());
+    int *label = malloc(((size_t)M + 1) * sizeof(int));
+    int *size = calloc((size_t)M + 1, sizeof(int));
+    if (!label || !size) exit(1);
+    CHECK(bspgemm_matrix_download(ctx, P, NULL, label), "download");
+    int largest = 0;
+    for (uint32_t v = 0; v < M; v++)
+        if (++size[label[v]] > largest) largest = size[label[v]];
+    if (labels_path) cli_write_ints(labels_path, label, M);
+    printf("%u,%u,%d,%d,%d,%d,%.3f\n", M, nnz, info.communities, largest, info.iterations, info.converged, ms);
+    free(label); free(size);
+    bspgemm_matrix_free(P);
+    bspgemm_matrix_free(A);
+    bspgemm_destroy(ctx);
+    free(Arow); free(Acol);
+    return 0;
+}

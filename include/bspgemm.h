@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -191,7 +191,9 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  *                    wave kernel; a very large value: none does (bspgemm_dot_info.heavy_entries says how many did).  Read
  *                    at every call.
  *   BFS_ALPHA, BFS_BETA (>= 1; defaults 15 and 18) and BFS_PUSH_LANES (0 automatic, or 4, 16, 64): the direction rule and the
- *                    lanes per frontier vertex of bspgemm_bfs_tree, described there.  Read at every call.  */
+ *                    lanes per frontier vertex of bspgemm_bfs_tree, described there.  Read at every call.
+ *   LP_MIN_CLASS     0 (default) .. 3: the smallest degree class that bspgemm_label_propagation gives a vertex to (0 lane, 1 wave,
+ *                    2 workgroup, 3 hub), described there.  It changes no result.  Read at every call.  */
 typedef enum bspgemm_option {
     BSPGEMM_OPT_CLASS_STREAMS   = 1,
     BSPGEMM_OPT_BLOCKED_EXTENTS = 2,
@@ -202,7 +204,8 @@ typedef enum bspgemm_option {
     BSPGEMM_OPT_DOT_LIGHT       = 7,
     BSPGEMM_OPT_BFS_ALPHA       = 8,
     BSPGEMM_OPT_BFS_BETA        = 9,
-    BSPGEMM_OPT_BFS_PUSH_LANES  = 10
+    BSPGEMM_OPT_BFS_PUSH_LANES  = 10,
+    BSPGEMM_OPT_LP_MIN_CLASS    = 11
 } bspgemm_option;
 bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_option opt, int value);
 /* current value of a knob (INT32_MIN for an unknown option or a NULL context) */
@@ -713,6 +716,64 @@ typedef enum bspgemm_color_order { BSPGEMM_COLOR_NATURAL = 1, BSPGEMM_COLOR_RAND
                                    BSPGEMM_COLOR_LARGEST_FIRST = 3 } bspgemm_color_order;
 bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_color_order order,
                                       unsigned seed, bspgemm_matrix **P, int *ncolors, int *rounds);
+
+/* Community detection by synchronous label propagation (CDLP as LDBC Graphalytics defines it), everything device-resident
+ * and without a product.  A is square and its entries are read as undirected edges exactly as bspgemm_core_numbers and
+ * bspgemm_graph_coloring read them: the graph is S = bspgemm_matrix_symmetrize(A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL), computed
+ * inside the call and freed on every path, so unsorted rows, repeats, self-loops, one-direction storage and the in-edges
+ * that bspgemm_readCOO hands back all give the same answer: an edge counts once however it is stored.
+ *   - The definition.  L_0(v) = initial_labels[v], or v when initial_labels == NULL.  For t = 1 .. max_iter, synchronously
+ *     (every vertex reads L_(t-1) only): L_t(v) = the smallest label among those that occur most often in the multiset
+ *     { L_(t-1)(w) : w in S_v }, and L_t(v) = L_(t-1)(v) when S_v is empty.  The result is L after exactly max_iter
+ *     iterations.  The call may stop early at the first iteration that changes no label: that is a fixpoint, so the bits
+ *     are the same; it then reports converged = 1.  Counts are integers and the argmax with its tie rule is unique, so
+ *     every run gives the same bits, independent of scheduling.
+ *   - Synchronous propagation OSCILLATES with period 2 on bipartite components -- a single edge swaps its two labels
+ *     forever -- and max_iter is what ends it: the result then depends on whether max_iter is even or odd.  The 2-cycle is
+ *     not detected.
+ *   - *P is the n x n assignment operand, exactly as bspgemm_connected_components returns it: P.row_ptr = 0, 1, ..., n and
+ *     P.col_idx[v] = label(v).  bspgemm_matrix_transpose(P) holds the ascending member list of community c in row c, and
+ *     P^T * S * P by two multiplies is the community graph.  It is an owned operand laid out like an uploaded one
+ *     (bspgemm_matrix_free), usable in every product, transpose and select, complete on the context's stream when the call
+ *     returns.
+ *   - initial_labels is a HOST array of n ints in [0, n), or NULL: warm starts and seeded communities.  It is checked on
+ *     the host before anything is launched; a value outside [0, n) is BSPGEMM_ERR_INVALID and the message names the
+ *     function and the index.  The array is free again when the call returns.
+ *   - max_iter == 0: P holds L_0, iterations 0, converged 0.  max_iter < 0: BSPGEMM_ERR_INVALID.  Any n, n == 0 and
+ *     nnz == 0 included: when S has no entries (max_iter == 0 or not) the labels are L_0, iterations 0 and converged 1 --
+ *     no label can ever change.
+ *   - info may be NULL; it is zeroed on failure.  iterations = propagation iterations run, the one that changed nothing
+ *     included; converged; communities = distinct labels in the result, counted on the device; changed = vertices whose
+ *     label the last iteration changed (0 without an iteration); class_vertices: below.
+ *   - The scheme.  S does not change, so its vertices are sorted once per call into four degree classes: lane (1 <= d <= 8,
+ *     one lane per vertex, the row's labels in registers), wave (d <= 256, one wave per vertex: the labels gathered into
+ *     LDS, sorted there, run lengths by a binary search from each run's last element, (count, label) reduced across the
+ *     wave), workgroup (d <= 4096, the same at workgroup scope) and hub (longer: the row's entries are walked
+ *     entry-parallel, so a hub costs what its entries cost, and inserted into the hub's own open-addressing table of 2 d
+ *     slots in the context's workspace by a device-scope atomicCAS and atomicAdd; a second launch reduces every table to
+ *     its argmax).  Every iteration launches each non-empty class over its list, reads the labels of the iteration before
+ *     from one array and writes the new ones to another (P.col_idx and one workspace array), and reads back one counter
+ *     (64 words that the host sums), its only synchronisation.  Isolated vertices are in no class.  No kernel waits for another workgroup
+ *     (csrc/lp.hip).  Workspace: about 7 n ints, and 4 ints per stored entry of a hub's row.
+ *   - BSPGEMM_OPT_LP_MIN_CLASS (0 default .. 3), read at every call: a vertex of degree >= 1 runs in the class max(its own,
+ *     value) -- a row that fits a smaller class fits every larger one.  It changes no result; class_vertices reports what
+ *     ran.  Environment BSPGEMM_LP_TIMING=1 (read in bspgemm_create): the stage split on stderr -- symmetrize, class lists,
+ *     the iterations' launches and read-backs, and the longest iteration; it then synchronises twice per iteration.
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *P = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A or P,
+ *     max_iter < 0, a non-square A, A from another context, an initial label out of range.  Otherwise the errors of
+ *     bspgemm_matrix_symmetrize: BSPGEMM_ERR_INVALID for a column outside [0, n) anywhere in A (the context stays usable),
+ *     BSPGEMM_ERR_OVERFLOW for more than INT_MAX entries in S, BSPGEMM_ERR_ALLOC.  Nothing is leaked on any path.            */
+typedef struct bspgemm_lp_info {
+    int     iterations;         /* propagation launches run, the one that changed nothing included          */
+    int     converged;          /* 1: an iteration changed no label; 0: max_iter ended it                    */
+    int     communities;        /* distinct labels in the result, counted on the device                      */
+    int     changed;            /* vertices whose label the last iteration changed                           */
+    int64_t class_vertices[4];  /* vertices of S per degree class: [0] lane, [1] wave, [2] workgroup, [3] hub;
+                                   isolated vertices are in none                                             */
+} bspgemm_lp_info;
+bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const bspgemm_matrix *A, const int *initial_labels,
+                                         int max_iter, bspgemm_matrix **P, bspgemm_lp_info *info);
 
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
