@@ -59,6 +59,7 @@ EXPORTS = [
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
     "bspgemm_strongly_connected_components", "bspgemm_graph_coloring", "bspgemm_label_propagation",
+    "bspgemm_local_clustering",
     "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
@@ -84,6 +85,7 @@ OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4
            "lp_min_class": 11}                                                                           # bspgemm_option
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
 BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
+LCC_DIRECTED = 1                                                                         # BSPGEMM_LCC_DIRECTED
 
 
 class DotInfo(C.Structure):
@@ -113,6 +115,14 @@ class LpInfo(C.Structure):
         d = {k: int(getattr(self, k)) for k, _ in self._fields_[:4]}
         d["class_vertices"] = [int(x) for x in self.class_vertices]
         return d
+
+
+class LccInfo(C.Structure):
+    """bspgemm_lcc_info"""
+    _fields_ = [("triangles", C.c_int64), ("entries", C.c_int64), ("heavy_entries", C.c_int64), ("reciprocal", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -248,6 +258,7 @@ def lib():
     L.bspgemm_strongly_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_graph_coloring.argtypes = [VP, VP, C.c_int, C.c_uint, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_label_propagation.argtypes = [VP, VP, VP, C.c_int, PVP, C.POINTER(LpInfo)]
+    L.bspgemm_local_clustering.argtypes = [VP, VP, C.c_uint, PVP, VP, VP, C.POINTER(LccInfo)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -648,6 +659,19 @@ class Context:
         _chk(lib().bspgemm_label_propagation(self._h, A._h, initial.ctypes.data if initial is not None else None, int(max_iter),
                                              C.byref(m), C.byref(info)), "bspgemm_label_propagation")
         return Matrix(self, m, keep=None), info.as_dict()
+
+    def local_clustering(self, A, directed=False):
+        """bspgemm_local_clustering: (counts as a Result, degree int32[n], lcc float64[n], info dict) -- the local clustering
+        coefficient of every vertex of the simple undirected graph S of A's entries; row v of the result holds the one entry
+        (v, v), Result.download_values()[v] = num(v): the ordered pairs of distinct neighbours of v that are joined in S
+        (twice the triangles at v), or with directed=True (BSPGEMM_LCC_DIRECTED) joined by an entry of A.  degree = |S_v|,
+        lcc = num / (d (d - 1)) in double, 0 where d < 2.  info: triangles, entries, heavy_entries, reciprocal"""
+        r, info = C.c_void_p(), LccInfo()
+        degree, lcc = np.zeros(A.rows, np.int32), np.zeros(A.rows, np.float64)
+        _chk(lib().bspgemm_local_clustering(self._h, A._h, LCC_DIRECTED if directed else 0, C.byref(r),
+                                            degree.ctypes.data if A.rows else None, lcc.ctypes.data if A.rows else None,
+                                            C.byref(info)), "bspgemm_local_clustering")
+        return Result(self, r), degree, lcc, info.as_dict()
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

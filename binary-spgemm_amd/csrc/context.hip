@@ -280,6 +280,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     ctx->color_timing = getenv("BSPGEMM_COLOR_TIMING") != nullptr;
     ctx->bfs_tree_timing = getenv("BSPGEMM_BFS_TREE_TIMING") != nullptr;
     ctx->lp_timing = getenv("BSPGEMM_LP_TIMING") != nullptr;
+    if (const char *e = getenv("BSPGEMM_LCC_TIMING")) ctx->lcc_timing = atoi(e) == 2 ? 2 : 1;
     if (ctx->debug_alloc)
         fprintf(stderr, "[bspgemm] device %d: %s, %zu MiB, %d CUs; result cache budget %zu MiB\n", device,
                 prop.gcnArchName, (size_t)(prop.totalGlobalMem >> 20), prop.multiProcessorCount, ctx->cache_budget >> 20);

@@ -151,6 +151,7 @@ struct bspgemm_context {
     bool bfs_tree_timing = false;       // BSPGEMM_BFS_TREE_TIMING: stage times of the single-source search on stderr (it then synchronises twice per launch)
     bool color_timing = false;          // BSPGEMM_COLOR_TIMING: stage times of the graph colouring on stderr (it then synchronises twice per launch)
     bool lp_timing = false;             // BSPGEMM_LP_TIMING: stage times of the label propagation on stderr (it then synchronises twice per iteration)
+    int lcc_timing = 0;                 // BSPGEMM_LCC_TIMING: 1 stage times of the local clustering on stderr (it then synchronises behind every stage); 2: the same on the half that is not kept (lcc.hip)
 };
 
 extern "C" int bspgemm_par_max_plus_one(const int *idx, long long n);              // host/par_copy.c
@@ -292,7 +293,7 @@ static inline bspgemm_status fail_stuck(const char *who)
     snprintf(g_err, sizeof g_err, "%s: did not converge", who);
     return BSPGEMM_ERR_HIP;
 }
-// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING)
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING)
 using host_clock = std::chrono::steady_clock;
 static inline double ms_since(host_clock::time_point t)
 {

@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING=1|2; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -774,6 +774,65 @@ typedef struct bspgemm_lp_info {
 } bspgemm_lp_info;
 bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const bspgemm_matrix *A, const int *initial_labels,
                                          int max_iter, bspgemm_matrix **P, bspgemm_lp_info *info);
+
+/* The local clustering coefficient (LCC as LDBC Graphalytics defines it) with an integer count per vertex, everything
+ * device-resident and without a product.  A is square and its entries are read exactly as bspgemm_core_numbers reads them:
+ * S = bspgemm_matrix_symmetrize(A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL) is computed inside the call and freed on every path,
+ * N(v) = S_v and d(v) = |S_v|, so unsorted rows, repeats, self-loops, one-direction storage and the in-edges that
+ * bspgemm_readCOO hands back all give the same answer; any n, n == 0 and nnz == 0 included.
+ *   - The numerator.  flags == 0 (undirected): num(v) = #{(u, w) : u, w in N(v), u != w, (u, w) in S} = 2 * triangles(v).
+ *     flags == BSPGEMM_LCC_DIRECTED (Graphalytics' directed LCC): num(v) = #{(u, w) : u, w in N(v), u != w, (u, w) stored
+ *     in A}; repeats count once, and N(v) is still the union of in- and out-neighbours.  The value is invariant under
+ *     transposing A -- (u, w) is stored in A^T exactly when (w, u) is stored in A, and the pairs are ordered -- so the
+ *     loader's in-edges give the file's answer and no bspgemm_matrix_transpose is needed.  For a symmetric A it equals the
+ *     undirected value.  Any other flag bit is BSPGEMM_ERR_INVALID.
+ *   - The coefficient.  lcc(v) = 0.0 when d(v) < 2, otherwise (double)num / ((double)d * (double)(d - 1)), computed on the
+ *     host in plain C from the read-back integers: bit for bit numpy's num.astype(float64) / (d.astype(float64) *
+ *     (d - 1).astype(float64)); no tolerance is involved anywhere.
+ *   - The range.  num(v) counts distinct stored entries among v's neighbours, so num(v) <= nnz(S) (undirected) or <= the
+ *     number of distinct off-diagonal entries of A (directed); both are <= INT_MAX, or the symmetrize has already failed with
+ *     BSPGEMM_ERR_OVERFLOW.  An int32 per vertex is therefore exact, and every partial sum an atomic holds is bounded by
+ *     the final value.  Integer addition commutes: every run gives the same bits, independent of scheduling.
+ *   - *counts is a counted result of n rows laid out exactly like bspgemm_core_numbers' result: row v holds the one entry
+ *     (v, v) with the int32 value num(v); zeros are stored.  bspgemm_result_download, _download_values, _values_device,
+ *     _values_sum and _free work on it unchanged; bspgemm_matrix_from_result_where gives vertex selectors.  n == 0: a result
+ *     without rows.  It is complete on the context's stream when the call returns.
+ *   - degree_host (n ints, d(v)) and lcc_host (n doubles) are HOST arrays; each may be NULL.  info may be NULL; it is zeroed
+ *     on failure.  triangles = the triangles of S, each once, summed on the device (= bspgemm_triangle_count(S)).
+ *   - The scheme.  Every triangle is walked ONCE, on an oriented half T = bspgemm_matrix_select(S, TRIL) of S, and all three
+ *     corners are credited: entry (i, j) of T and a common element k of T_i and T_j are the triangle i > j > k, and the
+ *     corner opposite to an edge receives the number of directions that edge is stored in (always 2 when undirected;
+ *     DIRECTED: a byte per entry of T, 2 when the entry is in R = A' and A'^T, A' = A without its diagonal, else 1, written
+ *     by an entry-parallel search of T's entries in R).  The count is entry-parallel over T in select's geometry: an entry
+ *     whose shorter row has at most BSPGEMM_OPT_DOT_LIGHT elements (the masked dot's option; it changes no result) is
+ *     intersected by one lane, a longer one is appended to a list and walked by ONE wave in a second launch, 64 elements
+ *     of the shorter row per step.  The credits of num[k], one per hit, are summed per workgroup in a cache of 1024 slots
+ *     in LDS and reach num[k] by one device-scope atomicAdd per cached k and workgroup (a k whose slot another k holds:
+ *     one per hit); num[j] gets one atomic per entry, num[i] one per row and lane; the counts accumulate in the result's
+ *     values.  Which half is walked is internal and changes no result.
+ *     One synchronisation reads the counters (and the degrees and counts where the caller asked for them).  No kernel
+ *     waits for another workgroup (csrc/lcc.hip).  Workspace: 8 bytes per entry of T for the list, one byte per entry for
+ *     the weights, in the context's workspace, grown before anything is launched.
+ *   - Cost: sum over the entries (i, j) of T of min(|T_i|, |T_j|) searches and one credit per triangle to the counter of
+ *     its lowest corner -- on a skewed graph the hubs' counters, which is what the cache is for.  A
+ *     hub-hub entry is a serial tail of one wave.  nnz(S) == 0: all zeros, and no intersection kernel is launched.  Environment BSPGEMM_LCC_TIMING=1 (read in
+ *     bspgemm_create): the stage split on stderr -- symmetrize and select, weights, count, heavy, finish; it then
+ *     synchronises behind every stage (=2: the same on the other half, TRIU, for the comparison).
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *counts = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A or
+ *     counts, an unknown flag, a non-square A, A from another context.  Otherwise the errors of bspgemm_matrix_symmetrize:
+ *     BSPGEMM_ERR_INVALID for a column outside [0, n) anywhere in A (the context stays usable), BSPGEMM_ERR_OVERFLOW for
+ *     more than INT_MAX entries in S, BSPGEMM_ERR_ALLOC.  Nothing is leaked on any path.                                      */
+#define BSPGEMM_LCC_DIRECTED 1u
+typedef struct bspgemm_lcc_info {
+    int64_t triangles;      /* triangles of S, each counted once (a by-product, summed on the device)     */
+    int64_t entries;        /* entries of the oriented triangle of S that were walked (= nnz(S) / 2)      */
+    int64_t heavy_entries;  /* of them, intersected by a whole wave                                       */
+    int64_t reciprocal;     /* DIRECTED: edges {i,j} of S stored in both directions in A; else 0          */
+} bspgemm_lcc_info;
+bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags,
+                                        bspgemm_result **counts, int *degree_host, double *lcc_host,
+                                        bspgemm_lcc_info *info);
 
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
