@@ -28,12 +28,16 @@ static int wave_top_words(int levels, int cols)
 // shared slots"; profiles/r07_shared_slots_*): every loser costs a pass over the row's chunks, the masks it saves cost the
 // same whatever their number.  Up to 4 chunks: 4 -- n = 2^18 uniform (every row 256 products, 4 shared slots on average) is
 // level up to 4 and 1.5 % of its numeric phase slower from 5 on.  5 .. 8 chunks: 8 -- the bench matrix still gains from 4 to
-// 8 (numeric phase 3.25 -> 3.23 ms) and is level above.  10 .. 16 chunks: 4, as the chunks per loser double.
+// 8 (numeric phase 3.25 -> 3.23 ms) and is level above.  10, 12 chunks: 4, as the chunks per loser double -- 8 is within
+// their run-to-run spread.  14, 16 chunks: 8 -- at 4, 18 % and 37 % of the bench matrix's rows of these classes still build
+// their masks, at 8 under 2 %; measured per class on one stream, 0.165 -> 0.161 ms and 0.078 -> 0.075 ms, level from 8 to 16
+// (profiles/large_classes_per_class.log).  Above 16 chunks the path is not compiled: it gains 3 % in the class of 20 chunks
+// (1.2 % of the products) and loses from 24 chunks on.
 int wave_shared_max(int bin, int shared_slots)
 {
     static_assert(kWaveBins == 16, "one entry per capacity class");
     //                                          chunks: -  1  2  3  4  5  6  7  8 10 12 14 16 20 24 28 32
-    static const int auto_max[kWaveBins + 1] = {0, 4, 4, 4, 4, 8, 8, 8, 8, 4, 4, 4, 4, 0, 0, 0, 0};
+    static const int auto_max[kWaveBins + 1] = {0, 4, 4, 4, 4, 8, 8, 8, 8, 4, 4, 8, 8, 0, 0, 0, 0};
     if (bin < 1 || bin > kWaveBins || kWaveChunks[bin] > 16) return 0;       // (no such path above 16 chunks)
     if (shared_slots < 0) return auto_max[bin];
     return shared_slots > kSharedSlotsMax ? kSharedSlotsMax : shared_slots;

@@ -20,7 +20,8 @@
 //   Per product: one B.col_idx load, LEVELS ds_or_b32, LEVELS-1 (ds_read_b32 + ds_read_u16);
 //   rank = v_bcnt_u32_b32(word & below, prefix) -- popcount and add in one instruction.
 //   32-bit words (not 64): every mask op is a single full-rate VALU instruction and the slot
-//   arrays take 14 B of LDS per product of capacity, which is what sets the occupancy.
+//   arrays take 10 B of LDS per product of capacity, which is what sets the occupancy: ONE slot buffer S holds every
+//   ranked level in turn -- a level is dead once its words and prefixes are in registers, so its child is built in place.
 //
 // Gather: the F_i products of a row are the concatenation of the B rows selected by A's row.
 //   The prepass left ab[jj] = (start, length) of the B row behind every A-nonzero, so lanes read
@@ -68,9 +69,8 @@ struct WaveCfg {
     static constexpr int SLOTS = 64 * SW;
     static constexpr int TOPW = 64 * TWP;
     static constexpr int bytes_per_wave = 4 * TOPW + 2 * TOPW + 8 * CHUNKS + 4 * SLOTS         // top, topPre, starts, L0w
-                                          + (LEVELS >= 2 ? 4 * SLOTS : 16)                       // SA
-                                          + (LEVELS >= 3 ? 4 * SLOTS + 2 * SLOTS : 32)           // SB, preB
-                                          + (LEVELS >= 4 ? 2 * SLOTS : 16);                      // preA
+                                          + (LEVELS >= 2 ? 4 * SLOTS : 16)                       // S
+                                          + (LEVELS >= 3 ? 2 * SLOTS : 16);                      // pre
     // workgroup size that keeps the most waves resident (LDS is what limits occupancy here)
     static constexpr int w4 = waves_per_cu(4, bytes_per_wave), w2 = waves_per_cu(2, bytes_per_wave);
     static constexpr int WAVES = (w4 >= w2 && w4 > 0) ? 4 : (w2 > 0 ? 2 : 1);
@@ -178,7 +178,7 @@ __device__ __forceinline__ int drop_mask_cols(u32 *stage, int n, u32 *hit, const
 
 // COUNT instances, round 4: a HASH FILTER in front of the sweeps.  The count pass only has to answer "how many of the row's
 // products repeat an earlier column", and on most inputs the answer is none (98 % of the rows of the bench matrix).  Every
-// product test-and-sets ONE bit of a hash bitmap (all of SA: 32 bits per product of capacity; one returning ds_or): a product
+// product test-and-sets ONE bit of a hash bitmap (all of S: 32 bits per product of capacity; one returning ds_or): a product
 // that finds its bit clear is the first with its column for certain.  The few that find it set ("ambiguous": a true repeat or
 // a hash collision, ~F/64 of them) are settled exactly, one by one, by comparing their column with every product of the
 // row in registers: an ambiguous product repeats an earlier column iff an equal product exists that is not ambiguous (it
@@ -220,10 +220,9 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
     __shared__ __attribute__((aligned(16))) unsigned short s_topPre[WAVES][TOPW];
     __shared__ __attribute__((aligned(16))) u64 s_starts[WAVES][CHUNKS];
     __shared__ __attribute__((aligned(16))) u32 s_L0w[WAVES][SLOTS];       // also the gather's delta[] and the emit staging
-    __shared__ __attribute__((aligned(16))) u32 s_SA[WAVES][LEVELS >= 2 ? SLOTS : 4];
-    __shared__ __attribute__((aligned(16))) u32 s_SB[WAVES][LEVELS >= 3 ? SLOTS : 4];
-    __shared__ __attribute__((aligned(16))) unsigned short s_preB[WAVES][LEVELS >= 3 ? SLOTS : 8];
-    __shared__ __attribute__((aligned(16))) unsigned short s_preA[WAVES][LEVELS >= 4 ? SLOTS : 8];
+    // the ranked levels, one after the other: level `lev` is built in the words that held level lev + 1 (see the descent)
+    __shared__ __attribute__((aligned(16))) u32 s_S[WAVES][LEVELS >= 2 ? SLOTS : 4];
+    __shared__ __attribute__((aligned(16))) unsigned short s_pre[WAVES][LEVELS >= 3 ? SLOTS : 8];
 
     const int lane = lane_id();
     // product slot of this lane inside a 64-product chunk: bit-reversed, so that neighbouring
@@ -255,17 +254,14 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
     u64 *starts = s_starts[wave_in_wg];
     u32 *L0w = s_L0w[wave_in_wg];
     int *delta = reinterpret_cast<int *>(s_L0w[wave_in_wg]);      // dead before L0w lives
-    u32 *SA = s_SA[wave_in_wg];
-    u32 *SB = s_SB[wave_in_wg];
-    unsigned short *preA = s_preA[wave_in_wg];
-    unsigned short *preB = s_preB[wave_in_wg];
+    u32 *S = s_S[wave_in_wg];
+    unsigned short *Spre = s_pre[wave_in_wg];
 
     // zero the structures that must be all-zero at the start of a row (kept so by every row)
     constexpr int TW = TOPW / 64;                                  // top words per lane
     clear_blocked<TW>(top, lane);
     if (lane < CHUNKS) starts[lane] = 0ull;
-    if (LEVELS >= 2) clear_blocked<SW>(SA, lane);
-    if (LEVELS >= 3) clear_blocked<SW>(SB, lane);
+    if (LEVELS >= 2) clear_blocked<SW>(S, lane);
     wave_lds_fence();
 
     // prefetch of the first row's B-row extents
@@ -380,8 +376,8 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
         bool row_counted = false;   // wave-uniform: the hash filter has settled |C_i|
         int running = 0;            // |C_i|
         if constexpr (COUNT && LEVELS >= 2 && CHUNKS <= 16) {       // (beyond 16 chunks the per-chunk masks spill: the sweeps stay)
-            constexpr int HB = wr_floor_log2(32 * SLOTS);          // bits of the hash bitmap (SA, all zero between rows)
-            u32 *hb = SA;
+            constexpr int HB = wr_floor_log2(32 * SLOTS);          // bits of the hash bitmap (S, all zero between rows)
+            u32 *hb = S;
             bool amb[CHUNKS];
             u64 am[CHUNKS];
             int namb = 0;
@@ -400,7 +396,7 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                 am[c] = __ballot(amb[c]);
                 namb += __popcll(am[c]);
             }
-            clear_blocked<SW>(hb, lane);                           // SA is all zero again, whichever way the row goes
+            clear_blocked<SW>(hb, lane);                           // S is all zero again, whichever way the row goes
             wave_lds_fence();
             if (namb <= kMaxAmbiguous) {
                 int dups = 0;
@@ -460,7 +456,6 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
             wave_lds_fence();
             const u32 *P = top;
             const unsigned short *Ppre = topPre;
-            u32 *Pmut = top;
             bool parent_is_top = true;
 #pragma unroll
             for (int lev = LEVELS - 2; lev >= 0; lev--) {
@@ -469,9 +464,9 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                 const bool sparse = lev == 0 && nslots0 == F;
                 // nearly sparse: the row never touches its masks either, and is put in order from the columns alone (below)
                 if constexpr (FEW) few = lev == 0 && nslots0 != F && F - nslots0 <= shared_max;
-                // level `lev` slot buffers alternate: lev even -> SA/preA, lev odd -> SB/preB
-                u32 *S = (lev & 1) ? SB : SA;
-                unsigned short *Spre = (lev & 1) ? preB : preA;
+                // Level `lev` goes to S, all zero here.  Below the first ranked level its parent is in S too: the parent is
+                // dead once every chunk's word and prefix are in px[] / ppre[], so it is cleared between those reads and the
+                // first OR, and the child is built in its place (DS operations of one wave execute in issue order).
                 u32 px[CHUNKS];
                 int ppre[CHUNKS];
 #pragma unroll
@@ -480,6 +475,11 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                         px[c] = P[rank[c]];
                         ppre[c] = Ppre[rank[c]];
                     }
+                if (!parent_is_top) {
+                    wave_lds_fence();
+                    clear_blocked<SW>(S, lane);                    // parent level is consumed
+                    wave_lds_fence();
+                }
 #pragma unroll
                 for (int c = 0; c < CHUNKS; c++)                   // ... then all the ORs
                     {
@@ -501,18 +501,16 @@ void k_wave_rows(const int2 *__restrict__ ab, const int *__restrict__ Bcol,
                         rank[c] = r2;
                     }
                 wave_lds_fence();
-                if (parent_is_top) clear_blocked<TW>(Pmut, lane);  // parent level is consumed
-                else clear_blocked<SW>(Pmut, lane);
+                if (parent_is_top) clear_blocked<TW>(top, lane);   // parent level is consumed
                 parent_is_top = false;
                 if (lev > 0) {
                     nslots0 = scan_blocked<SW>(S, Spre, lane);
                     P = S;
-                    Pmut = S;
                     Ppre = Spre;
                 }
                 wave_lds_fence();
             }
-            S0 = SA;                                               // level 0 is even
+            S0 = S;
         }
 
         // ---- few shared slots: F - nslots0 <= shared_max products more than slots.  Such a row is a sparse row but for

@@ -16,7 +16,7 @@ for line in err.splitlines():
         continue
     k, v = m.group(1).strip(), m.group(2)
     if k in ("Function Name", "Name"):
-        cur = {"name": subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip().split("(")[0]}
+        cur = {"name": subprocess.run(["c++filt", "-p", v], capture_output=True, text=True).stdout.strip()}   # -p: no parameter list
         rows.append(cur)
     else:
         cur[k] = v
