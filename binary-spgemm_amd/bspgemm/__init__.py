@@ -59,7 +59,7 @@ EXPORTS = [
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
     "bspgemm_strongly_connected_components", "bspgemm_graph_coloring", "bspgemm_label_propagation",
-    "bspgemm_local_clustering",
+    "bspgemm_local_clustering", "bspgemm_pagerank",
     "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
@@ -82,10 +82,11 @@ SYMMETRIZE_DROP_DIAGONAL = 1                                                    
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
            "shared_slots": 6, "dot_light": 7, "bfs_alpha": 8, "bfs_beta": 9, "bfs_push_lanes": 10,
-           "lp_min_class": 11}                                                                           # bspgemm_option
+           "lp_min_class": 11, "pr_min_class": 12}                                                                           # bspgemm_option
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
 BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
 LCC_DIRECTED = 1                                                                         # BSPGEMM_LCC_DIRECTED
+PR_AUTO, PR_PULL, PR_PUSH = 0, 1, 2                                                      # bspgemm_pr_method
 
 
 class DotInfo(C.Structure):
@@ -123,6 +124,18 @@ class LccInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class PrInfo(C.Structure):
+    """bspgemm_pr_info"""
+    _fields_ = [("mass", C.c_uint64), ("delta", C.c_uint64), ("dangling", C.c_int64), ("class_vertices", C.c_int64 * 4),
+                ("iterations", C.c_int), ("converged", C.c_int), ("method", C.c_int), ("transposed", C.c_int),
+                ("canonicalised", C.c_int)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "class_vertices"}
+        d["class_vertices"] = [int(x) for x in self.class_vertices]
+        return d
 
 
 class Stats(C.Structure):
@@ -259,6 +272,7 @@ def lib():
     L.bspgemm_graph_coloring.argtypes = [VP, VP, C.c_int, C.c_uint, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bspgemm_label_propagation.argtypes = [VP, VP, VP, C.c_int, PVP, C.POINTER(LpInfo)]
     L.bspgemm_local_clustering.argtypes = [VP, VP, C.c_uint, PVP, VP, VP, C.POINTER(LccInfo)]
+    L.bspgemm_pagerank.argtypes = [VP, VP, VP, C.c_int, C.c_double, C.c_int, C.c_double, VP, VP, C.POINTER(PrInfo)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -441,7 +455,7 @@ class Context:
     def set_option(self, name, value):
         """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
         "shared_slots" -1/0/k, "dot_light" T >= 0, "bfs_alpha" >= 1, "bfs_beta" >= 1, "bfs_push_lanes" 0/4/16/64,
-        "lp_min_class" 0..3"""
+        "lp_min_class" 0..3, "pr_min_class" 0..3"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):
@@ -672,6 +686,19 @@ class Context:
                                             degree.ctypes.data if A.rows else None, lcc.ctypes.data if A.rows else None,
                                             C.byref(info)), "bspgemm_local_clustering")
         return Result(self, r), degree, lcc, info.as_dict()
+
+    def pagerank(self, A, AT=None, method=PR_AUTO, damping=0.85, max_iter=20, tolerance=0.0):
+        """bspgemm_pagerank: (fixed uint64[n], rank float64[n], info dict) -- PageRank of the directed graph whose row u
+        lists u's out-neighbours, exact in unsigned 64-bit fixed point (2^62 = 1.0; include/bspgemm.h holds the definition):
+        the same bits on every run and under either method.  AT: the transpose of A (A itself for a symmetric canonical A),
+        or None: a PULL call transposes A itself.  method PR_AUTO | PR_PULL | PR_PUSH; tolerance 0: exactly max_iter
+        iterations, else the loop ends at the first iteration whose L1 change is at most tolerance.  rank = fixed * 2**-62.
+        info: mass, delta, dangling, class_vertices, iterations, converged, method, transposed, canonicalised"""
+        fixed, rank, info = np.zeros(A.rows, np.uint64), np.zeros(A.rows, np.float64), PrInfo()
+        _chk(lib().bspgemm_pagerank(self._h, A._h, AT._h if AT is not None else None, int(method), float(damping), int(max_iter),
+                                    float(tolerance), fixed.ctypes.data if A.rows else None,
+                                    rank.ctypes.data if A.rows else None, C.byref(info)), "bspgemm_pagerank")
+        return fixed, rank, info.as_dict()
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""
