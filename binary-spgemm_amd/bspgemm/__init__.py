@@ -59,7 +59,7 @@ EXPORTS = [
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
     "bspgemm_strongly_connected_components", "bspgemm_graph_coloring", "bspgemm_label_propagation",
-    "bspgemm_local_clustering", "bspgemm_pagerank",
+    "bspgemm_local_clustering", "bspgemm_pagerank", "bspgemm_betweenness",
     "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
@@ -82,7 +82,7 @@ SYMMETRIZE_DROP_DIAGONAL = 1                                                    
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
            "shared_slots": 6, "dot_light": 7, "bfs_alpha": 8, "bfs_beta": 9, "bfs_push_lanes": 10,
-           "lp_min_class": 11, "pr_min_class": 12}                                                                           # bspgemm_option
+           "lp_min_class": 11, "pr_min_class": 12, "bc_lanes": 13}                                                                           # bspgemm_option
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
 BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
 LCC_DIRECTED = 1                                                                         # BSPGEMM_LCC_DIRECTED
@@ -136,6 +136,15 @@ class PrInfo(C.Structure):
         d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "class_vertices"}
         d["class_vertices"] = [int(x) for x in self.class_vertices]
         return d
+
+
+class BcInfo(C.Structure):
+    """bspgemm_bc_info"""
+    _fields_ = [("sigma_max", C.c_uint64), ("reached", C.c_int64), ("edges_forward", C.c_int64), ("hub_chunks", C.c_int64),
+                ("sources", C.c_int), ("depth_max", C.c_int), ("levels", C.c_int), ("canonicalised", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -273,6 +282,7 @@ def lib():
     L.bspgemm_label_propagation.argtypes = [VP, VP, VP, C.c_int, PVP, C.POINTER(LpInfo)]
     L.bspgemm_local_clustering.argtypes = [VP, VP, C.c_uint, PVP, VP, VP, C.POINTER(LccInfo)]
     L.bspgemm_pagerank.argtypes = [VP, VP, VP, C.c_int, C.c_double, C.c_int, C.c_double, VP, VP, C.POINTER(PrInfo)]
+    L.bspgemm_betweenness.argtypes = [VP, VP, C.c_int, VP, VP, VP, C.POINTER(BcInfo)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -455,7 +465,7 @@ class Context:
     def set_option(self, name, value):
         """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
         "shared_slots" -1/0/k, "dot_light" T >= 0, "bfs_alpha" >= 1, "bfs_beta" >= 1, "bfs_push_lanes" 0/4/16/64,
-        "lp_min_class" 0..3, "pr_min_class" 0..3"""
+        "lp_min_class" 0..3, "pr_min_class" 0..3, "bc_lanes" 0/4/16/64"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):
@@ -699,6 +709,19 @@ class Context:
                                     float(tolerance), fixed.ctypes.data if A.rows else None,
                                     rank.ctypes.data if A.rows else None, C.byref(info)), "bspgemm_pagerank")
         return fixed, rank, info.as_dict()
+
+    def betweenness(self, A, sources):
+        """bspgemm_betweenness: (fixed uint64[n], bc float64[n], info dict) -- Brandes' unnormalised betweenness centrality of
+        the directed graph whose row u lists u's out-neighbours, restricted to the given sources (a vertex named twice
+        counts twice), exact in 64-bit integers with 2^32 = 1.0 (include/bspgemm.h holds the definition): the same bits on
+        every run and under every "bc_lanes".  For a symmetric A and all n sources it is twice the undirected betweenness.
+        bc = fixed * 2**-32.  info: sigma_max, reached, edges_forward, hub_chunks, sources, depth_max, levels, canonicalised"""
+        src = np.ascontiguousarray(sources, dtype=np.int32)
+        fixed, bc, info = np.zeros(A.rows, np.uint64), np.zeros(A.rows, np.float64), BcInfo()
+        _chk(lib().bspgemm_betweenness(self._h, A._h, int(src.size), src.ctypes.data if src.size else None,
+                                       fixed.ctypes.data if A.rows else None, bc.ctypes.data if A.rows else None,
+                                       C.byref(info)), "bspgemm_betweenness")
+        return fixed, bc, info.as_dict()
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""
