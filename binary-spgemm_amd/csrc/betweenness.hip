@@ -46,6 +46,7 @@
 // Cost.  One read-back per forward level (32 bytes) and one per call for the sources' out-degrees; the backward sweep has
 // none, the host knows every offset.
 #include "internal.hpp"
+#include "hub_chunks.hpp"
 #include "wave.hpp"
 
 #include <algorithm>
@@ -96,21 +97,8 @@ struct BcBwd {
     u64 *bc;
 };
 
-__device__ __forceinline__ int bc_chunks_of(int len) { return len > kBcHubChunk ? (len + kBcHubChunk - 1) / kBcHubChunk : 0; }
-
-// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave (bt_append of bfs_tree.hip; a copy, so
-// that the search's kernels stay instruction for instruction what they were).  Whole wave, uniform control flow.  A vertex
-// is appended once per source, so the list never passes n entries; the store is bounded all the same.
-__device__ __forceinline__ void bc_append(bool take, int v, int *list, int *size, int n, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = v;
-}
+// the chunk records of a row: none for one that a group of lanes walks itself.  Host and device.
+__host__ __device__ __forceinline__ int bc_chunks_of(int len) { return len > kBcHubChunk ? hub_chunks_of<kBcHubChunk>(len) : 0; }
 
 // one entry (u, w) of the frontier, su = sigma(u).  Whole wave; `live` lanes hold an entry.
 __device__ __forceinline__ void bc_forward_entry(const BcFwd &a, bool live, int w, u64 su, long long &dsum, unsigned &err, int lane)
@@ -134,22 +122,18 @@ __device__ __forceinline__ void bc_forward_entry(const BcFwd &a, bool live, int 
                 const int len = a.rpA[w + 1] - a.rpA[w];
                 dsum += len;
                 const int k = bc_chunks_of(len);
-                if (k) {
-                    const int base = atomicAdd(&a.cnt->ctail, k);
-                    for (int j = 0; j < k; j++)
-                        if ((unsigned)(base + j) < (unsigned)a.chunk_cap) a.chunk[base + j] = make_int2(w, j);
-                }
+                if (k) hub_chunks_emit(w, k, &a.cnt->ctail, a.chunk, a.chunk_cap);
             }
         }
     }
-    bc_append(take, w, a.order, &a.cnt->tail, a.n, lane);
+    // (a vertex is appended once per source, so order[] never passes n entries; the list is read plainly by this launch)
+    wave_append(take, w, a.order, &a.cnt->tail, a.n, lane);
 }
 
 // the end of a forward launch: the wave's out-degree sum and error bits, one atomic each per wave.  Whole wave.
 __device__ __forceinline__ void bc_forward_end(long long dsum, unsigned err, BcCounters *cnt, int lane)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dsum += __shfl_xor(dsum, off, 64);
+    dsum = wave_sum(dsum);
     const unsigned bits = (__ballot(err & kBcErrRange) ? kBcErrRange : 0u) | (__ballot(err & kBcErrOverflow) ? kBcErrOverflow : 0u);
     if (lane == 0) {
         if (dsum) atomicAdd(&cnt->deg, (u64)dsum);
@@ -230,8 +214,8 @@ __global__ __launch_bounds__(kBcThreads) void k_bc_forward_chunk(BcFwd a, int cf
 {
     const int lane = lane_id();
     const int2 rec = a.chunk[cfirst + blockIdx.x];
-    const long long b = (long long)a.rpA[rec.x] + (long long)rec.y * kBcHubChunk;
-    const long long e = min((long long)a.rpA[rec.x + 1], b + kBcHubChunk);
+    long long b, e;
+    hub_chunk_range<kBcHubChunk>(a.rpA, rec, b, e);
     const u64 su = a.sigma[rec.x];
     long long dsum = 0;
     unsigned err = 0;
@@ -289,7 +273,7 @@ __global__ __launch_bounds__(kBcThreads) void k_bc_backward(BcBwd a, int fsize, 
 #pragma unroll 4
     for (; pos < e; pos += W) s += bc_summand(a, colA[pos], sv);
 #pragma unroll
-    for (int off = W / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    for (int off = W / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);   // (open code: a helper compiles to other code here)
     if (mine && sub == 0) bc_finish_vertex(a, v, s);
 }
 
@@ -299,14 +283,14 @@ __global__ __launch_bounds__(kBcThreads) void k_bc_backward_chunk(BcBwd a, int c
 {
     __shared__ u64 part[kBcWaves];
     const int2 rec = chunk[cfirst + blockIdx.x];
-    const long long b = (long long)a.rpA[rec.x] + (long long)rec.y * kBcHubChunk;
-    const long long e = min((long long)a.rpA[rec.x + 1], b + kBcHubChunk);
+    long long b, e;
+    hub_chunk_range<kBcHubChunk>(a.rpA, rec, b, e);
     const double sv = __ull2double_rn(a.sigma[rec.x]);
     u64 s = 0;
 #pragma unroll 4
     for (long long pos = b + threadIdx.x; pos < e; pos += kBcThreads) s += bc_summand(a, colA[pos], sv);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);      // (open code: wave_sum compiles to other code here)
     if (lane_id() == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -343,7 +327,7 @@ __global__ __launch_bounds__(kBcThreads) void k_bc_reset(int reached, const int 
         delta[v] = 0;
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sg = max(sg, (u64)__shfl_xor(sg, off, 64));
+    for (int off = 32; off > 0; off >>= 1) sg = max(sg, (u64)__shfl_xor(sg, off, 64));   // (open code: wave_max compares the other way round)
     if (lane_id() == 0 && sg > __hip_atomic_load(&cnt->sigma_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
         atomicMax(&cnt->sigma_max, sg);
 }
@@ -363,17 +347,15 @@ static int bc_lanes(long long m_f, long long n_f)
 static void launch_forward(int W, const BcFwd &a, int fsize, int first, const int *colA, hipStream_t s)
 {
     const dim3 grid = bc_grid((long long)fsize * W), block(kBcThreads);
-    if (W == 4) hipLaunchKernelGGL(k_bc_forward<4>, grid, block, 0, s, a, fsize, first, colA);
-    else if (W == 16) hipLaunchKernelGGL(k_bc_forward<16>, grid, block, 0, s, a, fsize, first, colA);
-    else hipLaunchKernelGGL(k_bc_forward<64>, grid, block, 0, s, a, fsize, first, colA);
+    dispatch_lanes(W, [&](auto w) { hipLaunchKernelGGL(k_bc_forward<decltype(w)::value>, grid, block, 0, s, a, fsize, first, colA); });
 }
 
 static void launch_backward(int W, const BcBwd &a, int fsize, int first, const int *order, const int *colA, hipStream_t s)
 {
     const dim3 grid = bc_grid((long long)fsize * W), block(kBcThreads);
-    if (W == 4) hipLaunchKernelGGL(k_bc_backward<4>, grid, block, 0, s, a, fsize, first, order, colA);
-    else if (W == 16) hipLaunchKernelGGL(k_bc_backward<16>, grid, block, 0, s, a, fsize, first, order, colA);
-    else hipLaunchKernelGGL(k_bc_backward<64>, grid, block, 0, s, a, fsize, first, order, colA);
+    dispatch_lanes(W, [&](auto w) {
+        hipLaunchKernelGGL(k_bc_backward<decltype(w)::value>, grid, block, 0, s, a, fsize, first, order, colA);
+    });
 }
 
 // a level of the current source, as the host knows it after the level's read-back
@@ -456,7 +438,7 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
     BcCounters *d_cnt = reinterpret_cast<BcCounters *>(ctx->tmp);
     BcCounters h = {};
     HIPCHK_B(hipMemsetAsync(d_cnt, 0, sizeof(BcCounters), s));
-    launch_canonical_check(A->d_row_ptr, A->d_col_idx, n, n, A->nnz, 0, ctx->tile_row, &d_cnt->canon, s);
+    launch_graph_canonical_checks(ctx, A, nullptr, &d_cnt->canon, s);
     HIPCHK_B(round_fetch(&h, d_cnt, sizeof h, s));
     if (h.canon & kSetErrRange) return bail(fail_bad_column(who, n));
     int canonicalised = 0;
@@ -508,7 +490,7 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
             const host_clock::time_point t_src = host_clock::now();
             if (h_deg[i] < 0 || h_deg[i] > A->nnz) return bail(fail_stuck(who));
             L.clear();
-            L.push_back(BcLevelRec{0, 1, 0, h_deg[i] > kBcHubChunk ? (h_deg[i] + kBcHubChunk - 1) / kBcHubChunk : 0, h_deg[i]});
+            L.push_back(BcLevelRec{0, 1, 0, bc_chunks_of(h_deg[i]), h_deg[i]});
             if ((size_t)L[0].chunks > chunk_cap) return bail(fail_stuck(who));
             hipLaunchKernelGGL(k_bc_source, dim3(1), block, 0, s, src, h_deg[i], level, sigma, order, chunk, (int)chunk_cap, d_cnt);
             HIPCHK_B(hipGetLastError());

@@ -63,25 +63,13 @@ struct BtCounters {
     int pad[3];
 };
 
-// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave (kc_append of kcore.hip; a copy, so that
-// the k-core kernels stay instruction for instruction what they were).  Whole wave, uniform control flow.  A vertex is
-// appended once in its life, so a list never passes n entries; the store is bounded all the same.
-__device__ __forceinline__ void bt_append(bool take, int v, int *__restrict__ list, int *size, int n, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = v;
-}
+// The frontier lists are appended to by wave_append (wave.hpp).  A vertex is appended once in its life, so a list never
+// passes n entries; the store is bounded all the same.
 
 // the end of a launch: the wave's out-degree sum and error bit, one atomic each per wave.  Whole wave.
 __device__ __forceinline__ void bt_finish(long long dsum, bool bad, BtLevel *out, int lane)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dsum += __shfl_xor(dsum, off, 64);
+    dsum = wave_sum(dsum);
     const u64 b = __ballot(bad);
     if (lane == 0) {
         if (dsum) atomicAdd(&out->deg, (unsigned long long)dsum);
@@ -146,7 +134,7 @@ __global__ __launch_bounds__(kBtThreads) void k_bfs_push(int n, int d, int fsize
                 }
             }
         }
-        bt_append(take, v, next, &out->size, n, lane);
+        wave_append(take, v, next, &out->size, n, lane);
         pos += W;
     }
     bt_finish(dsum, bad, out, lane);
@@ -211,7 +199,7 @@ __global__ __launch_bounds__(kBtThreads) void k_bfs_pull(int n, int d, const int
         level[v] = d;
         dsum = rpA[v + 1] - rpA[v];
     }
-    bt_append(found, (int)v, next, &out->size, n, lane);
+    wave_append(found, (int)v, next, &out->size, n, lane);
     bt_finish(dsum, bad, out, lane);
 }
 
@@ -271,14 +259,7 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
         return BSPGEMM_ERR_INVALID;
     }
     if (direction == BSPGEMM_BFS_PUSH) AT = nullptr;         // ignored
-    if (AT) {
-        if (bspgemm_status st = check_graph_operand(ctx, AT, kBtWho, 0)) return st;
-        if (AT->rows != n || AT->cols != n) {
-            snprintf(g_err, sizeof g_err, "%s: AT is %d x %d, A is %d x %d", kBtWho, AT->rows, AT->cols, n, n);
-            return BSPGEMM_ERR_INVALID;
-        }
-        if (bspgemm_status st = check_operand(ctx, AT, kBtWho, NEED_ENTRIES_CONSISTENT)) return st;
-    }
+    if (bspgemm_status st = check_transposed_operand(ctx, A, AT, kBtWho)) return st;
     if (bspgemm_status st = check_operand(ctx, A, kBtWho, NEED_ENTRIES_CONSISTENT)) return st;
     // BSPGEMM_BFS_TREE_TIMING: host clocks around the stages; a launch is then synchronised before its read-back is issued,
     // so that the two are told apart
@@ -333,17 +314,12 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
     // the first read-back: the source's out-degree, and the check of every distinct handle (A: its columns' range alone,
     // its rows may be in any order; AT: range and ascending order).  The checks write d_cnt->canon after the memset.
     HIPCHK_B(start());
-    launch_canonical_check(A->d_row_ptr, A->d_col_idx, n, n, A->nnz, 0, ctx->tile_row, &d_cnt->canon, s);
-    if (AT && AT != A) launch_canonical_check(AT->d_row_ptr, AT->d_col_idx, n, n, AT->nnz, 2, ctx->tile_row, &d_cnt->canon, s);
+    launch_graph_canonical_checks(ctx, A, AT, &d_cnt->canon, s);
     BtCounters h = {};
     host_clock::time_point t = host_clock::now();
     HIPCHK_B(round_fetch(&h, d_cnt, sizeof h, s));
     if (timed) ms_back += ms_since(t);
-    if (h.canon & (kSetErrRange | (kSetErrRange << 2))) {
-        snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) in operand %s", kBtWho, n,
-                 (h.canon & kSetErrRange) ? "A" : "AT");
-        return bail(BSPGEMM_ERR_INVALID);
-    }
+    if (h.canon & (kSetErrRange | (kSetErrRange << 2))) return bail(fail_bad_column_in(kBtWho, n, h.canon));
     int canonicalised = 0;
     if (AT && (h.canon & (AT == A ? kSetErrOrder : kSetErrOrder << 2))) {
         // transposed twice, in the leading part of the workspace, which may grow for it: the state is set up again
@@ -389,9 +365,9 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
             if (d <= 64) pull_mask |= (uint64_t)1 << (d - 1);
         } else {
             const int W = forced_w ? forced_w : push_lanes(m_f, n_f);
-            if (W == 4) launch_push<4>(n, d, (int)n_f, list[cur], A, level, parent, list[cur ^ 1], out, reset, s);
-            else if (W == 16) launch_push<16>(n, d, (int)n_f, list[cur], A, level, parent, list[cur ^ 1], out, reset, s);
-            else launch_push<64>(n, d, (int)n_f, list[cur], A, level, parent, list[cur ^ 1], out, reset, s);
+            dispatch_lanes(W, [&](auto w) {
+                launch_push<decltype(w)::value>(n, d, (int)n_f, list[cur], A, level, parent, list[cur ^ 1], out, reset, s);
+            });
             pushes++;
             edges_pushed += m_f;
         }

@@ -73,19 +73,8 @@ __device__ __forceinline__ u32 col_mix32(u32 x)
 // (key[w], w) < (key[u], u)
 __device__ __forceinline__ bool col_precedes(u64 kw, int w, u64 ku, int u) { return kw < ku || (kw == ku && w < u); }
 
-// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave (kc_append of kcore.hip; a copy, so that
-// the k-core kernels stay instruction for instruction what they were).  Whole wave, uniform control flow.  A vertex is
-// appended once in its life, so a list never passes n entries; the store is bounded all the same.
-__device__ __forceinline__ void col_append(bool take, int v, int *__restrict__ list, int *size, int n, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = v;
-}
+// The frontier lists are appended to by wave_append (wave.hpp).  A vertex is appended once in its life, so a list never
+// passes n entries; the store is bounded all the same.
 
 // order: a bspgemm_color_order.  rpS NULL (S has no entries): every degree is 0 and the colours are final (fill = 0).
 __global__ __launch_bounds__(kColThreads) void k_color_init(int n, int order, u32 seed, const int *__restrict__ rpS,
@@ -141,7 +130,7 @@ __global__ __launch_bounds__(kColThreads) void k_color_seed(int n, const int *__
 {
     const long long v = (long long)blockIdx.x * kColThreads + threadIdx.x;
     const bool take = v < n && cnt[v] == 0;
-    col_append(take, (int)v, list, &flags->size[0], n, lane_id());
+    wave_append(take, (int)v, list, &flags->size[0], n, lane_id());
 }
 
 // one wave per vertex of `list` (fsize entries, from the host).  cnt is lowered by atomics only; colour is loaded plainly
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(kColThreads) void k_color_round(int n, int fsize, c
             }
         }
 #pragma unroll
-        for (int j = 0; j < kColDeep; j++) col_append(old[j] == 1, x[j], next, next_size, n, lane);
+        for (int j = 0; j < kColDeep; j++) wave_append(old[j] == 1, x[j], next, next_size, n, lane);
     }
     int c = 0;
     if (__ballot(prev)) {                                    // (wave-uniform)

@@ -15,7 +15,7 @@
 //                 vals[p] = 0.  LIGHT, m <= T: the lane walks the shorter row and searches the longer one
 //                 (sel_lower_bound) from a lower bound that only advances; vals[p] = the hits.  HEAVY, m > T: the lane
 //                 writes nothing and remembers the entry; when the walk is over the wave appends its heavy entries
-//                 {p, i} to a list (ballot, one atomicAdd per wave, rank by popcount: kc_append of kcore.hip, a copy).
+//                 {p, i} to a list (ballot, one atomicAdd per wave, rank by popcount: wave_append of wave.hpp).
 //   k_dot_heavy   a fixed grid, one wave per list entry, striding over the list; its length is read from device memory (the
 //                 launch follows k_dot_count on the stream, nothing in between).  The lanes stride over the shorter row 64
 //                 elements per step, kDotDeep steps in flight; each lane searches the longer row (the kDotDeep searches of
@@ -50,19 +50,8 @@ struct DotCounters {
     int pad[2];
 };
 
-// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave (kc_append of kcore.hip; a copy, so that
-// the k-core kernels stay instruction for instruction what they were).  Whole wave, uniform control flow.  A mask entry
-// is appended at most once, so the list never passes cap = nnz(F) entries; the store is bounded all the same.
-__device__ __forceinline__ void dot_append(bool take, int2 v, int2 *__restrict__ list, int *size, long long cap, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned long long)at < (unsigned long long)cap) list[at] = v;
-}
+// The heavy list is appended to by wave_append (wave.hpp).  A mask entry is appended at most once, so the list never
+// passes nnz(F) entries; the store is bounded all the same.
 
 // The count as an op of sel_walk_entries.  A's and B's columns are only compared, never used as an index; F's column is
 // tested unsigned against B.rows before it indexes B.row_ptr.
@@ -120,7 +109,7 @@ __global__ __launch_bounds__(kSelThreads) void k_dot_count(const int *__restrict
 #pragma unroll
     for (int s = 0; s < kDotEntries; s++) {
         const long long p = w0 + (s >> 2) * kSelGroup + 4 * lane + (s & 3);  // the lane's s-th entry (sel_walk_entries)
-        dot_append((op.heavy >> s) & 1u, int2{(int)p, op.hrow[s]}, list, nheavy, E, lane);
+        wave_append((op.heavy >> s) & 1u, int2{(int)p, op.hrow[s]}, list, nheavy, E, lane);
     }
 }
 

@@ -3,7 +3,9 @@
 // workspace / result-cache helpers (context.hip) that the flows (multiply.hip), the int32 drop-ins (dropin.hip: dropin_run in
 // stages -- check and bound, operands, multiply, destination, download, hand-over -- over the early destination that
 // early_dest.hpp owns) and the communicator layer (comm.hip) use, the drop-ins' host steps that SpGEMM_hip_multi repeats, the
-// flag scratch of select.hip and setop.hip, the host helpers of the round-based algorithms (cc.hip, scc.hip, kcore.hip).  Not installed; nothing here is part of the C ABI.
+// flag scratch of select.hip and setop.hip, the host helpers of the round-based graph algorithms (cc.hip to betweenness.hip:
+// the operand checks, the canonical checks of A and an optional AT, the read-back of a round, the lanes-per-vertex dispatch).
+// Not installed; nothing here is part of the C ABI.
 #pragma once
 #include "../../include/bspgemm.h"
 #include "kernels.hpp"
@@ -16,6 +18,7 @@
 #include <cstring>
 #include <chrono>
 #include <new>
+#include <type_traits>
 
 // ------------------------------------------------------------------ errors ---------------
 // text of the last failure on this thread (bspgemm_last_error); defined in context.hip
@@ -257,9 +260,10 @@ size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratc
 size_t transpose_workspace_ints(long long E, int cols);
 size_t symmetrize_workspace_ints(long long E, int n);
 
-// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip) ---
+// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip, lcc.hip, pagerank.hip, betweenness.hip) ---
 // What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
-// each algorithm's own.  who: the entry point's name, which every message starts with.
+// each algorithm's own, and so is what it does about an untidy operand.  who: the entry point's name, which every message
+// starts with.
 // the graph operand: check_operand with `flags`, then an entry count that an int32 entry index cannot hold
 static inline bspgemm_status check_graph_operand(const bspgemm_context *ctx, const bspgemm_matrix *A, const char *who, unsigned flags)
 {
@@ -268,6 +272,44 @@ static inline bspgemm_status check_graph_operand(const bspgemm_context *ctx, con
     char what[128];
     snprintf(what, sizeof what, "%s: more than INT_MAX nonzeros", who);
     return FAIL(BSPGEMM_ERR_OVERFLOW, what);
+}
+// the optional transposed operand of an entry point that takes A (square: checked already) and AT, tested in this order:
+// it belongs to ctx, an int32 entry count, n x n like A, consistent entries.  AT NULL: nothing to check.
+static inline bspgemm_status check_transposed_operand(const bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *AT,
+                                                      const char *who)
+{
+    if (!AT) return BSPGEMM_OK;
+    if (bspgemm_status st = check_graph_operand(ctx, AT, who, 0)) return st;
+    const int n = A->rows;
+    if (AT->rows != n || AT->cols != n) {
+        snprintf(g_err, sizeof g_err, "%s: AT is %d x %d, A is %d x %d", who, AT->rows, AT->cols, n, n);
+        return BSPGEMM_ERR_INVALID;
+    }
+    return check_operand(ctx, AT, who, NEED_ENTRIES_CONSISTENT);
+}
+// The canonical check (kernels.hpp) of every distinct handle into *d_word, two bits per operand (kSetErrRange,
+// kSetErrOrder): A at shift 0, an AT that is not A at shift 2.  The workspace and ctx->tile_row are there; no synchronisation.
+static inline void launch_graph_canonical_checks(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *AT,
+                                                 unsigned *d_word, hipStream_t s)
+{
+    const int n = A->rows;
+    bsp::launch_canonical_check(A->d_row_ptr, A->d_col_idx, n, n, A->nnz, 0, ctx->tile_row, d_word, s);
+    if (AT && AT != A) bsp::launch_canonical_check(AT->d_row_ptr, AT->d_col_idx, n, n, AT->nnz, 2, ctx->tile_row, d_word, s);
+}
+// the failure where that word holds a range bit: canon_bits & (kSetErrRange | kSetErrRange << 2)
+static inline bspgemm_status fail_bad_column_in(const char *who, int n, unsigned canon_bits)
+{
+    snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) in operand %s", who, n,
+             (canon_bits & bsp::kSetErrRange) ? "A" : "AT");
+    return BSPGEMM_ERR_INVALID;
+}
+// f(std::integral_constant<int, W>{}) for the lanes per vertex W = 4 or 16; any other W runs the 64-lane instance
+template <class F>
+static inline void dispatch_lanes(int W, F &&f)
+{
+    if (W == 4) f(std::integral_constant<int, 4>{});
+    else if (W == 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 64>{});
 }
 // the assignment operand of n vertices, laid out like an uploaded one: row v holds one entry, and its col_idx is the label
 // array while the rounds run, so nothing is copied at the end (operand_finish(m, n) completes it).  After a failure *m is

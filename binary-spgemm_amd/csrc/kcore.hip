@@ -49,19 +49,8 @@ struct KcFlags {
     int pad;
 };
 
-// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave.  Whole wave, uniform control flow.
-// A vertex is appended once in its life, so a list never passes n entries; the store is bounded all the same and the host
-// refuses a size above n.
-__device__ __forceinline__ void kc_append(bool take, int v, int *__restrict__ list, int *size, int n, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = v;
-}
+// The frontier lists are appended to by wave_append (wave.hpp).  A vertex is appended once in its life, so a list never
+// passes n entries; the store is bounded all the same and the host refuses a size above n.
 
 // deg from S.row_ptr, core = -1, and the result's pattern: row v holds (v, v)
 __global__ __launch_bounds__(kKcThreads) void k_kcore_init(int n, const int *__restrict__ rpS, int *__restrict__ deg,
@@ -92,9 +81,8 @@ __global__ __launch_bounds__(kKcThreads) void k_kcore_scan(int n, int k, const i
         if (take) core[v] = k;
         else left = d;
     }
-    kc_append(take, (int)v, list, &flags->size[0], n, lane);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) left = min(left, __shfl_xor(left, off, 64));
+    wave_append(take, (int)v, list, &flags->size[0], n, lane);
+    left = wave_min(left);
     if (lane == 0) wmin[w] = left;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(kKcThreads) void k_kcore_peel(int n, int k, int fsi
                 hit = true;
             }
         }
-        kc_append(hit, x, next, next_size, n, lane);
+        wave_append(hit, x, next, next_size, n, lane);
     }
 }
 

@@ -22,7 +22,7 @@
 //   k_lcc_count    entry-parallel over T.  j is tested unsigned against n before it indexes row_ptr.  m = min(|T_i|, |T_j|):
 //                  0 nothing; LIGHT, m <= BSPGEMM_OPT_DOT_LIGHT: the lane walks the shorter row and searches the longer one
 //                  from a lower bound that only advances, crediting as above; HEAVY: the lane remembers the entry and the
-//                  wave appends its heavy entries {p, i} to a list (one atomic per wave; dot_append of dot.hip, a copy).
+//                  wave appends its heavy entries {p, i} to a list (one atomic per wave: wave_append of wave.hpp).
 //                  The wave's hits go to the 64-bit triangle counter by one atomic.
 //   k_lcc_heavy    a fixed grid, one wave per list entry; a workgroup takes kLccChunk consecutive entries of the list at a
 //                  time and drains its cache behind each chunk; the list's length is read from device memory (the launch
@@ -117,27 +117,8 @@ __device__ __forceinline__ void lcc_cache_drain(int *tag, int *val, int *num)
     __syncthreads();
 }
 
-// the sum of x over the wave, in every lane.  Whole wave.
-__device__ __forceinline__ int lcc_wave_sum(int x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
-// dot_append of dot.hip (kc_append of kcore.hip): a copy, so that those kernels stay instruction for instruction what they
-// were.  An entry of T is appended at most once, so the list never passes cap = nnz(T) entries; the store is bounded all
-// the same.
-__device__ __forceinline__ void lcc_append(bool take, int2 v, int2 *__restrict__ list, int *size, long long cap, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned long long)at < (unsigned long long)cap) list[at] = v;
-}
+// The heavy list is appended to by wave_append (wave.hpp).  An entry of T is appended at most once, so the list never
+// passes nnz(T) entries; the store is bounded all the same.
 
 // row v of the result holds (v, v); its value starts at 0
 __global__ __launch_bounds__(256) void k_lcc_init(int n, long long *__restrict__ row_ptr, int *__restrict__ col_idx,
@@ -179,7 +160,7 @@ __global__ __launch_bounds__(kSelThreads) void k_lcc_weights(const int *__restri
 {
     LccWeights op = {rpR, colR, wgt, 0, 0, 0};
     sel_walk_entries<false>(rpT, colT, n, E, vec, tile_row, op);         // (T's columns are read again by k_lcc_count)
-    const int found = lcc_wave_sum(op.found);
+    const int found = wave_sum(op.found);
     if (found && lane_id() == 0) atomicAdd(reciprocal, (u64)found);
 }
 
@@ -261,14 +242,14 @@ __global__ __launch_bounds__(kSelThreads) void k_lcc_count(const int *__restrict
     lcc_cache_flush(tag, val, num);
     const int lane = lane_id(), w = threadIdx.x >> 6;
     op.flush();
-    const int hits = lcc_wave_sum(op.hits);
+    const int hits = wave_sum(op.hits);
     if (hits && lane == 0) atomicAdd(&cnt->triangles, (u64)hits);
     if (__ballot(op.heavy != 0u) == 0) return;                           // (wave-uniform)
     const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
 #pragma unroll
     for (int s = 0; s < kLccEntries; s++) {
         const long long p = w0 + (s >> 2) * kSelGroup + 4 * lane + (s & 3);  // the lane's s-th entry (sel_walk_entries)
-        lcc_append((op.heavy >> s) & 1u, int2{(int)p, op.hrow[s]}, list, &cnt->heavy, E, lane);
+        wave_append((op.heavy >> s) & 1u, int2{(int)p, op.hrow[s]}, list, &cnt->heavy, E, lane);
     }
 }
 
@@ -349,9 +330,9 @@ __global__ __launch_bounds__(kSelThreads) void k_lcc_heavy(const int *__restrict
                     if (in[q]) from = lo[q];
                 }
             }
-            sx = lcc_wave_sum(sx);
-            sy = lcc_wave_sum(sy);
-            hits = lcc_wave_sum(hits);
+            sx = wave_sum(sx);
+            sy = wave_sum(sy);
+            hits = wave_sum(hits);
             if (lane == 0) {
                 const int wik = a_short ? sx : sy, wjk = a_short ? sy : sx;
                 if (wik) atomicAdd(&num[j], wik);

@@ -96,36 +96,6 @@ __device__ __forceinline__ u32 lp_mix32(u32 x)
 __device__ __forceinline__ u64 lp_pack(int count, int label) { return ((u64)(u32)count << 32) | (u32)~(u32)label; }
 __device__ __forceinline__ int lp_label(u64 best) { return (int)~(u32)best; }
 
-__device__ __forceinline__ u64 lp_wave_max(u64 x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const u64 y = __shfl_xor(x, off, 64);
-        x = y > x ? y : x;
-    }
-    return x;
-}
-
-// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave (col_append of color.hip; a copy, so that
-// the colouring kernels stay instruction for instruction what they were).  Whole wave, uniform control flow.
-__device__ __forceinline__ void lp_append(bool take, int v, int *__restrict__ list, int *size, int n, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = v;
-}
-
-// the wave's count of `x` added to *word by one atomic.  Whole wave, uniform control flow.
-__device__ __forceinline__ void lp_count(bool x, int *word, int lane)
-{
-    const u64 m = __ballot(x);
-    if (m && lane == 0) atomicAdd(word, __popcll(m));
-}
-
 // The `changed` counter is kLpShards words, kLpShardStride ints apart (a 128-byte line each); a workgroup adds to the one
 // its number picks and the host sums them.  On a graph whose labels all move, one word would take an atomic from every
 // wave of k_lp_wave, and atomics on one address run one after the other (10 ns each, 6.8 ms an iteration).
@@ -163,7 +133,7 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_classify(int n, int min_class
         tab_of[v] = cls == 3 ? (long long)atomicAdd(&flags->slots, 2ull * (u64)d) : -1;
     }
 #pragma unroll
-    for (int c = 0; c < kLpClasses; c++) lp_append(cls == c, (int)v, list + c * stride, &flags->size[c], n, lane);
+    for (int c = 0; c < kLpClasses; c++) wave_append(cls == c, (int)v, list + c * stride, &flags->size[c], n, lane);
 }
 
 // ---------------------------------------------------------------- class 0: one lane per vertex -------------------------
@@ -197,7 +167,7 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_lane(int count, const int *__
             label_out[v] = l;
         }
     }
-    lp_count(moved, lp_shard(changed), lane_id());
+    wave_count(moved, lp_shard(changed), lane_id());
 }
 
 // ---------------------------------------------------------------- classes 1 and 2: sort in LDS -------------------------
@@ -268,11 +238,11 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_wave(int count, const int *__
 #pragma unroll
     for (int j = 0; j < kLpWaveCap / 64; j++)
         if (64 * j + lane < N) buf[64 * j + lane] = x[j];
-    const u64 best = lp_wave_max(lp_sorted_mode<64>(buf, d, N, lane));
+    const u64 best = wave_max(lp_sorted_mode<64>(buf, d, N, lane));
     const int l = lp_label(best);
     const bool moved = lane == 0 && l != label_in[v];
     if (lane == 0) label_out[v] = l;
-    lp_count(moved, lp_shard(changed), lane);
+    wave_count(moved, lp_shard(changed), lane);
 }
 
 __global__ __launch_bounds__(kLpThreads) void k_lp_group(int count, const int *__restrict__ list, const int *__restrict__ rpS,
@@ -288,7 +258,7 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_group(int count, const int *_
     const int N = lp_pow2_at_least(d);
 #pragma unroll 4
     for (int q = t; q < N; q += kLpThreads) buf[q] = q < d ? label_in[colS[b + q]] : kLpPad;
-    const u64 best = lp_wave_max(lp_sorted_mode<kLpThreads>(buf, d, N, t));
+    const u64 best = wave_max(lp_sorted_mode<kLpThreads>(buf, d, N, t));
     if (lane_id() == 0) wbest[t >> 6] = best;
     __syncthreads();
     if (t == 0) {
@@ -379,7 +349,7 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_hub_mode(const int *__restric
             if (key > best) best = key;
         }
     }
-    best = lp_wave_max(best);
+    best = wave_max(best);
     if (lane_id() == 0) wbest[t >> 6] = best;
     __syncthreads();
     if (t == 0 && size) {
@@ -401,7 +371,7 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_mark(int n, const int *__rest
         const unsigned l = (unsigned)label[v];
         if (l < (unsigned)n && mark[l] == 0) first = atomicExch(&mark[l], 1) == 0;
     }
-    lp_count(first, communities, lane_id());
+    wave_count(first, communities, lane_id());
 }
 
 }  // namespace bsp

@@ -39,6 +39,7 @@
 // give the same bits.  With tolerance == 0 the loop has no read-back and no synchronisation; with tolerance > 0 one
 // 8-byte read-back per iteration.
 #include "internal.hpp"
+#include "hub_chunks.hpp"
 #include "sel_rows.hpp"
 
 #include <algorithm>
@@ -84,13 +85,6 @@ struct PrSums {
     u64 delta, dang;
 };
 
-__device__ __forceinline__ u64 pr_wave_sum(u64 x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
 __device__ __forceinline__ void pr_begin(const PrArgs &a)
 {
     if (a.zero0 && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -115,10 +109,12 @@ __device__ __forceinline__ void pr_vertex(const PrArgs &a, int v, u64 s, u64 sha
 }
 
 // the workgroup's sums to the two counters, one atomic each.  Every thread of the workgroup, once, at the kernel's end.
+// (The join through LDS is written out here and in pr_group_sum: the two sums share one barrier here, and there the wave
+// sum stands in front of the leading barrier; a shared workgroup sum compiles to other code in both.)
 __device__ __forceinline__ void pr_commit(PrSums sums, u64 *delta, u64 *dang)
 {
     __shared__ u64 red[2][kPrWaves];
-    const u64 d = pr_wave_sum(sums.delta), g = pr_wave_sum(sums.dang);
+    const u64 d = wave_sum(sums.delta), g = wave_sum(sums.dang);
     if (lane_id() == 0) {
         red[0][threadIdx.x >> 6] = d;
         red[1][threadIdx.x >> 6] = g;
@@ -159,19 +155,6 @@ __device__ __forceinline__ int pr_class_of(int d)
     return d <= kPrLaneCap ? 0 : d <= kPrWaveCap ? 1 : d <= kPrGroupCap ? 2 : 3;
 }
 
-// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave (lp_append of lp.hip; a copy, so that
-// the label propagation kernels stay instruction for instruction what they were).  Whole wave, uniform control flow.
-__device__ __forceinline__ void pr_append(bool take, int v, int *__restrict__ list, int *size, int n, int lane)
-{
-    const u64 m = __ballot(take);
-    if (m == 0) return;                                      // (wave-uniform)
-    int base = 0;
-    if (lane == 0) base = atomicAdd(size, __popcll(m));
-    base = wave_first(base);
-    const int at = base + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = v;
-}
-
 // list: kPrClasses lists, `stride` ints apart; chunk: chunk_cap records
 __global__ __launch_bounds__(kPrThreads) void k_pr_classify(int n, int min_class, const int *__restrict__ rpT,
                                                            int *__restrict__ list, size_t stride, int2 *__restrict__ chunk,
@@ -185,15 +168,10 @@ __global__ __launch_bounds__(kPrThreads) void k_pr_classify(int n, int min_class
         const int d = rpT[v + 1] - rpT[v];
         cls = max(pr_class_of(d), min_class);
         if (cls == 1) sums.delta = (u64)d;
-        if (cls == 3 && d > 0) {
-            const int k = (d + kPrHubChunk - 1) / kPrHubChunk;
-            const int base = atomicAdd(&cnt->chunks, k);
-            for (int j = 0; j < k; j++)
-                if ((unsigned)(base + j) < (unsigned)chunk_cap) chunk[base + j] = make_int2((int)v, j);
-        }
+        if (cls == 3 && d > 0) hub_chunks_emit((int)v, hub_chunks_of<kPrHubChunk>(d), &cnt->chunks, chunk, chunk_cap);
     }
 #pragma unroll
-    for (int c = 0; c < kPrClasses; c++) pr_append(cls == c, (int)v, list + c * stride, &cnt->size[c], n, lane);
+    for (int c = 0; c < kPrClasses; c++) wave_append(cls == c, (int)v, list + c * stride, &cnt->size[c], n, lane);
     pr_commit(sums, &cnt->wave_entries, &cnt->wave_entries); // (the second sum is 0: no atomic)
 }
 
@@ -242,7 +220,7 @@ __global__ __launch_bounds__(kPrThreads) void k_pr_wave(PrArgs a, int count, con
 #pragma unroll 4
         for (long long p = live ? (long long)rpT[v] + sub : 0; p < e; p += W) s += a.c_in[colT[p]];
 #pragma unroll
-        for (int off = W / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        for (int off = W / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);   // (open code: a helper compiles to other code here)
         if (live && sub == 0) pr_vertex(a, v, s, share, sums);
     }
     pr_commit(sums, a.delta, a.dang_out);
@@ -255,7 +233,7 @@ __device__ __forceinline__ u64 pr_group_sum(const u64 *__restrict__ c_in, const 
     u64 s = 0;
 #pragma unroll 4
     for (long long p = b + threadIdx.x; p < e; p += kPrThreads) s += c_in[colT[p]];
-    s = pr_wave_sum(s);
+    s = wave_sum(s);
     __syncthreads();                                         // (the words' readers of the round before are done)
     if (lane_id() == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -288,8 +266,8 @@ __global__ __launch_bounds__(kPrThreads) void k_pr_hub_chunk(PrArgs a, int nchun
     pr_begin(a);
     for (int i = blockIdx.x; i < nchunks; i += gridDim.x) {  // (uniform over the workgroup)
         const int2 rec = chunk[i];
-        const long long b = (long long)rpT[rec.x] + (long long)rec.y * kPrHubChunk;
-        const long long e = min((long long)rpT[rec.x + 1], b + kPrHubChunk);
+        long long b, e;
+        hub_chunk_range<kPrHubChunk>(rpT, rec, b, e);
         const u64 s = pr_group_sum(a.c_in, colT, b, e, part);
         if (threadIdx.x == 0 && s) atomicAdd(&acc[rec.x], s);
     }
@@ -372,14 +350,7 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
     const int n = A->rows;
     const bool pull = method != BSPGEMM_PR_PUSH;             // AUTO is PULL (include/bspgemm.h)
     if (!pull) AT = nullptr;                                 // ignored
-    if (AT) {
-        if (bspgemm_status st = check_graph_operand(ctx, AT, who, 0)) return st;
-        if (AT->rows != n || AT->cols != n) {
-            snprintf(g_err, sizeof g_err, "%s: AT is %d x %d, A is %d x %d", who, AT->rows, AT->cols, n, n);
-            return BSPGEMM_ERR_INVALID;
-        }
-        if (bspgemm_status st = check_operand(ctx, AT, who, NEED_ENTRIES_CONSISTENT)) return st;
-    }
+    if (bspgemm_status st = check_transposed_operand(ctx, A, AT, who)) return st;
     if (bspgemm_status st = check_operand(ctx, A, who, NEED_ENTRIES_CONSISTENT)) return st;
     const u64 thr = tolerance >= 4.0 ? ~0ull : (u64)std::floor(std::ldexp(tolerance, 62));
     if (n == 0) {                                            // no vertex: every sum is empty, every delta 0
@@ -433,15 +404,10 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
     PrCounters *d_cnt = reinterpret_cast<PrCounters *>(ctx->tmp);
     PrCounters h = {};
     HIPCHK_B(hipMemsetAsync(d_cnt, 0, sizeof(PrCounters), s));
-    launch_canonical_check(A->d_row_ptr, A->d_col_idx, n, n, A->nnz, 0, ctx->tile_row, &d_cnt->canon, s);
-    if (AT && AT != A) launch_canonical_check(AT->d_row_ptr, AT->d_col_idx, n, n, AT->nnz, 2, ctx->tile_row, &d_cnt->canon, s);
+    launch_graph_canonical_checks(ctx, A, AT, &d_cnt->canon, s);
     HIPCHK_B(round_fetch(&h, d_cnt, sizeof h, s));
     if (timed) ms_check = ms_since(t);
-    if (h.canon & (kSetErrRange | (kSetErrRange << 2))) {
-        snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) in operand %s", who, n,
-                 (h.canon & kSetErrRange) ? "A" : "AT");
-        return bail(BSPGEMM_ERR_INVALID);
-    }
+    if (h.canon & (kSetErrRange | (kSetErrRange << 2))) return bail(fail_bad_column_in(who, n, h.canon));
     const bool a_untidy = (h.canon & kSetErrOrder) != 0;
     const bool at_untidy = AT && (AT == A ? a_untidy : (h.canon & (kSetErrOrder << 2)) != 0);
     int canonicalised = (a_untidy ? 1 : 0) | (at_untidy ? 2 : 0), transposed = 0;

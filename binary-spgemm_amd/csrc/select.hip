@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void k_values_sum(const int *__restrict__ vals
         acc += (long long)v.x + v.y + v.z + v.w;
     }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);          // (open code: wave_sum compiles to other code here)
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(sum, (unsigned long long)(wsum[0] + wsum[1] + wsum[2] + wsum[3]));

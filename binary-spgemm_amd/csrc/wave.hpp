@@ -113,6 +113,63 @@ __device__ __forceinline__ void clear_blocked(u32 *P, int lane)
     for (int k = 0; k < W; k++) P[lane * W + k] = 0u;
 }
 
+// sum / maximum / minimum of x over the wave, in every lane (xor shuffles, off = 32 .. 1); T: int, long long, u64
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_max(T x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const T y = __shfl_xor(x, off, 64);
+        x = y > x ? y : x;
+    }
+    return x;
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_min(T x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = min(x, __shfl_xor(x, off, 64));
+    return x;
+}
+
+// the wave's lanes with `take` append `v` to list[*size ...]: one atomic per wave, the lane's rank by its mask of lower
+// lanes.  The store is bounded by `cap` entries (C: int or long long, compared in its own width) whatever *size holds; a
+// caller whose list cannot pass `cap` says why at its call.  list is not __restrict__: a launch may read the list plainly
+// elsewhere.
+template <typename T, typename C>
+__device__ __forceinline__ void wave_append(bool take, T v, T *list, int *size, C cap, int lane)
+{
+    const u64 m = __ballot(take);
+    if (m == 0) return;                                      // (wave-uniform)
+    int base = 0;
+    if (lane == 0) base = atomicAdd(size, __popcll(m));
+    base = wave_first(base);
+    const int at = base + __popcll(m & mask_lt(lane));
+    // (the test stands inside the condition in either width: computed into a bool first, or widened for both, it compiles
+    // to other code in the callers)
+    if constexpr (sizeof(C) == 8) {
+        if (take && (unsigned long long)at < (unsigned long long)cap) list[at] = v;
+    } else {
+        if (take && (unsigned)at < (unsigned)cap) list[at] = v;
+    }
+}
+
+// the wave's count of `x` added to *word by one atomic
+__device__ __forceinline__ void wave_count(bool x, int *word, int lane)
+{
+    const u64 m = __ballot(x);
+    if (m && lane == 0) atomicAdd(word, __popcll(m));
+}
+
 // the workgroup's count of `x` added to *word (and *also, unless NULL) by one atomic each; wsum: THREADS / 64 ints of LDS.
 // Called by every thread of the workgroup (THREADS of them).
 template <int THREADS>
