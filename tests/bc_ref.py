@@ -1,7 +1,8 @@
 """The reference of the betweenness tests (bspgemm_betweenness): the numpy model of the header's definition (exact uint64 path
 counts, 2^32-scaled integer dependencies, the two double operations as numpy does them), which also predicts every field of
 bspgemm_bc_info; a naive model in Python integers and floats to check it with; networkx's Brandes in float64 to measure the
-deviation against; and the graphs the tests use.  Nothing here touches the GPU.
+deviation against; a host model of the edges of the hub code that a call reaches (cells); and the graphs the tests use.
+Nothing here touches the GPU.
 """
 import math
 import zlib
@@ -41,8 +42,9 @@ def _rows(crp, cci, F):
     return np.repeat(np.asarray(F, np.int64), lens), cci[idx].astype(np.int64)
 
 
-def model(rp, ci, n, sources):
-    """{"fixed", "bc", and every field of bspgemm_bc_info} of the definition; raises Overflow"""
+def model(rp, ci, n, sources, trace=None):
+    """{"fixed", "bc", and every field of bspgemm_bc_info} of the definition; raises Overflow.  trace: a list that takes,
+    per source, {"fronts", "level", "sigma", "delta"} as the sweep left them (cells() reads them)"""
     crp, cci, _ = canonical(rp, ci, n)
     crp = np.asarray(crp, np.int64)
     outdeg = np.diff(crp)
@@ -90,6 +92,8 @@ def model(rp, ci, n, sources):
                 np.add.at(delta, es[down], summand)
                 info["hub_chunks"] += int(chunks_of[F].sum())
             c[F] = (U(ONE) + delta[F]).astype(np.float64) / sigma[F].astype(np.float64)
+        if trace is not None:
+            trace.append({"fronts": fronts, "level": level, "sigma": sigma, "delta": delta.copy()})
         delta[s] = 0
         bc += delta
         info["sigma_max"] = max(info["sigma_max"], int(sigma.max()))
@@ -137,6 +141,82 @@ def naive(rp, ci, n, sources):
             if v != s:
                 bc[v] += delta[v]
     return bc
+
+
+# ---------------------------------------------------------------- the kernel edges ("cells") an input reaches ---------
+THREADS = 256            # csrc/betweenness.hip kBcThreads: k_bc_source writes that many chunk records per trip
+
+CELLS = frozenset([
+    "source is a hub", "source hub of more than 256 records", "two hubs in one level", "hub level with a non-zero chunk offset",
+    "hub length chunk + 1", "hub length an exact multiple of the chunk", "hub length otherwise", "hub in the last level",
+    "hub with a self-loop", "hub entry to the source", "hub entry to an earlier level", "hub entry to the same level",
+    "hub with backward sum 0", "hub reached from two sources in a row", "stored row over the chunk, distinct row not",
+    "stored and distinct row over the chunk", "hub successor with sigma > 1 fed from two chunks"])
+
+
+def cells(rp, ci, n, sources, chunk=HUB_CHUNK):
+    """the edges of csrc/betweenness.hip's hub code that the sweeps from `sources` reach, as a subset of CELLS: read off the
+    model's own fronts.  A hub is a reached vertex whose canonical row is longer than `chunk`; its records lie in chunk[]
+    behind those of the levels before it (BcLevelRec::coff)."""
+    rp = np.asarray(rp, np.int64)
+    crp, cci, _ = canonical(rp, ci, n)
+    crp = np.asarray(crp, np.int64)
+    stored, outdeg = np.diff(rp), np.diff(crp)
+    hub = outdeg > chunk
+    records = np.where(hub, (outdeg + chunk - 1) // chunk, 0)
+    trace, out, before = [], set(), None
+    model(rp, ci, n, sources, trace)
+    for s, t in zip((int(x) for x in sources), trace):
+        fronts, level, sigma, delta = t["fronts"], t["level"], t["sigma"], t["delta"]
+        depth, coff, mine = len(fronts) - 1, 0, set()
+        if hub[s]:
+            out.add("source is a hub")
+            if records[s] > THREADS:
+                out.add("source hub of more than 256 records")
+        for d, F in enumerate(fronts):
+            H = F[hub[F]]
+            if ((stored[F] > chunk) & ~hub[F]).any():
+                out.add("stored row over the chunk, distinct row not")
+            if (stored[H] != outdeg[H]).any():
+                out.add("stored and distinct row over the chunk")
+            if H.size == 0:
+                continue
+            if H.size >= 2:
+                out.add("two hubs in one level")
+            if coff > 0:
+                out.add("hub level with a non-zero chunk offset")
+            coff += int(records[H].sum())
+            mine.update(H.tolist())
+            for cell, hit in (("hub length chunk + 1", outdeg[H] == chunk + 1),
+                              ("hub length an exact multiple of the chunk", outdeg[H] % chunk == 0),
+                              ("hub length otherwise", (outdeg[H] != chunk + 1) & (outdeg[H] % chunk != 0))):
+                if hit.any():
+                    out.add(cell)
+            if d == depth:
+                out.add("hub in the last level")
+            elif (delta[H] == 0).any():
+                out.add("hub with backward sum 0")
+            es, ed = _rows(crp, cci, H)
+            lw = level[ed]
+            for cell, hit in (("hub with a self-loop", ed == es), ("hub entry to the source", (ed == s) & (es != s)),
+                              ("hub entry to an earlier level", (lw >= 0) & (lw < d) & (ed != s)),
+                              ("hub entry to the same level", (lw == d) & (ed != es))):
+                if hit.any():
+                    out.add(cell)
+            # the successors one level down that two different chunks add to (of one hub or of two)
+            lens = outdeg[H]
+            record = (np.arange(es.size) - np.repeat(np.cumsum(lens) - lens, lens)) // chunk + \
+                np.repeat(np.cumsum(records[H]) - records[H], lens)
+            down = lw == d + 1
+            fed = np.unique(ed[down] * int(records[H].sum()) + record[down]) // int(records[H].sum())
+            w, times = np.unique(fed, return_counts=True)
+            if (sigma[w[times >= 2]] > U(1)).any():
+                out.add("hub successor with sigma > 1 fed from two chunks")
+        if before is not None and before & mine:
+            out.add("hub reached from two sources in a row")
+        before = mine
+    assert out <= CELLS
+    return out
 
 
 def symmetric(rp, ci, n):
@@ -263,13 +343,73 @@ SMALL = ("empty0", "empty1", "loop1", "two_cycle", "path5", "dipath6", "star_in"
          "diamond_ladder", "untidy", "layers_2p62", "layers_3p39")
 ALL_SOURCES_UP_TO = 600
 
+
+# ---------------------------------------------------------------- the edge graphs (tests/test_gpu_bc_edges.py) -------
+# Kept out of GRAPHS: the parametrised tests and the naive model that go over GRAPHS would become slow.  The builders take
+# the chunk as a parameter, so that a twin with a chunk of 16 has the same structure at a size the naive model walks.
+def hub_levels(chunk=HUB_CHUNK):
+    """Hubs in four levels of the sweep from vertex 0, in canonical form:
+        0 -> 1, 2, 3        rows of chunk + 1, 2 * chunk (two full chunks) and chunk entries (no hub) over 5 * chunk / 2
+                            leaves (the vertices 4 ...): the ranges overlap, so leaves have sigma 2 and 3, also where two
+                            chunks of different hubs add to them
+        three leaves -> g   the second-generation hub, 2 * chunk + 1 entries: itself, the source, vertex 2 (level 1), p (its
+                            own level; a fourth leaf -> p), and 2 * chunk - 3 fresh vertices.  Its records lie behind the
+                            four of vertices 1 and 2.
+        fresh: X, Y         X: chunk + 1 entries, all leaves (two levels up): a hub whose sum is 0, not in the last level,
+        Y -> Z              Z: chunk + 1 entries, all leaves: a hub in the last level whose forward chunks find nothing
+    (g, p, X, Y, Z are what hub_levels_names returns.)  From vertex 2 the source is a hub; from the first leaf, g is alone in
+    level 1 and vertices 2 and X share level 2."""
+    C = chunk
+    leaves = 4 + np.arange(5 * C // 2)
+    g, p, fresh, X, Y, Z = hub_levels_names(C)
+    pairs = [([0, 0, 0], [1, 2, 3]), (np.full(C + 1, 1), leaves[:C + 1]), (np.full(2 * C, 2), leaves[C // 2:C // 2 + 2 * C]),
+             (np.full(C, 3), leaves[C:2 * C]), (leaves[[0, C, -1]], [g, g, g]), ([leaves[1]], [p]),
+             (np.full(4 + fresh.size, g), np.concatenate([[g, 0, 2, p], fresh])), ([p], [fresh[0]]),
+             (np.full(C + 1, X), leaves[:C + 1]), ([Y], [Z]), (np.full(C + 1, Z), leaves[C - 1:2 * C])]
+    return canonical(*cc_ref.csr(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), Z + 1))
+
+
+def hub_levels_names(chunk=HUB_CHUNK):
+    """(g, p, the fresh vertices, X, Y, Z) of hub_levels"""
+    g = 4 + 5 * chunk // 2
+    fresh = g + 2 + np.arange(2 * chunk - 3)
+    return g, g + 1, fresh, int(fresh[1]), int(fresh[2]), int(fresh[-1]) + 1
+
+
+def hub_levels_sources(chunk=HUB_CHUNK):
+    """vertex 0, a first-generation hub, a leaf, and the same hub again"""
+    return np.array([0, 2, 4, 2], np.int32)
+
+
+def hub_stored(stored, distinct):
+    """hub(distinct) with the hub's row stored `stored` entries long: its entries in descending order, again and again"""
+    rp, ci, n = hub(distinct)
+    row = np.resize(ci[rp[1]:rp[2]][::-1], stored)
+    rp = rp.copy()
+    rp[2:] += stored - distinct
+    return rp, np.concatenate([ci[:rp[1]], row, ci[rp[1] + distinct:]]).astype(np.int32), n
+
+
+EDGE_GRAPHS = {
+    "hub_levels": hub_levels,
+    "hub_258_records": lambda: hub((THREADS + 1) * HUB_CHUNK + 1),
+    "stored_5000_of_4000": lambda: hub_stored(5000, 4000),
+    "stored_9000_of_4097": lambda: hub_stored(9000, 4097),
+}
+EDGE_SOURCES = {
+    "hub_levels": hub_levels_sources(),
+    "hub_258_records": np.array([1, 0], np.int32),
+    "stored_5000_of_4000": np.array([0, 1, 3], np.int32),
+    "stored_9000_of_4097": np.array([0, 1, 3], np.int32),
+}
+
 _cache = {}
 
 
 def graph(name):
     """the named graph, built once"""
     if name not in _cache:
-        rp, ci, n = layers(REFUSED[name][0]) if name in REFUSED else GRAPHS[name]()
+        rp, ci, n = layers(REFUSED[name][0]) if name in REFUSED else (EDGE_GRAPHS[name] if name in EDGE_GRAPHS else GRAPHS[name])()
         rp, ci = np.ascontiguousarray(rp, np.int32), np.ascontiguousarray(ci, np.int32)
         rp.setflags(write=False)
         ci.setflags(write=False)
@@ -294,6 +434,27 @@ def expected(name):
         res["fixed"].setflags(write=False)
         res["bc"].setflags(write=False)
         _cache[key] = res
+    return _cache[key]
+
+
+def edge_expected(name, backwards=False):
+    """(sources, the model) of an edge graph from EDGE_SOURCES[name], in the given or the opposite order, computed once
+    and shared (read-only)"""
+    key = ("edge", name, backwards)
+    if key not in _cache:
+        sources = np.ascontiguousarray(EDGE_SOURCES[name][::-1] if backwards else EDGE_SOURCES[name])
+        res = model(*graph(name), sources)
+        res["fixed"].setflags(write=False)
+        res["bc"].setflags(write=False)
+        _cache[key] = (sources, res)
+    return _cache[key]
+
+
+def edge_cells(name):
+    """cells() of an edge graph from EDGE_SOURCES[name], computed once"""
+    key = ("cells", name)
+    if key not in _cache:
+        _cache[key] = frozenset(cells(*graph(name), EDGE_SOURCES[name]))
     return _cache[key]
 
 
