@@ -60,6 +60,7 @@ EXPORTS = [
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
     "bspgemm_strongly_connected_components", "bspgemm_graph_coloring", "bspgemm_label_propagation",
     "bspgemm_local_clustering", "bspgemm_pagerank", "bspgemm_betweenness",
+    "bspgemm_matrix_extract", "bspgemm_matrix_extract_rows_of",
     "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
 ]
@@ -82,9 +83,10 @@ SYMMETRIZE_DROP_DIAGONAL = 1                                                    
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
            "shared_slots": 6, "dot_light": 7, "bfs_alpha": 8, "bfs_beta": 9, "bfs_push_lanes": 10,
-           "lp_min_class": 11, "pr_min_class": 12, "bc_lanes": 13}                                                                           # bspgemm_option
+           "lp_min_class": 11, "pr_min_class": 12, "bc_lanes": 13, "extract_lanes": 14}                                                                           # bspgemm_option
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
 BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
+EXTRACT_KEEP_SHAPE = 1                                                                   # BSPGEMM_EXTRACT_KEEP_SHAPE
 LCC_DIRECTED = 1                                                                         # BSPGEMM_LCC_DIRECTED
 PR_AUTO, PR_PULL, PR_PUSH = 0, 1, 2                                                      # bspgemm_pr_method
 
@@ -142,6 +144,15 @@ class BcInfo(C.Structure):
     """bspgemm_bc_info"""
     _fields_ = [("sigma_max", C.c_uint64), ("reached", C.c_int64), ("edges_forward", C.c_int64), ("hub_chunks", C.c_int64),
                 ("sources", C.c_int), ("depth_max", C.c_int), ("levels", C.c_int), ("canonicalised", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ExtractInfo(C.Structure):
+    """bspgemm_extract_info"""
+    _fields_ = [("kept", C.c_int64), ("scanned", C.c_int64), ("hub_chunks", C.c_int64), ("lanes", C.c_int),
+                ("cols_monotone", C.c_int), ("sorted_by", C.c_int), ("canonicalised", C.c_int)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -283,6 +294,8 @@ def lib():
     L.bspgemm_local_clustering.argtypes = [VP, VP, C.c_uint, PVP, VP, VP, C.POINTER(LccInfo)]
     L.bspgemm_pagerank.argtypes = [VP, VP, VP, C.c_int, C.c_double, C.c_int, C.c_double, VP, VP, C.POINTER(PrInfo)]
     L.bspgemm_betweenness.argtypes = [VP, VP, C.c_int, VP, VP, VP, C.POINTER(BcInfo)]
+    L.bspgemm_matrix_extract.argtypes = [VP, VP, C.c_int, VP, C.c_int, VP, C.c_uint, PVP, C.POINTER(ExtractInfo)]
+    L.bspgemm_matrix_extract_rows_of.argtypes = [VP, VP, VP, C.c_int, VP, C.c_int, C.c_uint, PVP, C.POINTER(ExtractInfo)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
     L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
     L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
@@ -465,7 +478,7 @@ class Context:
     def set_option(self, name, value):
         """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
         "shared_slots" -1/0/k, "dot_light" T >= 0, "bfs_alpha" >= 1, "bfs_beta" >= 1, "bfs_push_lanes" 0/4/16/64,
-        "lp_min_class" 0..3, "pr_min_class" 0..3, "bc_lanes" 0/4/16/64"""
+        "lp_min_class" 0..3, "pr_min_class" 0..3, "bc_lanes" 0/4/16/64, "extract_lanes" 0/4/16/64"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):
@@ -722,6 +735,33 @@ class Context:
                                        fixed.ctypes.data if A.rows else None, bc.ctypes.data if A.rows else None,
                                        C.byref(info)), "bspgemm_betweenness")
         return fixed, bc, info.as_dict()
+
+    def extract(self, A, rows=None, cols=None, keep_shape=False):
+        """bspgemm_matrix_extract: (Matrix, info dict) -- out = A[rows, cols] on the device.  rows / cols: int sequences, None =
+        all in order.  Default: out is len(rows) x len(cols), entry (r, c) where A has (rows[r], cols[c]); rows may repeat, cols
+        must not.  keep_shape=True: A's shape, the entries (i, j) of A with i in rows and j in cols (D_I * A * D_J).  The rows
+        of out are ascending and duplicate-free.  info: kept, scanned, hub_chunks, lanes, cols_monotone, sorted_by,
+        canonicalised."""
+        I = None if rows is None else _i32(np.asarray(rows).reshape(-1))
+        J = None if cols is None else _i32(np.asarray(cols).reshape(-1))
+        keep = (C.c_int * 1)()                              # (an empty array's data pointer may be NULL, which means "all")
+        pi = None if I is None else C.c_void_p(I.ctypes.data if I.size else C.addressof(keep))
+        pj = None if J is None else C.c_void_p(J.ctypes.data if J.size else C.addressof(keep))
+        m, info = C.c_void_p(), ExtractInfo()
+        _chk(lib().bspgemm_matrix_extract(self._h, A._h, 0 if I is None else int(I.size), pi, 0 if J is None else int(J.size), pj,
+                                          EXTRACT_KEEP_SHAPE if keep_shape else 0, C.byref(m), C.byref(info)),
+             "bspgemm_matrix_extract")
+        return Matrix(self, m, keep=None), info.as_dict()
+
+    def extract_rows_of(self, A, MI=None, ri=-1, MJ=None, rj=-1, keep_shape=False):
+        """bspgemm_matrix_extract_rows_of: (Matrix, info dict) -- as extract, with the lists read on the device: the stored
+        col_idx of row ri of MI and of row rj of MJ (-1: the operand's whole col_idx in storage order; None: all)."""
+        m, info = C.c_void_p(), ExtractInfo()
+        _chk(lib().bspgemm_matrix_extract_rows_of(self._h, A._h, None if MI is None else MI._h, int(ri),
+                                                  None if MJ is None else MJ._h, int(rj),
+                                                  EXTRACT_KEEP_SHAPE if keep_shape else 0, C.byref(m), C.byref(info)),
+             "bspgemm_matrix_extract_rows_of")
+        return Matrix(self, m, keep=None), info.as_dict()
 
     def transpose(self, A):
         """bspgemm_matrix_transpose: pattern(A)^T as a new operand on the device (rows ascending, duplicates dropped)"""

@@ -149,6 +149,7 @@ struct bspgemm_context {
     int lp_min_class = 0;               // BSPGEMM_OPT_LP_MIN_CLASS: 0 .. 3, the smallest degree class of bspgemm_label_propagation (lp.hip)
     int pr_min_class = 0;               // BSPGEMM_OPT_PR_MIN_CLASS: 0 .. 3, the smallest in-degree class of bspgemm_pagerank under PULL (pagerank.hip)
     int bc_lanes = 0;                   // BSPGEMM_OPT_BC_LANES: 0 per level from a quarter of its mean out-degree, or 4, 16, 64 lanes per vertex in both sweeps of bspgemm_betweenness (betweenness.hip)
+    int extract_lanes = 0;              // BSPGEMM_OPT_EXTRACT_LANES: 0 from a quarter of the mean length of the rows read, or 4, 16, 64 lanes per out row in the count and the emit of bspgemm_matrix_extract (extract.hip)
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
     bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
@@ -158,7 +159,8 @@ struct bspgemm_context {
     bool lp_timing = false;             // BSPGEMM_LP_TIMING: stage times of the label propagation on stderr (it then synchronises twice per iteration)
     bool pr_timing = false;             // BSPGEMM_PR_TIMING: stage times of the PageRank on stderr (it then synchronises behind every class launch)
     bool bc_timing = false;             // BSPGEMM_BC_TIMING: stage times of the betweenness centrality on stderr (it then synchronises behind every launch group)
-    int lcc_timing = 0;                 // BSPGEMM_LCC_TIMING: 1 stage times of the local clustering on stderr (it then synchronises behind every stage); 2: the same on the half that is not kept (lcc.hip)
+    bool extract_timing = false;        // BSPGEMM_EXTRACT_TIMING: stage times of the submatrix extraction on stderr (it then synchronises behind every stage)
+    int lcc_timing = 0;                // BSPGEMM_LCC_TIMING: 1 stage times of the local clustering on stderr (it then synchronises behind every stage); 2: the same on the half that is not kept (lcc.hip)
 };
 
 extern "C" int bspgemm_par_max_plus_one(const int *idx, long long n);              // host/par_copy.c
@@ -339,7 +341,7 @@ static inline bspgemm_status fail_stuck(const char *who)
     snprintf(g_err, sizeof g_err, "%s: did not converge", who);
     return BSPGEMM_ERR_HIP;
 }
-// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING)
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING)
 using host_clock = std::chrono::steady_clock;
 static inline double ms_since(host_clock::time_point t)
 {

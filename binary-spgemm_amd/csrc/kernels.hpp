@@ -283,6 +283,11 @@ constexpr unsigned kSetErrOrder = 2u;      // a row that is not strictly ascendi
 void launch_canonical_check(const int *row_ptr, const int *col_idx, int rows, int cols, long long nnz, int err_shift,
                             int *tile_row, unsigned *err, hipStream_t s);
 
+// ---- the submatrix extraction (extract.hip; tests/extract_ref.py mirrors the three) ------------------------------------
+constexpr int kExHubChunk = 4096;          // the longest row of A left to one group of lanes; entries per chunk of a longer one
+constexpr int kExSortWave = 256;           // the longest out row that one wave sorts in its LDS segment
+constexpr int kExSortBlock = 4096;         // the longest out row that a workgroup sorts in 16 KiB of LDS
+
 // row_ptr rebasing helper for interior-pointer uploads
 void launch_rebase_i32(int *row_ptr, int n, int base, hipStream_t s);
 

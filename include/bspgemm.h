@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING=1|2, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING=1|2, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -198,7 +198,9 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  *                    1 wave, 2 workgroup, 3 hub), described there.  It changes no result.  Read at every call.
  *   BC_LANES         0 (default): the lanes per vertex of every launch of bspgemm_betweenness follow a quarter of the
  *                    level's mean out-degree; or 4, 16, 64 for every launch of both sweeps.  It changes no result.  Read at
- *                    every call.  */
+ *                    every call.
+ *   EXTRACT_LANES    0 (default): the lanes per out row of the count and the emit of bspgemm_matrix_extract follow a quarter
+ *                    of the mean length of the rows read; or 4, 16, 64.  It changes no result.  Read at every call.  */
 typedef enum bspgemm_option {
     BSPGEMM_OPT_CLASS_STREAMS   = 1,
     BSPGEMM_OPT_BLOCKED_EXTENTS = 2,
@@ -212,7 +214,8 @@ typedef enum bspgemm_option {
     BSPGEMM_OPT_BFS_PUSH_LANES  = 10,
     BSPGEMM_OPT_LP_MIN_CLASS    = 11,
     BSPGEMM_OPT_PR_MIN_CLASS    = 12,
-    BSPGEMM_OPT_BC_LANES        = 13
+    BSPGEMM_OPT_BC_LANES        = 13,
+    BSPGEMM_OPT_EXTRACT_LANES   = 14
 } bspgemm_option;
 bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_option opt, int value);
 /* current value of a knob (INT32_MIN for an unknown option or a NULL context) */
@@ -385,6 +388,61 @@ bspgemm_status bspgemm_matrix_equal(bspgemm_context *ctx, const bspgemm_matrix *
  * non-square A, any other flag bit, a NULL argument, A from another context; otherwise the errors of the three calls.    */
 #define BSPGEMM_SYMMETRIZE_DROP_DIAGONAL 1u
 bspgemm_status bspgemm_matrix_symmetrize(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags, bspgemm_matrix **out);
+
+/* Submatrix extraction, GraphBLAS' GrB_extract for patterns: out = A[I, J], on the device, without a product -- a filtered
+ * copy that reads every selected row of A once, keeps the entries whose column is selected and writes the new column number.
+ *
+ * Host lists (bspgemm_matrix_extract).  I (ni entries) and J (nj entries) are host arrays; NULL means "all, in order", and
+ * then ni or nj is ignored.
+ *   - Default (relabelling) mode: out is ni x nj, and (r, c) in out  <=>  (I[r], J[c]) in pattern(A).  I may be unsorted and
+ *     may name a row more than once: the row is then copied that many times.  J may be unsorted.  J must not name a column
+ *     twice: BSPGEMM_ERR_INVALID.  So extract(A, p, p) with a permutation p is the relabelled graph, and extract(A, V, V) is the
+ *     induced subgraph on V, renumbered by position in V.
+ *   - BSPGEMM_EXTRACT_KEEP_SHAPE: out has A's shape, and (i, j) in out  <=>  (i, j) in A, i in set(I) and j in set(J): this is
+ *     D_I * A * D_J.  Repeats and order inside either list are harmless.
+ *   - Both modes: every row of out is strictly ascending and duplicate-free, whatever A looks like (an upload with an
+ *     interior row_ptr, wrapped device arrays off 16-byte alignment, any derived operand; rows unsorted or with repeats).  An A
+ *     that fails the canonical check is first canonicalised (transposed twice, as bspgemm_matrix_setop does with its
+ *     operands), and info.canonicalised = 1.  out is an owned operand with the layout of an uploaded one: usable in every
+ *     product, transpose, select, setop and graph call; release it with bspgemm_matrix_free.  ni == 0, nj == 0, A.rows == 0,
+ *     A.cols == 0, nnz == 0 and rectangular A are all valid.  Both lists NULL gives the canonical copy of A.
+ *
+ * Device lists (bspgemm_matrix_extract_rows_of).  The row list is the stored col_idx of row ri of MI, the column list the same
+ * of row rj of MJ; ri == -1 (rj == -1) means the whole col_idx of the operand in storage order, which is what a diagonal
+ * selector from bspgemm_matrix_from_result_where holds.  A NULL operand means "all".  The lists never leave the device: only
+ * their lengths are read back.  MI and MJ need not have A's shape; their entries must lie in [0, A.rows) and [0, A.cols).
+ * Typical uses: row c of the transpose of an assignment operand P is the member list of component, colour or community c;
+ * from_result_where(cores, GE, k) with ri = -1 is the k-core's vertex set.  The result is bit for bit that of the host-list
+ * call with the same lists.
+ *
+ * info (may be NULL): kept = nnz(out); scanned = the entries of A that the call looked at, the sum of len(A row I[r]) over r
+ * (under KEEP_SHAPE over the distinct rows that I names); hub_chunks = the chunk records written, ceil(len / 4096) for every
+ * row read that is longer than 4096 entries; lanes = the lane width that ran; cols_monotone = 1 when the column map
+ * preserves order (J NULL, no J[c] < J[c - 1], or KEEP_SHAPE); sorted_by = 0 when no sort was needed (cols_monotone, or
+ * nothing kept), 1 when the out rows were sorted in LDS (a wave for rows of up to 256 kept entries, a workgroup for rows of
+ * up to 4096), 2 when an out row had more than 4096 kept entries and out went once through two transposes; canonicalised.
+ *   - BSPGEMM_OPT_EXTRACT_LANES (0 default, 4, 16, 64), read at every call: the lanes per out row.  It changes no result.
+ *     Environment BSPGEMM_EXTRACT_TIMING=1 (read in bspgemm_create): the stage split on stderr (maps and checks, count, hub
+ *     launches, scan, read-back two, emit, sort); every stage is then synchronised.
+ *   - Runs on the context's stream; out is complete on that stream when the call returns.  It does not touch the multiply
+ *     statistics.  Synchronisations: TWO with host lists -- the error bits, scanned and the chunk count; the kept total -- plus
+ *     one length read-back for _rows_of (none where ri and rj are -1 or their operand is NULL).  An untidy A adds the
+ *     transposes' and one more round.  State: the context's workspace, 4 bytes per column of A (the map), per row of A
+ *     (KEEP_SHAPE with a row list), per list entry, and 20 bytes per out row.  No kernel waits for another workgroup.
+ *   - BSPGEMM_ERR_INVALID with *out = NULL, a zeroed info and bspgemm_last_error naming the function and the cause: a NULL
+ *     ctx, A or out; an unknown flag bit; an operand of another context; ni < 0 or nj < 0 with a list; a list entry outside
+ *     its range (the message says which list); a column named twice in J in relabelling mode; ri or rj outside [-1, rows);
+ *     a column of A outside [0, A.cols).  Argument errors on host lists are found before anything is launched.
+ *     BSPGEMM_ERR_OVERFLOW: more than INT_MAX kept entries, or A above INT_MAX entries.  BSPGEMM_ERR_ALLOC: an allocation
+ *     failed.  Nothing is leaked and the context stays usable.                                                            */
+#define BSPGEMM_EXTRACT_KEEP_SHAPE 1u
+typedef struct bspgemm_extract_info { int64_t kept; int64_t scanned; int64_t hub_chunks; int lanes; int cols_monotone;
+                                      int sorted_by; int canonicalised; } bspgemm_extract_info;
+bspgemm_status bspgemm_matrix_extract(bspgemm_context *ctx, const bspgemm_matrix *A, int ni, const int *I, int nj,
+                                      const int *J, unsigned flags, bspgemm_matrix **out, bspgemm_extract_info *info);
+bspgemm_status bspgemm_matrix_extract_rows_of(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *MI,
+                                              int ri, const bspgemm_matrix *MJ, int rj, unsigned flags,
+                                              bspgemm_matrix **out, bspgemm_extract_info *info);
 
 /* *sum = the exact int64 sum of the values of a counted result, reduced on the device (integer addition: the order does
  * not matter); 8 bytes come back.  A pattern-only result: BSPGEMM_ERR_INVALID, *sum untouched.                           */
