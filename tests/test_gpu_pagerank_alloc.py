@@ -12,22 +12,19 @@ anything else), which after an out-of-memory answer drops the cache of freed res
 may succeed", as include/bspgemm.h says of the hook.  The test accepts BSPGEMM_OK from an armed call only with the exact
 ranks and with exactly one request more than a cold call makes, and from at most that one k.  The sweep ends within the
 request count of a first unarmed run (plus the one k at which the hook no longer fires): a condition, not a loop until
-something breaks.
+something breaks (tests/alloc_sweep.py).
 """
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
 
 import bspgemm
 import pagerank_ref as P
+from alloc_sweep import Case, L, Out, fields, filled, sweep
 
 pytestmark = pytest.mark.gpu
 
-VP = C.c_void_p
-OK, ERR_ALLOC = 0, 2
-NAME = "bspgemm_pagerank"
 VARIANTS = {
     # name: (graph, method, AT given, the fewest k that must end in ERR_ALLOC)
     "pull_at_null_untidy": ("untidy", P.PR_PULL, False, 7),    # the tile rows and two operands of three arrays each
@@ -36,101 +33,31 @@ VARIANTS = {
 }
 
 
-def _last_error():
-    return bspgemm.lib().bspgemm_last_error().decode(errors="replace")
+def pagerank_case(variant):
+    name, method, with_at, least = VARIANTS[variant]
+    rp, ci, n = P.graph(name)
 
+    def setup(env):
+        return dict(A=env.upload(rp, ci, n), AT=env.upload(*P.transposed(rp, ci, n)[:2], n) if with_at else None)
 
-class _Env:
-    """one context with the graph (and its transpose) uploaded"""
+    def call(env, inp):
+        info = filled(bspgemm.PrInfo)
+        fixed, rank = np.zeros(n, np.uint64), np.zeros(n, np.float64)
+        st = L().bspgemm_pagerank(env.ctx, inp["A"], inp["AT"], method, 0.85, 20, 0.0, fixed.ctypes.data, rank.ctypes.data,
+                                  C.byref(info))
+        return Out(st, structs={"info": info}, arrays={"fixed": fixed, "rank": rank})
 
-    def __init__(self, rp, ci, n, with_at):
-        L = bspgemm.lib()
-        self.n = n
-        self.ctx, self.A, self.AT = VP(), VP(), VP()
-        assert L.bspgemm_create(0, C.byref(self.ctx)) == OK and self.ctx.value, _last_error()
-        assert L.bspgemm_matrix_upload(self.ctx, n, n, rp.ctypes.data, ci.ctypes.data, C.byref(self.A)) == OK, _last_error()
-        if with_at:
-            t_rp, t_ci, _ = P.transposed(rp, ci, n)
-            assert L.bspgemm_matrix_upload(self.ctx, n, n, t_rp.ctypes.data, t_ci.ctypes.data, C.byref(self.AT)) == OK, _last_error()
+    def expect():
+        exp = P.pagerank(rp, ci, n, 0.85, 20)
+        return exp["fixed"], exp["rank"].view(np.uint64), exp["mass"], exp["delta"], exp["dangling"], 20
 
-    def call(self, method):
-        """(status, fixed, rank, info)"""
-        info = bspgemm.PrInfo()
-        C.memset(C.byref(info), 0x5A, C.sizeof(info))
-        fixed, rank = np.zeros(self.n, np.uint64), np.zeros(self.n, np.float64)
-        st = getattr(bspgemm.lib(), NAME)(self.ctx, self.A, self.AT if self.AT.value else None, method, 0.85, 20, 0.0,
-                                          fixed.ctypes.data, rank.ctypes.data, C.byref(info))
-        return st, fixed, rank, info
+    def read(env, inp, out):
+        return (out.arrays["fixed"], out.arrays["rank"].view(np.uint64)) + fields(
+            out.structs["info"], ("mass", "delta", "dangling", "iterations"))
 
-    def close(self):
-        L = bspgemm.lib()
-        if self.AT.value:
-            L.bspgemm_matrix_free(self.AT)
-        L.bspgemm_matrix_free(self.A)
-        L.bspgemm_destroy(self.ctx)
+    return Case(variant, setup, call, read, expect, zeroed=("info",), cap=40, min_failed=least, max_retried=1, strict_requests=True)
 
 
 @pytest.mark.parametrize("variant", sorted(VARIANTS))
 def test_every_allocation_failure_of_the_call(variant):
-    L = bspgemm.lib()
-    name, method, with_at, least = VARIANTS[variant]
-    rp, ci, n = P.graph(name)
-    exp = P.pagerank(rp, ci, n, 0.85, 20)
-
-    def exact(fixed, rank, info, what):
-        assert np.array_equal(fixed, exp["fixed"]) and rank.tobytes() == exp["rank"].tobytes(), what
-        assert (info.mass, info.delta, info.dangling, info.iterations) == (exp["mass"], exp["delta"], exp["dangling"], 20), what
-
-    def good(env, what):
-        st, fixed, rank, info = env.call(method)
-        assert st == OK, "%s: status %d (%s)" % (what, st, _last_error())
-        exact(fixed, rank, info, what)
-
-    gc.collect()                                     # (contexts that earlier tests dropped go now, not in the middle)
-    L.bspgemm_debug_fail_alloc(0)
-    base = bspgemm.debug_alloc_state()
-    # a first unarmed run: its request count bounds the sweep
-    env = _Env(rp, ci, n, with_at)
-    try:
-        before = bspgemm.debug_alloc_state()
-        good(env, "unarmed")
-        cold = bspgemm.debug_alloc_state()[0] - before[0]
-    finally:
-        env.close()
-    assert bspgemm.debug_alloc_state()[1:3] == base[1:3]
-    assert 1 <= cold <= 40, cold
-    failed, retried, fired = [], [], True
-    for k in range(1, cold + 2):
-        what = "%s k=%d" % (variant, k)
-        env = _Env(rp, ci, n, with_at)
-        try:
-            before = bspgemm.debug_alloc_state()
-            L.bspgemm_debug_fail_alloc(k)
-            st, fixed, rank, info = env.call(method)
-            L.bspgemm_debug_fail_alloc(0)
-            after = bspgemm.debug_alloc_state()
-            fired = after[3] - before[3]
-            if not fired:
-                assert k == cold + 1, "%s: the hook is not reached, a cold call makes %d requests" % (what, cold)
-                assert st == OK, "%s (hook not reached): status %d (%s)" % (what, st, _last_error())
-                exact(fixed, rank, info, what)
-            else:
-                assert fired == 1
-                if st == OK:                         # (the documented retry: proven by its request count)
-                    exact(fixed, rank, info, what + " armed")
-                    retried.append((k, after[0] - before[0]))
-                else:
-                    assert st == ERR_ALLOC, "%s armed: status %d (%s), not BSPGEMM_ERR_ALLOC" % (what, st, _last_error())
-                    assert bytes(info) == bytes(C.sizeof(info)) and _last_error(), what
-                    failed.append(k)
-                good(env, what + " repeated")
-        finally:
-            L.bspgemm_debug_fail_alloc(0)
-            env.close()
-        now = bspgemm.debug_alloc_state()
-        assert now[1:3] == base[1:3], "%s: leak: live (count, bytes) %r, before the context %r" % (what, now[1:3], base[1:3])
-    assert not fired, "the hook still fires at k = %d, one past the %d requests of a cold call" % (cold + 1, cold)
-    print("ALLOCSWEEP %-28s cold %3d  ERR_ALLOC at %s  retried at %s" % (variant, cold, failed, retried))
-    assert len(failed) + len(retried) == cold, (cold, failed, retried)                # every request of the call was failed once
-    assert len(retried) <= 1 and len(failed) >= least, (failed, retried)
-    assert all(requests == cold + 1 for _, requests in retried), (retried, cold)    # the failed request was made again
+    sweep(pagerank_case(variant))
