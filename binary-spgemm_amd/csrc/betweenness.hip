@@ -71,7 +71,6 @@ struct BcCounters {
     unsigned err;                       // kBcErrRange | kBcErrOverflow
     unsigned canon;                     // the canonical check (kSetErrRange, kSetErrOrder)
 };
-static_assert(sizeof(BcCounters) % 16 == 0, "the 64-bit arrays behind the counters stay aligned");
 
 // what every forward launch gets.  level and order are loaded plainly and changed in the same launch (at other places, or
 // as described above): neither const nor __restrict__.
@@ -401,23 +400,27 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
     }
 
     // BSPGEMM_BC_TIMING: host clocks around the stages; every launch group is then synchronised
-    const bool timed = ctx->bc_timing;
-    double ms_check = 0, ms_fwd = 0, ms_back = 0, ms_bwd = 0, ms_hub = 0, ms_out = 0, ms_src_max = 0;
-    int src_max_at = -1;
-    const host_clock::time_point t_call = host_clock::now();
+    StageClock clk(ctx->bc_timing, ctx->stream);
+    clk.max_tag[0] = -1;
+    double ms_check = 0, ms_fwd = 0, ms_back = 0, ms_bwd = 0, ms_hub = 0, ms_out = 0;
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
     const int forced_w = ctx->bc_lanes;
 
     // The workspace grows ONCE here: to what the canonicalisation takes (two transposes) or, if that is more, to the
     // call's own state, which is set up only after the canonical A is there.
-    const size_t n4 = ((size_t)n + 3) & ~(size_t)3, ns4 = ((size_t)nsources + 3) & ~(size_t)3;
-    const size_t cnt_ints = sizeof(BcCounters) / sizeof(int);
+    const size_t n4 = ws_pad4((size_t)n), ns4 = ws_pad4((size_t)nsources);
     const size_t chunk_cap = 2 * (size_t)(A->nnz / kBcHubChunk) + 2;   // sum of ceil(len / chunk) over the rows longer than a chunk
-    const size_t o_sigma = cnt_ints, o_delta = o_sigma + 2 * n4, o_c = o_delta + 2 * n4, o_bc = o_c + 2 * n4;
-    const size_t o_level = o_bc + 2 * n4, o_order = o_level + n4, o_chunk = o_order + n4, o_src = o_chunk + 2 * chunk_cap;
-    const size_t own_ints = o_src + 2 * ns4;
-    const size_t total = std::max(own_ints, transpose_workspace_ints(A->nnz, n));
+    BcCounters *d_cnt = nullptr;
+    u64 *sigma = nullptr, *delta = nullptr, *bc = nullptr;
+    double *c = nullptr;
+    int *level = nullptr, *order = nullptr, *d_src = nullptr, *d_deg = nullptr;
+    int2 *chunk = nullptr;
+    auto carve = [&](int *tmp) {
+        return WsCursor(tmp).take(d_cnt, 1).take(sigma, n4).take(delta, n4).take(c, n4).take(bc, n4).take(level, n4).take(order, n4)
+            .take(chunk, chunk_cap).take(d_src, ns4).take(d_deg, ns4).ints();
+    };
+    const size_t total = std::max(carve(nullptr), transpose_workspace_ints(A->nnz, n));
     if (bspgemm_status st = ensure_tmp(ctx, total)) return st;
     if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)A->nnz)) return st;
 
@@ -434,8 +437,8 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
     };
 
     // the canonical check and its read-back: the call's first synchronisation
-    host_clock::time_point t = host_clock::now();
-    BcCounters *d_cnt = reinterpret_cast<BcCounters *>(ctx->tmp);
+    clk.start();
+    carve(ctx->tmp);
     BcCounters h = {};
     HIPCHK_B(hipMemsetAsync(d_cnt, 0, sizeof(BcCounters), s));
     launch_graph_canonical_checks(ctx, A, nullptr, &d_cnt->canon, s);
@@ -448,10 +451,7 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
         A = mineA;
         canonicalised = 1;
     }
-    if (timed) {
-        HIPCHK_B(hipStreamSynchronize(s));
-        ms_check = ms_since(t);
-    }
+    HIPCHK_B(clk.lap(ms_check, true));
     if (!bc_fixed_host && bc_host) {
         h_fixed = static_cast<u64 *>(malloc((size_t)n * sizeof(u64)));
         if (!h_fixed) return bail(FAIL(BSPGEMM_ERR_ALLOC, "bspgemm_betweenness: host sums"));
@@ -461,16 +461,10 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
         if (!h_deg) return bail(FAIL(BSPGEMM_ERR_ALLOC, "bspgemm_betweenness: host degrees"));
     }
 
-    d_cnt = reinterpret_cast<BcCounters *>(ctx->tmp);
-    u64 *sigma = reinterpret_cast<u64 *>(ctx->tmp + o_sigma), *delta = reinterpret_cast<u64 *>(ctx->tmp + o_delta);
-    double *c = reinterpret_cast<double *>(ctx->tmp + o_c);
-    u64 *bc = reinterpret_cast<u64 *>(ctx->tmp + o_bc);
-    int *level = ctx->tmp + o_level, *order = ctx->tmp + o_order;
-    int2 *chunk = reinterpret_cast<int2 *>(ctx->tmp + o_chunk);
-    int *d_src = ctx->tmp + o_src, *d_deg = d_src + ns4;
+    carve(ctx->tmp);                                         // (again: the canonicalisation may have moved the workspace)
     const dim3 block(kBcThreads);
 
-    t = host_clock::now();
+    clk.start();
     HIPCHK_B(hipMemsetAsync(d_cnt, 0, sizeof(BcCounters), s));
     hipLaunchKernelGGL(k_bc_init, bc_grid(n), block, 0, s, n, level, sigma, delta, bc);
     HIPCHK_B(hipGetLastError());
@@ -479,7 +473,7 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
         hipLaunchKernelGGL(k_bc_degrees, bc_grid(nsources), block, 0, s, nsources, d_src, A->d_row_ptr, d_deg);
         HIPCHK_B(round_fetch(h_deg, d_deg, (size_t)nsources * sizeof(int), s));
     }
-    if (timed) ms_back += ms_since(t);
+    (void)clk.lap(ms_back);
 
     long long reached = 0, edges_forward = 0, hub_chunks = 0;
     int depth_max = 0, levels = 0;
@@ -502,29 +496,21 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
                 if (d > n) return bail(fail_stuck(who));     // defensive: a level holds at least one new vertex
                 const BcLevelRec f = L.back();
                 const BcFwd a = {n, d, A->d_row_ptr, level, sigma, order, chunk, (int)chunk_cap, d_cnt};
-                t = host_clock::now();
+                clk.start();
                 launch_forward(forced_w ? forced_w : bc_lanes(f.m, f.size), a, f.size, f.off, A->d_col_idx, s);
                 HIPCHK_B(hipGetLastError());
-                if (timed) {
-                    HIPCHK_B(hipStreamSynchronize(s));
-                    ms_fwd += ms_since(t);
-                    t = host_clock::now();
-                }
+                HIPCHK_B(clk.lap(ms_fwd, true));
                 if (f.chunks) {
                     hipLaunchKernelGGL(k_bc_forward_chunk, dim3((unsigned)f.chunks), block, 0, s, a, f.coff, A->d_col_idx);
                     HIPCHK_B(hipGetLastError());
-                    if (timed) {
-                        HIPCHK_B(hipStreamSynchronize(s));
-                        ms_hub += ms_since(t);
-                        t = host_clock::now();
-                    }
+                    HIPCHK_B(clk.lap(ms_hub, true));
                 }
                 levels++;
                 edges_forward += f.m;
                 hub_chunks += f.chunks;
                 HIPCHK_B(hipMemcpyAsync(&h, d_cnt, sizeof h, hipMemcpyDeviceToHost, s));
                 HIPCHK_B(hipStreamSynchronize(s));           // the level's one synchronisation
-                if (timed) ms_back += ms_since(t);
+                (void)clk.lap(ms_back);
                 if (h.err & kBcErrRange) return bail(fail_bad_column(who, n));
                 if (h.err & kBcErrOverflow) {
                     snprintf(g_err, sizeof g_err, "%s: a shortest-path count of 2^63 or more from source %d (sources[%d]) at level %d",
@@ -544,40 +530,24 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
 
             // ---- backward: no read-backs, the host knows every offset
             BcBwd b = {n, depth, src, A->d_row_ptr, level, sigma, delta, c, bc};
-            t = host_clock::now();
+            clk.start();
             hipLaunchKernelGGL(k_bc_leaf, bc_grid(L[depth].size), block, 0, s, b, L[depth].size, L[depth].off, order);
             for (int d = depth - 1; d >= 0; d--) {
                 const BcLevelRec &f = L[d];
                 b.d = d;
                 launch_backward(forced_w ? forced_w : bc_lanes(f.m, f.size), b, f.size, f.off, order, A->d_col_idx, s);
                 if (f.chunks) {
-                    host_clock::time_point t_hub = host_clock::now();
-                    if (timed) {
-                        HIPCHK_B(hipStreamSynchronize(s));
-                        t_hub = host_clock::now();
-                    }
+                    HIPCHK_B(clk.lap(ms_bwd, true));            // (timed: the hub launches are a lap of their own)
                     hipLaunchKernelGGL(k_bc_backward_chunk, dim3((unsigned)f.chunks), block, 0, s, b, f.coff, chunk, A->d_col_idx);
                     hipLaunchKernelGGL(k_bc_hub_finish, bc_grid(f.chunks), block, 0, s, b, f.chunks, f.coff, chunk);
                     hub_chunks += f.chunks;
-                    if (timed) {
-                        HIPCHK_B(hipStreamSynchronize(s));
-                        const double ms = ms_since(t_hub);
-                        ms_hub += ms;
-                        ms_bwd -= ms;
-                    }
+                    HIPCHK_B(clk.lap(ms_hub, true));
                 }
             }
             hipLaunchKernelGGL(k_bc_reset, bc_grid(tail), block, 0, s, tail, order, level, sigma, delta, d_cnt);
             HIPCHK_B(hipGetLastError());
-            if (timed) {
-                HIPCHK_B(hipStreamSynchronize(s));
-                ms_bwd += ms_since(t);
-                const double ms = ms_since(t_src);
-                if (ms > ms_src_max) {
-                    ms_src_max = ms;
-                    src_max_at = i;
-                }
-            }
+            HIPCHK_B(clk.lap(ms_bwd, true));
+            clk.longest(ms_since(t_src), i);
             reached += tail;
             depth_max = std::max(depth_max, depth);
         }
@@ -586,20 +556,20 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
     }
 
     // the read-out: the sums and the largest path count, behind the call's last synchronisation
-    t = host_clock::now();
+    clk.start();
     u64 *fixed = bc_fixed_host ? reinterpret_cast<u64 *>(bc_fixed_host) : h_fixed;
     if (fixed) HIPCHK_B(hipMemcpyAsync(fixed, bc, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost, s));
     HIPCHK_B(hipMemcpyAsync(&h, d_cnt, sizeof h, hipMemcpyDeviceToHost, s));
     HIPCHK_B(hipStreamSynchronize(s));
     if (bc_host)
         for (int v = 0; v < n; v++) bc_host[v] = std::ldexp((double)fixed[v], -32);
-    if (timed) {
-        ms_out = ms_since(t);
+    if (clk.on) {
+        (void)clk.lap(ms_out);
         fprintf(stderr, "[bspgemm] %s: n %d nnz %lld sources %d reached %lld depth %d levels %d hub chunks %lld (%d lanes) | total %.3f ms = "
                         "canonical check %.3f + forward launches %.3f + read-backs %.3f + backward launches %.3f + hub launches %.3f + "
                         "read-out %.3f + rest | slowest source %.3f ms (sources[%d])\n",
-                who, n, (long long)A->nnz, nsources, reached, depth_max, levels, hub_chunks, forced_w, ms_since(t_call), ms_check, ms_fwd,
-                ms_back, ms_bwd, ms_hub, ms_out, ms_src_max, src_max_at);
+                who, n, (long long)A->nnz, nsources, reached, depth_max, levels, hub_chunks, forced_w, clk.total(), ms_check, ms_fwd,
+                ms_back, ms_bwd, ms_hub, ms_out, clk.max_ms, clk.max_tag[0]);
     }
     bspgemm_matrix_free(mineA);
     free(h_fixed);

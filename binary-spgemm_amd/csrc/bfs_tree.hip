@@ -263,10 +263,8 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
     if (bspgemm_status st = check_operand(ctx, A, kBtWho, NEED_ENTRIES_CONSISTENT)) return st;
     // BSPGEMM_BFS_TREE_TIMING: host clocks around the stages; a launch is then synchronised before its read-back is issued,
     // so that the two are told apart
-    const bool timed = ctx->bfs_tree_timing;
-    double ms_tr = 0, ms_push = 0, ms_pull = 0, ms_back = 0, ms_out = 0, ms_max = 0;
-    int max_level = 0, max_size = 0;
-    const host_clock::time_point t_call = host_clock::now();
+    StageClock clk(ctx->bfs_tree_timing, ctx->stream);
+    double ms_tr = 0, ms_push = 0, ms_pull = 0, ms_back = 0, ms_out = 0;
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
     const long long alpha = ctx->bfs_alpha, beta = ctx->bfs_beta;
@@ -276,26 +274,21 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
     // The workspace, grown ONCE, before anything is launched (growing it synchronises and moves it): the transpose that
     // the call may run works in the leading part, so the state of the search starts behind it; then the counters, level,
     // parent, the two lists and the flag scratch of the read-out.
-    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
-    const size_t cnt_ints = sizeof(BtCounters) / sizeof(int);
-    const size_t o_cnt = (own_at ? transpose_workspace_ints(A->nnz, n) + 3 : 0) & ~(size_t)3;
-    const size_t o_level = o_cnt + cnt_ints, o_parent = o_level + n4, o_list = o_parent + n4, o_flags = o_list + 2 * n4;
-    const size_t total = flag_scratch_carve(nullptr, o_flags, n, false, nullptr);
-    if (!total) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_bfs_tree: too many vertices for the word scan");
-    if (bspgemm_status st = ensure_tmp(ctx, total)) return st;
-    if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)std::max(A->nnz, AT ? AT->nnz : 0))) return st;
+    const size_t n4 = ws_pad4((size_t)n);
+    const size_t o_cnt = own_at ? transpose_workspace_ints(A->nnz, n) : 0;
     BtCounters *d_cnt = nullptr;
     int *level = nullptr, *parent = nullptr, *list[2] = {nullptr, nullptr};
     FlagScratch sc;
-    auto carve = [&]() {                                     // (again after anything that may have moved the workspace)
-        d_cnt = reinterpret_cast<BtCounters *>(ctx->tmp + o_cnt);
-        level = ctx->tmp + o_level;
-        parent = ctx->tmp + o_parent;
-        list[0] = ctx->tmp + o_list;
-        list[1] = list[0] + n4;
-        flag_scratch_carve(ctx->tmp, o_flags, n, false, &sc);
+    auto carve = [&](int *tmp) {                             // (again after anything that may have moved the workspace)
+        WsCursor c(tmp, o_cnt);
+        c.take(d_cnt, 1).take(level, n4).take(parent, n4).take(list[0], n4).take(list[1], n4);
+        return flag_scratch_carve(tmp, c.aligned(), n, false, tmp ? &sc : nullptr);
     };
-    carve();
+    const size_t total = carve(nullptr);
+    if (!total) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_bfs_tree: too many vertices for the word scan");
+    if (bspgemm_status st = ensure_tmp(ctx, total)) return st;
+    if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)std::max(A->nnz, AT ? AT->nnz : 0))) return st;
+    carve(ctx->tmp);
 
     bspgemm_matrix *mine = nullptr;                          // the transpose or the canonical AT that the call owns
     bspgemm_result *R = nullptr;
@@ -316,24 +309,21 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
     HIPCHK_B(start());
     launch_graph_canonical_checks(ctx, A, AT, &d_cnt->canon, s);
     BtCounters h = {};
-    host_clock::time_point t = host_clock::now();
+    clk.start();
     HIPCHK_B(round_fetch(&h, d_cnt, sizeof h, s));
-    if (timed) ms_back += ms_since(t);
+    (void)clk.lap(ms_back);
     if (h.canon & (kSetErrRange | (kSetErrRange << 2))) return bail(fail_bad_column_in(kBtWho, n, h.canon));
     int canonicalised = 0;
     if (AT && (h.canon & (AT == A ? kSetErrOrder : kSetErrOrder << 2))) {
         // transposed twice, in the leading part of the workspace, which may grow for it: the state is set up again
-        t = host_clock::now();
+        clk.start();
         if (bspgemm_status st = operand_canonical(ctx, AT, &mine)) return bail(st);
         if (bspgemm_status st = ensure_tmp(ctx, total)) return bail(st);
         AT = mine;
         canonicalised = 1;
-        carve();
+        carve(ctx->tmp);
         HIPCHK_B(start());
-        if (timed) {
-            HIPCHK_B(hipStreamSynchronize(s));
-            ms_tr += ms_since(t);
-        }
+        HIPCHK_B(clk.lap(ms_tr, true));
     }
 
     long long n_f = h.lvl[0].size, m_f = (long long)h.lvl[0].deg, prev_nf = 0;
@@ -350,14 +340,14 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
             else pulling = !(n_f * beta < n);
         }
         if (pulling && !AT) {
-            t = host_clock::now();
+            clk.start();
             if (bspgemm_status st = bspgemm_matrix_transpose(ctx, A, &mine)) return bail(st);   // (works in front of o_cnt)
             AT = mine;
             transposed = 1;
-            if (timed) ms_tr += ms_since(t);
+            (void)clk.lap(ms_tr);
         }
         BtLevel *out = &d_cnt->lvl[cur ^ 1], *reset = &d_cnt->lvl[cur];
-        t = host_clock::now();
+        clk.start();
         if (pulling) {
             hipLaunchKernelGGL(k_bfs_pull, vgrid, block, 0, s, n, d, AT->d_row_ptr, AT->d_col_idx, A->d_row_ptr, level, parent,
                                list[cur ^ 1], out, reset);
@@ -372,21 +362,12 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
             edges_pushed += m_f;
         }
         HIPCHK_B(hipGetLastError());
-        if (timed) {
-            HIPCHK_B(hipStreamSynchronize(s));
-            const double ms = ms_since(t);
-            (pulling ? ms_pull : ms_push) += ms;
-            if (ms > ms_max) {
-                ms_max = ms;
-                max_level = d;
-                max_size = (int)n_f;
-            }
-            t = host_clock::now();
-        }
+        HIPCHK_B(clk.lap(pulling ? ms_pull : ms_push, true));
+        clk.longest(clk.last, d, (int)n_f);
         BtLevel hl = {};
         HIPCHK_B(hipMemcpyAsync(&hl, out, sizeof hl, hipMemcpyDeviceToHost, s));
         HIPCHK_B(hipStreamSynchronize(s));                   // the launch's one synchronisation
-        if (timed) ms_back += ms_since(t);
+        (void)clk.lap(ms_back);
         if (hl.err) return bail(fail_bad_column(kBtWho, n));
         prev_nf = n_f;
         n_f = hl.size;
@@ -400,7 +381,7 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
 
     // the read-out: an ordinary counted result, released the way a product's is; its size is the sum of the frontier
     // sizes, which the host knows, so nothing is read back for it
-    t = host_clock::now();
+    clk.start();
     R = new (std::nothrow) bspgemm_result{ctx, n, reached, nullptr, nullptr, 0};
     if (!R) return bail(FAIL(BSPGEMM_ERR_ALLOC, "result"));
     HIPCHK_B(tree_buffer(ctx, reinterpret_cast<void **>(&R->d_row_ptr), result_bytes_rowptr(n)));
@@ -415,13 +396,13 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
                        R->d_row_ptr);
     HIPCHK_B(hipGetLastError());
     HIPCHK_B(hipStreamSynchronize(s));
-    if (timed) {
-        ms_out = ms_since(t);
+    if (clk.on) {
+        (void)clk.lap(ms_out);
         fprintf(stderr, "[bspgemm] %s: n %d nnz %lld source %d reached %lld depth %d | total %.3f ms = transpose %.3f + %d push "
                         "launches %.3f + %d pull launches %.3f + read-backs %.3f + read-out %.3f + rest | longest launch %.3f ms "
                         "(level %d, %d frontier vertices)\n",
-                kBtWho, n, (long long)A->nnz, source, reached, depth, ms_since(t_call), ms_tr, pushes, ms_push, pulls, ms_pull,
-                ms_back, ms_out, ms_max, max_level, max_size);
+                kBtWho, n, (long long)A->nnz, source, reached, depth, clk.total(), ms_tr, pushes, ms_push, pulls, ms_pull,
+                ms_back, ms_out, clk.max_ms, clk.max_tag[0], clk.max_tag[1]);
     }
     bspgemm_matrix_free(mine);
     if (info) {

@@ -107,9 +107,11 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
     hipStream_t s = ctx->stream;
     const int n = A->rows;
     const long long E = A->nnz;
+    CcFlags *d_flags = nullptr;
+    auto carve = [&](int *tmp) { return WsCursor(tmp).take(d_flags, 1).ints(); };
     if (E > 0) {                                            // (before anything is launched: growing them synchronises)
         if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return st;
-        if (bspgemm_status st = ensure_tmp(ctx, sizeof(CcFlags) / sizeof(int))) return st;
+        if (bspgemm_status st = ensure_tmp(ctx, carve(nullptr))) return st;
     }
     bspgemm_matrix *m = nullptr;                            // the assignment operand: its col_idx is parent[]
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
@@ -122,7 +124,7 @@ extern "C" bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, con
     h.roots = n;                                            // without entries every vertex is a component
     int r = 0;
     if (E > 0) {
-        CcFlags *d_flags = reinterpret_cast<CcFlags *>(ctx->tmp);
+        carve(ctx->tmp);
         launch_select_tile_rows(A->d_row_ptr, n, ctx->tile_row, s);
         const dim3 egrid(select_tiles(E)), eblock(kSelThreads);
         const bool vec = aligned16(A->d_col_idx);

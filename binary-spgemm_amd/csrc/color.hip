@@ -245,23 +245,24 @@ extern "C" bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bsp
     if (bspgemm_status st = check_operand(ctx, A, who, NEED_SQUARE)) return st;
     // BSPGEMM_COLOR_TIMING: host clocks around the stages; a launch is then synchronised before its read-back is issued, so
     // that the two are told apart
-    const bool timed = ctx->color_timing;
-    double ms_sym = 0, ms_count = 0, ms_launch = 0, ms_launch_max = 0, ms_back = 0;
-    int launch_max_size = 0;
-    const host_clock::time_point t_call = host_clock::now();
+    StageClock clk(ctx->color_timing, ctx->stream);
+    double ms_sym = 0, ms_count = 0, ms_launch = 0, ms_back = 0;
     if (bspgemm_status st = use_device(ctx)) return st;
     // The workspace grows ONCE per call: to what the symmetrize takes at most over its stages or, if that is more, to the
     // call's own state (the counters, key, cnt and the two lists), instead of stage by stage with a synchronisation each.
-    const size_t flag_ints = sizeof(ColFlags) / sizeof(int);
-    const size_t own_ints = flag_ints + 5 * (((size_t)A->rows + 3) & ~(size_t)3);
+    const size_t n4 = ws_pad4((size_t)A->rows);
+    ColFlags *d_flags = nullptr;
+    u64 *key = nullptr;
+    int *cnt = nullptr, *list[2] = {nullptr, nullptr};
+    auto carve = [&](int *tmp) {
+        return WsCursor(tmp).take(d_flags, 1).take(key, n4).take(cnt, n4).take(list[0], n4).take(list[1], n4).ints();
+    };
+    const size_t own_ints = carve(nullptr);
     if (bspgemm_status st = ensure_tmp(ctx, std::max(symmetrize_workspace_ints(A->nnz, A->rows), A->nnz > 0 ? own_ints : 0)))
         return st;
     bspgemm_matrix *S = nullptr;
     if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &S)) return st;
-    if (timed) {
-        hipStreamSynchronize(ctx->stream);
-        ms_sym = ms_since(t_call);
-    }
+    (void)clk.lap(ms_sym, true);
     hipStream_t s = ctx->stream;
     const int n = S->rows;
     const long long E = S->nnz;                             // <= INT_MAX: symmetrize refuses more
@@ -274,25 +275,15 @@ extern "C" bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bsp
         return st;
     };
     // the counters, key, cnt and the two lists: carved before anything is launched (own_ints: there already, see above)
-    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
     if (edges) {
         if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return bail(st);
         if (bspgemm_status st = ensure_tmp(ctx, own_ints)) return bail(st);
+        carve(ctx->tmp);
     }
     if (bspgemm_status st = assignment_operand(ctx, n, &m)) return bail(st);
     int *colour = m->d_col_idx;
-    ColFlags *d_flags = nullptr;
-    u64 *key = nullptr;
-    int *cnt = nullptr, *list[2] = {nullptr, nullptr};
-    if (edges) {
-        d_flags = reinterpret_cast<ColFlags *>(ctx->tmp);
-        key = reinterpret_cast<u64 *>(ctx->tmp + flag_ints);   // (16 bytes into the allocation: aligned for 64-bit words)
-        cnt = ctx->tmp + flag_ints + 2 * n4;
-        list[0] = cnt + n4;
-        list[1] = cnt + 2 * n4;
-    }
     const dim3 vgrid = vertex_grid(n, kColThreads), block(kColThreads);
-    host_clock::time_point t = host_clock::now();
+    clk.start();
     // without edges every vertex is isolated: colour 0, nothing to release
     hipLaunchKernelGGL(k_color_init, vgrid, block, 0, s, n, (int)order, (u32)seed, edges ? S->d_row_ptr : nullptr, key, cnt, colour,
                        m->d_row_ptr, edges ? -1 : 0);
@@ -305,15 +296,11 @@ extern "C" bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bsp
                            aligned16(S->d_col_idx), ctx->tile_row, key, cnt);
         hipLaunchKernelGGL(k_color_seed, vgrid, block, 0, s, n, cnt, list[0], d_flags);
         HIPCHK_B(hipGetLastError());
-        if (timed) {
-            HIPCHK_B(hipStreamSynchronize(s));
-            ms_count = ms_since(t);
-            t = host_clock::now();
-        }
+        HIPCHK_B(clk.lap(ms_count, true));
         int fsize = 0, cur = 0;
         HIPCHK_B(hipMemcpyAsync(&fsize, &d_flags->size[0], sizeof fsize, hipMemcpyDeviceToHost, s));
         HIPCHK_B(hipStreamSynchronize(s));
-        if (timed) ms_back += ms_since(t);
+        HIPCHK_B(clk.lap(ms_back));
         if (fsize <= 0 || fsize > n) return bail(fail_stuck(who));   // the first vertex of the order precedes everybody
         long long coloured = 0;
         while (fsize > 0) {
@@ -321,23 +308,15 @@ extern "C" bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bsp
             launches++;
             coloured += fsize;
             const dim3 rgrid((unsigned)(((long long)fsize + kColWaves - 1) / kColWaves));
-            t = host_clock::now();
+            clk.start();
             hipLaunchKernelGGL(k_color_round, rgrid, block, 0, s, n, fsize, list[cur], S->d_row_ptr, S->d_col_idx, key, cnt, colour,
                                list[cur ^ 1], &d_flags->size[cur ^ 1], &d_flags->size[cur], &d_flags->top);
             HIPCHK_B(hipGetLastError());
-            if (timed) {
-                HIPCHK_B(hipStreamSynchronize(s));
-                const double ms = ms_since(t);
-                ms_launch += ms;
-                if (ms > ms_launch_max) {
-                    ms_launch_max = ms;
-                    launch_max_size = fsize;
-                }
-                t = host_clock::now();
-            }
+            HIPCHK_B(clk.lap(ms_launch, true));
+            clk.longest(clk.last, fsize);
             HIPCHK_B(hipMemcpyAsync(&fsize, &d_flags->size[cur ^ 1], sizeof fsize, hipMemcpyDeviceToHost, s));
             HIPCHK_B(hipStreamSynchronize(s));              // the launch's one synchronisation
-            if (timed) ms_back += ms_since(t);
+            HIPCHK_B(clk.lap(ms_back));
             if (fsize < 0 || fsize > n) return bail(fail_stuck(who));
             cur ^= 1;
         }
@@ -347,11 +326,11 @@ extern "C" bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bsp
     if (bspgemm_status st = operand_finish(m, n)) return bail(st);   // one colour per vertex
     HIPCHK_B(hipStreamSynchronize(s));
     if (top < 0 || (n > 0 && top >= n)) return bail(fail_stuck(who));
-    if (timed)
+    if (clk.on)
         fprintf(stderr, "[bspgemm] %s: n %d nnz(S) %lld order %d colors %d | total %.3f ms = symmetrize %.3f + count %.3f + %d "
                         "launches %.3f + read-backs %.3f + rest | longest launch %.3f ms (%d frontier vertices)\n",
-                who, n, E, (int)order, n ? top + 1 : 0, ms_since(t_call), ms_sym, ms_count, launches, ms_launch, ms_back,
-                ms_launch_max, launch_max_size);
+                who, n, E, (int)order, n ? top + 1 : 0, clk.total(), ms_sym, ms_count, launches, ms_launch, ms_back,
+                clk.max_ms, clk.max_tag[0]);
     bspgemm_matrix_free(S);
     if (ncolors) *ncolors = n ? top + 1 : 0;
     if (rounds) *rounds = launches;

@@ -207,18 +207,21 @@ static bspgemm_status dot_run(bspgemm_context *ctx, const bspgemm_matrix *A, con
     const int rows = A->rows;
     const int T = ctx->dot_light;
     // the workspace: the counters, vals (whole tiles), the heavy list {p, row} and the flag scratch of the filter
-    const size_t W = select_words(E);
-    const size_t o_vals = 4, o_list = o_vals + 64 * W, o_flags = o_list + ((2 * (size_t)E + 3) & ~(size_t)3);
-    const size_t total = flag_scratch_carve(nullptr, o_flags, E, false, nullptr);
+    DotCounters *d_cnt = nullptr;
+    int *vals = nullptr;
+    int2 *list = nullptr;
+    FlagScratch sc;
+    auto carve = [&](int *tmp) {
+        WsCursor c(tmp);
+        c.take(d_cnt, 1).take(vals, 64 * select_words(E)).take(list, (size_t)E);
+        return flag_scratch_carve(tmp, c.aligned(), E, false, tmp ? &sc : nullptr);
+    };
+    const size_t total = carve(nullptr);
     if (!total) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_multiply_masked_dot: too many mask entries for the word scan");
     if (bspgemm_status st = ensure_tmp(ctx, total)) return st;
     const long long Emax = std::max(E, std::max(A->nnz, B->nnz));
     if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)Emax)) return st;
-    DotCounters *d_cnt = reinterpret_cast<DotCounters *>(ctx->tmp);
-    int *vals = ctx->tmp + o_vals;
-    int2 *list = reinterpret_cast<int2 *>(ctx->tmp + o_list);
-    FlagScratch sc;
-    flag_scratch_carve(ctx->tmp, o_flags, E, false, &sc);
+    carve(ctx->tmp);
 
     // every distinct handle is checked once, under the bits of the first role it plays; the kernels follow each other on
     // the stream, so they share tile_row, and F's comes last: k_dot_count walks F

@@ -62,7 +62,6 @@ struct ExCounters {
     int walked;                         // the rows that are read (under KEEP_SHAPE the distinct rows of the list)
     int pad[2];
 };
-static_assert(sizeof(ExCounters) % 16 == 0, "the arrays behind the counters stay aligned");
 
 struct ExMaps {
     int rowsA, colsA;
@@ -374,9 +373,7 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
 {
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
-    const bool timed = ctx->extract_timing;
-    const host_clock::time_point t_call = host_clock::now();
-    host_clock::time_point t = t_call;
+    StageClock clk(ctx->extract_timing, s);
     double ms_maps = 0, ms_back = 0, ms_count = 0, ms_hub = 0, ms_scan = 0, ms_emit = 0, ms_sort = 0;
     const bool keep = (flags & BSPGEMM_EXTRACT_KEEP_SHAPE) != 0;
     const int rowsA = A->rows, colsA = A->cols;
@@ -386,24 +383,21 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
     const int forced_w = ctx->extract_lanes;
 
     // the workspace, every array on a 16-byte boundary; it grows ONCE, before anything is launched
-    size_t at = 0;
-    auto take = [&](size_t ints) { const size_t o = at; at += (ints + 3) & ~(size_t)3; return o; };
-    const size_t o_cnt = take(sizeof(ExCounters) / sizeof(int));
-    const size_t o_cmap = take(LJ.all || keep ? 0 : (size_t)colsA), o_cbits = take(LJ.all ? 0 : ((size_t)colsA + 31) / 32), o_rflag = take(keep && !LI.all ? (size_t)rowsA : 0);
-    const size_t o_li = take(LI.host ? (size_t)LI.n : 0), o_lj = take(LJ.host ? (size_t)LJ.n : 0);
-    const size_t o_rc = take((size_t)R), o_pre = take(2 * ((size_t)R + 1)), o_part = take(2 * ((size_t)R / 2048 + 4));
-    const size_t o_big = take((size_t)R);
+    ExCounters *d_cnt = nullptr;
+    int *cmap = nullptr, *rflag = nullptr, *li = nullptr, *lj = nullptr, *cnt = nullptr, *big = nullptr;
+    unsigned *cbits = nullptr;
+    long long *pre = nullptr, *part = nullptr;
+    auto carve = [&](int *tmp) {
+        return WsCursor(tmp).take(d_cnt, 1).take_if(!(LJ.all || keep), cmap, (size_t)colsA).take_if(!LJ.all, cbits, ((size_t)colsA + 31) / 32)
+            .take_if(keep && !LI.all, rflag, (size_t)rowsA).take_if(LI.host, li, (size_t)LI.n).take_if(LJ.host, lj, (size_t)LJ.n)
+            .take(cnt, (size_t)R).take(pre, (size_t)R + 1).take(part, (size_t)R / 2048 + 4).take(big, ws_pad4((size_t)R)).ints();
+    };
     // (to what the canonicalisation of A takes, two transposes, if that is more: an untidy A then grows nothing again)
-    const size_t ws_ints = std::max(at, canonical ? (size_t)0 : std::max(transpose_workspace_ints(E, colsA), transpose_workspace_ints(E, rowsA)));
+    const size_t ws_ints = std::max(carve(nullptr), canonical ? (size_t)0 : std::max(transpose_workspace_ints(E, colsA), transpose_workspace_ints(E, rowsA)));
     if (bspgemm_status st = ensure_tmp(ctx, ws_ints)) return st;
     if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return st;
-    int *ws = ctx->tmp;
-    ExCounters *d_cnt = reinterpret_cast<ExCounters *>(ws + o_cnt);
-    int *cmap = LJ.all || keep ? nullptr : ws + o_cmap, *rflag = keep && !LI.all ? ws + o_rflag : nullptr;
-    unsigned *cbits = LJ.all ? nullptr : reinterpret_cast<unsigned *>(ws + o_cbits);
-    int *cnt = ws + o_rc, *big = ws + o_big;
-    long long *pre = reinterpret_cast<long long *>(ws + o_pre), *part = reinterpret_cast<long long *>(ws + o_part);
-    const int *dI = LI.host ? ws + o_li : LI.dev, *dJ = LJ.host ? ws + o_lj : LJ.dev;
+    carve(ctx->tmp);
+    const int *dI = LI.host ? li : LI.dev, *dJ = LJ.host ? lj : LJ.dev;
 
     bspgemm_matrix *m = nullptr;
     auto bail = [&](bspgemm_status st) {
@@ -412,13 +406,7 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
         if (info) memset(info, 0, sizeof *info);
         return st;
     };
-    auto stage = [&](double &acc) -> hipError_t {                             // BSPGEMM_EXTRACT_TIMING: a stage ends
-        if (!timed) return hipSuccess;
-        const hipError_t e = hipStreamSynchronize(s);
-        acc += ms_since(t);
-        t = host_clock::now();
-        return e;
-    };
+    auto stage = [&](double &acc) { return clk.lap(acc, true); };             // BSPGEMM_EXTRACT_TIMING: a stage ends
     if (bspgemm_status st = operand_new(ctx, R, out_cols, &m)) return bail(st);
 
     // ---- the maps, the lists' checks, `scanned` and the chunk count; with them the canonical check of A
@@ -426,8 +414,8 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
     if (cmap && colsA > 0) HIPCHK_B(hipMemsetAsync(cmap, 0xFF, (size_t)colsA * sizeof(int), s));
     if (cbits && colsA > 0) HIPCHK_B(hipMemsetAsync(cbits, 0, (((size_t)colsA + 31) / 32) * sizeof(unsigned), s));
     if (rflag && rowsA > 0) HIPCHK_B(hipMemsetAsync(rflag, 0, (size_t)rowsA * sizeof(int), s));
-    if (LI.host && LI.n > 0) HIPCHK_B(hipMemcpyAsync(ws + o_li, LI.host, (size_t)LI.n * sizeof(int), hipMemcpyHostToDevice, s));
-    if (LJ.host && LJ.n > 0) HIPCHK_B(hipMemcpyAsync(ws + o_lj, LJ.host, (size_t)LJ.n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (LI.host && LI.n > 0) HIPCHK_B(hipMemcpyAsync(li, LI.host, (size_t)LI.n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (LJ.host && LJ.n > 0) HIPCHK_B(hipMemcpyAsync(lj, LJ.host, (size_t)LJ.n * sizeof(int), hipMemcpyHostToDevice, s));
     if (std::max(nwalk, nj) > 0) {
         const ExMaps a = {rowsA, colsA, A->d_row_ptr, dI, dJ, LI.all ? 0 : LI.n, nj, !LI.all, !LJ.all, keep, cmap, rflag, cbits, d_cnt};
         hipLaunchKernelGGL(k_ex_maps, ex_grid(std::max(nwalk, nj)), dim3(kExThreads), 0, s, a);
@@ -435,10 +423,7 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
     if (!canonical) launch_canonical_check(A->d_row_ptr, A->d_col_idx, rowsA, colsA, E, 0, ctx->tile_row, &d_cnt->canon, s);
     ExCounters h = {};
     HIPCHK_B(round_fetch(&h, d_cnt, sizeof h, s));                            // read-back one
-    if (timed) {
-        ms_maps = ms_since(t);
-        t = host_clock::now();
-    }
+    (void)clk.lap(ms_maps);
     if (h.canon & kSetErrRange) {
         snprintf(g_err, sizeof g_err, "%s: a column index outside [0, %d) in operand A", who, colsA);
         return bail(BSPGEMM_ERR_INVALID);
@@ -513,10 +498,7 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
         HIPCHK_B(stage(ms_scan));
         HIPCHK_B(hipMemcpyAsync(&kept, pre + R, sizeof kept, hipMemcpyDeviceToHost, s));
         HIPCHK_B(round_fetch(&h, d_cnt, sizeof h, s));                        // read-back two
-        if (timed) {
-            ms_back = ms_since(t);
-            t = host_clock::now();
-        }
+        (void)clk.lap(ms_back);
         if (kept < 0 || kept > scanned || h.big < 0 || h.big > R || h.cursor != chunks)
             return bail(FAIL(BSPGEMM_ERR_HIP, "extract: inconsistent counts"));
         if (kept > INT_MAX) {
@@ -558,11 +540,11 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
         m = sorted;
     }
     HIPCHK_B(stage(ms_sort));
-    if (timed)
+    if (clk.on)
         fprintf(stderr, "[bspgemm] %s: A %d x %d nnz %lld -> %d x %d kept %lld scanned %lld hub chunks %d (%d lanes) monotone %d sorted by %d "
                         "| total %.3f ms = maps and checks %.3f + count %.3f + hub launches %.3f + scan %.3f + read-back two %.3f + "
                         "emit %.3f + sort %.3f + rest\n",
-                who, rowsA, colsA, E, R, out_cols, kept, scanned, chunks, W, monotone ? 1 : 0, sorted_by, ms_since(t_call), ms_maps,
+                who, rowsA, colsA, E, R, out_cols, kept, scanned, chunks, W, monotone ? 1 : 0, sorted_by, clk.total(), ms_maps,
                 ms_count, ms_hub, ms_scan, ms_back, ms_emit, ms_sort);
     if (info) {
         info->kept = kept;

@@ -4,11 +4,13 @@
 // stages -- check and bound, operands, multiply, destination, download, hand-over -- over the early destination that
 // early_dest.hpp owns) and the communicator layer (comm.hip) use, the drop-ins' host steps that SpGEMM_hip_multi repeats, the
 // flag scratch of select.hip and setop.hip, the host helpers of the round-based graph algorithms (cc.hip to betweenness.hip:
-// the operand checks, the canonical checks of A and an optional AT, the read-back of a round, the lanes-per-vertex dispatch).
+// the operand checks, the canonical checks of A and an optional AT, the read-back of a round, the lanes-per-vertex dispatch,
+// the stage clock of their timing modes), and through ws_layout.hpp the cursor that lays their arrays out in ctx->tmp.
 // Not installed; nothing here is part of the C ABI.
 #pragma once
 #include "../../include/bspgemm.h"
 #include "kernels.hpp"
+#include "ws_layout.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -347,6 +349,36 @@ static inline double ms_since(host_clock::time_point t)
 {
     return std::chrono::duration<double, std::milli>(host_clock::now() - t).count();
 }
+// The stage clock of a timing mode.  A lap runs from start() or the last lap() to this lap(), which adds it to `acc`;
+// sync: the timed mode first waits for the stream, so that the lap holds what was launched in it.  Off, start() and lap()
+// do nothing: no synchronisation, the call's sequence of HIP calls is the untimed one.  The fprintf stays with the mode.
+struct StageClock {
+    bool on;
+    hipStream_t s;
+    host_clock::time_point t0, t;       // the call's start, the current lap's start
+    double last = 0, max_ms = 0;        // the lap closed last; the longest that longest() was shown, and its tags
+    int max_tag[2] = {0, 0};
+    StageClock(bool timed, hipStream_t stream) : on(timed), s(stream), t0(host_clock::now()), t(t0) {}
+    void start() { if (on) t = host_clock::now(); }
+    hipError_t lap(double &acc, bool sync = false)
+    {
+        if (!on) return hipSuccess;
+        const hipError_t e = sync ? hipStreamSynchronize(s) : hipSuccess;
+        const host_clock::time_point now = host_clock::now();
+        last = std::chrono::duration<double, std::milli>(now - t).count();
+        acc += last;
+        t = now;
+        return e;
+    }
+    void longest(double ms, int tag0, int tag1 = 0)
+    {
+        if (!on || ms <= max_ms) return;
+        max_ms = ms;
+        max_tag[0] = tag0;
+        max_tag[1] = tag1;
+    }
+    double total() const { return ms_since(t0); }
+};
 
 // ------------------------------------------------------------------ drop-in host steps (dropin.hip) ---
 // one line on stderr for a failed drop-in ("SpGEMM_hip: <status>: <last error>"), returns the status as int

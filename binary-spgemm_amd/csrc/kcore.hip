@@ -132,16 +132,11 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
     if (bspgemm_status st = check_operand(ctx, A, who, NEED_SQUARE)) return st;
     // BSPGEMM_KCORE_TIMING: host clocks around the stages; a launch is then synchronised before its read-back is issued, so
     // that the two are told apart
-    const bool timed = ctx->kcore_timing;
-    double ms_sym = 0, ms_scan = 0, ms_peel = 0, ms_peel_max = 0, ms_back = 0;
-    int peel_max_size = 0, peel_max_k = 0;
-    const host_clock::time_point t_call = host_clock::now();
+    StageClock clk(ctx->kcore_timing, ctx->stream);
+    double ms_sym = 0, ms_scan = 0, ms_peel = 0, ms_back = 0;
     bspgemm_matrix *S = nullptr;
     if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &S)) return st;
-    if (timed) {
-        hipStreamSynchronize(ctx->stream);
-        ms_sym = ms_since(t_call);
-    }
+    (void)clk.lap(ms_sym, true);
     if (bspgemm_status st = use_device(ctx)) {
         bspgemm_matrix_free(S);
         return st;
@@ -157,10 +152,15 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
         return st;
     };
     auto stuck = [&]() { return bail(fail_stuck(who)); };
-    // deg, the two lists and the counters (before anything is launched: growing the workspace synchronises)
-    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
-    if (edges)
-        if (bspgemm_status st = ensure_tmp(ctx, 3 * n4 + sizeof(KcFlags) / sizeof(int))) return bail(st);
+    // the counters, deg and the two lists (before anything is launched: growing the workspace synchronises)
+    const size_t n4 = ws_pad4((size_t)n);
+    KcFlags *d_flags = nullptr;
+    int *deg = nullptr, *list[2] = {nullptr, nullptr};
+    auto carve = [&](int *tmp) { return WsCursor(tmp).take(d_flags, 1).take(deg, n4).take(list[0], n4).take(list[1], n4).ints(); };
+    if (edges) {
+        if (bspgemm_status st = ensure_tmp(ctx, carve(nullptr))) return bail(st);
+        carve(ctx->tmp);
+    }
     // the result, allocated as a product's is: its values are the core array while the levels run
     R = new (std::nothrow) bspgemm_result{ctx, n, n, nullptr, nullptr, n};
     if (!R) return bail(FAIL(BSPGEMM_ERR_ALLOC, "result"));
@@ -168,14 +168,6 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
     HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_col_idx), result_bytes_colidx(n)));
     HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_values), result_bytes_colidx(n)));
     int *core = R->d_values;
-    KcFlags *d_flags = nullptr;
-    int *deg = nullptr, *list[2] = {nullptr, nullptr};
-    if (edges) {
-        d_flags = reinterpret_cast<KcFlags *>(ctx->tmp);
-        deg = ctx->tmp + sizeof(KcFlags) / sizeof(int);
-        list[0] = deg + n4;
-        list[1] = deg + 2 * n4;
-    }
     const dim3 vgrid = vertex_grid(n, kKcThreads), block(kKcThreads);
     // without edges every vertex is isolated: core 0, nothing to peel
     hipLaunchKernelGGL(k_kcore_init, vgrid, block, 0, s, n, edges ? S->d_row_ptr : nullptr, deg, core, R->d_row_ptr,
@@ -190,17 +182,13 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
             if (++scans > scan_cap) return stuck();
             KcFlags h = {};
             HIPCHK_B(round_reset(d_flags, sizeof(KcFlags), s));
-            host_clock::time_point t = host_clock::now();
+            clk.start();
             hipLaunchKernelGGL(k_kcore_scan, vgrid, block, 0, s, n, k, deg, core, list[0], d_flags);
             HIPCHK_B(hipGetLastError());
-            if (timed) {
-                HIPCHK_B(hipStreamSynchronize(s));
-                ms_scan += ms_since(t);
-                t = host_clock::now();
-            }
+            HIPCHK_B(clk.lap(ms_scan, true));
             HIPCHK_B(hipMemcpyAsync(&h, d_flags, sizeof h, hipMemcpyDeviceToHost, s));
             HIPCHK_B(hipStreamSynchronize(s));
-            if (timed) ms_back += ms_since(t);
+            HIPCHK_B(clk.lap(ms_back));
             int fsize = h.size[0], cur = 0;
             if (fsize == 0) {                               // nobody at this level: on to the smallest degree that is left
                 const int least = INT_MAX - h.left;
@@ -214,24 +202,15 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
                 peels++;
                 assigned += fsize;
                 const dim3 pgrid((unsigned)(((long long)fsize + kKcWaves - 1) / kKcWaves));
-                t = host_clock::now();
+                clk.start();
                 hipLaunchKernelGGL(k_kcore_peel, pgrid, block, 0, s, n, k, fsize, list[cur], S->d_row_ptr, S->d_col_idx, deg, core,
                                    list[cur ^ 1], &d_flags->size[cur ^ 1], &d_flags->size[cur]);
                 HIPCHK_B(hipGetLastError());
-                if (timed) {
-                    HIPCHK_B(hipStreamSynchronize(s));
-                    const double ms = ms_since(t);
-                    ms_peel += ms;
-                    if (ms > ms_peel_max) {
-                        ms_peel_max = ms;
-                        peel_max_size = fsize;
-                        peel_max_k = k;
-                    }
-                    t = host_clock::now();
-                }
+                HIPCHK_B(clk.lap(ms_peel, true));
+                clk.longest(clk.last, k, fsize);
                 HIPCHK_B(hipMemcpyAsync(&fsize, &d_flags->size[cur ^ 1], sizeof fsize, hipMemcpyDeviceToHost, s));
                 HIPCHK_B(hipStreamSynchronize(s));          // the launch's one synchronisation
-                if (timed) ms_back += ms_since(t);
+                HIPCHK_B(clk.lap(ms_back));
                 if (fsize < 0 || fsize > n) return stuck();
                 cur ^= 1;
             }
@@ -239,11 +218,11 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
         }
     }
     HIPCHK_B(hipStreamSynchronize(s));
-    if (timed)
+    if (clk.on)
         fprintf(stderr, "[bspgemm] %s: n %d nnz(S) %lld degeneracy %d | total %.3f ms = symmetrize %.3f + %lld scans %.3f + %d peel "
                         "launches %.3f + read-backs %.3f + rest | longest peel launch %.3f ms (level %d, %d frontier vertices)\n",
-                who, n, (long long)S->nnz, top, ms_since(t_call), ms_sym, scans, ms_scan, peels, ms_peel, ms_back, ms_peel_max,
-                peel_max_k, peel_max_size);
+                who, n, (long long)S->nnz, top, clk.total(), ms_sym, scans, ms_scan, peels, ms_peel, ms_back, clk.max_ms,
+                clk.max_tag[0], clk.max_tag[1]);
     if (degeneracy) *degeneracy = top;
     if (rounds) *rounds = peels;
     *cores = R;

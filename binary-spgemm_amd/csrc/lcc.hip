@@ -64,7 +64,7 @@ struct LccCounters {
     int heavy;              // entries appended to the heavy list
     int pad;
 };
-constexpr size_t kLccCounterInts = 8;   // (a multiple of four: what follows stays 16-byte aligned)
+constexpr size_t kLccCounterInts = 8;   // the block that is zeroed: the counters in whole 16-byte units
 static_assert(sizeof(LccCounters) <= kLccCounterInts * sizeof(int), "the counters fit their block");
 
 // The per-hit credit num[k] += w goes through a small cache in LDS, one per workgroup: slot k mod kLccSlots belongs to the
@@ -353,13 +353,6 @@ using namespace bsp;
 // ------------------------------------------------------------------ the host side --------
 static const char kLccWho[] = "bspgemm_local_clustering";
 
-// ints of the workspace behind the counters for E entries of T: the heavy list (an int2 per entry) and, DIRECTED, the
-// weight bytes, each in whole 16-byte units
-static inline size_t lcc_state_ints(long long E, bool directed)
-{
-    return ((2 * (size_t)E + 3) & ~(size_t)3) + (directed ? (((size_t)E + 15) / 16) * 4 : 0);
-}
-
 extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned flags,
                                                    bspgemm_result **counts, int *degree_host, double *lcc_host,
                                                    bspgemm_lcc_info *info)
@@ -371,10 +364,9 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
     if (bspgemm_status st = check_operand(ctx, A, kLccWho, NEED_SQUARE)) return st;
     const bool directed = (flags & BSPGEMM_LCC_DIRECTED) != 0;
     // BSPGEMM_LCC_TIMING: host clocks around the stages, each synchronised; 2: the stage split on the half that is NOT kept
-    const bool timed = ctx->lcc_timing != 0;
+    StageClock clk(ctx->lcc_timing != 0, ctx->stream);
     const bspgemm_select side = ctx->lcc_timing == 2 ? BSPGEMM_SELECT_TRIU : BSPGEMM_SELECT_TRIL;
     double ms_sym = 0, ms_weights = 0, ms_count = 0, ms_heavy = 0, ms_finish = 0;
-    const host_clock::time_point t_call = host_clock::now();
 
     // the operands: S, its oriented half T and (DIRECTED) R = A' and A'^T, A' = A without its diagonal.  DIRECTED spells
     // bspgemm_matrix_symmetrize out, so that A' and its transpose serve both the union and the intersection
@@ -398,8 +390,17 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
     // the symmetrize's stages and the intersection (setop.hip), the select of a half of S (at most 2 nnz(A) entries), and
     // the call's own state for at most nnz(A) entries of T (the counters, the heavy list {p, row} and the weight bytes)
     if (bspgemm_status st0 = use_device(ctx)) return st0;
+    // the call's own state for e entries of T: the counter block, the heavy list {p, row} and (DIRECTED) the weight bytes,
+    // the two arrays in whole 16-byte units
+    LccCounters *d_cnt = nullptr;
+    int2 *list = nullptr;
+    unsigned char *wgt = nullptr;
+    auto carve = [&](int *tmp, long long e) {
+        return WsCursor(tmp).take(d_cnt, 1).take(list, ws_pad4(2 * (size_t)e) / 2)
+            .take_if(directed, wgt, ((size_t)e + 15) & ~(size_t)15).ints();
+    };
     {
-        const size_t own = kLccCounterInts + lcc_state_ints(A->nnz, directed);
+        const size_t own = carve(nullptr, A->nnz);
         const size_t sel = A->nnz <= INT_MAX ? flag_scratch_carve(nullptr, 0, 2 * A->nnz, false, nullptr) : 0;
         if (bspgemm_status st0 = ensure_tmp(ctx, std::max(std::max(symmetrize_workspace_ints(A->nnz, A->rows), sel), own))) return st0;
     }
@@ -418,18 +419,13 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
     if (!st) st = bspgemm_matrix_select(ctx, S, side, &T);
     if (st) return bail(st);
     hipStream_t s = ctx->stream;
-    if (timed) {
-        hipStreamSynchronize(s);
-        ms_sym = ms_since(t_call);
-    }
+    (void)clk.lap(ms_sym, true);
     const int n = S->rows;
     const long long E = T->nnz;
 
     // the call's own state: the counters, the heavy list {p, row} and the weight bytes
-    const size_t o_list = kLccCounterInts, o_wgt = o_list + lcc_state_ints(E, false);
-    const size_t total = o_list + lcc_state_ints(E, directed);
     if (E > 0) {
-        if (bspgemm_status st2 = ensure_tmp(ctx, total)) return bail(st2);   // (there already, see above: E <= nnz(A))
+        if (bspgemm_status st2 = ensure_tmp(ctx, carve(nullptr, E))) return bail(st2);   // (there already, see above: E <= nnz(A))
         if (bspgemm_status st2 = ensure_tile_rows(ctx, (size_t)E)) return bail(st2);
     }
     if (degree_host || lcc_host) {
@@ -452,19 +448,11 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
 
     LccCounters h = {};
     if (E > 0) {                                             // without entries in T: all zeros, no intersection kernel
-        LccCounters *d_cnt = reinterpret_cast<LccCounters *>(ctx->tmp);
-        int2 *list = reinterpret_cast<int2 *>(ctx->tmp + o_list);
-        unsigned char *wgt = directed ? reinterpret_cast<unsigned char *>(ctx->tmp + o_wgt) : nullptr;
+        carve(ctx->tmp, E);
         const dim3 grid(select_tiles(E)), block(kSelThreads);
         const bool vec = aligned16(T->d_col_idx);
-        host_clock::time_point t = host_clock::now();
-        auto stage = [&](double &ms) {                       // (timed only: a synchronisation behind the stage)
-            if (!timed) return hipSuccess;
-            const hipError_t e = hipStreamSynchronize(s);
-            ms = ms_since(t);
-            t = host_clock::now();
-            return e;
-        };
+        clk.start();
+        auto stage = [&](double &ms) { return clk.lap(ms, true); };   // (timed only: a synchronisation behind the stage)
         HIPCHK_B(hipMemsetAsync(d_cnt, 0, kLccCounterInts * sizeof(int), s));
         launch_select_tile_rows(T->d_row_ptr, n, ctx->tile_row, s);
         if (directed) {
@@ -487,7 +475,7 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
         HIPCHK_B(stage(ms_heavy));
         HIPCHK_B(hipMemcpyAsync(&h, d_cnt, sizeof h, hipMemcpyDeviceToHost, s));
     }
-    const host_clock::time_point t_finish = host_clock::now();
+    clk.start();
     if (h_rp) HIPCHK_B(hipMemcpyAsync(h_rp, S->d_row_ptr, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
     if (h_num && n > 0) HIPCHK_B(hipMemcpyAsync(h_num, num, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK_B(hipStreamSynchronize(s));                                        // the call's one synchronisation
@@ -498,12 +486,12 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
         if (degree_host) degree_host[v] = d;
         if (lcc_host) lcc_host[v] = d < 2 ? 0.0 : (double)h_num[v] / ((double)d * (double)(d - 1));
     }
-    if (timed) {
-        ms_finish = ms_since(t_finish);
+    if (clk.on) {
+        (void)clk.lap(ms_finish);
         fprintf(stderr, "[bspgemm] %s: n %d nnz(S) %lld %s %s | total %.3f ms = symmetrize and select %.3f + weights %.3f + count %.3f "
                         "+ heavy %.3f (%d of %lld entries) + finish %.3f + rest | triangles %llu\n",
                 kLccWho, n, (long long)S->nnz, directed ? "directed" : "undirected", side == BSPGEMM_SELECT_TRIL ? "TRIL" : "TRIU",
-                ms_since(t_call), ms_sym, ms_weights, ms_count, ms_heavy, h.heavy, E, ms_finish, h.triangles);
+                clk.total(), ms_sym, ms_weights, ms_count, ms_heavy, h.heavy, E, ms_finish, h.triangles);
     }
     if (info) {
         info->triangles = (int64_t)h.triangles;

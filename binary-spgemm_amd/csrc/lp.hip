@@ -396,25 +396,25 @@ extern "C" bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const 
             }
     // BSPGEMM_LP_TIMING: host clocks around the stages; every class's launch is then synchronised, and so the iteration
     // before its read-back is issued, so that they are told apart
-    const bool timed = ctx->lp_timing;
-    double ms_sym = 0, ms_lists = 0, ms_launch = 0, ms_launch_max = 0, ms_back = 0, ms_class[kLpClasses] = {};
-    int launch_max_at = 0;
-    const host_clock::time_point t_call = host_clock::now();
+    StageClock clk(ctx->lp_timing, ctx->stream);
+    double ms_sym = 0, ms_lists = 0, ms_launch = 0, ms_back = 0, ms_class[kLpClasses] = {};
     if (bspgemm_status st = use_device(ctx)) return st;
     // The workspace grows ONCE here: to what the symmetrize takes at most over its stages or, if that is more, to the
     // call's own state (the counters, tab_of, the second label array, the four lists and the words of `changed`).  The hubs' tables live in the
     // values workspace, whose size is known only after the lists are: growing it leaves this one where it is.
-    const size_t flag_ints = sizeof(LpFlags) / sizeof(int);
-    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
+    const size_t n4 = ws_pad4((size_t)n);
     const size_t shard_ints = (size_t)kLpShards * kLpShardStride;
-    const size_t own_ints = n > 0 ? flag_ints + (3 + kLpClasses) * n4 + shard_ints : 0;
+    LpFlags *d_flags = nullptr;
+    long long *tab_of = nullptr;
+    int *label[2] = {nullptr, nullptr}, *list = nullptr, *d_changed = nullptr;
+    auto carve = [&](int *tmp) {
+        return WsCursor(tmp).take(d_flags, 1).take(tab_of, n4).take(label[1], n4).take(list, kLpClasses * n4).take(d_changed, shard_ints).ints();
+    };
+    const size_t own_ints = n > 0 ? carve(nullptr) : 0;
     if (bspgemm_status st = ensure_tmp(ctx, std::max(symmetrize_workspace_ints(A->nnz, A->rows), own_ints))) return st;
     bspgemm_matrix *S = nullptr;
     if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &S)) return st;
-    if (timed) {
-        hipStreamSynchronize(ctx->stream);
-        ms_sym = ms_since(t_call);
-    }
+    (void)clk.lap(ms_sym, true);
     hipStream_t s = ctx->stream;
     const long long E = S->nnz;                             // <= INT_MAX: symmetrize refuses more
     const bool edges = E > 0;
@@ -429,16 +429,8 @@ extern "C" bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const 
         if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return bail(st);
     if (bspgemm_status st = ensure_tmp(ctx, own_ints)) return bail(st);   // (there already, see above)
     if (bspgemm_status st = assignment_operand(ctx, n, &m)) return bail(st);
-    LpFlags *d_flags = nullptr;
-    long long *tab_of = nullptr;
-    int *label[2] = {m->d_col_idx, nullptr}, *list = nullptr, *d_changed = nullptr;
-    if (n > 0) {
-        d_flags = reinterpret_cast<LpFlags *>(ctx->tmp);
-        tab_of = reinterpret_cast<long long *>(ctx->tmp + flag_ints);   // (32 bytes into the allocation: aligned for 64-bit words)
-        label[1] = ctx->tmp + flag_ints + 2 * n4;
-        list = label[1] + n4;
-        d_changed = list + kLpClasses * n4;
-    }
+    label[0] = m->d_col_idx;
+    if (n > 0) carve(ctx->tmp);
     const dim3 vgrid = vertex_grid(n, kLpThreads), block(kLpThreads);
     LpFlags h = {};
     if (n > 0) HIPCHK_B(round_reset(d_flags, sizeof(LpFlags), s));
@@ -450,7 +442,7 @@ extern "C" bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const 
     int iterations = 0, converged = edges ? 0 : 1, changed = 0;
     size_t tab_ints = 0;
     if (edges) {
-        host_clock::time_point t = host_clock::now();
+        clk.start();
         hipLaunchKernelGGL(k_lp_classify, vgrid, block, 0, s, n, ctx->lp_min_class, S->d_row_ptr, list, n4, tab_of, d_flags);
         HIPCHK_B(round_fetch(&h, d_flags, sizeof h, s));
         long long listed = 0;
@@ -464,40 +456,30 @@ extern "C" bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const 
         if (bspgemm_status st = ensure_tmpv(ctx, tab_ints)) return bail(st);   // sized and carved before any iteration
         if (h.size[3]) launch_select_tile_rows(S->d_row_ptr, n, ctx->tile_row, s);
         HIPCHK_B(hipGetLastError());
-        if (timed) {
-            HIPCHK_B(hipStreamSynchronize(s));
-            ms_lists = ms_since(t);
-        }
+        HIPCHK_B(clk.lap(ms_lists, true));
         int h_changed[kLpShards * kLpShardStride];          // 8 KiB: the counter's words and the gaps between them
         while (iterations < max_iter) {
             const int *in = label[iterations & 1];
             int *out = label[(iterations & 1) ^ 1];
             iterations++;
-            t = host_clock::now();
-            HIPCHK_B(hipMemsetAsync(d_changed, 0, shard_ints * sizeof(int), s));
-            host_clock::time_point t_cls = t;
             // under BSPGEMM_LP_TIMING: a synchronisation behind every class, so that their times are told apart
-            auto lap = [&](int c) {
-                if (!timed) return hipSuccess;
-                if (hipError_t e = hipStreamSynchronize(s)) return e;
-                ms_class[c] += ms_since(t_cls);
-                t_cls = host_clock::now();
-                return hipSuccess;
-            };
+            StageClock cls(clk.on, s);
+            clk.start();
+            HIPCHK_B(hipMemsetAsync(d_changed, 0, shard_ints * sizeof(int), s));
             if (h.size[0]) {
                 hipLaunchKernelGGL(k_lp_lane, dim3((unsigned)(((long long)h.size[0] + kLpThreads - 1) / kLpThreads)), block, 0, s,
                                    h.size[0], list, S->d_row_ptr, S->d_col_idx, in, out, d_changed);
-                HIPCHK_B(lap(0));
+                HIPCHK_B(cls.lap(ms_class[0], true));
             }
             if (h.size[1]) {
                 hipLaunchKernelGGL(k_lp_wave, dim3((unsigned)(((long long)h.size[1] + kLpWaves - 1) / kLpWaves)), block, 0, s,
                                    h.size[1], list + n4, S->d_row_ptr, S->d_col_idx, in, out, d_changed);
-                HIPCHK_B(lap(1));
+                HIPCHK_B(cls.lap(ms_class[1], true));
             }
             if (h.size[2]) {
                 hipLaunchKernelGGL(k_lp_group, dim3((unsigned)h.size[2]), block, 0, s, h.size[2], list + 2 * n4, S->d_row_ptr,
                                    S->d_col_idx, in, out, d_changed);
-                HIPCHK_B(lap(2));
+                HIPCHK_B(cls.lap(ms_class[2], true));
             }
             if (h.size[3]) {
                 HIPCHK_B(hipMemsetAsync(ctx->tmpv, 0, tab_ints * sizeof(int), s));
@@ -505,21 +487,14 @@ extern "C" bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const 
                                    aligned16(S->d_col_idx), ctx->tile_row, tab_of, in, ctx->tmpv);
                 hipLaunchKernelGGL(k_lp_hub_mode, dim3((unsigned)h.size[3]), block, 0, s, list + 3 * n4, S->d_row_ptr, tab_of,
                                    ctx->tmpv, in, out, d_changed);
-                HIPCHK_B(lap(3));
+                HIPCHK_B(cls.lap(ms_class[3], true));
             }
             HIPCHK_B(hipGetLastError());
-            if (timed) {
-                const double ms = ms_since(t);
-                ms_launch += ms;
-                if (ms > ms_launch_max) {
-                    ms_launch_max = ms;
-                    launch_max_at = iterations;
-                }
-                t = host_clock::now();
-            }
+            (void)clk.lap(ms_launch);
+            clk.longest(clk.last, iterations);
             HIPCHK_B(hipMemcpyAsync(h_changed, d_changed, sizeof h_changed, hipMemcpyDeviceToHost, s));
             HIPCHK_B(hipStreamSynchronize(s));              // the iteration's one synchronisation
-            if (timed) ms_back += ms_since(t);
+            HIPCHK_B(clk.lap(ms_back));
             long long moved = 0;
             for (int q = 0; q < kLpShards; q++) moved += h_changed[q * kLpShardStride];
             if (moved < 0 || moved > n) return bail(fail_stuck(who));
@@ -542,13 +517,13 @@ extern "C" bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const 
     if (bspgemm_status st = operand_finish(m, n)) return bail(st);   // one label per vertex
     HIPCHK_B(hipStreamSynchronize(s));
     if (h.communities < (n > 0 ? 1 : 0) || h.communities > n) return bail(fail_stuck(who));
-    if (timed)
+    if (clk.on)
         fprintf(stderr, "[bspgemm] %s: n %d nnz(S) %lld classes %d/%d/%d/%d table slots %llu communities %d | total %.3f ms = "
                         "symmetrize %.3f + class lists %.3f + %d iterations %.3f (lane %.3f, wave %.3f, workgroup %.3f, hub %.3f) + "
                         "read-backs %.3f + rest | longest iteration %.3f ms (iteration %d)\n",
                 who, n, E, h.size[0], h.size[1], h.size[2], h.size[3], (unsigned long long)h.slots, h.communities,
-                ms_since(t_call), ms_sym, ms_lists, iterations, ms_launch, ms_class[0], ms_class[1], ms_class[2], ms_class[3], ms_back,
-                ms_launch_max, launch_max_at);
+                clk.total(), ms_sym, ms_lists, iterations, ms_launch, ms_class[0], ms_class[1], ms_class[2], ms_class[3], ms_back,
+                clk.max_ms, clk.max_tag[0]);
     bspgemm_matrix_free(S);
     if (info) {
         info->iterations = iterations;

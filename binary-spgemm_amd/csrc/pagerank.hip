@@ -67,7 +67,6 @@ struct PrCounters {
     int chunks;                         // chunk records handed out
     int size[kPrClasses];               // vertices of the class lists
 };
-static_assert(sizeof(PrCounters) % 16 == 0, "the 64-bit arrays behind the counters stay aligned");
 
 // what every launch of an iteration gets
 struct PrArgs {
@@ -367,10 +366,8 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
     const u64 B = Dc * (q >> 32) + ((Dc * (q & 0xffffffffull)) >> 32);
 
     // BSPGEMM_PR_TIMING: host clocks around the stages; every class's launch is then synchronised
-    const bool timed = ctx->pr_timing;
-    double ms_check = 0, ms_tr = 0, ms_lists = 0, ms_iter = 0, ms_iter_max = 0, ms_out = 0, ms_class[kPrClasses + 1] = {};
-    int iter_max_at = 0;
-    const host_clock::time_point t_call = host_clock::now();
+    StageClock clk(ctx->pr_timing, ctx->stream);
+    double ms_check = 0, ms_tr = 0, ms_lists = 0, ms_iter = 0, ms_out = 0, ms_class[kPrClasses + 1] = {};
     if (bspgemm_status st = use_device(ctx)) return st;
     hipStream_t s = ctx->stream;
     const bool own_at = pull && !AT;
@@ -378,13 +375,18 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
     // The workspace grows ONCE here: to what a transpose takes (the call may run up to two) or, if that is more, to the
     // call's own state, which is set up only after the last transpose has finished with the leading part.
     const long long nnz_max = std::max(A->nnz, AT ? AT->nnz : 0);
-    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
-    const size_t cnt_ints = sizeof(PrCounters) / sizeof(int);
+    const size_t n4 = ws_pad4((size_t)n);
     const size_t chunk_cap = pull ? (size_t)n + (size_t)(nnz_max / kPrHubChunk) + 1 : 0;
     if (chunk_cap > (size_t)INT_MAX) return FAIL(BSPGEMM_ERR_OVERFLOW, "bspgemm_pagerank: too many hub chunks");
-    const size_t o_r = cnt_ints, o_c = o_r + 2 * n4, o_acc = o_c + 4 * n4, o_list = o_acc + 2 * n4;
-    const size_t o_chunk = o_list + (pull ? kPrClasses * n4 : 0), own_ints = o_chunk + 2 * chunk_cap;
-    const size_t total = std::max(own_ints, transpose_workspace_ints(nnz_max, n));
+    PrCounters *d_cnt = nullptr;
+    u64 *r = nullptr, *c[2] = {nullptr, nullptr}, *acc = nullptr;
+    int *list = nullptr;
+    int2 *chunk = nullptr;
+    auto carve = [&](int *tmp) {
+        return WsCursor(tmp).take(d_cnt, 1).take(r, n4).take(c[0], n4).take(c[1], n4).take(acc, n4)
+            .take(list, pull ? kPrClasses * n4 : 0).take(chunk, chunk_cap).ints();
+    };
+    const size_t total = std::max(carve(nullptr), transpose_workspace_ints(nnz_max, n));
     if (bspgemm_status st = ensure_tmp(ctx, total)) return st;
     if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)nnz_max)) return st;
 
@@ -400,18 +402,17 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
     };
 
     // the canonical check of every distinct handle, and its read-back: the call's first synchronisation
-    host_clock::time_point t = host_clock::now();
-    PrCounters *d_cnt = reinterpret_cast<PrCounters *>(ctx->tmp);
+    clk.start();
+    carve(ctx->tmp);
     PrCounters h = {};
     HIPCHK_B(hipMemsetAsync(d_cnt, 0, sizeof(PrCounters), s));
     launch_graph_canonical_checks(ctx, A, AT, &d_cnt->canon, s);
     HIPCHK_B(round_fetch(&h, d_cnt, sizeof h, s));
-    if (timed) ms_check = ms_since(t);
+    (void)clk.lap(ms_check);
     if (h.canon & (kSetErrRange | (kSetErrRange << 2))) return bail(fail_bad_column_in(who, n, h.canon));
     const bool a_untidy = (h.canon & kSetErrOrder) != 0;
     const bool at_untidy = AT && (AT == A ? a_untidy : (h.canon & (kSetErrOrder << 2)) != 0);
     int canonicalised = (a_untidy ? 1 : 0) | (at_untidy ? 2 : 0), transposed = 0;
-    t = host_clock::now();
     if (own_at) {                                            // the transpose of any A is canonical, and so is its transpose
         if (bspgemm_status st = bspgemm_matrix_transpose(ctx, A, &mineT)) return bail(st);
         transposed = 1;
@@ -431,27 +432,19 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
         }
     }
     if (mineA) A = mineA;
-    if (timed) {
-        HIPCHK_B(hipStreamSynchronize(s));
-        ms_tr = ms_since(t);
-    }
+    HIPCHK_B(clk.lap(ms_tr, true));
     if (bspgemm_status st = ensure_tmp(ctx, total)) return bail(st);   // (there already, see above)
     if (!rank_fixed_host && rank_host) {
         h_fixed = static_cast<u64 *>(malloc((size_t)n * sizeof(u64)));
         if (!h_fixed) return bail(FAIL(BSPGEMM_ERR_ALLOC, "bspgemm_pagerank: host ranks"));
     }
 
-    d_cnt = reinterpret_cast<PrCounters *>(ctx->tmp);
-    u64 *r = reinterpret_cast<u64 *>(ctx->tmp + o_r);
-    u64 *c[2] = {reinterpret_cast<u64 *>(ctx->tmp + o_c), reinterpret_cast<u64 *>(ctx->tmp + o_c + 2 * n4)};
-    u64 *acc = reinterpret_cast<u64 *>(ctx->tmp + o_acc);
-    int *list = ctx->tmp + o_list;
-    int2 *chunk = reinterpret_cast<int2 *>(ctx->tmp + o_chunk);
+    carve(ctx->tmp);                                         // (again: the transposes may have moved the workspace)
     const long long E = A->nnz;
     const dim3 block(kPrThreads);
     int wave_lanes = 64;
 
-    t = host_clock::now();
+    clk.start();
     HIPCHK_B(hipMemsetAsync(d_cnt, 0, sizeof(PrCounters), s));
     hipLaunchKernelGGL(k_pr_init, pr_grid(n, kPrThreads), block, 0, s, n, q, A->d_row_ptr, r, c[0], acc, d_cnt);
     HIPCHK_B(hipGetLastError());
@@ -471,26 +464,17 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
         launch_select_tile_rows(A->d_row_ptr, n, ctx->tile_row, s);
         HIPCHK_B(hipGetLastError());
     }
-    if (timed) {
-        HIPCHK_B(hipStreamSynchronize(s));
-        ms_lists = ms_since(t);
-    }
+    HIPCHK_B(clk.lap(ms_lists, true));
 
     int iterations = 0, converged = 0;
-    const host_clock::time_point t_loop = host_clock::now();
     while (iterations < max_iter) {
         const int it = ++iterations;
         PrArgs a = {n, B, D, A->d_row_ptr, c[(it - 1) & 1], c[it & 1], r, &d_cnt->dang[(it - 1) % 3], &d_cnt->dang[it % 3],
                     &d_cnt->delta[it & 1], &d_cnt->dang[(it + 1) % 3], &d_cnt->delta[(it + 1) & 1]};
-        t = host_clock::now();
-        host_clock::time_point t_cls = t;
-        auto lap = [&](int k) {                              // under BSPGEMM_PR_TIMING: a synchronisation behind every class
+        StageClock cls(clk.on, s);                           // under BSPGEMM_PR_TIMING: a synchronisation behind every class
+        auto lap = [&](int k) {
             a.zero0 = a.zero1 = nullptr;                     // (the launches behind the first)
-            if (!timed) return hipSuccess;
-            if (hipError_t e = hipStreamSynchronize(s)) return e;
-            ms_class[k] += ms_since(t_cls);
-            t_cls = host_clock::now();
-            return hipSuccess;
+            return cls.lap(ms_class[k], true);
         };
         if (pull) {
             if (h.size[0]) {
@@ -531,13 +515,7 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
             HIPCHK_B(lap(kPrClasses));
         }
         HIPCHK_B(hipGetLastError());
-        if (timed) {
-            const double ms = ms_since(t);
-            if (ms > ms_iter_max) {
-                ms_iter_max = ms;
-                iter_max_at = it;
-            }
-        }
+        clk.longest(cls.total(), it);
         if (tolerance > 0) {                                 // the iteration's one read-back, 8 bytes
             u64 delta = 0;
             HIPCHK_B(hipMemcpyAsync(&delta, &d_cnt->delta[it & 1], sizeof delta, hipMemcpyDeviceToHost, s));
@@ -548,13 +526,9 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
             }
         }
     }
-    if (timed) {
-        HIPCHK_B(hipStreamSynchronize(s));
-        ms_iter = ms_since(t_loop);
-    }
+    HIPCHK_B(clk.lap(ms_iter, true));
 
     // the read-out: the mass, the counters and the ranks, behind the call's one synchronisation of the tolerance == 0 form
-    t = host_clock::now();
     u64 *fixed = rank_fixed_host ? reinterpret_cast<u64 *>(rank_fixed_host) : h_fixed;
     hipLaunchKernelGGL(k_pr_mass, pr_grid(n, kPrThreads), block, 0, s, n, r, d_cnt);
     HIPCHK_B(hipGetLastError());
@@ -565,14 +539,14 @@ extern "C" bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspgemm_m
     if (h.ndangling > (u64)n) return bail(fail_stuck(who));   // (the mass is no test: under a wrong AT it is whatever the sums wrap to)
     if (rank_host)
         for (int v = 0; v < n; v++) rank_host[v] = std::ldexp((double)fixed[v], -62);
-    if (timed) {
-        ms_out = ms_since(t);
+    if (clk.on) {
+        (void)clk.lap(ms_out);
         fprintf(stderr, "[bspgemm] %s: n %d nnz %lld %s classes %d/%d/%d/%d (%d lanes per wave-class row) chunks %d dangling %llu | total %.3f ms = canonical "
                         "check %.3f + transpose %.3f + classify %.3f + %d iterations %.3f (lane %.3f, wave %.3f, workgroup %.3f, "
                         "hub %.3f, push %.3f) + read-out %.3f + rest | longest iteration %.3f ms (iteration %d)\n",
                 who, n, E, pull ? "pull" : "push", sizes[0], sizes[1], sizes[2], sizes[3], wave_lanes, pull ? h.chunks : 0,
-                (unsigned long long)h.ndangling, ms_since(t_call), ms_check, ms_tr, ms_lists, iterations, ms_iter, ms_class[0],
-                ms_class[1], ms_class[2], ms_class[3], ms_class[4], ms_out, ms_iter_max, iter_max_at);
+                (unsigned long long)h.ndangling, clk.total(), ms_check, ms_tr, ms_lists, iterations, ms_iter, ms_class[0],
+                ms_class[1], ms_class[2], ms_class[3], ms_class[4], ms_out, clk.max_ms, clk.max_tag[0]);
     }
     bspgemm_matrix_free(mineA);
     bspgemm_matrix_free(mineT);

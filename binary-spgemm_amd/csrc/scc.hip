@@ -69,7 +69,6 @@ struct SccFlags : SweepFlags {
     int components;         // vertices with label[v] == v so far: the trimmed ones and the roots
     int pad[3];
 };
-constexpr size_t kSccFlagInts = sizeof(SccFlags) / sizeof(int);
 
 // P.row_ptr = 0 .. n, label = fill (-1, or v itself for a graph without entries: every vertex is an SCC), no marks
 __global__ __launch_bounds__(kSccThreads) void k_scc_init(int n, int *__restrict__ row_ptr, int *__restrict__ label, bool alive,
@@ -230,28 +229,23 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
     const int n = A->rows;
     const long long E = A->nnz;
     const bool edges = E > 0;
-    const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
+    const size_t n4 = ws_pad4((size_t)n);
+    SccFlags *d_flags = nullptr;
+    int *color = nullptr, *has_out = nullptr, *has_in = nullptr;
+    auto carve = [&](int *tmp) { return WsCursor(tmp).take(d_flags, 1).take(color, n4).take(has_out, n4).take(has_in, n4).ints(); };
     if (edges) {                                            // (before anything is launched: growing them synchronises)
         if (bspgemm_status st = ensure_tile_rows(ctx, (size_t)E)) return st;
-        if (bspgemm_status st = ensure_tmp(ctx, kSccFlagInts + 3 * n4)) return st;
+        if (bspgemm_status st = ensure_tmp(ctx, carve(nullptr))) return st;
+        carve(ctx->tmp);
     }
     // BSPGEMM_SCC_TIMING: host clocks around the repetitions, each of which ends synchronised anyway
-    const bool timed = ctx->scc_timing;
-    const host_clock::time_point t_call = host_clock::now();
+    StageClock clk(ctx->scc_timing, s);
     double ms_trim = 0, ms_fwd = 0, ms_bwd = 0;
     bspgemm_matrix *m = nullptr;                            // the assignment operand: its col_idx is label[]
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_matrix_free(m); return st; };
     auto stuck = [&]() { return bail(fail_stuck(who)); };
     if (bspgemm_status st = assignment_operand(ctx, n, &m)) return bail(st);
     int *label = m->d_col_idx;
-    SccFlags *d_flags = nullptr;
-    int *color = nullptr, *has_out = nullptr, *has_in = nullptr;
-    if (edges) {
-        d_flags = reinterpret_cast<SccFlags *>(ctx->tmp);
-        color = ctx->tmp + kSccFlagInts;
-        has_out = color + n4;
-        has_in = color + 2 * n4;
-    }
     const dim3 vgrid = vertex_grid(n, kSccThreads), vblock(kSccThreads);
     hipLaunchKernelGGL(k_scc_init, vgrid, vblock, 0, s, n, m->d_row_ptr, label, edges, has_out, has_in, d_flags);
     HIPCHK_B(hipGetLastError());
@@ -269,7 +263,7 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
         auto fetch = [&]() { return round_fetch(&h, d_flags, sizeof h, s); };
         for (;;) {
             // trim to the fixpoint; the last pass leaves color[] ready for the round
-            host_clock::time_point t = host_clock::now();
+            clk.start();
             for (long long it = 0;; it++) {
                 if (it >= cap) return stuck();
                 trims++;
@@ -281,11 +275,10 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
                 if (h.bad) return bail(fail_bad_column(who, n));
                 if (h.removed == 0 || h.alive == 0) break;
             }
-            if (timed) ms_trim += ms_since(t);
+            (void)clk.lap(ms_trim);
             if (h.alive == 0) break;
             if (r >= n) return stuck();                     // (a round labels at least one vertex)
             r++;
-            t = host_clock::now();
             for (long long it = 0;; it++) {
                 if (it >= cap) return stuck();
                 fwd++;
@@ -296,8 +289,7 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
                 HIPCHK_B(fetch());
                 if (!h.changed) break;
             }
-            if (timed) ms_fwd += ms_since(t);
-            t = host_clock::now();
+            (void)clk.lap(ms_fwd);
             hipLaunchKernelGGL(k_scc_roots, vgrid, vblock, 0, s, n, color, label, d_flags);
             for (long long it = 0;; it++) {
                 if (it >= cap) return stuck();
@@ -308,15 +300,15 @@ extern "C" bspgemm_status bspgemm_strongly_connected_components(bspgemm_context 
                 HIPCHK_B(fetch());
                 if (!h.changed) break;
             }
-            if (timed) ms_bwd += ms_since(t);
+            (void)clk.lap(ms_bwd);
         }
     }
     if (bspgemm_status st = operand_finish(m, n)) return bail(st);   // one label per vertex
     HIPCHK_B(hipStreamSynchronize(s));
-    if (timed)
+    if (clk.on)
         fprintf(stderr, "[bspgemm] %s: n %d nnz %lld components %d rounds %d | total %.3f ms = %lld trim passes %.3f + %lld forward "
                         "sweeps %.3f + %lld backward sweeps %.3f + rest\n",
-                who, n, E, h.components, r, ms_since(t_call), trims, ms_trim, fwd, ms_fwd, bwd, ms_bwd);
+                who, n, E, h.components, r, clk.total(), trims, ms_trim, fwd, ms_fwd, bwd, ms_bwd);
     if (ncomponents) *ncomponents = h.components;
     if (rounds) *rounds = r;
     if (sweeps) *sweeps = (int)(trims + fwd + bwd > INT_MAX ? INT_MAX : trims + fwd + bwd);

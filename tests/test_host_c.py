@@ -192,6 +192,22 @@ def test_early_destination_under_sanitizers(san):
     assert "early_dest ok" in r.stdout and "ERROR" not in r.stderr and "WARNING" not in r.stderr and "runtime error" not in r.stderr, r.stderr
 
 
+def test_workspace_layout_under_sanitizers():
+    """csrc/ws_layout.hpp, the cursor that lays the graph algorithms' arrays out in the context's workspace
+    (oracle/ws_layout_main.cpp): sequences of int, byte, 8-byte, 64-bit and 24-byte arrays of 0, 1, 3, 4, 5 and 70 entries from
+    offsets 0 and 5 -- every start on a 16-byte boundary, ascending and disjoint, the sizing pass and two placing passes
+    agree, every byte written in a heap block of exactly the reported size -- and the totals of the colouring, the core
+    numbers and PageRank under PULL against their layouts as plain arithmetic, under -fsanitize=address,undefined."""
+    import subprocess
+    exe = os.path.join(ROOT, "oracle", "asan", "ws_layout_asan")
+    if not os.path.exists(exe):
+        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "asan"], check=True, stdout=subprocess.DEVNULL)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ws_layout ok" in r.stdout and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+
+
 def test_powerlaw_generator_hits_the_requested_mean_degree():
     """the generator drew deg_i columns per row ONCE and let duplicates collapse (mean 52 for a requested
     64 at BASELINE config 5); rows are now topped up to deg_i DISTINCT columns"""
