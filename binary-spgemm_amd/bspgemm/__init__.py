@@ -59,7 +59,7 @@ EXPORTS = [
     "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
     "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
     "bspgemm_strongly_connected_components", "bspgemm_graph_coloring", "bspgemm_label_propagation",
-    "bspgemm_local_clustering", "bspgemm_pagerank", "bspgemm_betweenness",
+    "bspgemm_local_clustering", "bspgemm_pagerank", "bspgemm_betweenness", "bspgemm_maximal_matching",
     "bspgemm_matrix_extract", "bspgemm_matrix_extract_rows_of",
     "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
     "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
@@ -83,7 +83,7 @@ SYMMETRIZE_DROP_DIAGONAL = 1                                                    
 COMPARES = {">=": 1, ">": 2, "<=": 3, "<": 4, "==": 5, "!=": 6}                          # bspgemm_compare
 OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4, "padded_rows": 5,
            "shared_slots": 6, "dot_light": 7, "bfs_alpha": 8, "bfs_beta": 9, "bfs_push_lanes": 10,
-           "lp_min_class": 11, "pr_min_class": 12, "bc_lanes": 13, "extract_lanes": 14}                                                                           # bspgemm_option
+           "lp_min_class": 11, "pr_min_class": 12, "bc_lanes": 13, "extract_lanes": 14, "match_lanes": 15}                                                                         # bspgemm_option
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
 BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
 EXTRACT_KEEP_SHAPE = 1                                                                   # BSPGEMM_EXTRACT_KEEP_SHAPE
@@ -144,6 +144,15 @@ class BcInfo(C.Structure):
     """bspgemm_bc_info"""
     _fields_ = [("sigma_max", C.c_uint64), ("reached", C.c_int64), ("edges_forward", C.c_int64), ("hub_chunks", C.c_int64),
                 ("sources", C.c_int), ("depth_max", C.c_int), ("levels", C.c_int), ("canonicalised", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class MatchInfo(C.Structure):
+    """bspgemm_match_info"""
+    _fields_ = [("pairs", C.c_int64), ("entries_walked", C.c_int64), ("hub_chunks", C.c_int64), ("rounds", C.c_int),
+                ("lanes", C.c_int)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -294,6 +303,7 @@ def lib():
     L.bspgemm_local_clustering.argtypes = [VP, VP, C.c_uint, PVP, VP, VP, C.POINTER(LccInfo)]
     L.bspgemm_pagerank.argtypes = [VP, VP, VP, C.c_int, C.c_double, C.c_int, C.c_double, VP, VP, C.POINTER(PrInfo)]
     L.bspgemm_betweenness.argtypes = [VP, VP, C.c_int, VP, VP, VP, C.POINTER(BcInfo)]
+    L.bspgemm_maximal_matching.argtypes = [VP, VP, C.c_int, C.c_uint, PVP, VP, C.POINTER(MatchInfo)]
     L.bspgemm_matrix_extract.argtypes = [VP, VP, C.c_int, VP, C.c_int, VP, C.c_uint, PVP, C.POINTER(ExtractInfo)]
     L.bspgemm_matrix_extract_rows_of.argtypes = [VP, VP, VP, C.c_int, VP, C.c_int, C.c_uint, PVP, C.POINTER(ExtractInfo)]
     L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
@@ -478,7 +488,7 @@ class Context:
     def set_option(self, name, value):
         """bspgemm_set_option: "class_streams" 1..3, "blocked_extents" -1/0/1, "check" 0/1, "small_path" -1/0/1, "padded_rows" -1/0/1,
         "shared_slots" -1/0/k, "dot_light" T >= 0, "bfs_alpha" >= 1, "bfs_beta" >= 1, "bfs_push_lanes" 0/4/16/64,
-        "lp_min_class" 0..3, "pr_min_class" 0..3, "bc_lanes" 0/4/16/64, "extract_lanes" 0/4/16/64"""
+        "lp_min_class" 0..3, "pr_min_class" 0..3, "bc_lanes" 0/4/16/64, "extract_lanes" 0/4/16/64, "match_lanes" 0/4/16/64"""
         _chk(lib().bspgemm_set_option(self._h, OPTIONS[name], int(value)), "set_option(%s)" % name)
 
     def get_option(self, name):
@@ -735,6 +745,23 @@ class Context:
                                        fixed.ctypes.data if A.rows else None, bc.ctypes.data if A.rows else None,
                                        C.byref(info)), "bspgemm_betweenness")
         return fixed, bc, info.as_dict()
+
+    MATCH_ORDERS = {"natural": 1, "random": 2, "light": 3}
+
+    def maximal_matching(self, A, order="random", seed=0, mate=False):
+        """bspgemm_maximal_matching: (P as a Matrix, mate int32[n] or None, info dict) -- the maximal matching of the simple
+        undirected graph of A's entries that sequential greedy gives in the edge order that include/bspgemm.h defines for
+        order ("natural", "random", "light") and seed: the same bits on every run and under every "match_lanes".
+        P.download()[1][v] = min(v, mate(v)), v itself when v is unmatched, so P^T * S * P is the contracted graph; mate=True
+        also returns the partners, -1 = unmatched.  info: pairs, entries_walked, hub_chunks, rounds, lanes"""
+        if order not in self.MATCH_ORDERS:
+            raise ValueError("order must be one of %s" % sorted(self.MATCH_ORDERS))
+        m, info = C.c_void_p(), MatchInfo()
+        mates = np.zeros(A.rows, np.int32) if mate else None
+        _chk(lib().bspgemm_maximal_matching(self._h, A._h, self.MATCH_ORDERS[order], int(seed) & 0xFFFFFFFF, C.byref(m),
+                                            mates.ctypes.data if mate and A.rows else None, C.byref(info)),
+             "bspgemm_maximal_matching")
+        return Matrix(self, m, keep=None), mates, info.as_dict()
 
     def extract(self, A, rows=None, cols=None, keep_shape=False):
         """bspgemm_matrix_extract: (Matrix, info dict) -- out = A[rows, cols] on the device.  rows / cols: int sequences, None =

@@ -282,6 +282,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     ctx->lp_timing = getenv("BSPGEMM_LP_TIMING") != nullptr;
     ctx->pr_timing = getenv("BSPGEMM_PR_TIMING") != nullptr;
     ctx->bc_timing = getenv("BSPGEMM_BC_TIMING") != nullptr;
+    ctx->match_timing = getenv("BSPGEMM_MATCH_TIMING") != nullptr;
     ctx->extract_timing = getenv("BSPGEMM_EXTRACT_TIMING") != nullptr;
     if (const char *e = getenv("BSPGEMM_LCC_TIMING")) ctx->lcc_timing = atoi(e) == 2 ? 2 : 1;
     if (ctx->debug_alloc)
@@ -778,6 +779,10 @@ extern "C" bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_optio
         if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "extract lanes: 0, 4, 16 or 64");
         ctx->extract_lanes = value;
         return BSPGEMM_OK;
+    case BSPGEMM_OPT_MATCH_LANES:
+        if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "match lanes: 0, 4, 16 or 64");
+        ctx->match_lanes = value;
+        return BSPGEMM_OK;
     }
     return FAIL(BSPGEMM_ERR_INVALID, "unknown option");
 }
@@ -800,6 +805,7 @@ extern "C" int bspgemm_get_option(const bspgemm_context *ctx, bspgemm_option opt
     case BSPGEMM_OPT_PR_MIN_CLASS: return ctx->pr_min_class;
     case BSPGEMM_OPT_BC_LANES: return ctx->bc_lanes;
     case BSPGEMM_OPT_EXTRACT_LANES: return ctx->extract_lanes;
+    case BSPGEMM_OPT_MATCH_LANES: return ctx->match_lanes;
     }
     return INT_MIN;
 }

@@ -152,6 +152,7 @@ struct bspgemm_context {
     int pr_min_class = 0;               // BSPGEMM_OPT_PR_MIN_CLASS: 0 .. 3, the smallest in-degree class of bspgemm_pagerank under PULL (pagerank.hip)
     int bc_lanes = 0;                   // BSPGEMM_OPT_BC_LANES: 0 per level from a quarter of its mean out-degree, or 4, 16, 64 lanes per vertex in both sweeps of bspgemm_betweenness (betweenness.hip)
     int extract_lanes = 0;              // BSPGEMM_OPT_EXTRACT_LANES: 0 from a quarter of the mean length of the rows read, or 4, 16, 64 lanes per out row in the count and the emit of bspgemm_matrix_extract (extract.hip)
+    int match_lanes = 0;                // BSPGEMM_OPT_MATCH_LANES: 0 from a quarter of the mean degree of the listed vertices, or 4, 16, 64 lanes per live vertex in the point launches of bspgemm_maximal_matching (match.hip)
     bool debug_alloc = false;           // BSPGEMM_DEBUG_ALLOC: allocation trace on stderr
     bool dropin_timing = false;         // BSPGEMM_DROPIN_TIMING: stage times of the int32 drop-ins on stderr
     bool kcore_timing = false;          // BSPGEMM_KCORE_TIMING: stage times of the k-core peeling on stderr (it then synchronises twice per launch)
@@ -162,6 +163,7 @@ struct bspgemm_context {
     bool pr_timing = false;             // BSPGEMM_PR_TIMING: stage times of the PageRank on stderr (it then synchronises behind every class launch)
     bool bc_timing = false;             // BSPGEMM_BC_TIMING: stage times of the betweenness centrality on stderr (it then synchronises behind every launch group)
     bool extract_timing = false;        // BSPGEMM_EXTRACT_TIMING: stage times of the submatrix extraction on stderr (it then synchronises behind every stage)
+    bool match_timing = false;          // BSPGEMM_MATCH_TIMING: stage times of the maximal matching on stderr (it then synchronises behind every launch)
     int lcc_timing = 0;                // BSPGEMM_LCC_TIMING: 1 stage times of the local clustering on stderr (it then synchronises behind every stage); 2: the same on the half that is not kept (lcc.hip)
 };
 
@@ -264,7 +266,7 @@ size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratc
 size_t transpose_workspace_ints(long long E, int cols);
 size_t symmetrize_workspace_ints(long long E, int n);
 
-// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip, lcc.hip, pagerank.hip, betweenness.hip) ---
+// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip, lcc.hip, pagerank.hip, betweenness.hip, match.hip) ---
 // What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
 // each algorithm's own, and so is what it does about an untidy operand.  who: the entry point's name, which every message
 // starts with.
@@ -343,7 +345,7 @@ static inline bspgemm_status fail_stuck(const char *who)
     snprintf(g_err, sizeof g_err, "%s: did not converge", who);
     return BSPGEMM_ERR_HIP;
 }
-// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING)
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING, BSPGEMM_MATCH_TIMING)
 using host_clock = std::chrono::steady_clock;
 static inline double ms_since(host_clock::time_point t)
 {

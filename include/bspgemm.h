@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING=1|2, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING=1|2, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING, BSPGEMM_MATCH_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -200,7 +200,10 @@ bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on);
  *                    level's mean out-degree; or 4, 16, 64 for every launch of both sweeps.  It changes no result.  Read at
  *                    every call.
  *   EXTRACT_LANES    0 (default): the lanes per out row of the count and the emit of bspgemm_matrix_extract follow a quarter
- *                    of the mean length of the rows read; or 4, 16, 64.  It changes no result.  Read at every call.  */
+ *                    of the mean length of the rows read; or 4, 16, 64.  It changes no result.  Read at every call.
+ *   MATCH_LANES      0 (default): the lanes per live vertex of the point launches of bspgemm_maximal_matching follow a
+ *                    quarter of the mean degree of the vertices that have one; or 4, 16, 64.  It changes no result.  Read at
+ *                    every call.  */
 typedef enum bspgemm_option {
     BSPGEMM_OPT_CLASS_STREAMS   = 1,
     BSPGEMM_OPT_BLOCKED_EXTENTS = 2,
@@ -215,7 +218,8 @@ typedef enum bspgemm_option {
     BSPGEMM_OPT_LP_MIN_CLASS    = 11,
     BSPGEMM_OPT_PR_MIN_CLASS    = 12,
     BSPGEMM_OPT_BC_LANES        = 13,
-    BSPGEMM_OPT_EXTRACT_LANES   = 14
+    BSPGEMM_OPT_EXTRACT_LANES   = 14,
+    BSPGEMM_OPT_MATCH_LANES     = 15
 } bspgemm_option;
 bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_option opt, int value);
 /* current value of a knob (INT32_MIN for an unknown option or a NULL context) */
@@ -1050,6 +1054,69 @@ typedef struct bspgemm_bc_info {
 } bspgemm_bc_info;
 bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgemm_matrix *A, int nsources, const int *sources,
                                    uint64_t *bc_fixed_host, double *bc_host, bspgemm_bc_info *info);
+
+/* Maximal matching with deterministic mates, everything device-resident and without a product: the third of the colouring /
+ * independent-set / matching trio, what multilevel partitioning coarsens a graph with.  A is square and its entries are
+ * read as undirected edges exactly as bspgemm_graph_coloring reads them: the graph is S = bspgemm_matrix_symmetrize(A,
+ * BSPGEMM_SYMMETRIZE_DROP_DIAGONAL), computed inside the call and freed on every path, so unsorted rows, repeats,
+ * self-loops, one-direction storage and the in-edges that bspgemm_readCOO hands back all give the same answer; any n,
+ * n == 0 and nnz == 0 included.
+ *   - The order.  An edge {a, b} with a < b has a 32-bit key, and the edges are ordered by (key32, a, b)
+ *     lexicographically.  With mix32 as bspgemm_graph_coloring defines it (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ *     x *= 0x846ca68b; x ^= x >> 16, all in uint32) and h = mix32(mix32((uint32)a ^ seed) ^ (uint32)b):
+ *         BSPGEMM_MATCH_NATURAL      key32 = 0                                                  (seed is ignored)
+ *         BSPGEMM_MATCH_RANDOM       key32 = h
+ *         BSPGEMM_MATCH_LIGHT_FIRST  key32 = (min(deg_S(a) + deg_S(b), 0xffff) << 16) | (h >> 16)
+ *     LIGHT_FIRST visits pairs of low degree first, the usual coarsening heuristic.  The formula is part of the contract:
+ *     the result is defined by it.
+ *   - The result.  The matching that sequential greedy gives when it visits the edges of S in that order and takes an edge
+ *     when both of its ends are free.  That is unique, so every run, every lane width and every hub split gives the same
+ *     bits.  It is a matching (mate(mate(v)) = v, {v, mate(v)} is an edge of S) and it is maximal: no edge of S has two
+ *     unmatched ends.
+ *   - *P is the n x n assignment operand, exactly as bspgemm_connected_components returns it: P.row_ptr = 0, 1, ..., n and
+ *     P.col_idx[v] = min(v, mate(v)), v itself when v is unmatched.  Every row of P^T then has 0, 1 or 2 entries, and P^T * S * P
+ *     by two multiplies is the contracted graph, whose diagonal marks the contracted edges.  It is an owned operand laid out
+ *     like an uploaded one (bspgemm_matrix_free), usable in every product, transpose, select and extract, complete on the
+ *     context's stream when the call returns.
+ *   - mate_host: a host array of n ints, or NULL: mate(v) is v's partner, -1 when v is unmatched.
+ *   - info may be NULL; it is zeroed on failure.  rounds, entries_walked and hub_chunks are deterministic as well.
+ *   - The scheme is the locally-dominant-edge algorithm: an edge that is the smallest live edge (both ends free) at both of
+ *     its ends belongs to the greedy matching.  For a fixed u, comparing (key32, a, b) across its neighbours w equals
+ *     comparing (key32, w), so a vertex's candidate is one 64-bit word key32 << 32 | w.  In the context's workspace, grown
+ *     once per call: best[n] (64-bit), mate[n], two live lists, the chunk records of the long rows and a counter block,
+ *     about 5 n ints.  The first live list holds the vertices of degree > 0.  A round is a POINT launch (4, 16 or 64 lanes per
+ *     live vertex u stride over u's row of S; a neighbour w with mate[w] < 0 gives a candidate, and the minimum is stored
+ *     in best[u]), for the live rows of more than 4096 entries a HUB launch (one workgroup per chunk of 4096 entries, one
+ *     device-scope 64-bit atomicMin per chunk on best[u], so a hub costs what its entries cost), and a PAIR launch (one
+ *     thread per live u: without a candidate u retires, unmatched for good; when its candidate w points back, mate[u] = w;
+ *     otherwise u is appended to the other list and, if it is a hub, its chunk records are written), then ONE read-back of
+ *     8 bytes: the other list's size and its number of chunk records, the grids of the next round.  The lists swap until
+ *     one comes back empty.  Decisions rest only on values from earlier launches and on atomic return values; no kernel
+ *     waits for another workgroup (csrc/match.hip).
+ *   - Cost: one synchronisation per round, and a row is walked AGAIN in every round in which its vertex is still live
+ *     (info.entries_walked).  The smallest live edge is matched in every round, so at most n / 2 + 1 rounds run: NATURAL on a
+ *     path stored in ascending order takes n / 2, RANDOM took 3 to 7 on the test graphs.  Defensive cap of n
+ *     rounds (BSPGEMM_ERR_HIP, "did not converge").
+ *   - BSPGEMM_OPT_MATCH_LANES (0 default, 4, 16, 64), read at every call: the lanes per live vertex of the point launches.
+ *     It changes no result; info.lanes says what ran.  Environment BSPGEMM_MATCH_TIMING=1 (read in bspgemm_create): the stage
+ *     split on stderr -- symmetrize, point launches, hub launches, pair launches, read-backs and the longest round; it then
+ *     synchronises behind every launch.
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with *P = NULL, bspgemm_last_error naming the function and the cause: a NULL ctx, A or P and an
+ *     unknown order (refused before any operand is dereferenced), a non-square A, A from another context.  Otherwise the
+ *     errors of bspgemm_matrix_symmetrize: BSPGEMM_ERR_INVALID for a column outside [0, n) anywhere in A (the context stays
+ *     usable), BSPGEMM_ERR_OVERFLOW for more than INT_MAX entries in S, BSPGEMM_ERR_ALLOC.  Nothing is leaked on any path.  */
+typedef enum bspgemm_match_order { BSPGEMM_MATCH_NATURAL = 1, BSPGEMM_MATCH_RANDOM = 2,
+                                   BSPGEMM_MATCH_LIGHT_FIRST = 3 } bspgemm_match_order;
+typedef struct bspgemm_match_info {
+    int64_t pairs;            /* matched edges                                                          */
+    int64_t entries_walked;   /* sum over rounds of deg_S(u) over the live vertices u of the round       */
+    int64_t hub_chunks;       /* chunk records launched over all rounds                                  */
+    int     rounds;           /* point launches (below); 0 when S has no entries                         */
+    int     lanes;            /* lanes per live vertex that ran: 4, 16 or 64 (0 without a round)         */
+} bspgemm_match_info;
+bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_match_order order,
+                                        unsigned seed, bspgemm_matrix **P, int *mate_host, bspgemm_match_info *info);
 
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
