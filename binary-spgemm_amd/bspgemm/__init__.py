@@ -36,36 +36,6 @@ _I64P = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 STATUS = {0: "OK", 1: "ERR_INVALID", 2: "ERR_ALLOC", 3: "ERR_HIP", 4: "ERR_NO_DEVICE",
           5: "ERR_OVERFLOW", 6: "ERR_IO", 7: "ERR_FORMAT", 8: "ERR_COMM", 9: "ERR_SIZE"}
 
-# every symbol include/bspgemm.h declares (checked by tests/test_abi.py)
-EXPORTS = [
-    "bspgemm_status_string", "bspgemm_last_error", "bspgemm_create", "bspgemm_destroy",
-    "bspgemm_set_stream", "bspgemm_synchronize", "bspgemm_matrix_upload", "bspgemm_matrix_wrap_device",
-    "bspgemm_matrix_free", "bspgemm_matrix_rows", "bspgemm_matrix_cols", "bspgemm_matrix_nnz",
-    "bspgemm_multiply", "bspgemm_multiply_masked", "bspgemm_multiply_masked_ex", "bspgemm_result_rows", "bspgemm_result_nnz",
-    "bspgemm_result_row_ptr_device", "bspgemm_result_col_idx_device", "bspgemm_result_download",
-    "bspgemm_result_free", "bspgemm_row_work_prefix", "bspgemm_partition_rows", "bspgemm_last_stats",
-    "SpGEMM_hip", "SpGEMM_hip_bigslice", "SpGEMM_hip_mat", "SpGEMM_hip_masked", "bspgemm_dropin_set_device",
-    "bspgemm_comm_unique_id", "bspgemm_comm_create", "bspgemm_comm_destroy", "bspgemm_comm_stitch_row_ptr", "bspgemm_lengths_to_row_ptr",
-    "bspgemm_readCOO", "bspgemm_write_mtx", "bspgemm_write_result_mtx", "bspgemm_csr_equal",
-    "bspgemm_csr_equal64", "bspgemm_gen_uniform", "bspgemm_gen_rmat", "bspgemm_gen_powerlaw",
-    "bspgemm_matrix_from_result", "bspgemm_closure",
-    "bspgemm_readCOO_ex", "bspgemm_comm_create_host", "bspgemm_comm_rank", "bspgemm_comm_size",
-    "bspgemm_comm_gather_col_idx", "SpGEMM_hip_multi", "bspgemm_device_count", "bspgemm_stats_at",
-    "bspgemm_set_flow", "bspgemm_set_class_timing", "bspgemm_build_info", "bspgemm_matrix_invalidate", "bspgemm_comm_agree", "bspgemm_comm_inject_failure",
-    "bspgemm_set_option", "bspgemm_get_option", "bspgemm_matrix_uses_blocked_table", "bspgemm_matrix_uses_padded_rows",
-    "bspgemm_matrix_transpose", "bspgemm_matrix_download", "bspgemm_multiply_accumulate", "bspgemm_closure_ex",
-    "bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values",
-    "bspgemm_matrix_select", "bspgemm_matrix_from_result_where", "bspgemm_result_values_sum", "bspgemm_triangle_count",
-    "bspgemm_ktruss", "bspgemm_matrix_setop", "bspgemm_matrix_equal", "bspgemm_matrix_symmetrize",
-    "bspgemm_bfs", "bspgemm_connected_components", "bspgemm_core_numbers", "bspgemm_kcore",
-    "bspgemm_strongly_connected_components", "bspgemm_graph_coloring", "bspgemm_label_propagation",
-    "bspgemm_local_clustering", "bspgemm_pagerank", "bspgemm_betweenness", "bspgemm_maximal_matching",
-    "bspgemm_matrix_extract", "bspgemm_matrix_extract_rows_of",
-    "bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex", "bspgemm_bfs_tree",
-    "bspgemm_debug_fail_alloc", "bspgemm_debug_alloc_state",
-]
-
-
 class BspgemmError(RuntimeError):
     def __init__(self, status, where=""):
         self.status = status
@@ -91,80 +61,63 @@ LCC_DIRECTED = 1                                                                
 PR_AUTO, PR_PULL, PR_PUSH = 0, 1, 2                                                      # bspgemm_pr_method
 
 
-class DotInfo(C.Structure):
+class _Info(C.Structure):
+    """what the bspgemm_*_info structs share: as_dict() with every scalar field as an int, every array field as a list of ints"""
+
+    def as_dict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = [int(x) for x in v] if isinstance(v, C.Array) else int(v)
+        return d
+
+
+class DotInfo(_Info):
     """bspgemm_dot_info"""
     _fields_ = [("entries", C.c_int64), ("heavy_entries", C.c_int64), ("kept", C.c_int64), ("canonicalised", C.c_int)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class BfsTreeInfo(C.Structure):
+class BfsTreeInfo(_Info):
     """bspgemm_bfs_tree_info"""
     _fields_ = [("reached", C.c_int64), ("edges_pushed", C.c_int64), ("pull_mask", C.c_uint64), ("depth", C.c_int),
                 ("complete", C.c_int), ("push_levels", C.c_int), ("pull_levels", C.c_int), ("transposed", C.c_int),
                 ("canonicalised", C.c_int)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class LpInfo(C.Structure):
+class LpInfo(_Info):
     """bspgemm_lp_info"""
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("communities", C.c_int), ("changed", C.c_int),
                 ("class_vertices", C.c_int64 * 4)]
 
-    def as_dict(self):
-        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:4]}
-        d["class_vertices"] = [int(x) for x in self.class_vertices]
-        return d
 
-
-class LccInfo(C.Structure):
+class LccInfo(_Info):
     """bspgemm_lcc_info"""
     _fields_ = [("triangles", C.c_int64), ("entries", C.c_int64), ("heavy_entries", C.c_int64), ("reciprocal", C.c_int64)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class PrInfo(C.Structure):
+class PrInfo(_Info):
     """bspgemm_pr_info"""
     _fields_ = [("mass", C.c_uint64), ("delta", C.c_uint64), ("dangling", C.c_int64), ("class_vertices", C.c_int64 * 4),
                 ("iterations", C.c_int), ("converged", C.c_int), ("method", C.c_int), ("transposed", C.c_int),
                 ("canonicalised", C.c_int)]
 
-    def as_dict(self):
-        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "class_vertices"}
-        d["class_vertices"] = [int(x) for x in self.class_vertices]
-        return d
 
-
-class BcInfo(C.Structure):
+class BcInfo(_Info):
     """bspgemm_bc_info"""
     _fields_ = [("sigma_max", C.c_uint64), ("reached", C.c_int64), ("edges_forward", C.c_int64), ("hub_chunks", C.c_int64),
                 ("sources", C.c_int), ("depth_max", C.c_int), ("levels", C.c_int), ("canonicalised", C.c_int)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class MatchInfo(C.Structure):
+class MatchInfo(_Info):
     """bspgemm_match_info"""
     _fields_ = [("pairs", C.c_int64), ("entries_walked", C.c_int64), ("hub_chunks", C.c_int64), ("rounds", C.c_int),
                 ("lanes", C.c_int)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class ExtractInfo(C.Structure):
+class ExtractInfo(_Info):
     """bspgemm_extract_info"""
     _fields_ = [("kept", C.c_int64), ("scanned", C.c_int64), ("hub_chunks", C.c_int64), ("lanes", C.c_int),
                 ("cols_monotone", C.c_int), ("sorted_by", C.c_int), ("canonicalised", C.c_int)]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class Stats(C.Structure):
@@ -192,6 +145,113 @@ GATHERV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p
 class HostTransport(C.Structure):
     """bspgemm_host_transport: all-gather / gatherv callbacks on host buffers"""
     _fields_ = [("user", C.c_void_p), ("allgather", ALLGATHER_FN), ("gatherv", GATHERV_FN)]
+
+
+_VP, _PVP = C.c_void_p, C.POINTER(C.c_void_p)
+_IPP = C.POINTER(C.POINTER(C.c_int))
+_U32PP = C.POINTER(C.POINTER(C.c_uint32))
+_INT = C.c_int                                       # bspgemm_status and the plain int returns (ctypes' default)
+# The C ABI, once: every symbol include/bspgemm.h declares (checked by tests/test_abi.py) -> (restype, argtypes).
+# lib() binds them; EXPORTS is this table's names.
+_SIGNATURES = {
+    "bspgemm_status_string": (C.c_char_p, [C.c_int]),
+    "bspgemm_last_error": (C.c_char_p, []),
+    "bspgemm_create": (_INT, [C.c_int, _PVP]),
+    "bspgemm_destroy": (None, [_VP]),
+    "bspgemm_set_stream": (_INT, [_VP, _VP]),
+    "bspgemm_synchronize": (_INT, [_VP]),
+    "bspgemm_set_flow": (_INT, [_VP, C.c_int]),
+    "bspgemm_set_class_timing": (_INT, [_VP, C.c_int]),
+    "bspgemm_build_info": (C.c_char_p, []),
+    "bspgemm_matrix_invalidate": (_INT, [_VP]),
+    "bspgemm_set_option": (_INT, [_VP, C.c_int, C.c_int]),
+    "bspgemm_get_option": (_INT, [_VP, C.c_int]),
+    "bspgemm_matrix_uses_blocked_table": (_INT, [_VP]),
+    "bspgemm_matrix_uses_padded_rows": (_INT, [_VP]),
+    "bspgemm_matrix_upload": (_INT, [_VP, C.c_int, C.c_int, _VP, _VP, _PVP]),
+    "bspgemm_matrix_wrap_device": (_INT, [_VP, C.c_int, C.c_int, C.c_int64, _VP, _VP, _PVP]),
+    "bspgemm_matrix_free": (None, [_VP]),
+    "bspgemm_matrix_transpose": (_INT, [_VP, _VP, _PVP]),
+    "bspgemm_matrix_download": (_INT, [_VP, _VP, _VP, _VP]),
+    "bspgemm_matrix_rows": (_INT, [_VP]),
+    "bspgemm_matrix_cols": (_INT, [_VP]),
+    "bspgemm_matrix_nnz": (C.c_int64, [_VP]),
+    "bspgemm_multiply": (_INT, [_VP, _VP, _VP, C.c_int, C.c_int, _PVP]),
+    "bspgemm_multiply_masked": (_INT, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _PVP]),
+    "bspgemm_multiply_masked_ex": (_INT, [_VP, _VP, _VP, _VP, C.c_uint, C.c_int, C.c_int, _PVP]),
+    "bspgemm_result_rows": (_INT, [_VP]),
+    "bspgemm_result_nnz": (C.c_int64, [_VP]),
+    "bspgemm_result_row_ptr_device": (_VP, [_VP]),
+    "bspgemm_result_col_idx_device": (_VP, [_VP]),
+    "bspgemm_result_download": (_INT, [_VP, _VP, _VP, _VP]),
+    "bspgemm_multiply_masked_count": (_INT, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _PVP]),
+    "bspgemm_result_values_device": (_VP, [_VP]),
+    "bspgemm_result_download_values": (_INT, [_VP, _VP, _VP]),
+    "bspgemm_result_free": (None, [_VP]),
+    "bspgemm_matrix_from_result": (_INT, [_VP, _VP, C.c_int, _PVP]),
+    "bspgemm_matrix_select": (_INT, [_VP, _VP, C.c_int, _PVP]),
+    "bspgemm_matrix_from_result_where": (_INT, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP]),
+    "bspgemm_result_values_sum": (_INT, [_VP, _VP, C.POINTER(C.c_int64)]),
+    "bspgemm_triangle_count": (_INT, [_VP, _VP, C.POINTER(C.c_int64)]),
+    "bspgemm_ktruss": (_INT, [_VP, _VP, C.c_int, C.c_int, _PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bspgemm_multiply_masked_dot": (_INT, [_VP, _VP, _VP, _VP, C.c_uint, _PVP, C.POINTER(DotInfo)]),
+    "bspgemm_triangle_count_ex": (_INT, [_VP, _VP, C.c_int, C.POINTER(C.c_int64)]),
+    "bspgemm_ktruss_ex": (_INT, [_VP, _VP, C.c_int, C.c_int, C.c_int, _PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bspgemm_bfs": (_INT, [_VP, _VP, C.c_int, _VP, C.c_int, _PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bspgemm_bfs_tree": (_INT, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _PVP, C.POINTER(BfsTreeInfo)]),
+    "bspgemm_connected_components": (_INT, [_VP, _VP, _PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bspgemm_core_numbers": (_INT, [_VP, _VP, _PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bspgemm_kcore": (_INT, [_VP, _VP, C.c_int, _PVP, C.POINTER(C.c_int)]),
+    "bspgemm_strongly_connected_components": (_INT, [_VP, _VP, _PVP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bspgemm_graph_coloring": (_INT, [_VP, _VP, C.c_int, C.c_uint, _PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bspgemm_label_propagation": (_INT, [_VP, _VP, _VP, C.c_int, _PVP, C.POINTER(LpInfo)]),
+    "bspgemm_local_clustering": (_INT, [_VP, _VP, C.c_uint, _PVP, _VP, _VP, C.POINTER(LccInfo)]),
+    "bspgemm_pagerank": (_INT, [_VP, _VP, _VP, C.c_int, C.c_double, C.c_int, C.c_double, _VP, _VP, C.POINTER(PrInfo)]),
+    "bspgemm_betweenness": (_INT, [_VP, _VP, C.c_int, _VP, _VP, _VP, C.POINTER(BcInfo)]),
+    "bspgemm_maximal_matching": (_INT, [_VP, _VP, C.c_int, C.c_uint, _PVP, _VP, C.POINTER(MatchInfo)]),
+    "bspgemm_matrix_extract": (_INT, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_uint, _PVP, C.POINTER(ExtractInfo)]),
+    "bspgemm_matrix_extract_rows_of": (_INT, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_uint, _PVP, C.POINTER(ExtractInfo)]),
+    "bspgemm_matrix_setop": (_INT, [_VP, _VP, _VP, C.c_int, _PVP]),
+    "bspgemm_matrix_equal": (_INT, [_VP, _VP, _VP, C.POINTER(C.c_int)]),
+    "bspgemm_matrix_symmetrize": (_INT, [_VP, _VP, C.c_uint, _PVP]),
+    "bspgemm_closure": (_INT, [_VP, _VP, C.c_int, _PVP, C.POINTER(C.c_int)]),
+    "bspgemm_multiply_accumulate": (_INT, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _PVP]),
+    "bspgemm_closure_ex": (_INT, [_VP, _VP, C.c_uint, C.c_int, _PVP, C.POINTER(C.c_int)]),
+    "bspgemm_row_work_prefix": (_INT, [_VP, _VP, _VP, _I64P]),
+    "bspgemm_partition_rows": (_INT, [_VP, _VP, _VP, C.c_int, _I32P]),
+    "bspgemm_last_stats": (_INT, [_VP, C.POINTER(Stats)]),
+    "bspgemm_stats_at": (_INT, [_VP, C.c_int, C.POINTER(Stats)]),
+    "SpGEMM_hip": (_INT, [_I32P, _VP, C.c_int, _I32P, _I32P, C.c_int, _IPP, _I32P, C.c_int]),
+    "SpGEMM_hip_bigslice": (_INT, [_I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, _IPP, _I32P, C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "SpGEMM_hip_mat": (_INT, [_I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, _I32P, _I32P]),
+    "SpGEMM_hip_masked": (_INT, [_I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, _I32P, _I32P, _IPP, _I32P, C.POINTER(C.c_int)]),
+    "bspgemm_dropin_set_device": (_INT, [C.c_int]),
+    "bspgemm_debug_fail_alloc": (None, [C.c_int]),
+    "bspgemm_debug_alloc_state": (None, [_I64P]),
+    "bspgemm_comm_unique_id": (_INT, [C.c_char_p]),
+    "bspgemm_comm_create": (_INT, [_VP, C.c_char_p, C.c_int, C.c_int, _PVP]),
+    "bspgemm_comm_destroy": (None, [_VP]),
+    "bspgemm_comm_stitch_row_ptr": (_INT, [_VP, _VP, _I32P, _PVP, _VP]),
+    "bspgemm_lengths_to_row_ptr": (_INT, [_VP, _VP, C.c_int, C.c_int, _I32P, _VP, _VP]),
+    "bspgemm_readCOO": (_INT, [C.c_char_p, _U32PP, _U32PP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "bspgemm_readCOO_ex": (_INT, [C.c_char_p, C.c_uint, _U32PP, _U32PP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "bspgemm_comm_create_host": (_INT, [_VP, C.POINTER(HostTransport), C.c_int, C.c_int, _PVP]),
+    "bspgemm_comm_rank": (_INT, [_VP]),
+    "bspgemm_comm_size": (_INT, [_VP]),
+    "bspgemm_comm_gather_col_idx": (_INT, [_VP, _VP, _I64P, C.c_int, _VP]),
+    "SpGEMM_hip_multi": (_INT, [_VP, _I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, _IPP, _I32P, C.c_int]),
+    "bspgemm_write_mtx": (_INT, [C.c_char_p, C.c_int, C.c_int, _I32P, _I32P]),
+    "bspgemm_write_result_mtx": (_INT, [C.c_char_p, C.c_int, C.c_int, _I64P, _I32P]),
+    "bspgemm_csr_equal": (_INT, [_I32P, _I32P, _I32P, _I32P, C.c_int]),
+    "bspgemm_csr_equal64": (_INT, [_I32P, _I64P, _I32P, _I64P, C.c_int]),
+    "bspgemm_gen_uniform": (_INT, [C.c_int, C.c_int, C.c_uint64, _IPP, _IPP]),
+    "bspgemm_gen_rmat": (_INT, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint64, _IPP, _IPP]),
+    "bspgemm_gen_powerlaw": (_INT, [C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, _IPP, _IPP]),
+    "bspgemm_device_count": (_INT, []),
+    "bspgemm_comm_agree": (_INT, [_VP, C.c_int]),
+    "bspgemm_comm_inject_failure": (None, [_VP, C.c_int]),
+}
+EXPORTS = list(_SIGNATURES)
 
 
 def build():
@@ -239,118 +299,9 @@ def lib():
         import torch  # noqa: F401  (a broken torch install raises here: loudly, not a later segfault)
     L = C.CDLL(LIB_PATH)
     check_single_hip_runtime()
-    VP, PVP = C.c_void_p, C.POINTER(C.c_void_p)
-    L.bspgemm_status_string.restype = C.c_char_p
-    L.bspgemm_status_string.argtypes = [C.c_int]
-    L.bspgemm_last_error.restype = C.c_char_p
-    L.bspgemm_create.argtypes = [C.c_int, PVP]
-    L.bspgemm_destroy.argtypes = [VP]
-    L.bspgemm_destroy.restype = None
-    L.bspgemm_set_stream.argtypes = [VP, VP]
-    L.bspgemm_synchronize.argtypes = [VP]
-    L.bspgemm_set_flow.argtypes = [VP, C.c_int]
-    L.bspgemm_set_class_timing.argtypes = [VP, C.c_int]
-    L.bspgemm_build_info.restype = C.c_char_p
-    L.bspgemm_matrix_invalidate.argtypes = [VP]
-    L.bspgemm_set_option.argtypes = [VP, C.c_int, C.c_int]
-    L.bspgemm_get_option.argtypes = [VP, C.c_int]
-    L.bspgemm_matrix_uses_blocked_table.argtypes = [VP]
-    L.bspgemm_matrix_uses_padded_rows.argtypes = [VP]
-    L.bspgemm_matrix_upload.argtypes = [VP, C.c_int, C.c_int, VP, VP, PVP]
-    L.bspgemm_matrix_wrap_device.argtypes = [VP, C.c_int, C.c_int, C.c_int64, VP, VP, PVP]
-    L.bspgemm_matrix_free.argtypes = [VP]
-    L.bspgemm_matrix_free.restype = None
-    L.bspgemm_matrix_transpose.argtypes = [VP, VP, PVP]
-    L.bspgemm_matrix_download.argtypes = [VP, VP, VP, VP]
-    L.bspgemm_matrix_rows.argtypes = [VP]
-    L.bspgemm_matrix_cols.argtypes = [VP]
-    L.bspgemm_matrix_nnz.argtypes = [VP]
-    L.bspgemm_matrix_nnz.restype = C.c_int64
-    L.bspgemm_multiply.argtypes = [VP, VP, VP, C.c_int, C.c_int, PVP]
-    L.bspgemm_multiply_masked.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, PVP]
-    L.bspgemm_multiply_masked_ex.argtypes = [VP, VP, VP, VP, C.c_uint, C.c_int, C.c_int, PVP]
-    L.bspgemm_result_rows.argtypes = [VP]
-    L.bspgemm_result_nnz.argtypes = [VP]
-    L.bspgemm_result_nnz.restype = C.c_int64
-    L.bspgemm_result_row_ptr_device.argtypes = [VP]
-    L.bspgemm_result_row_ptr_device.restype = VP
-    L.bspgemm_result_col_idx_device.argtypes = [VP]
-    L.bspgemm_result_col_idx_device.restype = VP
-    L.bspgemm_result_download.argtypes = [VP, VP, VP, VP]
-    L.bspgemm_multiply_masked_count.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, PVP]
-    L.bspgemm_result_values_device.argtypes = [VP]
-    L.bspgemm_result_values_device.restype = VP
-    L.bspgemm_result_download_values.argtypes = [VP, VP, VP]
-    L.bspgemm_result_free.argtypes = [VP]
-    L.bspgemm_result_free.restype = None
-    L.bspgemm_matrix_from_result.argtypes = [VP, VP, C.c_int, PVP]
-    L.bspgemm_matrix_select.argtypes = [VP, VP, C.c_int, PVP]
-    L.bspgemm_matrix_from_result_where.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, PVP]
-    L.bspgemm_result_values_sum.argtypes = [VP, VP, C.POINTER(C.c_int64)]
-    L.bspgemm_triangle_count.argtypes = [VP, VP, C.POINTER(C.c_int64)]
-    L.bspgemm_ktruss.argtypes = [VP, VP, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.bspgemm_multiply_masked_dot.argtypes = [VP, VP, VP, VP, C.c_uint, PVP, C.POINTER(DotInfo)]
-    L.bspgemm_triangle_count_ex.argtypes = [VP, VP, C.c_int, C.POINTER(C.c_int64)]
-    L.bspgemm_ktruss_ex.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.bspgemm_bfs.argtypes = [VP, VP, C.c_int, VP, C.c_int, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.bspgemm_bfs_tree.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, PVP, C.POINTER(BfsTreeInfo)]
-    L.bspgemm_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.bspgemm_core_numbers.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.bspgemm_kcore.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
-    L.bspgemm_strongly_connected_components.argtypes = [VP, VP, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.bspgemm_graph_coloring.argtypes = [VP, VP, C.c_int, C.c_uint, PVP, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.bspgemm_label_propagation.argtypes = [VP, VP, VP, C.c_int, PVP, C.POINTER(LpInfo)]
-    L.bspgemm_local_clustering.argtypes = [VP, VP, C.c_uint, PVP, VP, VP, C.POINTER(LccInfo)]
-    L.bspgemm_pagerank.argtypes = [VP, VP, VP, C.c_int, C.c_double, C.c_int, C.c_double, VP, VP, C.POINTER(PrInfo)]
-    L.bspgemm_betweenness.argtypes = [VP, VP, C.c_int, VP, VP, VP, C.POINTER(BcInfo)]
-    L.bspgemm_maximal_matching.argtypes = [VP, VP, C.c_int, C.c_uint, PVP, VP, C.POINTER(MatchInfo)]
-    L.bspgemm_matrix_extract.argtypes = [VP, VP, C.c_int, VP, C.c_int, VP, C.c_uint, PVP, C.POINTER(ExtractInfo)]
-    L.bspgemm_matrix_extract_rows_of.argtypes = [VP, VP, VP, C.c_int, VP, C.c_int, C.c_uint, PVP, C.POINTER(ExtractInfo)]
-    L.bspgemm_matrix_setop.argtypes = [VP, VP, VP, C.c_int, PVP]
-    L.bspgemm_matrix_equal.argtypes = [VP, VP, VP, C.POINTER(C.c_int)]
-    L.bspgemm_matrix_symmetrize.argtypes = [VP, VP, C.c_uint, PVP]
-    L.bspgemm_closure.argtypes = [VP, VP, C.c_int, PVP, C.POINTER(C.c_int)]
-    L.bspgemm_multiply_accumulate.argtypes = [VP, VP, VP, VP, C.c_int, C.c_int, PVP]
-    L.bspgemm_closure_ex.argtypes = [VP, VP, C.c_uint, C.c_int, PVP, C.POINTER(C.c_int)]
-    L.bspgemm_row_work_prefix.argtypes = [VP, VP, VP, _I64P]
-    L.bspgemm_partition_rows.argtypes = [VP, VP, VP, C.c_int, _I32P]
-    L.bspgemm_last_stats.argtypes = [VP, C.POINTER(Stats)]
-    L.bspgemm_stats_at.argtypes = [VP, C.c_int, C.POINTER(Stats)]
-    IPP = C.POINTER(C.POINTER(C.c_int))
-    L.SpGEMM_hip.argtypes = [_I32P, VP, C.c_int, _I32P, _I32P, C.c_int, IPP, _I32P, C.c_int]
-    L.SpGEMM_hip_bigslice.argtypes = [_I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, IPP, _I32P,
-                                      C.POINTER(C.c_int), C.c_int, C.c_int]
-    L.SpGEMM_hip_mat.argtypes = [_I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, _I32P, _I32P]
-    L.SpGEMM_hip_masked.argtypes = [_I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, _I32P, _I32P, IPP, _I32P,
-                                    C.POINTER(C.c_int)]
-    L.bspgemm_dropin_set_device.argtypes = [C.c_int]
-    L.bspgemm_debug_fail_alloc.argtypes = [C.c_int]
-    L.bspgemm_debug_fail_alloc.restype = None
-    L.bspgemm_debug_alloc_state.argtypes = [_I64P]
-    L.bspgemm_debug_alloc_state.restype = None
-    L.bspgemm_comm_unique_id.argtypes = [C.c_char_p]
-    L.bspgemm_comm_create.argtypes = [VP, C.c_char_p, C.c_int, C.c_int, PVP]
-    L.bspgemm_comm_destroy.argtypes = [VP]
-    L.bspgemm_comm_destroy.restype = None
-    L.bspgemm_comm_stitch_row_ptr.argtypes = [VP, VP, _I32P, PVP, VP]
-    L.bspgemm_lengths_to_row_ptr.argtypes = [VP, VP, C.c_int, C.c_int, _I32P, VP, VP]
-    U32PP = C.POINTER(C.POINTER(C.c_uint32))
-    L.bspgemm_readCOO.argtypes = [C.c_char_p, U32PP, U32PP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                  C.POINTER(C.c_uint32)]
-    L.bspgemm_readCOO_ex.argtypes = [C.c_char_p, C.c_uint, U32PP, U32PP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                     C.POINTER(C.c_uint32)]
-    L.bspgemm_comm_create_host.argtypes = [VP, C.POINTER(HostTransport), C.c_int, C.c_int, PVP]
-    L.bspgemm_comm_rank.argtypes = [VP]
-    L.bspgemm_comm_size.argtypes = [VP]
-    L.bspgemm_comm_gather_col_idx.argtypes = [VP, VP, _I64P, C.c_int, VP]
-    L.SpGEMM_hip_multi.argtypes = [VP, _I32P, _I32P, C.c_int, _I32P, _I32P, C.c_int, IPP, _I32P, C.c_int]
-    L.bspgemm_write_mtx.argtypes = [C.c_char_p, C.c_int, C.c_int, _I32P, _I32P]
-    L.bspgemm_write_result_mtx.argtypes = [C.c_char_p, C.c_int, C.c_int, _I64P, _I32P]
-    L.bspgemm_csr_equal.argtypes = [_I32P, _I32P, _I32P, _I32P, C.c_int]
-    L.bspgemm_csr_equal64.argtypes = [_I32P, _I64P, _I32P, _I64P, C.c_int]
-    L.bspgemm_gen_uniform.argtypes = [C.c_int, C.c_int, C.c_uint64, IPP, IPP]
-    L.bspgemm_gen_rmat.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint64, IPP, IPP]
-    L.bspgemm_gen_powerlaw.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, IPP, IPP]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

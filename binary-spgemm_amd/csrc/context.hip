@@ -106,6 +106,19 @@ extern "C" void bspgemm_debug_alloc_state(int64_t out[4])
     out[3] = g.fired;
 }
 
+// Frees an operand's derived tables and forgets them: deg8 and the blocked table when `all`, the padded copy always.  The
+// states and nnz_pad are the caller's.
+static void drop_derived(const bspgemm_matrix *m, bool all)
+{
+    if (all) {
+        dev_free(m->d_deg8);
+        dev_free(m->d_blk16);
+        m->d_deg8 = nullptr;
+        m->d_blk16 = nullptr;
+    }
+    dev_free(m->d_col_pad); dev_free(m->d_row_ptr_pad); dev_free(m->d_ext);
+    m->d_col_pad = nullptr; m->d_row_ptr_pad = nullptr; m->d_ext = nullptr;
+}
 
 bspgemm_status ensure_deg8(const bspgemm_matrix *m)
 {
@@ -143,8 +156,7 @@ bspgemm_status ensure_pad(const bspgemm_matrix *m)
     auto bail = [&](bspgemm_status st) {
         hipStreamSynchronize(s);
         drop();
-        dev_free(m->d_col_pad); dev_free(m->d_row_ptr_pad); dev_free(m->d_ext);
-        m->d_col_pad = nullptr; m->d_row_ptr_pad = nullptr; m->d_ext = nullptr;
+        drop_derived(m, false);
         if (st != BSPGEMM_OK) m->pad_state = 0;                // a failed build decides nothing: the next use as B tries again
         return st;
     };
@@ -442,11 +454,7 @@ extern "C" void bspgemm_matrix_free(bspgemm_matrix *m)
         dev_free(m->d_row_ptr);
         dev_free(m->d_col_idx);
     }
-    dev_free(m->d_deg8);
-    dev_free(m->d_blk16);
-    dev_free(m->d_col_pad);
-    dev_free(m->d_row_ptr_pad);
-    dev_free(m->d_ext);
+    drop_derived(m, true);
     delete m;
 }
 extern "C" bspgemm_status bspgemm_matrix_download(bspgemm_context *ctx, const bspgemm_matrix *m, int *row_ptr, int *col_idx)
@@ -466,17 +474,8 @@ extern "C" bspgemm_status bspgemm_matrix_invalidate(bspgemm_matrix *m)
     if (!m) return FAIL(BSPGEMM_ERR_INVALID, "matrix is NULL");
     if (bspgemm_status st = use_device(m->ctx)) return st;
     HIPCHK(hipStreamSynchronize(m->ctx->stream));          // a multiply may still be reading the tables
-    dev_free(m->d_deg8);
-    dev_free(m->d_blk16);
-    dev_free(m->d_col_pad);
-    dev_free(m->d_row_ptr_pad);
-    dev_free(m->d_ext);
-    m->d_deg8 = nullptr;
-    m->d_blk16 = nullptr;
+    drop_derived(m, true);
     m->blk16_state = 0;
-    m->d_col_pad = nullptr;
-    m->d_row_ptr_pad = nullptr;
-    m->d_ext = nullptr;
     m->pad_state = 0;
     m->nnz_pad = 0;
     return BSPGEMM_OK;
@@ -521,84 +520,54 @@ bspgemm_status ensure_rows(bspgemm_context *ctx, size_t rows)
     return BSPGEMM_OK;
 }
 
-bspgemm_status ensure_ab(bspgemm_context *ctx, size_t pairs)
+static void result_cache_drop(bspgemm_context *ctx)
 {
-    if (pairs <= ctx->ab_cap) return BSPGEMM_OK;
+    for (auto &c : ctx->cache) if (c.p) { dev_free(c.p); c.p = nullptr; }
+}
+
+// The one grower of the flat workspaces: `*p` holds at least `need` elements of `elem` bytes afterwards, with a sixteenth
+// and `slack` elements to spare.  `retry`: an out-of-memory drops the cache of freed results, which may hold what is
+// missing, and asks once more.  A failure leaves *p NULL and *cap 0.
+static bspgemm_status grow(bspgemm_context *ctx, void **p, size_t *cap, size_t need, size_t elem, size_t slack, bool retry)
+{
+    if (need <= *cap) return BSPGEMM_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->ab);
-    ctx->ab = nullptr;
-    ctx->ab_cap = 0;
-    const size_t cap = pairs + pairs / 16 + 64;
-    HIPCHK(dev_alloc(&ctx->ab, cap * sizeof(int2)));
-    ctx->ab_cap = cap;
+    dev_free(*p);
+    *p = nullptr;
+    *cap = 0;
+    const size_t n = need + need / 16 + slack;
+    hipError_t e = dev_alloc_bytes(p, n * elem);
+    if (e == hipErrorOutOfMemory && retry) {
+        result_cache_drop(ctx);
+        (void)hipGetLastError();
+        e = dev_alloc_bytes(p, n * elem);
+    }
+    HIPCHK(e);
+    *cap = n;
     return BSPGEMM_OK;
 }
+template <class T>
+static bspgemm_status grow(bspgemm_context *ctx, T **p, size_t *cap, size_t need, size_t slack, bool retry)
+{
+    return grow(ctx, reinterpret_cast<void **>(p), cap, need, sizeof(T), slack, retry);
+}
+
+bspgemm_status ensure_ab(bspgemm_context *ctx, size_t pairs) { return grow(ctx, &ctx->ab, &ctx->ab_cap, pairs, 64, false); }
 
 // the flat prepass's first row per tile: `items` = nonzeros + rows of the row range (csrc/prepass.hip k_tile_rows)
 bspgemm_status ensure_tile_rows(bspgemm_context *ctx, size_t items)
 {
-    const size_t need = items / kRowWorkTile + 2;
-    if (need <= ctx->tile_row_cap) return BSPGEMM_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->tile_row);
-    ctx->tile_row = nullptr;
-    ctx->tile_row_cap = 0;
-    const size_t cap = need + need / 16 + 64;
-    HIPCHK(dev_alloc(&ctx->tile_row, cap * sizeof(int)));
-    ctx->tile_row_cap = cap;
-    return BSPGEMM_OK;
+    return grow(ctx, &ctx->tile_row, &ctx->tile_row_cap, items / kRowWorkTile + 2, 64, false);
 }
 
-bspgemm_status ensure_tmp(bspgemm_context *ctx, size_t ints)
-{
-    if (ints <= ctx->tmp_cap) return BSPGEMM_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->tmp);
-    ctx->tmp = nullptr;
-    ctx->tmp_cap = 0;
-    const size_t cap = ints + ints / 16 + 1024;
-    hipError_t e = dev_alloc(&ctx->tmp, cap * sizeof(int));
-    if (e == hipErrorOutOfMemory) {                     // the cache of freed results may hold what is missing
-        for (auto &c : ctx->cache) if (c.p) { dev_free(c.p); c.p = nullptr; }
-        (void)hipGetLastError();
-        e = dev_alloc(&ctx->tmp, cap * sizeof(int));
-    }
-    HIPCHK(e);
-    ctx->tmp_cap = cap;
-    return BSPGEMM_OK;
-}
+bspgemm_status ensure_tmp(bspgemm_context *ctx, size_t ints) { return grow(ctx, &ctx->tmp, &ctx->tmp_cap, ints, 1024, true); }
 
 // the counting product's values workspace: grows like tmp
-bspgemm_status ensure_tmpv(bspgemm_context *ctx, size_t ints)
-{
-    if (ints <= ctx->tmpv_cap) return BSPGEMM_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->tmpv);
-    ctx->tmpv = nullptr;
-    ctx->tmpv_cap = 0;
-    const size_t cap = ints + ints / 16 + 1024;
-    hipError_t e = dev_alloc(&ctx->tmpv, cap * sizeof(int));
-    if (e == hipErrorOutOfMemory) {                     // the cache of freed results may hold what is missing
-        for (auto &c : ctx->cache) if (c.p) { dev_free(c.p); c.p = nullptr; }
-        (void)hipGetLastError();
-        e = dev_alloc(&ctx->tmpv, cap * sizeof(int));
-    }
-    HIPCHK(e);
-    ctx->tmpv_cap = cap;
-    return BSPGEMM_OK;
-}
+bspgemm_status ensure_tmpv(bspgemm_context *ctx, size_t ints) { return grow(ctx, &ctx->tmpv, &ctx->tmpv_cap, ints, 1024, true); }
 
 bspgemm_status ensure_chunk_rows(bspgemm_context *ctx, size_t entries)
 {
-    if (entries <= ctx->chunk_cap) return BSPGEMM_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    dev_free(ctx->chunk_row);
-    ctx->chunk_row = nullptr;
-    ctx->chunk_cap = 0;
-    const size_t cap = entries + entries / 16 + 64;
-    HIPCHK(dev_alloc(&ctx->chunk_row, cap * sizeof(int)));
-    ctx->chunk_cap = cap;
-    return BSPGEMM_OK;
+    return grow(ctx, &ctx->chunk_row, &ctx->chunk_cap, entries, 64, false);
 }
 
 // result buffers: best fit from the context's cache of freed results, else hipMalloc
@@ -633,7 +602,7 @@ hipError_t result_alloc(bspgemm_context *ctx, void **out, size_t bytes)
         fprintf(stderr, "\n");
     }
     if (e == hipErrorOutOfMemory) {                     // drop the cache and retry once
-        for (auto &c : ctx->cache) if (c.p) { dev_free(c.p); c.p = nullptr; }
+        result_cache_drop(ctx);
         (void)hipGetLastError();
         e = dev_alloc(out, bytes);
     }
@@ -720,94 +689,62 @@ extern "C" bspgemm_status bspgemm_set_class_timing(bspgemm_context *ctx, int on)
     return BSPGEMM_OK;
 }
 
+// Every bspgemm_option once: where it lives, what bspgemm_set_option accepts and what it says when it refuses.
+namespace {
+enum OptKind { OPT_RANGE, OPT_LANES, OPT_FLAG, OPT_CLAMP };   // lo..hi; 0, 4, 16 or 64; any value, kept as 0/1; at least lo, clamped at hi
+struct OptRow {
+    bspgemm_option opt;
+    int bspgemm_context::*field;
+    OptKind kind;
+    int lo, hi;
+    const char *refusal;
+};
+const OptRow kOptions[] = {
+    {BSPGEMM_OPT_CLASS_STREAMS, &bspgemm_context::class_streams, OPT_RANGE, 1, 3, "class streams: 1..3"},
+    {BSPGEMM_OPT_BLOCKED_EXTENTS, &bspgemm_context::rw_blk, OPT_RANGE, -1, 1, "blocked extents: -1, 0 or 1"},
+    {BSPGEMM_OPT_CHECK, &bspgemm_context::check, OPT_FLAG, 0, 1, ""},
+    {BSPGEMM_OPT_SMALL_PATH, &bspgemm_context::small, OPT_RANGE, -1, 1, "small path: -1, 0 or 1"},
+    {BSPGEMM_OPT_PADDED_ROWS, &bspgemm_context::pad_rows, OPT_RANGE, -1, 1, "padded rows: -1, 0 or 1"},
+    {BSPGEMM_OPT_SHARED_SLOTS, &bspgemm_context::shared_slots, OPT_CLAMP, -1, kSharedSlotsMax, "shared slots: -1, 0 or a count"},
+    {BSPGEMM_OPT_DOT_LIGHT, &bspgemm_context::dot_light, OPT_RANGE, 0, INT_MAX, "dot light: 0 or a row length"},
+    {BSPGEMM_OPT_BFS_ALPHA, &bspgemm_context::bfs_alpha, OPT_RANGE, 1, INT_MAX, "bfs alpha: 1 or more"},
+    {BSPGEMM_OPT_BFS_BETA, &bspgemm_context::bfs_beta, OPT_RANGE, 1, INT_MAX, "bfs beta: 1 or more"},
+    {BSPGEMM_OPT_BFS_PUSH_LANES, &bspgemm_context::bfs_push_lanes, OPT_LANES, 0, 64, "bfs push lanes: 0, 4, 16 or 64"},
+    {BSPGEMM_OPT_LP_MIN_CLASS, &bspgemm_context::lp_min_class, OPT_RANGE, 0, 3, "lp min class: 0..3"},
+    {BSPGEMM_OPT_PR_MIN_CLASS, &bspgemm_context::pr_min_class, OPT_RANGE, 0, 3, "pr min class: 0..3"},
+    {BSPGEMM_OPT_BC_LANES, &bspgemm_context::bc_lanes, OPT_LANES, 0, 64, "bc lanes: 0, 4, 16 or 64"},
+    {BSPGEMM_OPT_EXTRACT_LANES, &bspgemm_context::extract_lanes, OPT_LANES, 0, 64, "extract lanes: 0, 4, 16 or 64"},
+    {BSPGEMM_OPT_MATCH_LANES, &bspgemm_context::match_lanes, OPT_LANES, 0, 64, "match lanes: 0, 4, 16 or 64"},
+};
+const OptRow *find_option(bspgemm_option opt)
+{
+    for (const OptRow &r : kOptions) if (r.opt == opt) return &r;
+    return nullptr;
+}
+}  // namespace
+
 extern "C" bspgemm_status bspgemm_set_option(bspgemm_context *ctx, bspgemm_option opt, int value)
 {
     if (!ctx) return FAIL(BSPGEMM_ERR_INVALID, "set_option: ctx is NULL");
-    switch (opt) {
-    case BSPGEMM_OPT_CLASS_STREAMS:
-        if (value < 1 || value > 3) return FAIL(BSPGEMM_ERR_INVALID, "class streams: 1..3");
-        ctx->class_streams = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_BLOCKED_EXTENTS:
-        if (value < -1 || value > 1) return FAIL(BSPGEMM_ERR_INVALID, "blocked extents: -1, 0 or 1");
-        ctx->rw_blk = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_CHECK:
-        ctx->check = value != 0;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_SMALL_PATH:
-        if (value < -1 || value > 1) return FAIL(BSPGEMM_ERR_INVALID, "small path: -1, 0 or 1");
-        ctx->small = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_PADDED_ROWS:
-        if (value < -1 || value > 1) return FAIL(BSPGEMM_ERR_INVALID, "padded rows: -1, 0 or 1");
-        ctx->pad_rows = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_SHARED_SLOTS:
-        if (value < -1) return FAIL(BSPGEMM_ERR_INVALID, "shared slots: -1, 0 or a count");
-        ctx->shared_slots = value > kSharedSlotsMax ? kSharedSlotsMax : value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_DOT_LIGHT:
-        if (value < 0) return FAIL(BSPGEMM_ERR_INVALID, "dot light: 0 or a row length");
-        ctx->dot_light = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_BFS_ALPHA:
-        if (value < 1) return FAIL(BSPGEMM_ERR_INVALID, "bfs alpha: 1 or more");
-        ctx->bfs_alpha = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_BFS_BETA:
-        if (value < 1) return FAIL(BSPGEMM_ERR_INVALID, "bfs beta: 1 or more");
-        ctx->bfs_beta = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_BFS_PUSH_LANES:
-        if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "bfs push lanes: 0, 4, 16 or 64");
-        ctx->bfs_push_lanes = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_LP_MIN_CLASS:
-        if (value < 0 || value > 3) return FAIL(BSPGEMM_ERR_INVALID, "lp min class: 0..3");
-        ctx->lp_min_class = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_PR_MIN_CLASS:
-        if (value < 0 || value > 3) return FAIL(BSPGEMM_ERR_INVALID, "pr min class: 0..3");
-        ctx->pr_min_class = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_BC_LANES:
-        if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "bc lanes: 0, 4, 16 or 64");
-        ctx->bc_lanes = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_EXTRACT_LANES:
-        if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "extract lanes: 0, 4, 16 or 64");
-        ctx->extract_lanes = value;
-        return BSPGEMM_OK;
-    case BSPGEMM_OPT_MATCH_LANES:
-        if (value != 0 && value != 4 && value != 16 && value != 64) return FAIL(BSPGEMM_ERR_INVALID, "match lanes: 0, 4, 16 or 64");
-        ctx->match_lanes = value;
-        return BSPGEMM_OK;
+    const OptRow *r = find_option(opt);
+    if (!r) return FAIL(BSPGEMM_ERR_INVALID, "unknown option");
+    bool ok = true;
+    switch (r->kind) {
+    case OPT_RANGE: ok = value >= r->lo && value <= r->hi; break;
+    case OPT_LANES: ok = value == 0 || value == 4 || value == 16 || value == 64; break;
+    case OPT_FLAG: value = value != 0; break;
+    case OPT_CLAMP: ok = value >= r->lo; if (value > r->hi) value = r->hi; break;
     }
-    return FAIL(BSPGEMM_ERR_INVALID, "unknown option");
+    if (!ok) return FAIL(BSPGEMM_ERR_INVALID, r->refusal);
+    ctx->*(r->field) = value;
+    return BSPGEMM_OK;
 }
 
 extern "C" int bspgemm_get_option(const bspgemm_context *ctx, bspgemm_option opt)
 {
     if (!ctx) return INT_MIN;
-    switch (opt) {
-    case BSPGEMM_OPT_CLASS_STREAMS: return ctx->class_streams;
-    case BSPGEMM_OPT_BLOCKED_EXTENTS: return ctx->rw_blk;
-    case BSPGEMM_OPT_CHECK: return ctx->check ? 1 : 0;
-    case BSPGEMM_OPT_SMALL_PATH: return ctx->small;
-    case BSPGEMM_OPT_PADDED_ROWS: return ctx->pad_rows;
-    case BSPGEMM_OPT_SHARED_SLOTS: return ctx->shared_slots;
-    case BSPGEMM_OPT_DOT_LIGHT: return ctx->dot_light;
-    case BSPGEMM_OPT_BFS_ALPHA: return ctx->bfs_alpha;
-    case BSPGEMM_OPT_BFS_BETA: return ctx->bfs_beta;
-    case BSPGEMM_OPT_BFS_PUSH_LANES: return ctx->bfs_push_lanes;
-    case BSPGEMM_OPT_LP_MIN_CLASS: return ctx->lp_min_class;
-    case BSPGEMM_OPT_PR_MIN_CLASS: return ctx->pr_min_class;
-    case BSPGEMM_OPT_BC_LANES: return ctx->bc_lanes;
-    case BSPGEMM_OPT_EXTRACT_LANES: return ctx->extract_lanes;
-    case BSPGEMM_OPT_MATCH_LANES: return ctx->match_lanes;
-    }
-    return INT_MIN;
+    const OptRow *r = find_option(opt);
+    return r ? ctx->*(r->field) : INT_MIN;
 }
 
 extern "C" int bspgemm_matrix_uses_padded_rows(const bspgemm_matrix *m)

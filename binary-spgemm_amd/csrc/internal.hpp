@@ -140,7 +140,7 @@ struct bspgemm_context {
     // environment knobs, read ONCE in bspgemm_create (include/bspgemm.h, "Environment")
     bool class_timing = false;          // bspgemm_set_class_timing / BSPGEMM_CLASS_TIMING=1: an event pair around every class launch
     int class_streams = 2;              // BSPGEMM_CLASS_STREAMS: streams the class launches alternate over (measured: 2 -8 %, 3 no better)
-    bool check = false;                 // BSPGEMM_CHECK: the exact flow never emits on unverified sizes
+    int check = 0;                      // BSPGEMM_CHECK (0/1): the exact flow never emits on unverified sizes
     int rw_blk = -1;                    // BSPGEMM_RW_BLK: 0 never / 1 always use the blocked extents table (default: per operand)
     int pad_rows = 0;                   // BSPGEMM_PAD_ROWS / BSPGEMM_OPT_PADDED_ROWS: 0 never (default), 1 always, -1 per operand: gather from a padded copy of B.col_idx
     int small = -1;                     // BSPGEMM_SMALL / BSPGEMM_OPT_SMALL_PATH: -1 automatic, 0 never, 1 whenever the product fits

@@ -26,6 +26,48 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert sorted(bspgemm.EXPORTS) == declared, "python binding list out of sync with the header"
 
 
+def _declared_parameter_counts():
+    """{function: number of parameters} from the prototypes of include/bspgemm.h (no prototype there has a function-pointer
+    parameter: the callbacks of bspgemm_host_transport are struct fields, which the `;` inside the braces keeps apart)"""
+    text = open(os.path.join(ROOT, "include", "bspgemm.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    counts = {}
+    for name, params in re.findall(r"\b(bspgemm_[a-zA-Z0-9_]+|SpGEMM_hip[a-zA-Z0-9_]*)\s*\(([^()]*)\)\s*;", text):
+        params = params.strip()
+        counts[name] = 0 if params in ("", "void") else params.count(",") + 1
+    return counts
+
+
+def test_every_export_is_bound_with_the_header_parameter_count():
+    """one table binds the ABI: every exported name has argtypes on bspgemm.lib(), as many as the header's prototype has
+    parameters -- a name without them would pass a 64-bit handle as a C int"""
+    L = bspgemm.lib()
+    counts = _declared_parameter_counts()
+    assert sorted(counts) == _declared_functions()
+    for name in bspgemm.EXPORTS:
+        argtypes = getattr(L, name).argtypes
+        assert argtypes is not None, "%s has no argtypes" % name
+        assert len(argtypes) == counts[name], "%s: %d argtypes, %d parameters in the header" % (name, len(argtypes), counts[name])
+    assert L.bspgemm_comm_inject_failure.restype is None
+    import ctypes
+    for name in ("bspgemm_last_error", "bspgemm_build_info", "bspgemm_status_string"):
+        assert getattr(L, name).restype is ctypes.c_char_p
+
+
+def test_info_as_dict_scalars_and_trailing_or_inner_arrays():
+    """as_dict of the info structs: scalars as int, an array field as a list of int -- LpInfo's array comes last, PrInfo's
+    in the middle"""
+    import ctypes
+    lp = bspgemm.LpInfo(3, 1, 7, 0, (ctypes.c_int64 * 4)(5, 6, 2 ** 40, 8))
+    assert lp.as_dict() == {"iterations": 3, "converged": 1, "communities": 7, "changed": 0, "class_vertices": [5, 6, 2 ** 40, 8]}
+    pr = bspgemm.PrInfo(2 ** 62, 9, 4, (ctypes.c_int64 * 4)(1, 2, 3, 4), 20, 0, 2, 1, 1)
+    d = pr.as_dict()
+    assert d == {"mass": 2 ** 62, "delta": 9, "dangling": 4, "class_vertices": [1, 2, 3, 4], "iterations": 20, "converged": 0,
+                 "method": 2, "transposed": 1, "canonicalised": 1}
+    assert all(type(v) is int for k, v in d.items() if k != "class_vertices") and all(type(v) is int for v in d["class_vertices"])
+    assert bspgemm.MatchInfo(pairs=2, lanes=16).as_dict() == {"pairs": 2, "entries_walked": 0, "hub_chunks": 0, "rounds": 0, "lanes": 16}
+
+
 def test_alloc_test_hooks_are_declared_and_idle_before_any_context():
     """the two test hooks of the device-memory gate: declared with these argument lists, exported, bound, and in a process
     that has created no context the gate has seen nothing (requests, live allocations, live bytes, injected failures)"""

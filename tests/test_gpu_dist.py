@@ -228,8 +228,6 @@ def test_spgemm_hip_multi_root_allocation_fails(world):
     import ctypes as C
     import time
     L = bspgemm.lib()
-    L.bspgemm_comm_inject_failure.argtypes = [C.c_void_p, C.c_int]
-    L.bspgemm_comm_inject_failure.restype = None
     rp, ci, n = bspgemm.gen_uniform(4096, 8, seed=17)
     rp, ci = bspgemm._i32(rp), bspgemm._i32(ci)
     make = _thread_transport(world)
@@ -261,7 +259,6 @@ def test_comm_agree_host_transport():
     """bspgemm_comm_agree: every rank gets the worst status of all ranks"""
     import ctypes as C
     L = bspgemm.lib()
-    L.bspgemm_comm_agree.argtypes = [C.c_void_p, C.c_int]
     world = 3
     make = _thread_transport(world)
 
@@ -287,9 +284,6 @@ def test_comm_agree_host_transport():
 def _rccl_comm_one_rank(ctx):
     import ctypes as C
     L = bspgemm.lib()
-    L.bspgemm_comm_inject_failure.argtypes = [C.c_void_p, C.c_int]
-    L.bspgemm_comm_inject_failure.restype = None
-    L.bspgemm_comm_agree.argtypes = [C.c_void_p, C.c_int]
     uid = C.create_string_buffer(128)
     assert L.bspgemm_comm_unique_id(uid) == 0
     comm = C.c_void_p()
@@ -352,8 +346,6 @@ def test_rank_local_allocation_failures_are_agreed_on(what, transport):
     import time
     from oracle import oracle as O
     L = bspgemm.lib()
-    L.bspgemm_comm_inject_failure.argtypes = [C.c_void_p, C.c_int]
-    L.bspgemm_comm_inject_failure.restype = None
     rp, ci, n = bspgemm.gen_uniform(4096, 8, seed=29)
     erp, eci = O.spgemm(rp, ci, rp, ci, n)
     rp, ci = bspgemm._i32(rp), bspgemm._i32(ci)

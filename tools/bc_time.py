@@ -19,53 +19,16 @@ vertices whose push search reaches at least half of what the best of 64 candidat
 --check compares the values under every BC_LANES with each other and (graphs of up to --numpy-max entries) with the numpy
 model of the definition.  No threshold: the numbers are the result."""
 import argparse
-import os
-import statistics
 import sys
-import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
-import bc_ref as B  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import show, stderr_of, timed_context, wall_ms
+import numpy as np
+import bspgemm
+import bc_ref as B
 
 LANES = (0, 4, 16, 64)
-
-
-def wall_ms(ctx, fn, reps):
-    out = []
-    for i in range(reps + 1):                                # (the first call is the warm-up)
-        ctx.synchronize()
-        t = time.perf_counter()
-        fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-    return out
-
-
-def show(name, ms):
-    print("    %-58s min %10.3f ms  median %10.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing line)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
 
 
 def generate(name):
@@ -98,15 +61,15 @@ def measure(ctx, ctx_timed, title, rp, ci, n, args):
     ok, values, whole = True, {}, {}
     for lanes in LANES:
         ctx.set_option("bc_lanes", lanes)
-        whole[lanes] = show("BC_LANES %d, %d sources (whole call)" % (lanes, k), wall_ms(ctx, lambda: ctx.betweenness(A, sources), args.reps))
+        whole[lanes] = show("    BC_LANES %d, %d sources (whole call)" % (lanes, k), wall_ms(ctx, lambda: (ctx.betweenness(A, sources), None)[1], args.reps))
         values[lanes] = ctx.betweenness(A, sources)
         print("      per source %.3f ms; info %s" % (whole[lanes] / max(k, 1), values[lanes][2]), flush=True)
     ctx.set_option("bc_lanes", 0)
-    ms0 = show("0 sources (checks, init, read-out)", wall_ms(ctx, lambda: ctx.betweenness(A, []), args.reps))
+    ms0 = show("    0 sources (checks, init, read-out)", wall_ms(ctx, lambda: (ctx.betweenness(A, []), None)[1], args.reps))
     singles, searches = [], []
     for s in sources:
-        singles.append(show("source %d alone" % s, wall_ms(ctx, lambda: ctx.betweenness(A, [s]), args.reps)))
-        searches.append(show("source %d, bspgemm_bfs_tree PUSH" % s, wall_ms(ctx, lambda: search(ctx, A, s), args.reps)))
+        singles.append(show("    source %d alone" % s, wall_ms(ctx, lambda: (ctx.betweenness(A, [s]), None)[1], args.reps)))
+        searches.append(show("    source %d, bspgemm_bfs_tree PUSH" % s, wall_ms(ctx, lambda: (search(ctx, A, s), None)[1], args.reps)))
         info = search(ctx, A, s)
         print("      the search: reached %d, depth %d, %d entries pushed" % (info["reached"], info["depth"], info["edges_pushed"]),
               flush=True)
@@ -151,9 +114,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the values with the numpy model and between the lane widths")
     args = ap.parse_args()
     ctx = bspgemm.Context(0)
-    os.environ["BSPGEMM_BC_TIMING"] = "1"                   # read once, in bspgemm_create: the second context alone
-    ctx_timed = bspgemm.Context(0)
-    del os.environ["BSPGEMM_BC_TIMING"]
+    ctx_timed = timed_context("BSPGEMM_BC_TIMING")
     ok = True
     for name in args.graphs:
         title, (rp, ci, n) = generate(name)

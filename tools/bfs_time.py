@@ -17,16 +17,12 @@ replacement (default_rng(9)).
 HIP events) and, for the whole call, what is left of the wall time beside the products -- matrix_from_result, the merge,
 the frees and the host's turn-arounds -- which bounds the merge's share from above."""
 import argparse
-import os
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import show, wall_ms
+import numpy as np
+import bspgemm
 
 
 def baseline(ctx, A, n, sources):
@@ -65,26 +61,6 @@ def bfs_dense(ctx, A, n, sources):
     level = np.full((len(sources), n), -1, np.int32)
     level[np.repeat(np.arange(len(sources)), np.diff(rp)), ci] = v
     return level, depth, complete
-
-
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
-
-
-def show(name, ms):
-    print("%-44s min %9.3f ms  median %9.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
 
 
 def measure(ctx, name, rp, ci, n, args):

@@ -20,18 +20,16 @@ stored edge more than one level down).  --sweeps adds alpha x beta under AUTO an
 on the first two sources.  The last line says whether AUTO with AT given was no slower than bspgemm_bfs, minimum against
 minimum, on every graph and source."""
 import argparse
-import os
 import statistics
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-from scipy.sparse import csr_matrix  # noqa: E402
-from scipy.sparse.csgraph import breadth_first_order  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import wall_ms
+import numpy as np
+from scipy.sparse import csr_matrix
+from scipy.sparse.csgraph import breadth_first_order
+import bspgemm
 
 LOG = None
 
@@ -41,21 +39,6 @@ def log(line):
     if LOG:
         LOG.write(line + "\n")
         LOG.flush()
-
-
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
 
 
 def dense(R, n):

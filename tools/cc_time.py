@@ -16,18 +16,14 @@ same size, (0.57, 0.19, 0.19), seed 1.
 model 4 nnz + 4 (n + 1) + 8 n (col_idx and row_ptr read by the hook, parent[] read and written by the jump; the gathers of
 parent[] come on top) against a copy rate of 6.0-6.3 TB/s."""
 import argparse
-import os
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-from scipy.sparse import csr_matrix  # noqa: E402
-from scipy.sparse.csgraph import connected_components  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import show, wall_ms
+import numpy as np
+from scipy.sparse import csr_matrix
+from scipy.sparse.csgraph import connected_components
+import bspgemm
 
 
 def baseline(A):
@@ -39,26 +35,6 @@ def baseline(A):
     smallest = np.full(ncomp, n, np.int64)
     np.minimum.at(smallest, comp, np.arange(n))
     return smallest[comp].astype(np.int32), int(ncomp)
-
-
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
-
-
-def show(name, ms):
-    print("%-44s min %9.3f ms  median %9.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
 
 
 def measure(ctx, name, rp, ci, n, args):

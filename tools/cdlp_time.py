@@ -21,55 +21,14 @@ and once per graph `symmetrize alone`, for comparison with the part above.
 --check compares the device's labels and counters with the host model where it ran, and the labels under every
 LP_MIN_CLASS with each other.  No threshold: the numbers are the result."""
 import argparse
-import os
 import re
-import statistics
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
-import cdlp_ref  # noqa: E402
-
-
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
-
-
-def show(name, ms):
-    print("    %-52s min %10.3f ms  median %10.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing line)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import host_baseline, show, stderr_of, timed_context, wall_ms
+import numpy as np
+import bspgemm
+import cdlp_ref
 
 
 def measure(ctx, ctx_timed, name, rp, ci, n, args):
@@ -77,8 +36,8 @@ def measure(ctx, ctx_timed, name, rp, ci, n, args):
     At = ctx_timed.upload(rp, ci, n)
     K = args.iterations
     print("%s: n = %d, nnz = %d, %d iterations" % (name, n, A.nnz, K), flush=True)
-    show("symmetrize alone", wall_ms(ctx, lambda: [ctx.symmetrize(A, drop_diagonal=True)], args.reps))
-    show("baseline: download of the operand", wall_ms(ctx, lambda: (A.download(), [])[1], args.reps))
+    show("    symmetrize alone", wall_ms(ctx, lambda: [ctx.symmetrize(A, drop_diagonal=True)], args.reps))
+    show("    baseline: download of the operand", wall_ms(ctx, lambda: (A.download(), [])[1], args.reps))
     ok, labels, res = True, {}, {}
 
     def run():
@@ -87,7 +46,7 @@ def measure(ctx, ctx_timed, name, rp, ci, n, args):
 
     for min_class in (0, 1, 2, 3):
         ctx.set_option("lp_min_class", min_class)
-        ms = show("label_propagation, LP_MIN_CLASS %d (whole call)" % min_class, wall_ms(ctx, run, args.reps))
+        ms = show("    label_propagation, LP_MIN_CLASS %d (whole call)" % min_class, wall_ms(ctx, run, args.reps))
         info = res["info"]
         print("      %d iterations, converged %d, %d communities, classes %s" %
               (info["iterations"], info["converged"], info["communities"], info["class_vertices"]), flush=True)
@@ -109,21 +68,14 @@ def measure(ctx, ctx_timed, name, rp, ci, n, args):
             k = int(m.group(1))
             print("      per iteration: %.1f us in the kernels, %.1f us in its read-back" %
                   (1e3 * float(m.group(2)) / k, 1e3 * float(m.group(3)) / k), flush=True)
-    if A.nnz > args.numpy_max:
-        print("      baseline: download + numpy model: not run (more than %d stored entries)" % args.numpy_max, flush=True)
-    else:
-        t = time.perf_counter()
-        h_rp, h_ci = A.download()
-        exp = cdlp_ref.label_propagation(h_rp, h_ci, n, K)
-        ms = (time.perf_counter() - t) * 1e3
-        print("      %-50s     %10.3f ms  (once): %.0f x the whole call" % ("baseline: download + numpy model", ms, ms / whole),
-              flush=True)
-        if args.check:
-            info = res["info"]
-            same = np.array_equal(labels[0], exp[0]) and exp[1:] == (info["iterations"], info["converged"], info["changed"],
-                                                                      info["communities"])
-            ok &= same
-            print("      check against the numpy model: %s" % ("equal" if same else "DIFFERENT"), flush=True)
+
+    def same(exp):
+        info = res["info"]
+        return np.array_equal(labels[0], exp[0]) and exp[1:] == (info["iterations"], info["converged"], info["changed"],
+                                                                  info["communities"])
+
+    ok &= host_baseline("numpy model", lambda: cdlp_ref.label_propagation(*A.download(), n, K), args.numpy_max, A.nnz, whole,
+                        same if args.check else None, check_label="the numpy model")
     At.free()
     A.free()
     return ok
@@ -140,9 +92,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the labels with the host model and between the classes")
     args = ap.parse_args()
     ctx = bspgemm.Context(0)
-    os.environ["BSPGEMM_LP_TIMING"] = "1"                   # read once, in bspgemm_create: the second context alone
-    ctx_timed = bspgemm.Context(0)
-    del os.environ["BSPGEMM_LP_TIMING"]
+    ctx_timed = timed_context("BSPGEMM_LP_TIMING")
     ok = True
     for scale in args.scales:
         ok &= measure(ctx, ctx_timed, "Graph500-skew R-MAT %d, edge factor %d, (0.57, 0.19, 0.19)" % (scale, args.ef),

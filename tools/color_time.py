@@ -20,20 +20,14 @@ generator with --powerlaw vertices, mean degree --ef, alpha 2.1.  Per graph and 
 and once per graph `symmetrize alone`, for comparison with the part above.
 --check compares the device's colours with each host baseline that ran.  No threshold: the numbers are the result."""
 import argparse
-import os
 import re
-import statistics
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
-import color_ref  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import host_baseline, show, stderr_of, timed_context, wall_ms
+import numpy as np
+import bspgemm
+import color_ref
 
 ORDERS = ("natural", "random", "largest")
 SEED = 0
@@ -60,47 +54,12 @@ def host_networkx(A, order):
     return np.fromiter((by_vertex[v] for v in range(n)), np.int32, n)
 
 
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
-
-
-def show(name, ms):
-    print("    %-52s min %10.3f ms  median %10.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing line)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
-
-
 def measure(ctx, ctx_timed, name, rp, ci, n, args):
     A = ctx.upload(rp, ci, n)
     At = ctx_timed.upload(rp, ci, n)
     print("%s: n = %d, nnz = %d" % (name, n, A.nnz), flush=True)
-    show("symmetrize alone", wall_ms(ctx, lambda: [ctx.symmetrize(A, drop_diagonal=True)], args.reps))
-    show("baseline: download of the operand", wall_ms(ctx, lambda: (A.download(), [])[1], args.reps))
+    show("    symmetrize alone", wall_ms(ctx, lambda: [ctx.symmetrize(A, drop_diagonal=True)], args.reps))
+    show("    baseline: download of the operand", wall_ms(ctx, lambda: (A.download(), [])[1], args.reps))
     ok = True
     for order in ORDERS:
         res = {}
@@ -109,7 +68,7 @@ def measure(ctx, ctx_timed, name, rp, ci, n, args):
             P, res["colors"], res["rounds"] = ctx.graph_coloring(A, order, SEED)
             return [P]
 
-        whole = show("graph_coloring %-8s (whole call)" % order, wall_ms(ctx, run, args.reps))
+        whole = show("    graph_coloring %-8s (whole call)" % order, wall_ms(ctx, run, args.reps))
         print("      %d colours, %d launches (rounds)" % (res["colors"], res["rounds"]), flush=True)
         stderr_of(lambda: ctx_timed.graph_coloring(At, order, SEED)[0].free())  # warm-up: workspaces
         lines = stderr_of(lambda: ctx_timed.graph_coloring(At, order, SEED)[0].free())
@@ -127,18 +86,7 @@ def measure(ctx, ctx_timed, name, rp, ci, n, args):
             P.free()
         for label, fn, limit in (("numpy level-synchronous model", host_model, args.numpy_max),
                                  ("networkx.greedy_color", host_networkx, args.nx_max)):
-            if A.nnz > limit:
-                print("      baseline: download + %s: not run (more than %d stored entries)" % (label, limit), flush=True)
-                continue
-            t = time.perf_counter()
-            exp = fn(A, order)
-            ms = (time.perf_counter() - t) * 1e3
-            print("      %-50s     %10.3f ms  (once): %.0f x the whole call" % ("baseline: download + " + label, ms, ms / whole),
-                  flush=True)
-            if got is not None:
-                same = np.array_equal(got, exp)
-                ok &= same
-                print("      check against %s: %s" % (label, "equal" if same else "DIFFERENT"), flush=True)
+            ok &= host_baseline(label, lambda: fn(A, order), limit, A.nnz, whole, got)
     At.free()
     A.free()
     return ok
@@ -155,9 +103,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the colours with the host baselines that run")
     args = ap.parse_args()
     ctx = bspgemm.Context(0)
-    os.environ["BSPGEMM_COLOR_TIMING"] = "1"                # read once, in bspgemm_create: the second context alone
-    ctx_timed = bspgemm.Context(0)
-    del os.environ["BSPGEMM_COLOR_TIMING"]
+    ctx_timed = timed_context("BSPGEMM_COLOR_TIMING")
     ok = True
     for scale in args.scales:
         ok &= measure(ctx, ctx_timed, "Graph500-skew R-MAT %d, edge factor %d, (0.57, 0.19, 0.19)" % (scale, args.ef),

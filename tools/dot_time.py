@@ -22,13 +22,11 @@ import argparse
 import os
 import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import ROOT, wall_ms
+import numpy as np
+import bspgemm
 
 GRAPHS = {"g500-18": (18, 16, (0.57, 0.19, 0.19)), "rmat-18": (18, 16, (0.30, 0.25, 0.25)), "rmat-20": (20, 16, (0.30, 0.25, 0.25))}
 
@@ -40,18 +38,6 @@ def symmetrise(rp, ci, n):
     key = np.unique((r[r != c] << 32) | c[r != c])
     counts = np.bincount(key >> 32, minlength=n)
     return np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), (key & 0xFFFFFFFF).astype(np.int32)
-
-
-def wall_ms(ctx, fn, reps):
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-    return out
 
 
 class Log:
@@ -66,7 +52,7 @@ class Log:
 
 
 def show(log, name, ms, extra=""):
-    log("%-62s min %9.3f ms  median %9.3f ms  %s" % (name, min(ms), statistics.median(ms), extra))
+    log(timing_common.line(name, ms, "  " + extra))
     return min(ms)
 
 

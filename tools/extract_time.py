@@ -19,53 +19,19 @@ both edge factor 16, seed 1, symmetrized without the diagonal on the device (S).
 --check verifies first that the routes give equal operands (always done for 1 and 2's product routes; --check adds scipy's).
 No threshold: the numbers are the result."""
 import argparse
-import os
 import statistics
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-from scipy.sparse import csr_matrix  # noqa: E402
-import bspgemm  # noqa: E402
-
-
-def wall_ms(ctx, fn, reps, warm=1):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up (warm = 0: none)"""
-    out = []
-    for i in range(1 - warm, reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import stderr_of, timed_context, wall_ms
+import numpy as np
+from scipy.sparse import csr_matrix
+import bspgemm
 
 
 def show(name, ms):
     print("    %-64s min %10.3f  median %10.3f  max %10.3f ms" % (name, min(ms), statistics.median(ms), max(ms)), flush=True)
     return statistics.median(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing line)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
 
 
 def same_operand(ctx, X, Y):
@@ -210,9 +176,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare with scipy's result too (graphs up to --scipy-max)")
     args = ap.parse_args()
     ctx = bspgemm.Context(0)
-    os.environ["BSPGEMM_EXTRACT_TIMING"] = "1"              # read once, in bspgemm_create: the second context alone
-    ctx_timed = bspgemm.Context(0)
-    del os.environ["BSPGEMM_EXTRACT_TIMING"]
+    ctx_timed = timed_context("BSPGEMM_EXTRACT_TIMING")
     ok = True
     for g in args.graphs:
         if g.startswith("rmat") and g[4:].isdigit():

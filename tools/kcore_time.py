@@ -19,18 +19,13 @@ generator with --powerlaw vertices, mean degree --ef, alpha 2.1.  Per graph:
               networkx.core_number (pure Python)               graphs of up to --nx-max stored entries
 --check compares the device's core numbers with each host baseline that ran.  No threshold: the numbers are the result."""
 import argparse
-import os
-import statistics
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-from scipy.sparse import csr_matrix  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import host_baseline, show, stderr_of, timed_context, wall_ms
+import numpy as np
+from scipy.sparse import csr_matrix
+import bspgemm
 
 
 def host_simple(rp, ci, n):
@@ -86,41 +81,6 @@ def host_networkx(A):
     return np.fromiter((by_vertex[v] for v in range(n)), np.int32, n)
 
 
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
-
-
-def show(name, ms):
-    print("    %-52s min %10.3f ms  median %10.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing line)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
-
-
 def measure(ctx, ctx_timed, name, rp, ci, n, args):
     A = ctx.upload(rp, ci, n)
     print("%s: n = %d, nnz = %d" % (name, n, A.nnz), flush=True)
@@ -130,16 +90,16 @@ def measure(ctx, ctx_timed, name, rp, ci, n, args):
         R, res["top"], res["rounds"] = ctx.core_numbers(A)
         return [R]
 
-    whole = show("core_numbers (whole call)", wall_ms(ctx, run, args.reps))
+    whole = show("    core_numbers (whole call)", wall_ms(ctx, run, args.reps))
     print("    degeneracy %d, %d peel launches" % (res["top"], res["rounds"]), flush=True)
-    show("symmetrize alone", wall_ms(ctx, lambda: [ctx.symmetrize(A, drop_diagonal=True)], args.reps))
+    show("    symmetrize alone", wall_ms(ctx, lambda: [ctx.symmetrize(A, drop_diagonal=True)], args.reps))
     At = ctx_timed.upload(rp, ci, n)
     stderr_of(lambda: ctx_timed.core_numbers(At)[0].free())  # warm-up: workspaces, result cache
     lines = stderr_of(lambda: ctx_timed.core_numbers(At)[0].free())
     At.free()
     for ln in lines.splitlines():
         print("    parts: " + ln.strip(), flush=True)
-    show("baseline: download of the operand", wall_ms(ctx, lambda: (A.download(), [])[1], args.reps))
+    show("    baseline: download of the operand", wall_ms(ctx, lambda: (A.download(), [])[1], args.reps))
     got = None
     if args.check:
         R = ctx.core_numbers(A)[0]
@@ -148,18 +108,7 @@ def measure(ctx, ctx_timed, name, rp, ci, n, args):
     ok = True
     for label, fn, limit in (("numpy level-synchronous peeling", host_numpy, args.numpy_max),
                              ("networkx.core_number", host_networkx, args.nx_max)):
-        if A.nnz > limit:
-            print("    baseline: download + %s: not run (more than %d stored entries)" % (label, limit), flush=True)
-            continue
-        t = time.perf_counter()
-        exp = fn(A)
-        ms = (time.perf_counter() - t) * 1e3
-        print("    %-52s     %10.3f ms  (once): %.0f x the whole call" % ("baseline: download + " + label, ms, ms / whole),
-              flush=True)
-        if got is not None:
-            same = np.array_equal(got, exp)
-            ok &= same
-            print("    check against %s: %s" % (label, "equal" if same else "DIFFERENT"), flush=True)
+        ok &= host_baseline(label, lambda: fn(A), limit, A.nnz, whole, got, indent="    ")
     A.free()
     return ok
 
@@ -175,9 +124,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the core numbers with the host baselines that run")
     args = ap.parse_args()
     ctx = bspgemm.Context(0)
-    os.environ["BSPGEMM_KCORE_TIMING"] = "1"                # read once, in bspgemm_create: the second context alone
-    ctx_timed = bspgemm.Context(0)
-    del os.environ["BSPGEMM_KCORE_TIMING"]
+    ctx_timed = timed_context("BSPGEMM_KCORE_TIMING")
     ok = True
     for scale in args.scales:
         ok &= measure(ctx, ctx_timed, "Graph500-skew R-MAT %d, edge factor %d, (0.57, 0.19, 0.19)" % (scale, args.ef),

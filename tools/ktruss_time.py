@@ -18,16 +18,12 @@ One process; every timed call is warmed up once and repeated --reps times (minim
      the new operand) -- the only way before the select existed.
 (iii) bspgemm_ktruss(k) and bspgemm_triangle_count on that graph, wall time around calls that end synchronised."""
 import argparse
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import wall_ms
+import torch
+import numpy as np
+import bspgemm
 
 
 def symmetrise(rp, ci, n):
@@ -61,21 +57,9 @@ def event_ms(stream, fn, reps):
     return out
 
 
-def wall_ms(ctx, fn, reps):
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-    return out
-
-
 def show(name, ms, nbytes=None, extra=""):
     rate = "  %8.1f GB/s" % (nbytes / min(ms) / 1e6) if nbytes else ""
-    print("%-58s min %9.3f ms  median %9.3f ms%s  %s" % (name, min(ms), statistics.median(ms), rate, extra), flush=True)
+    timing_common.show(name, ms, rate + "  " + extra)
 
 
 class _Freed:

@@ -19,30 +19,14 @@ Per graph:
 import argparse
 import os
 import re
-import statistics
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import ROOT, stderr_of, timed_context, wall_ms
+import numpy as np
+import bspgemm
 
 GRAPHS = {"g500-18": (18, 16, (0.57, 0.19, 0.19)), "rmat-18": (18, 16, (0.30, 0.25, 0.25)), "rmat-20": (20, 16, (0.30, 0.25, 0.25))}
-
-
-def wall_ms(ctx, fn, reps):
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-    return out
 
 
 class Log:
@@ -57,30 +41,13 @@ class Log:
 
 
 def show(log, name, ms, extra=""):
-    log("%-62s min %9.3f ms  median %9.3f ms  %s" % (name, min(ms), statistics.median(ms), extra))
+    log(timing_common.line(name, ms, "  " + extra))
     return min(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing lines)"""
-    sys.stderr.flush()
-    with tempfile.TemporaryFile() as f:
-        saved = os.dup(2)
-        os.dup2(f.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        f.seek(0)
-        return f.read().decode(errors="replace")
 
 
 def stage_split(log, mode, rp, ci, n, reps):
     """the library's own stage lines under BSPGEMM_LCC_TIMING=mode, the best of reps per direction; returns the counts"""
-    os.environ["BSPGEMM_LCC_TIMING"] = str(mode)
-    ctx = bspgemm.Context(0)                                  # (the environment is read in bspgemm_create)
-    del os.environ["BSPGEMM_LCC_TIMING"]
+    ctx = timed_context("BSPGEMM_LCC_TIMING", str(mode))
     A = ctx.upload(rp, ci, n)
     out = {}
     for directed in (False, True):

@@ -19,51 +19,14 @@ Graphs: rmatS = the benchmark's R-MAT (0.30, 0.25, 0.25), seed 1, scale S, edge 
 --check compares the device's ranks with the numpy model of the definition (graphs of up to --numpy-max entries) and the
 variants with each other.  No threshold: the numbers are the result."""
 import argparse
-import os
-import statistics
 import sys
-import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
-import pagerank_ref as P  # noqa: E402
-
-
-def wall_ms(ctx, fn, reps):
-    out = []
-    for i in range(reps + 1):                                # (the first call is the warm-up)
-        ctx.synchronize()
-        t = time.perf_counter()
-        fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-    return out
-
-
-def show(name, ms):
-    print("    %-58s min %10.3f ms  median %10.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing line)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import show, stderr_of, timed_context, wall_ms
+import numpy as np
+import bspgemm
+import pagerank_ref as P
 
 
 def generate(name):
@@ -100,13 +63,13 @@ def measure(ctx, ctx_timed, title, rp, ci, n, args):
     nnz = A.nnz
     must = 12 * nnz + 36 * n
     print("%s: n = %d, nnz = %d, %d iterations; an iteration must move %.1f MB" % (title, n, nnz, K, must / 1e6), flush=True)
-    show("transpose alone", wall_ms(ctx, lambda: ctx.transpose(A).free(), args.reps))
+    show("    transpose alone", wall_ms(ctx, lambda: ctx.transpose(A).free(), args.reps))
     ok, ranks, whole = True, {}, {}
     for what, at, method in (("PULL, AT given", AT, bspgemm.PR_PULL), ("PULL, AT NULL", None, bspgemm.PR_PULL),
                              ("PUSH", None, bspgemm.PR_PUSH)):
-        ms = show("%s, %d iterations (whole call)" % (what, K), wall_ms(ctx, lambda: ctx.pagerank(A, at, method, 0.85, K), args.reps))
-        ms0 = show("%s, 0 iterations (checks, transpose, lists, read-out)" % what,
-                   wall_ms(ctx, lambda: ctx.pagerank(A, at, method, 0.85, 0), args.reps))
+        ms = show("    %s, %d iterations (whole call)" % (what, K), wall_ms(ctx, lambda: (ctx.pagerank(A, at, method, 0.85, K), None)[1], args.reps))
+        ms0 = show("    %s, 0 iterations (checks, transpose, lists, read-out)" % what,
+                   wall_ms(ctx, lambda: (ctx.pagerank(A, at, method, 0.85, 0), None)[1], args.reps))
         per = (ms - ms0) / K
         print("      per iteration %.3f ms: %.0f GB/s against the %.1f MB" % (per, must / per / 1e6 if per > 0 else 0, must / 1e6),
               flush=True)
@@ -117,7 +80,7 @@ def measure(ctx, ctx_timed, title, rp, ci, n, args):
                                                                      info["class_vertices"]), flush=True)
     for min_class in (0, 1, 2, 3):
         ctx.set_option("pr_min_class", min_class)
-        show("PULL, AT given, PR_MIN_CLASS %d" % min_class, wall_ms(ctx, lambda: ctx.pagerank(A, AT, bspgemm.PR_PULL, 0.85, K), args.reps))
+        show("    PULL, AT given, PR_MIN_CLASS %d" % min_class, wall_ms(ctx, lambda: (ctx.pagerank(A, AT, bspgemm.PR_PULL, 0.85, K), None)[1], args.reps))
         got = ctx.pagerank(A, AT, bspgemm.PR_PULL, 0.85, K)
         print("      classes %s" % got[2]["class_vertices"], flush=True)
         if args.check:
@@ -164,9 +127,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the ranks with the numpy model and between the variants")
     args = ap.parse_args()
     ctx = bspgemm.Context(0)
-    os.environ["BSPGEMM_PR_TIMING"] = "1"                   # read once, in bspgemm_create: the second context alone
-    ctx_timed = bspgemm.Context(0)
-    del os.environ["BSPGEMM_PR_TIMING"]
+    ctx_timed = timed_context("BSPGEMM_PR_TIMING")
     ok = True
     for name in args.graphs:
         title, (rp, ci, n) = generate(name)

@@ -19,19 +19,14 @@ sweep of the model 4 nnz + 4 (n + 1) (col_idx and row_ptr; the gathers of the pe
 rate of 6.0 TB/s, and the trim / forward / backward split of the same call on a second context created under
 BSPGEMM_SCC_TIMING."""
 import argparse
-import os
-import statistics
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-from scipy.sparse import csr_matrix  # noqa: E402
-from scipy.sparse.csgraph import connected_components  # noqa: E402
-import bspgemm  # noqa: E402
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import show, stderr_of, timed_context, wall_ms
+import numpy as np
+from scipy.sparse import csr_matrix
+from scipy.sparse.csgraph import connected_components
+import bspgemm
 
 
 def baseline(A):
@@ -45,41 +40,6 @@ def baseline(A):
     smallest = np.full(ncomp, n, np.int64)
     np.minimum.at(smallest, comp, np.arange(n))
     return smallest[comp].astype(np.int32), int(ncomp)
-
-
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
-
-
-def show(name, ms):
-    print("%-44s min %9.3f ms  median %9.3f ms" % (name, min(ms), statistics.median(ms)), flush=True)
-    return min(ms)
-
-
-def stderr_of(fn):
-    """what fn() writes to file descriptor 2 (the library's timing line)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
 
 
 def measure(ctx, ctx_timed, name, rp, ci, n, args):
@@ -130,9 +90,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the two label arrays first")
     args = ap.parse_args()
     ctx = bspgemm.Context(0)
-    os.environ["BSPGEMM_SCC_TIMING"] = "1"                  # read once, in bspgemm_create: the second context alone
-    ctx_timed = bspgemm.Context(0)
-    del os.environ["BSPGEMM_SCC_TIMING"]
+    ctx_timed = timed_context("BSPGEMM_SCC_TIMING")
     ok = measure(ctx, ctx_timed, "R-MAT %d, edge factor %d, (0.45, 0.15, 0.15)" % (args.scale, args.ef),
                  *bspgemm.gen_rmat(args.scale, args.ef, (0.45, 0.15, 0.15), seed=1), args)
     ok &= measure(ctx, ctx_timed, "Graph500-skew R-MAT %d, edge factor %d, (0.57, 0.19, 0.19)" % (args.scale, args.ef),

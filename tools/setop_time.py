@@ -15,37 +15,16 @@ identity:
 Entries touched, for the rate per entry: a setop reads nnz(A) + nnz(B) entries, the select nnz(G).  --check compares every
 baseline's operand with the setop's, entry for entry, before anything is timed."""
 import argparse
-import os
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "binary-spgemm_amd"))
-import torch  # noqa: E402,F401  (first: one HIP runtime in the process)
-import numpy as np  # noqa: E402
-import bspgemm  # noqa: E402
-
-
-def wall_ms(ctx, fn, reps):
-    """fn() returns the handles to free outside the timed window; the first call is the warm-up"""
-    out = []
-    for i in range(reps + 1):
-        ctx.synchronize()
-        t = time.perf_counter()
-        hs = fn()
-        ctx.synchronize()
-        if i:
-            out.append((time.perf_counter() - t) * 1e3)
-        for h in hs:
-            h.free()
-    return out
+import timing_common  # noqa: F401  (first: the paths, and torch before bspgemm)
+from timing_common import wall_ms
+import numpy as np
+import bspgemm
 
 
 def show(name, ms, entries=None):
-    rate = "  %7.2f G entries/s" % (entries / min(ms) / 1e6) if entries else ""
-    print("%-58s min %9.3f ms  median %9.3f ms%s" % (name, min(ms), statistics.median(ms), rate), flush=True)
-    return min(ms)
+    return timing_common.show(name, ms, "  %7.2f G entries/s" % (entries / min(ms) / 1e6) if entries else "")
 
 
 def measure(ctx, name, rp, ci, n, args):
