@@ -57,6 +57,8 @@ OPTIONS = {"class_streams": 1, "blocked_extents": 2, "check": 3, "small_path": 4
 SUPPORT_METHODS = {"product": 0, "dot": 1}                                              # bspgemm_support_method
 BFS_DIRECTIONS = {"auto": 0, "push": 1, "pull": 2}                                      # bspgemm_bfs_direction
 EXTRACT_KEEP_SHAPE = 1                                                                   # BSPGEMM_EXTRACT_KEEP_SHAPE
+WEIGHTS_SYMMETRIC = 1                                                                    # BSPGEMM_WEIGHTS_SYMMETRIC
+SSSP_DELTA_C = 32                                                                        # BSPGEMM_SSSP_DELTA_C
 LCC_DIRECTED = 1                                                                         # BSPGEMM_LCC_DIRECTED
 PR_AUTO, PR_PULL, PR_PUSH = 0, 1, 2                                                      # bspgemm_pr_method
 
@@ -112,6 +114,18 @@ class MatchInfo(_Info):
     """bspgemm_match_info"""
     _fields_ = [("pairs", C.c_int64), ("entries_walked", C.c_int64), ("hub_chunks", C.c_int64), ("rounds", C.c_int),
                 ("lanes", C.c_int)]
+
+
+class SsspInfo(_Info):
+    """bspgemm_sssp_info"""
+    _fields_ = [("delta", C.c_uint64), ("dist_max", C.c_uint64), ("reached", C.c_int64), ("entries_walked", C.c_int64),
+                ("improved", C.c_int64), ("hub_chunks", C.c_int64), ("rounds", C.c_int), ("buckets", C.c_int),
+                ("lanes", C.c_int), ("reserved", C.c_int)]
+
+
+class SsspParams(C.Structure):
+    """bspgemm_sssp_params"""
+    _fields_ = [("delta", C.c_uint64), ("lanes", C.c_int), ("reserved", C.c_int)]
 
 
 class ExtractInfo(_Info):
@@ -209,6 +223,13 @@ _SIGNATURES = {
     "bspgemm_pagerank": (_INT, [_VP, _VP, _VP, C.c_int, C.c_double, C.c_int, C.c_double, _VP, _VP, C.POINTER(PrInfo)]),
     "bspgemm_betweenness": (_INT, [_VP, _VP, C.c_int, _VP, _VP, _VP, C.POINTER(BcInfo)]),
     "bspgemm_maximal_matching": (_INT, [_VP, _VP, C.c_int, C.c_uint, _PVP, _VP, C.POINTER(MatchInfo)]),
+    "bspgemm_weights_upload": (_INT, [_VP, _VP, _VP, _PVP]),
+    "bspgemm_weights_hashed": (_INT, [_VP, _VP, C.c_uint, C.c_uint32, C.c_uint32, C.c_uint, _PVP]),
+    "bspgemm_weights_download": (_INT, [_VP, _VP, _VP]),
+    "bspgemm_weights_nnz": (C.c_int64, [_VP]),
+    "bspgemm_weights_sum": (C.c_uint64, [_VP]),
+    "bspgemm_weights_free": (None, [_VP]),
+    "bspgemm_sssp": (_INT, [_VP, _VP, _VP, C.c_int, C.POINTER(SsspParams), _VP, _VP, C.POINTER(SsspInfo)]),
     "bspgemm_matrix_extract": (_INT, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_uint, _PVP, C.POINTER(ExtractInfo)]),
     "bspgemm_matrix_extract_rows_of": (_INT, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_uint, _PVP, C.POINTER(ExtractInfo)]),
     "bspgemm_matrix_setop": (_INT, [_VP, _VP, _VP, C.c_int, _PVP]),
@@ -714,6 +735,36 @@ class Context:
              "bspgemm_maximal_matching")
         return Matrix(self, m, keep=None), mates, info.as_dict()
 
+    def weights_upload(self, A, w):
+        """bspgemm_weights_upload: a Weights handle with w[k] (uint32) as the length of stored entry k of A, that is of
+        A.download()[1][k]"""
+        w = np.ascontiguousarray(w, dtype=np.uint32).reshape(-1)
+        if w.size != A.nnz:
+            raise ValueError("%d weights for an operand of %d entries" % (w.size, A.nnz))
+        h = C.c_void_p()
+        _chk(lib().bspgemm_weights_upload(self._h, A._h, w.ctypes.data if w.size else None, C.byref(h)), "bspgemm_weights_upload")
+        return Weights(self, h, A)
+
+    def weights_hashed(self, A, seed, wmin, wmax, symmetric=False):
+        """bspgemm_weights_hashed: a Weights handle with the hashed lengths of include/bspgemm.h in [wmin, wmax], generated on
+        the device; symmetric=True: both directions of an edge weigh the same"""
+        h = C.c_void_p()
+        _chk(lib().bspgemm_weights_hashed(self._h, A._h, int(seed) & 0xFFFFFFFF, int(wmin), int(wmax),
+                                          WEIGHTS_SYMMETRIC if symmetric else 0, C.byref(h)), "bspgemm_weights_hashed")
+        return Weights(self, h, A)
+
+    def sssp(self, A, W, source, delta=0, lanes=0, parents=False):
+        """bspgemm_sssp: (dist uint64[n], parent int32[n] or None, info dict) -- the exact shortest distances from `source`
+        under the lengths W (2**64 - 1 = unreached) and, with parents=True, the smallest tight predecessor of every
+        vertex (-1 = unreached): the same bits on every run and under every delta (0 = the default bucket width) and lanes
+        (0, 4, 16, 64).  info: delta, dist_max, reached, entries_walked, improved, hub_chunks, rounds, buckets, lanes, reserved"""
+        dist = np.zeros(A.rows, np.uint64)
+        parent = np.zeros(A.rows, np.int32) if parents else None
+        params, info = SsspParams(int(delta), int(lanes), 0), SsspInfo()
+        _chk(lib().bspgemm_sssp(self._h, A._h, W._h, int(source), C.byref(params), dist.ctypes.data if A.rows else None,
+                                parent.ctypes.data if parents and A.rows else None, C.byref(info)), "bspgemm_sssp")
+        return dist, parent, info.as_dict()
+
     def extract(self, A, rows=None, cols=None, keep_shape=False):
         """bspgemm_matrix_extract: (Matrix, info dict) -- out = A[rows, cols] on the device.  rows / cols: int sequences, None =
         all in order.  Default: out is len(rows) x len(cols), entry (r, c) where A has (rows[r], cols[c]); rows may repeat, cols
@@ -814,6 +865,33 @@ class Matrix:
     def free(self):
         if self._h:
             lib().bspgemm_matrix_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Weights:
+    """bspgemm_weights: one uint32 per stored entry of the operand A, on the device"""
+
+    def __init__(self, ctx, handle, A):
+        self.ctx, self._h, self._A = ctx, handle, A             # (A must outlive its weights)
+        ctx._children.add(self)
+        self.nnz = lib().bspgemm_weights_nnz(handle)
+        self.sum = lib().bspgemm_weights_sum(handle)
+
+    def download(self):
+        """bspgemm_weights_download: uint32[nnz], aligned with A.download()[1]"""
+        w = np.zeros(self.nnz, dtype=np.uint32)
+        _chk(lib().bspgemm_weights_download(self.ctx._h, self._h, w.ctypes.data if self.nnz else None), "weights_download")
+        return w
+
+    def free(self):
+        if self._h:
+            lib().bspgemm_weights_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -295,6 +295,7 @@ extern "C" bspgemm_status bspgemm_create(int device, bspgemm_context **out)
     ctx->pr_timing = getenv("BSPGEMM_PR_TIMING") != nullptr;
     ctx->bc_timing = getenv("BSPGEMM_BC_TIMING") != nullptr;
     ctx->match_timing = getenv("BSPGEMM_MATCH_TIMING") != nullptr;
+    ctx->sssp_timing = getenv("BSPGEMM_SSSP_TIMING") != nullptr;
     ctx->extract_timing = getenv("BSPGEMM_EXTRACT_TIMING") != nullptr;
     if (const char *e = getenv("BSPGEMM_LCC_TIMING")) ctx->lcc_timing = atoi(e) == 2 ? 2 : 1;
     if (ctx->debug_alloc)

@@ -164,6 +164,7 @@ struct bspgemm_context {
     bool bc_timing = false;             // BSPGEMM_BC_TIMING: stage times of the betweenness centrality on stderr (it then synchronises behind every launch group)
     bool extract_timing = false;        // BSPGEMM_EXTRACT_TIMING: stage times of the submatrix extraction on stderr (it then synchronises behind every stage)
     bool match_timing = false;          // BSPGEMM_MATCH_TIMING: stage times of the maximal matching on stderr (it then synchronises behind every launch)
+    bool sssp_timing = false;           // BSPGEMM_SSSP_TIMING: stage times of the shortest-path search on stderr (it then synchronises behind every launch)
     int lcc_timing = 0;                // BSPGEMM_LCC_TIMING: 1 stage times of the local clustering on stderr (it then synchronises behind every stage); 2: the same on the half that is not kept (lcc.hip)
 };
 
@@ -266,7 +267,7 @@ size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratc
 size_t transpose_workspace_ints(long long E, int cols);
 size_t symmetrize_workspace_ints(long long E, int n);
 
-// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip, lcc.hip, pagerank.hip, betweenness.hip, match.hip) ---
+// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip, lcc.hip, pagerank.hip, betweenness.hip, match.hip, sssp.hip) ---
 // What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
 // each algorithm's own, and so is what it does about an untidy operand.  who: the entry point's name, which every message
 // starts with.
@@ -345,7 +346,7 @@ static inline bspgemm_status fail_stuck(const char *who)
     snprintf(g_err, sizeof g_err, "%s: did not converge", who);
     return BSPGEMM_ERR_HIP;
 }
-// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING, BSPGEMM_MATCH_TIMING)
+// host clocks of the timing modes (BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING, BSPGEMM_MATCH_TIMING, BSPGEMM_SSSP_TIMING)
 using host_clock = std::chrono::steady_clock;
 static inline double ms_since(host_clock::time_point t)
 {

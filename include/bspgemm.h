@@ -68,7 +68,7 @@ const char *bspgemm_build_info(void);
  * _set_class_timing, which is what a running program uses): BSPGEMM_FLOW=auto|upper-bound|exact,
  * BSPGEMM_CLASS_STREAMS=1..3, BSPGEMM_CLASS_TIMING=0|1, BSPGEMM_RW_BLK=0|1, BSPGEMM_CHECK, BSPGEMM_SMALL=0|1, BSPGEMM_PAD_ROWS=-1|0|1,
  * BSPGEMM_SHARED_SLOTS=-1|0|k,
- * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING=1|2, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING, BSPGEMM_MATCH_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
+ * BSPGEMM_DEBUG_ALLOC, BSPGEMM_DROPIN_TIMING, BSPGEMM_KCORE_TIMING, BSPGEMM_SCC_TIMING, BSPGEMM_COLOR_TIMING, BSPGEMM_BFS_TREE_TIMING, BSPGEMM_LP_TIMING, BSPGEMM_LCC_TIMING=1|2, BSPGEMM_PR_TIMING, BSPGEMM_BC_TIMING, BSPGEMM_EXTRACT_TIMING, BSPGEMM_MATCH_TIMING, BSPGEMM_SSSP_TIMING; BSPGEMM_DEVICE picks the drop-ins' device.  (BSPGEMM_RANK_ROWS=0|1|2 is a
  * development switch of the rank class, read once per process: 0 none, 1 default, 2 also for single-window column counts.)        */
 typedef struct bspgemm_context bspgemm_context;   /* one per GPU: device, stream, workspaces  */
 typedef struct bspgemm_matrix  bspgemm_matrix;    /* device-resident CSR operand, int32 row_ptr */
@@ -1117,6 +1117,106 @@ typedef struct bspgemm_match_info {
 } bspgemm_match_info;
 bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const bspgemm_matrix *A, bspgemm_match_order order,
                                         unsigned seed, bspgemm_matrix **P, int *mate_host, bspgemm_match_info *info);
+
+/* Edge weights as a handle: a device-resident array of one uint32 per STORED entry of one operand, what the pattern operands
+ * do not carry.  w[k] belongs to stored entry k of A, that is to col_idx[k] as bspgemm_matrix_download shows it; nothing is
+ * sorted or deduplicated, so the alignment is never disturbed.  All values 0 .. 2^32 - 1 are legal.
+ *   - bspgemm_weights_upload: w_host holds nnz(A) values (it may be NULL when nnz(A) is 0).  The sum is taken on the host.
+ *   - bspgemm_weights_hashed generates the weights on the device, in one entry-parallel launch, so that tools and tests need
+ *     no weights file.  The formula is part of the contract.  With mix32 as bspgemm_graph_coloring defines it and
+ *     (a, b) = (row, col) of the entry, or (min(row, col), max(row, col)) under BSPGEMM_WEIGHTS_SYMMETRIC, so that both
+ *     directions of an undirected edge weigh the same:
+ *         w = wmin + (uint64) mix32(mix32((uint32)a ^ seed) ^ (uint32)b) % ((uint64)wmax - wmin + 1)
+ *     GAP's weights are this with [1, 255].  wmin > wmax and unknown flags are refused.  The sum is an integer reduction
+ *     on the device.
+ *   - bspgemm_weights_download: the nnz values into w_host.  bspgemm_weights_nnz, bspgemm_weights_sum: the count and the
+ *     exact sum of the values (0 for NULL).
+ *   - Lifetime.  The handle remembers its context, nnz(A) and A's identity; A is immutable while its handle lives, as
+ *     above, and must outlive the calls that take W.  bspgemm_matrix_invalidate(A) knows nothing of weights: after the
+ *     wrapped arrays of A were rewritten, W MUST BE REBUILT by the caller.  W does not survive bspgemm_matrix_free(A)
+ *     either: the identity is the operand's handle and its col_idx address, which a later operand may be given again, so
+ *     free W with A and never pass it on to another operand.  Free W before its context is destroyed.
+ *   - The device array goes through the same gate as every device allocation (bspgemm_debug_fail_alloc sees it).
+ *     BSPGEMM_ERR_INVALID with *W = NULL: a NULL ctx, A or W, A from another context; BSPGEMM_ERR_OVERFLOW for more than
+ *     INT_MAX entries; BSPGEMM_ERR_ALLOC.  Nothing is leaked on any path.  */
+typedef struct bspgemm_weights bspgemm_weights;
+#define BSPGEMM_WEIGHTS_SYMMETRIC 1u
+bspgemm_status bspgemm_weights_upload(bspgemm_context *ctx, const bspgemm_matrix *A, const uint32_t *w_host,
+                                      bspgemm_weights **W);
+bspgemm_status bspgemm_weights_hashed(bspgemm_context *ctx, const bspgemm_matrix *A, unsigned seed, uint32_t wmin,
+                                      uint32_t wmax, unsigned flags, bspgemm_weights **W);
+bspgemm_status bspgemm_weights_download(bspgemm_context *ctx, const bspgemm_weights *W, uint32_t *w_host);
+int64_t        bspgemm_weights_nnz(const bspgemm_weights *W);
+uint64_t       bspgemm_weights_sum(const bspgemm_weights *W);
+void           bspgemm_weights_free(bspgemm_weights *W);
+
+/* Single-source shortest paths with unsigned integer lengths, everything device-resident and without a product: the SSSP
+ * of LDBC Graphalytics and GAP, by delta-stepping in its near-far form.
+ *   - The definition.  A is square, row u lists the out-neighbours of u, and stored entry k = (u, v) has the length w[k]
+ *     of W, which was made for A.  dist(v) is the smallest sum of lengths over all walks from `source` to v, in uint64;
+ *     dist(source) = 0 and an unreached v has UINT64_MAX.  No sum can wrap: a shortest path has at most n - 1 <= 2^31
+ *     edges of at most 2^32 - 1 each.  A repeated entry relaxes more than once and its smallest length wins; a self-loop
+ *     never shortens anything; rows need not be sorted.
+ *   - parent(source) = source, parent(v) = -1 for an unreached v, and otherwise parent(v) is the SMALLEST u with a stored
+ *     entry k = (u, v) for which dist(u) + w[k] == dist(v) (a "tight" entry), found by one pass after the distances are
+ *     final.  With all lengths >= 1 the parents form a shortest-path tree.  With zero-length edges parent(v) is still
+ *     that well-defined tight predecessor, but zero-length cycles may make the parents CYCLIC (a zero-length self-loop
+ *     makes v a tight predecessor of itself): walk them with a bound.
+ *   - Both outputs are unique functions of (A, w, source): the same bits on every run and under every delta and lanes.
+ *     So are the counts of bspgemm_sssp_info for a given delta, because the rounds are synchronous (below).
+ *   - dist_host: a host array of n uint64, or NULL.  parent_host: a host array of n ints, or NULL (the parent pass then
+ *     does not run).  params NULL: the defaults.
+ *   - params->delta, the bucket width; 0 = the default
+ *         delta = max(1, BSPGEMM_SSSP_DELTA_C * (sum / nnz) / max(1, nnz / n)),
+ *     integer divisions in exactly this order, sum = bspgemm_weights_sum(W), and 1 when nnz is 0: "lanes x mean length /
+ *     mean degree" (Davidson et al., IPDPS 2014).  UINT64_MAX is legal and is Bellman-Ford in one bucket.  info.delta
+ *     says what ran.  params->lanes: 0 (default: the smallest of 4, 16, 64 at or above a quarter of the mean stored degree),
+ *     4, 16 or 64 lanes per near-list vertex; it changes no result and no count but info.lanes.
+ *   - The scheme (csrc/sssp.hip).  T is the exclusive upper end of the open bucket, delta at first.  A vertex is dirty
+ *     from the moment it is lowered until its row is walked, and a round's near list holds the dirty vertices below T.
+ *     A round is three launches at most: RELAX (W lanes per near vertex u stride over its stored row and send a 64-bit
+ *     atomicMin(dist[v], snap[u] + w[k]); snap[u] is u's distance when it was listed, so a round is a pure function of
+ *     the state before it; the lane that lowered v lists it as a candidate once per round), HUB (rows of more than 4096
+ *     entries: one workgroup per chunk of 4096) and SETTLE (per candidate v: snap[v] = dist[v]; below T it joins the next
+ *     near list, otherwise it is pending), then one read-back.  When the near list comes back empty, ADVANCE takes the
+ *     exact minimum m of the pending vertices, T = (m / delta + 1) * delta, and a vertex scan moves the pending vertices
+ *     below T to the near list; without a pending vertex the search is over.  Every opened bucket is non-empty.  Every
+ *     column is tested against [0, n) on the device before it indexes anything.  No kernel waits for another workgroup.
+ *   - In-bucket round k finalises the vertices at in-bucket depth k of the shortest-path forest, so a bucket takes at most
+ *     (vertices finalised in it) + 1 rounds and the search at most 2 n + 2.  Defensive cap there (BSPGEMM_ERR_HIP, "did not
+ *     converge").
+ *   - Cost: one synchronisation per round and one per opened bucket.  A small delta walks fewer entries in more rounds; a
+ *     high-diameter graph (a grid, a road network) takes about one round per hop and loses to a host Dijkstra
+ *     (DESIGN.md 4.25).
+ *   - Environment BSPGEMM_SSSP_TIMING=1 (read in bspgemm_create): the stage split on stderr -- relax, hub, settle and advance
+ *     launches, read-backs, the parent pass and the longest round; it then synchronises behind every launch.
+ *   - The multiply statistics (bspgemm_last_stats) are not touched.
+ *   - BSPGEMM_ERR_INVALID with bspgemm_last_error naming the function and the cause, *info zeroed and the host arrays
+ *     untouched: a NULL ctx, A or W, a negative source, lanes not in {0, 4, 16, 64} (refused before any operand is
+ *     dereferenced); then A or W from another context, a non-square A, a W whose nnz or operand is not A's, a source >= n;
+ *     a column outside [0, n) anywhere in A (the context stays usable).  n = 0 returns BSPGEMM_OK with *info zeroed; nnz = 0
+ *     reaches the source alone.  BSPGEMM_ERR_ALLOC leaks nothing.  */
+#define BSPGEMM_SSSP_DELTA_C 32
+typedef struct bspgemm_sssp_params {
+    uint64_t delta;           /* bucket width; 0 = the default above                                    */
+    int      lanes;           /* 0 default, 4, 16, 64                                                   */
+    int      reserved;        /* 0                                                                      */
+} bspgemm_sssp_params;
+typedef struct bspgemm_sssp_info {
+    uint64_t delta;           /* bucket width that ran                                                  */
+    uint64_t dist_max;        /* largest finite distance                                                */
+    int64_t  reached;         /* vertices with a finite distance, the source included                   */
+    int64_t  entries_walked;  /* sum over relax rounds of the stored row lengths of the near list        */
+    int64_t  improved;        /* sum over relax rounds of the vertices lowered in the round              */
+    int64_t  hub_chunks;      /* chunk records launched over all rounds                                  */
+    int      rounds;          /* relax rounds                                                           */
+    int      buckets;         /* buckets opened, the first included                                      */
+    int      lanes;           /* lanes per near-list vertex that ran: 4, 16 or 64 (0 without a round)    */
+    int      reserved;
+} bspgemm_sssp_info;
+bspgemm_status bspgemm_sssp(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_weights *W, int source,
+                            const bspgemm_sssp_params *params, uint64_t *dist_host, int *parent_host,
+                            bspgemm_sssp_info *info);
 
 /* Reflexive-transitive closure by repeated boolean squaring, everything device-resident -- the
  * application the reference's report motivates the kernel with (its old/BSpGEMM.c:75-126 keeps
