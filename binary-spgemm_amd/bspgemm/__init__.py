@@ -249,6 +249,10 @@ _SIGNATURES = {
     "bspgemm_dropin_set_device": (_INT, [C.c_int]),
     "bspgemm_debug_fail_alloc": (None, [C.c_int]),
     "bspgemm_debug_alloc_state": (None, [_I64P]),
+    "bspgemm_debug_fill_alloc": (None, [C.c_int, C.c_uint32]),
+    "bspgemm_debug_guard_alloc": (None, [C.c_int]),
+    "bspgemm_debug_check_guards": (C.c_int64, []),
+    "bspgemm_debug_scribble": (_INT, [_VP, C.c_uint32]),
     "bspgemm_comm_unique_id": (_INT, [C.c_char_p]),
     "bspgemm_comm_create": (_INT, [_VP, C.c_char_p, C.c_int, C.c_int, _PVP]),
     "bspgemm_comm_destroy": (None, [_VP]),
@@ -422,6 +426,23 @@ def debug_alloc_state():
     return tuple(int(v) for v in out)
 
 
+def debug_fill_alloc(on, word=0):
+    """bspgemm_debug_fill_alloc: while on, every device allocation is handed out filled with the 32-bit `word`"""
+    lib().bspgemm_debug_fill_alloc(1 if on else 0, int(word) & 0xFFFFFFFF)
+
+
+def debug_guard_alloc(on):
+    """bspgemm_debug_guard_alloc: while on, every device allocation gets a 256-byte canary zone in front and behind"""
+    lib().bspgemm_debug_guard_alloc(1 if on else 0)
+
+
+def debug_check_guards():
+    """bspgemm_debug_check_guards: (guarded allocations found damaged so far, live and freed; the first damage's description
+    or "" when there is none)"""
+    n = int(lib().bspgemm_debug_check_guards())
+    return n, (lib().bspgemm_last_error().decode(errors="replace") if n else "")
+
+
 # ------------------------------------------------------------------ native handle API -----
 class Context:
     """bspgemm_context: one GPU, one stream, reusable workspaces."""
@@ -452,6 +473,10 @@ class Context:
 
     def synchronize(self):
         _chk(lib().bspgemm_synchronize(self._h), "synchronize")
+
+    def debug_scribble(self, word):
+        """bspgemm_debug_scribble: every scratch array the context keeps between calls is filled with the 32-bit `word`"""
+        _chk(lib().bspgemm_debug_scribble(self._h, int(word) & 0xFFFFFFFF), "debug_scribble")
 
     def set_flow(self, flow):
         """"auto" | "upper-bound" | "exact" (BSPGEMM_FLOW_*, include/bspgemm.h)"""

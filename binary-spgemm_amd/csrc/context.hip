@@ -37,15 +37,68 @@ extern "C" const char *bspgemm_status_string(bspgemm_status s)
 // hooks").  Process-wide and locked: contexts of several threads share it.  Off the timed path: a steady-state multiply
 // allocates nothing (kept workspaces, result cache).  The state is never destroyed: the drop-in context may free after exit().
 namespace {
+constexpr int kHookFill = 1, kHookGuard = 2;
+constexpr size_t kGuardZone = 256;                          // bytes in front of and behind a guarded allocation
+constexpr int kGuardByte = 0xC5;                            // (neither byte of the two poison words of tests/test_gpu_dirty_state.py)
+struct DevRec {
+    size_t bytes;                                           // as requested: what live_bytes counts
+    int guarded_on;                                         // -1: no zones; else the device whose memory it is
+};
 struct DevGate {
     std::mutex mu;
-    std::unordered_map<void *, size_t> live;
+    std::unordered_map<void *, DevRec> live;
     long long requests = 0, live_bytes = 0, fired = 0, countdown = 0;
+    int hooks = 0;                                          // kHookFill | kHookGuard: the one word a request reads under the lock
+    uint32_t fill_word = 0;
+    long long damaged_freed = 0;                            // guarded allocations that were freed with a changed zone (sticky)
+    char first_damage[160] = "";
 };
 DevGate &dev_gate()
 {
     static DevGate *g = new DevGate();
     return *g;
+}
+
+// `bytes` at p become copies of `word`; a trailing 1-3 bytes take its low bytes.  s NULL: the null stream.  No synchronisation.
+hipError_t fill_words(void *p, size_t bytes, uint32_t word, hipStream_t s)
+{
+    if (!p || bytes == 0) return hipSuccess;
+    const size_t words = bytes / 4;
+    if (words)
+        if (hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)word, words, s)) return e;
+    for (size_t k = words * 4; k < bytes; k++)
+        if (hipError_t e = hipMemsetAsync(static_cast<char *>(p) + k, (int)((word >> (8 * (k & 3))) & 0xff), 1, s)) return e;
+    return hipSuccess;
+}
+
+// The zones of the guarded allocation whose caller pointer is p: 0 intact, 1 changed (*front, *off: the first changed
+// byte), -1 the read-back failed.  The device is drained first: a store in flight counts.
+int guard_zones_changed(const void *p, const DevRec &r, bool *front, int *off)
+{
+    unsigned char z[2 * kGuardZone];
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    if (cur != r.guarded_on) (void)hipSetDevice(r.guarded_on);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(z, static_cast<const char *>(p) - kGuardZone, kGuardZone, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(z + kGuardZone, static_cast<const char *>(p) + r.bytes, kGuardZone, hipMemcpyDeviceToHost);
+    if (cur != r.guarded_on) (void)hipSetDevice(cur);
+    if (e != hipSuccess) { (void)hipGetLastError(); return -1; }
+    for (size_t k = 0; k < 2 * kGuardZone; k++)
+        if (z[k] != (unsigned char)kGuardByte) {
+            *front = k < kGuardZone;
+            *off = (int)(k % kGuardZone);
+            return 1;
+        }
+    return 0;
+}
+
+void note_damage(DevGate &g, const DevRec &r, int changed, bool front, int off)   // g.mu held
+{
+    if (g.first_damage[0]) return;
+    if (changed < 0) snprintf(g.first_damage, sizeof g.first_damage, "guard zones of an allocation of %zu bytes could not be read back", r.bytes);
+    else snprintf(g.first_damage, sizeof g.first_damage, "guard damaged: allocation of %zu bytes, %s zone, offset %d", r.bytes,
+                  front ? "front" : "back", off);
 }
 }  // namespace
 
@@ -53,6 +106,8 @@ hipError_t dev_alloc_bytes(void **p, size_t bytes)
 {
     DevGate &g = dev_gate();
     *p = nullptr;
+    int hooks;
+    uint32_t word;
     {
         std::lock_guard<std::mutex> lk(g.mu);
         g.requests++;
@@ -60,13 +115,32 @@ hipError_t dev_alloc_bytes(void **p, size_t bytes)
             g.fired++;
             return hipErrorOutOfMemory;
         }
+        hooks = g.hooks;
+        word = g.fill_word;
     }
+    DevRec rec{bytes, -1};
     void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return e;
+    if (hooks == 0 || bytes == 0) {                         // the plain request: hipMalloc and nothing else
+        const hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return e;
+    } else {                                                // test hooks (include/bspgemm.h): zones around it, poison inside
+        const bool guard = hooks & kHookGuard;
+        char *base = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&base), bytes + (guard ? 2 * kGuardZone : 0));
+        if (e != hipSuccess) return e;
+        q = guard ? base + kGuardZone : base;
+        if (guard) {
+            e = hipGetDevice(&rec.guarded_on);
+            if (e == hipSuccess) e = hipMemsetAsync(base, kGuardByte, kGuardZone, nullptr);
+            if (e == hipSuccess) e = hipMemsetAsync(base + kGuardZone + bytes, kGuardByte, kGuardZone, nullptr);
+        }
+        if (e == hipSuccess && (hooks & kHookFill)) e = fill_words(q, bytes, word, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) { (void)hipFree(base); return e; }
+    }
     if (q) {
         std::lock_guard<std::mutex> lk(g.mu);
-        g.live[q] = bytes;
+        g.live[q] = rec;
         g.live_bytes += (long long)bytes;
     }
     *p = q;
@@ -77,15 +151,67 @@ hipError_t dev_free(void *p)
 {
     if (!p) return hipSuccess;
     DevGate &g = dev_gate();
+    DevRec rec{0, -1};
     {
         std::lock_guard<std::mutex> lk(g.mu);
         auto it = g.live.find(p);
         if (it != g.live.end()) {
-            g.live_bytes -= (long long)it->second;
+            rec = it->second;
+            g.live_bytes -= (long long)rec.bytes;
             g.live.erase(it);
         }
     }
-    return hipFree(p);
+    if (rec.guarded_on < 0) return hipFree(p);
+    bool front = false;
+    int off = 0;
+    if (const int changed = guard_zones_changed(p, rec, &front, &off)) {
+        std::lock_guard<std::mutex> lk(g.mu);
+        g.damaged_freed++;
+        note_damage(g, rec, changed, front, off);
+    }
+    return hipFree(static_cast<char *>(p) - kGuardZone);
+}
+
+// bytes of the live allocation at p as it was requested; 0: not the gate's (NULL, a wrapped array)
+static size_t dev_alloc_size(const void *p)
+{
+    DevGate &g = dev_gate();
+    std::lock_guard<std::mutex> lk(g.mu);
+    auto it = g.live.find(const_cast<void *>(p));
+    return it == g.live.end() ? 0 : it->second.bytes;
+}
+
+static void set_hook(int bit, bool on, uint32_t word)
+{
+    DevGate &g = dev_gate();
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (bit == kHookGuard && on && !(g.hooks & kHookGuard)) {   // a new guarded stretch starts clean
+        g.damaged_freed = 0;
+        g.first_damage[0] = 0;
+    }
+    g.hooks = on ? (g.hooks | bit) : (g.hooks & ~bit);
+    if (bit == kHookFill) g.fill_word = word;
+}
+
+extern "C" void bspgemm_debug_fill_alloc(int on, uint32_t word) { set_hook(kHookFill, on != 0, word); }
+extern "C" void bspgemm_debug_guard_alloc(int on) { set_hook(kHookGuard, on != 0, 0); }
+
+extern "C" int64_t bspgemm_debug_check_guards(void)
+{
+    DevGate &g = dev_gate();
+    std::lock_guard<std::mutex> lk(g.mu);
+    long long damaged = g.damaged_freed;
+    for (const auto &kv : g.live) {
+        if (kv.second.guarded_on < 0) continue;
+        bool front = false;
+        int off = 0;
+        if (const int changed = guard_zones_changed(kv.first, kv.second, &front, &off)) {
+            damaged++;
+            note_damage(g, kv.second, changed, front, off);
+        }
+    }
+    if (damaged) snprintf(g_err, sizeof g_err, "%s", g.first_damage);
+    return damaged;
 }
 
 extern "C" void bspgemm_debug_fail_alloc(int nth)
@@ -354,6 +480,24 @@ extern "C" bspgemm_status bspgemm_synchronize(bspgemm_context *ctx)
 {
     if (!ctx) return FAIL(BSPGEMM_ERR_INVALID, "ctx is NULL");
     if (bspgemm_status st = use_device(ctx)) return st;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return BSPGEMM_OK;
+}
+
+extern "C" bspgemm_status bspgemm_debug_scribble(bspgemm_context *ctx, uint32_t word)
+{
+    if (!ctx) return FAIL(BSPGEMM_ERR_INVALID, "debug_scribble: ctx is NULL");
+    if (bspgemm_status st = use_device(ctx)) return st;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream_b));
+    HIPCHK(hipStreamSynchronize(ctx->stream_c));
+    // every scratch array the context keeps between calls, each to the size it was allocated with (the gate knows it);
+    // d_err is state (zeroed once in bspgemm_create; the kernels only ever OR a bit into it) and stays as it is
+    void *const scratch[] = {ctx->F, ctx->Fmask, ctx->Fprefix, ctx->partials, ctx->hpartials, ctx->cnt, ctx->bin_tiles, ctx->rec,
+                             ctx->recpre, ctx->hub_rec, ctx->hub_pre, ctx->ab, ctx->tile_row, ctx->tmp, ctx->tmpv, ctx->chunk_row,
+                             ctx->d_prep, ctx->d_small, ctx->d_small_tiles, ctx->bin_count, ctx->stitch_partials};
+    for (void *p : scratch) HIPCHK(fill_words(p, dev_alloc_size(p), word, ctx->stream));
+    for (const auto &c : ctx->cache) HIPCHK(fill_words(c.p, dev_alloc_size(c.p), word, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return BSPGEMM_OK;
 }

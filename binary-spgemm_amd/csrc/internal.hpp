@@ -56,8 +56,10 @@ static inline bspgemm_status fail(bspgemm_status st, const char *what, const cha
 // ------------------------------------------------------------------ device memory (context.hip) ---
 // The one gate for device memory: every allocation and release of a device array outside comm.hip (which has hooks of its
 // own) goes through this pair -- the workspaces, the operands and their tables, the result buffers and their cache.  It
-// counts the live allocations and can fail the n-th request (bspgemm_debug_fail_alloc, include/bspgemm.h).  A failed
-// request leaves *p NULL.  Pinned (hipHostMalloc) and host memory (new, malloc) stay outside.
+// counts the live allocations and can fail the n-th request (bspgemm_debug_fail_alloc, include/bspgemm.h), hand every
+// allocation out filled with a poison word (bspgemm_debug_fill_alloc) and put a canary zone in front of and behind it
+// (bspgemm_debug_guard_alloc: the caller's pointer is then 256 bytes into the hipMalloc'ed block, so only dev_free may
+// release it).  A failed request leaves *p NULL.  Pinned (hipHostMalloc) and host memory (new, malloc) stay outside.
 hipError_t dev_alloc_bytes(void **p, size_t bytes);
 template <class T> static inline hipError_t dev_alloc(T **p, size_t bytes) { return dev_alloc_bytes(reinterpret_cast<void **>(p), bytes); }
 hipError_t dev_free(void *p);                           // NULL: nothing

@@ -1418,6 +1418,39 @@ void           bspgemm_debug_fail_alloc(int nth);
  * started.  Live: handed out by the gate and not yet freed, buffers held by a context's result cache included; all zero
  * before the first context exists.  Equal live counts before bspgemm_create and after bspgemm_destroy: nothing leaked.  */
 void           bspgemm_debug_alloc_state(int64_t out[4]);
+/* Three more test hooks of the same gate, for running every entry point on adversarial memory contents.  All are off by
+ * default and process-wide like the two above.  With all of them off a request is what it was: one more word read under
+ * the lock the gate already takes, hipMalloc and nothing else.
+ *
+ * fill: while `on` is not 0, every allocation the gate hands out holds copies of `word` before the caller sees it (a
+ * trailing 1-3 bytes take the word's low bytes); the fill has completed when the request returns.  A result buffer that
+ * comes out of the cache of freed results is no request and is not filled: bspgemm_debug_scribble reaches those.           */
+void           bspgemm_debug_fill_alloc(int on, uint32_t word);
+/* guard: while `on` is not 0, every request of one byte or more is made 512 bytes larger.  The caller's pointer is 256
+ * bytes into it (the 256-byte alignment of hipMalloc is kept), the back zone begins at the first byte past the REQUESTED
+ * size -- an overrun of one int is seen even where the request was no multiple of 16 -- and both zones hold a canary byte.
+ * Freeing a guarded allocation drains its device and verifies both zones; a changed zone is counted for good.
+ * bspgemm_debug_check_guards drains the devices, verifies every live guarded allocation and returns the number damaged so
+ * far, the live ones and the ones freed since the hook was last turned on (turning it on from off starts the count again).
+ * After a return other than 0, bspgemm_last_error() describes the first damage: "guard damaged: allocation of N bytes,
+ * front|back zone, offset K", N as requested, K the first changed byte of that zone.  Call it with no call of the library
+ * in flight on another thread.  An allocation keeps its zones until it is freed, whatever the hook says by then.
+ * bspgemm_debug_alloc_state goes on counting the requested bytes only.  What the zones see is a store outside a WHOLE
+ * allocation: the arrays that one call lays out side by side inside the context's workspace have no gaps between them, and
+ * arrays that the caller wraps (bspgemm_matrix_wrap_device) never pass the gate.                                          */
+void           bspgemm_debug_guard_alloc(int on);
+int64_t        bspgemm_debug_check_guards(void);
+/* scribble: waits for the context's streams, fills every scratch array the context keeps between calls with copies of
+ * `word`, each to the full size it was allocated with, and waits again.  Scratch is an array whose contents no call is
+ * documented to find as an earlier call left them: the per-row block (F, Fmask, Fprefix, partials, hpartials, cnt,
+ * bin_tiles, rec, recpre, hub_rec, hub_pre), the grown arrays (ab, tile_row, tmp, tmpv, chunk_row), the scalar blocks
+ * (d_prep, d_small, d_small_tiles, bin_count), the scan scratch of bspgemm_lengths_to_row_ptr, and every buffer in the
+ * cache of freed results.  A correct call computes the same bits after it as before.  Left out because it is state, not
+ * scratch: the device error word of the accumulate kernels (d_err), which bspgemm_create zeroes once (csrc/context.hip:
+ * hipMemset(ctx->d_err, 0, 64)) and the kernels only ever OR a bit into; the one reader, a product under
+ * BSPGEMM_OPT_CHECK, zeroes its first word again before it looks (csrc/multiply.hip, start_flow).  Operands, their
+ * derived tables, weights and live results belong to their handles and are not touched.                                  */
+bspgemm_status bspgemm_debug_scribble(bspgemm_context *ctx, uint32_t word);
 
 /* ---------------------------------------------------------------- host utilities (C) --
  * Plain C, no GPU needed.                                                                    */

@@ -96,6 +96,44 @@ def test_alloc_test_hooks_are_declared_and_idle_before_any_context():
     assert r.returncode == 0 and "idle" in r.stdout, r.stdout + r.stderr
 
 
+def test_poison_and_guard_hooks_are_declared_and_off_before_any_context():
+    """the fill, guard and scribble hooks: declared with these argument lists, exported, bound with the header's types, and
+    in a process that has created no context turning them on and off allocates nothing, finds no guard damaged and leaves
+    no error text; scribble refuses a NULL context without touching a device"""
+    import ctypes
+    import subprocess
+    import sys
+    text = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "bspgemm.h")).read())
+    for proto in ("void bspgemm_debug_fill_alloc(int on, uint32_t word);", "void bspgemm_debug_guard_alloc(int on);",
+                  "int64_t bspgemm_debug_check_guards(void);",
+                  "bspgemm_status bspgemm_debug_scribble(bspgemm_context *ctx, uint32_t word);"):
+        assert proto in text, proto
+    assert "whole" in text.lower() and "d_err" in text          # what the guards do not see, and what scribble leaves out
+    L = bspgemm.lib()
+    assert L.bspgemm_debug_fill_alloc.restype is None and L.bspgemm_debug_fill_alloc.argtypes == [ctypes.c_int, ctypes.c_uint32]
+    assert L.bspgemm_debug_guard_alloc.restype is None and L.bspgemm_debug_guard_alloc.argtypes == [ctypes.c_int]
+    assert L.bspgemm_debug_check_guards.restype is ctypes.c_int64 and L.bspgemm_debug_check_guards.argtypes == []
+    assert L.bspgemm_debug_scribble.argtypes == [ctypes.c_void_p, ctypes.c_uint32]
+    code = ("import ctypes\n"
+            "L = ctypes.CDLL(%r)\n"
+            "L.bspgemm_debug_check_guards.restype = ctypes.c_int64\n"
+            "L.bspgemm_last_error.restype = ctypes.c_char_p\n"
+            "L.bspgemm_debug_scribble.argtypes = [ctypes.c_void_p, ctypes.c_uint32]\n"
+            "out = (ctypes.c_int64 * 4)(7, 7, 7, 7)\n"
+            "assert L.bspgemm_debug_check_guards() == 0\n"
+            "L.bspgemm_debug_fill_alloc(1, 0xFFFFFFFF)\n"
+            "L.bspgemm_debug_guard_alloc(1)\n"
+            "assert L.bspgemm_debug_check_guards() == 0 and L.bspgemm_last_error() == b''\n"
+            "L.bspgemm_debug_fill_alloc(0, 0)\n"
+            "L.bspgemm_debug_guard_alloc(0)\n"
+            "L.bspgemm_debug_alloc_state(out)\n"
+            "assert list(out) == [0, 0, 0, 0], list(out)\n"
+            "assert L.bspgemm_debug_scribble(None, 1) == 1 and b'ctx is NULL' in L.bspgemm_last_error()\n"   # BSPGEMM_ERR_INVALID
+            "print('off')\n") % bspgemm.LIB_PATH
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "off" in r.stdout, r.stdout + r.stderr
+
+
 def test_header_cites_the_reference_interfaces():
     text = open(os.path.join(ROOT, "include", "bspgemm.h")).read()
     for cite in ("final/SpGEMM_mpi_omp.c:71-74", "final/SpGEMM_mpi_omp.c:15-18", "final/utils.c:47-81",
