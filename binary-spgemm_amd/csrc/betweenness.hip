@@ -96,9 +96,6 @@ struct BcBwd {
     u64 *bc;
 };
 
-// the chunk records of a row: none for one that a group of lanes walks itself.  Host and device.
-__host__ __device__ __forceinline__ int bc_chunks_of(int len) { return len > kBcHubChunk ? hub_chunks_of<kBcHubChunk>(len) : 0; }
-
 // one entry (u, w) of the frontier, su = sigma(u).  Whole wave; `live` lanes hold an entry.
 __device__ __forceinline__ void bc_forward_entry(const BcFwd &a, bool live, int w, u64 su, long long &dsum, unsigned &err, int lane)
 {
@@ -120,7 +117,7 @@ __device__ __forceinline__ void bc_forward_entry(const BcFwd &a, bool live, int 
             if (take) {
                 const int len = a.rpA[w + 1] - a.rpA[w];
                 dsum += len;
-                const int k = bc_chunks_of(len);
+                const int k = hub_chunks_over<kBcHubChunk>(len);
                 if (k) hub_chunks_emit(w, k, &a.cnt->ctail, a.chunk, a.chunk_cap);
             }
         }
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(kBcThreads) void k_bc_source(int src, int len, int 
                                                          int *__restrict__ order, int2 *__restrict__ chunk, int chunk_cap,
                                                          BcCounters *cnt)
 {
-    const int k = bc_chunks_of(len);
+    const int k = hub_chunks_over<kBcHubChunk>(len);
     if (threadIdx.x == 0) {
         level[src] = 0;
         sigma[src] = 1;
@@ -182,19 +179,11 @@ template <int W>
 __global__ __launch_bounds__(kBcThreads) void k_bc_forward(BcFwd a, int fsize, int first, const int *__restrict__ colA)
 {
     const int lane = lane_id();
-    const long long t = (long long)blockIdx.x * kBcThreads + threadIdx.x;
-    const long long f = t / W;
-    const int sub = (int)(t % W);
-    long long pos = 0, e = 0;
+    GroupRow<W, kBcThreads> g;
     u64 su = 0;
-    if (f < fsize) {
-        const int u = a.order[first + f];
-        const long long b = a.rpA[u];
-        e = a.rpA[u + 1];
-        if (e - b > kBcHubChunk) e = b;                      // (the chunks' row)
-        pos = b + sub;
-        su = a.sigma[u];
-    }
+    g.template row<kBcHubChunk>(fsize, a.order, first, a.rpA, [&](int u) { su = a.sigma[u]; });
+    const long long e = g.e;
+    long long pos = g.pos;
     long long dsum = 0;
     unsigned err = 0;
     // the groups of a wave have different trip counts: the loop runs to the wave's longest with the other lanes
@@ -252,6 +241,7 @@ template <int W>
 __global__ __launch_bounds__(kBcThreads) void k_bc_backward(BcBwd a, int fsize, int first, const int *__restrict__ order,
                                                            const int *__restrict__ colA)
 {
+    // (open code: with GroupRow of hub_chunks.hpp the same instructions come out in another order)
     const long long t = (long long)blockIdx.x * kBcThreads + threadIdx.x;
     const long long f = t / W;
     const int sub = (int)(t % W);
@@ -331,27 +321,21 @@ __global__ __launch_bounds__(kBcThreads) void k_bc_reset(int reached, const int 
         atomicMax(&cnt->sigma_max, sg);
 }
 
-static dim3 bc_grid(long long threads) { return dim3((unsigned)std::max(1ll, (threads + kBcThreads - 1) / kBcThreads)); }
-
-// The lanes per vertex of a level: the smallest W at or above a QUARTER of its mean out-degree.  push_lanes of bfs_tree.hip
+// The lanes per vertex of a level: the smallest W at or above a QUARTER of its mean out-degree.  The push of bfs_tree.hip
 // takes the smallest W at or above the mean, because there a frontier hub is a serial tail of degree / W steps; here no
 // group walks more than kBcHubChunk entries, and with the mean rule (64 lanes on every big level of an R-MAT of mean degree
 // 16) the forward sweep measured 2.2 times and the backward sweep 3 times slower than with 4 lanes.
-static int bc_lanes(long long m_f, long long n_f)
-{
-    if (m_f <= 16 * n_f) return 4;
-    return m_f <= 64 * n_f ? 16 : 64;
-}
+static int bc_lanes(long long m_f, long long n_f) { return lanes_for_mean(m_f, n_f, 4); }
 
 static void launch_forward(int W, const BcFwd &a, int fsize, int first, const int *colA, hipStream_t s)
 {
-    const dim3 grid = bc_grid((long long)fsize * W), block(kBcThreads);
+    const dim3 grid = grid_for((long long)fsize * W, kBcThreads), block(kBcThreads);
     dispatch_lanes(W, [&](auto w) { hipLaunchKernelGGL(k_bc_forward<decltype(w)::value>, grid, block, 0, s, a, fsize, first, colA); });
 }
 
 static void launch_backward(int W, const BcBwd &a, int fsize, int first, const int *order, const int *colA, hipStream_t s)
 {
-    const dim3 grid = bc_grid((long long)fsize * W), block(kBcThreads);
+    const dim3 grid = grid_for((long long)fsize * W, kBcThreads), block(kBcThreads);
     dispatch_lanes(W, [&](auto w) {
         hipLaunchKernelGGL(k_bc_backward<decltype(w)::value>, grid, block, 0, s, a, fsize, first, order, colA);
     });
@@ -466,11 +450,11 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
 
     clk.start();
     HIPCHK_B(hipMemsetAsync(d_cnt, 0, sizeof(BcCounters), s));
-    hipLaunchKernelGGL(k_bc_init, bc_grid(n), block, 0, s, n, level, sigma, delta, bc);
+    hipLaunchKernelGGL(k_bc_init, grid_for(n, kBcThreads), block, 0, s, n, level, sigma, delta, bc);
     HIPCHK_B(hipGetLastError());
     if (nsources > 0) {
         HIPCHK_B(hipMemcpyAsync(d_src, sources, (size_t)nsources * sizeof(int), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_bc_degrees, bc_grid(nsources), block, 0, s, nsources, d_src, A->d_row_ptr, d_deg);
+        hipLaunchKernelGGL(k_bc_degrees, grid_for(nsources, kBcThreads), block, 0, s, nsources, d_src, A->d_row_ptr, d_deg);
         HIPCHK_B(round_fetch(h_deg, d_deg, (size_t)nsources * sizeof(int), s));
     }
     (void)clk.lap(ms_back);
@@ -484,7 +468,7 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
             const host_clock::time_point t_src = host_clock::now();
             if (h_deg[i] < 0 || h_deg[i] > A->nnz) return bail(fail_stuck(who));
             L.clear();
-            L.push_back(BcLevelRec{0, 1, 0, bc_chunks_of(h_deg[i]), h_deg[i]});
+            L.push_back(BcLevelRec{0, 1, 0, hub_chunks_over<kBcHubChunk>(h_deg[i]), h_deg[i]});
             if ((size_t)L[0].chunks > chunk_cap) return bail(fail_stuck(who));
             hipLaunchKernelGGL(k_bc_source, dim3(1), block, 0, s, src, h_deg[i], level, sigma, order, chunk, (int)chunk_cap, d_cnt);
             HIPCHK_B(hipGetLastError());
@@ -531,7 +515,7 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
             // ---- backward: no read-backs, the host knows every offset
             BcBwd b = {n, depth, src, A->d_row_ptr, level, sigma, delta, c, bc};
             clk.start();
-            hipLaunchKernelGGL(k_bc_leaf, bc_grid(L[depth].size), block, 0, s, b, L[depth].size, L[depth].off, order);
+            hipLaunchKernelGGL(k_bc_leaf, grid_for(L[depth].size, kBcThreads), block, 0, s, b, L[depth].size, L[depth].off, order);
             for (int d = depth - 1; d >= 0; d--) {
                 const BcLevelRec &f = L[d];
                 b.d = d;
@@ -539,12 +523,12 @@ extern "C" bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const bspgem
                 if (f.chunks) {
                     HIPCHK_B(clk.lap(ms_bwd, true));            // (timed: the hub launches are a lap of their own)
                     hipLaunchKernelGGL(k_bc_backward_chunk, dim3((unsigned)f.chunks), block, 0, s, b, f.coff, chunk, A->d_col_idx);
-                    hipLaunchKernelGGL(k_bc_hub_finish, bc_grid(f.chunks), block, 0, s, b, f.chunks, f.coff, chunk);
+                    hipLaunchKernelGGL(k_bc_hub_finish, grid_for(f.chunks, kBcThreads), block, 0, s, b, f.chunks, f.coff, chunk);
                     hub_chunks += f.chunks;
                     HIPCHK_B(clk.lap(ms_hub, true));
                 }
             }
-            hipLaunchKernelGGL(k_bc_reset, bc_grid(tail), block, 0, s, tail, order, level, sigma, delta, d_cnt);
+            hipLaunchKernelGGL(k_bc_reset, grid_for(tail, kBcThreads), block, 0, s, tail, order, level, sigma, delta, d_cnt);
             HIPCHK_B(hipGetLastError());
             HIPCHK_B(clk.lap(ms_bwd, true));
             clk.longest(ms_since(t_src), i);

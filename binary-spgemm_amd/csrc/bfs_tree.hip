@@ -104,6 +104,7 @@ __global__ __launch_bounds__(kBtThreads) void k_bfs_push(int n, int d, int fsize
 {
     const int lane = lane_id();
     if (blockIdx.x == 0 && threadIdx.x == 0) *reset = BtLevel{0, 0u, 0ull};
+    // (open code: GroupRow of hub_chunks.hpp loads the row's end before it forms pos, and compiles to other code here)
     const long long t = (long long)blockIdx.x * kBtThreads + threadIdx.x;
     const long long f = t / W;
     const int sub = (int)(t % W);
@@ -216,16 +217,8 @@ template <int W>
 static void launch_push(int n, int d, int fsize, const int *list, const bspgemm_matrix *A, int *level, int *parent, int *next,
                         BtLevel *out, BtLevel *reset, hipStream_t s)
 {
-    const long long threads = (long long)fsize * W;
-    hipLaunchKernelGGL(k_bfs_push<W>, dim3((unsigned)((threads + kBtThreads - 1) / kBtThreads)), dim3(kBtThreads), 0, s, n, d, fsize,
-                       list, A->d_row_ptr, A->d_col_idx, level, parent, next, out, reset);
-}
-
-// the lanes per frontier vertex of a push launch: the smallest W at or above the frontier's mean out-degree
-static int push_lanes(long long m_f, long long n_f)
-{
-    if (m_f <= 4 * n_f) return 4;
-    return m_f <= 16 * n_f ? 16 : 64;
+    hipLaunchKernelGGL(k_bfs_push<W>, grid_for((long long)fsize * W, kBtThreads), dim3(kBtThreads), 0, s, n, d, fsize, list,
+                       A->d_row_ptr, A->d_col_idx, level, parent, next, out, reset);
 }
 
 }  // namespace bsp
@@ -354,7 +347,9 @@ extern "C" bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_m
             pulls++;
             if (d <= 64) pull_mask |= (uint64_t)1 << (d - 1);
         } else {
-            const int W = forced_w ? forced_w : push_lanes(m_f, n_f);
+            // the lanes per frontier vertex: the smallest W at or above the frontier's MEAN out-degree -- no chunk records
+            // here, so a frontier hub is a serial tail of degree / W steps
+            const int W = forced_w ? forced_w : lanes_for_mean(m_f, n_f, 1);
             dispatch_lanes(W, [&](auto w) {
                 launch_push<decltype(w)::value>(n, d, (int)n_f, list[cur], A, level, parent, list[cur ^ 1], out, reset, s);
             });

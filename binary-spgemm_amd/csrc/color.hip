@@ -60,16 +60,6 @@ struct ColFlags {
     int pad;
 };
 
-__device__ __forceinline__ u32 col_mix32(u32 x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // (key[w], w) < (key[u], u)
 __device__ __forceinline__ bool col_precedes(u64 kw, int w, u64 ku, int u) { return kw < ku || (kw == ku && w < u); }
 
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(kColThreads) void k_color_init(int n, int order, u3
     if (v < n) {
         colour[v] = fill;
         if (rpS) {
-            const u32 lo = order == BSPGEMM_COLOR_NATURAL ? (u32)v : col_mix32((u32)v ^ seed);
+            const u32 lo = order == BSPGEMM_COLOR_NATURAL ? (u32)v : mix32((u32)v ^ seed);
             const u32 hi = order == BSPGEMM_COLOR_LARGEST_FIRST ? 0x7fffffffu - (u32)(rpS[v + 1] - rpS[v]) : 0u;
             key[v] = ((u64)hi << 32) | lo;
             cnt[v] = 0;
@@ -258,11 +248,8 @@ extern "C" bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, const bsp
         return WsCursor(tmp).take(d_flags, 1).take(key, n4).take(cnt, n4).take(list[0], n4).take(list[1], n4).ints();
     };
     const size_t own_ints = carve(nullptr);
-    if (bspgemm_status st = ensure_tmp(ctx, std::max(symmetrize_workspace_ints(A->nnz, A->rows), A->nnz > 0 ? own_ints : 0)))
-        return st;
     bspgemm_matrix *S = nullptr;
-    if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &S)) return st;
-    (void)clk.lap(ms_sym, true);
+    if (bspgemm_status st = symmetrized_operand(ctx, A, own_ints, A->nnz > 0, clk, ms_sym, &S)) return st;
     hipStream_t s = ctx->stream;
     const int n = S->rows;
     const long long E = S->nnz;                             // <= INT_MAX: symmetrize refuses more

@@ -89,8 +89,6 @@ struct ExWalk {
 // whether column c is kept: a gather from A.cols / 8 bytes, which an L2 holds where the map's 4 bytes per column do not
 __device__ __forceinline__ int ex_kept(const ExWalk &a, int c) { return a.cbits ? (int)((a.cbits[c >> 5] >> (c & 31)) & 1u) : 1; }
 
-__host__ __device__ __forceinline__ int ex_chunks_of(int len) { return len > kExHubChunk ? hub_chunks_of<kExHubChunk>(len) : 0; }
-
 // the row of A that out row r reads, or -1 for a row that stays empty
 __device__ __forceinline__ int ex_src(const ExWalk &a, int r)
 {
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(kExThreads) void k_ex_maps(ExMaps a)
             const int len = a.rpA[i + 1] - a.rpA[i];
             sc = len;
             wk = 1;
-            ch = ex_chunks_of(len);
+            ch = hub_chunks_over<kExHubChunk>(len);
         }
     }
     sc = wave_sum(sc);
@@ -145,11 +143,12 @@ __global__ __launch_bounds__(kExThreads) void k_ex_hub_records(ExWalk a, int2 *_
     if (r >= a.R) return;
     const int i = ex_src(a, (int)r);
     if (i < 0) return;
-    const int k = ex_chunks_of(a.rpA[i + 1] - a.rpA[i]);
+    const int k = hub_chunks_over<kExHubChunk>(a.rpA[i + 1] - a.rpA[i]);
     if (k) hub_chunks_emit((int)r, k, &cnt->cursor, chunk, chunk_cap);
 }
 
-// the group's row: entries [pos, e) in steps of W, nothing for a hub (mine false) and for a row that stays empty
+// the group's row: entries [pos, e) in steps of W, nothing for a hub (mine false) and for a row that stays empty.  Not
+// GroupRow of hub_chunks.hpp: the vertex comes through ex_src, which may name no row at all, and such a group is still `mine`
 template <int W>
 __device__ __forceinline__ bool ex_group_row(const ExWalk &a, long long f, int sub, long long &pos, long long &e)
 {
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(kExThreads) void k_ex_hub_finish(ExWalk a, int nchu
     const int2 rec = chunk[t];
     if (rec.y != 0) return;
     const int i = ex_src(a, rec.x);
-    const long long k = ex_chunks_of(a.rpA[i + 1] - a.rpA[i]);
+    const long long k = hub_chunks_over<kExHubChunk>(a.rpA[i + 1] - a.rpA[i]);
     const long long last = min((t + k) * kExWaves, (long long)nchunks * kExWaves);
     int run = 0;
     for (long long q = t * kExWaves; q < last; q++) {
@@ -342,18 +341,6 @@ __global__ __launch_bounds__(kExThreads) void k_ex_sort_block(const int *__restr
     ex_sort_row<true>(s, out + b, k, threadIdx.x, kExThreads);
 }
 
-static dim3 ex_grid(long long threads) { return dim3((unsigned)std::max(1ll, (threads + kExThreads - 1) / kExThreads)); }
-
-// The lanes per out row: the smallest W at or above a QUARTER of the mean length of the rows that are read, betweenness.hip's
-// rule (no group walks more than kExHubChunk entries, so the mean, not the tail, sets the cost).  The mean is over the rows
-// READ: under KEEP_SHAPE the out rows that the list does not name cost a group that finds nothing, and dividing by all of them
-// chose 4 lanes for the 4048 core vertices of a Graph500-skew 18 (0.650 ms, against 0.351 ms under 64).
-static int ex_lanes(long long scanned, long long R)
-{
-    if (scanned <= 16 * R) return 4;
-    return scanned <= 64 * R ? 16 : 64;
-}
-
 }  // namespace bsp
 
 using namespace bsp;
@@ -418,7 +405,7 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
     if (LJ.host && LJ.n > 0) HIPCHK_B(hipMemcpyAsync(lj, LJ.host, (size_t)LJ.n * sizeof(int), hipMemcpyHostToDevice, s));
     if (std::max(nwalk, nj) > 0) {
         const ExMaps a = {rowsA, colsA, A->d_row_ptr, dI, dJ, LI.all ? 0 : LI.n, nj, !LI.all, !LJ.all, keep, cmap, rflag, cbits, d_cnt};
-        hipLaunchKernelGGL(k_ex_maps, ex_grid(std::max(nwalk, nj)), dim3(kExThreads), 0, s, a);
+        hipLaunchKernelGGL(k_ex_maps, grid_for(std::max(nwalk, nj), kExThreads), dim3(kExThreads), 0, s, a);
     }
     if (!canonical) launch_canonical_check(A->d_row_ptr, A->d_col_idx, rowsA, colsA, E, 0, ctx->tile_row, &d_cnt->canon, s);
     ExCounters h = {};
@@ -461,7 +448,11 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
     }
     const int chunks = (int)h.chunks;
     const bool monotone = keep || LJ.all || !(h.err & kExErrUnsorted);
-    const int W = forced_w ? forced_w : ex_lanes(scanned, h.walked);
+    // The lanes per out row: a QUARTER of the mean length of the rows that are read, betweenness.hip's rule (no group walks
+    // more than kExHubChunk entries, so the mean, not the tail, sets the cost).  The mean is over the rows READ: under
+    // KEEP_SHAPE the out rows that the list does not name cost a group that finds nothing, and dividing by all of them chose 4
+    // lanes for the 4048 core vertices of a Graph500-skew 18 (0.650 ms, against 0.351 ms under 64).
+    const int W = forced_w ? forced_w : lanes_for_mean(scanned, h.walked, 4);
     const ExWalk walk = {R, A->d_row_ptr, keep || LI.all ? nullptr : dI, rflag, cbits, cmap};
     const dim3 block(kExThreads);
 
@@ -477,23 +468,23 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
             if (bspgemm_status st = ensure_tmpv(ctx, (size_t)chunks * (2 + kExWaves))) return bail(st);
             chunk = reinterpret_cast<int2 *>(ctx->tmpv);
             sub = ctx->tmpv + 2 * (size_t)chunks;
-            hipLaunchKernelGGL(k_ex_hub_records, ex_grid(R), block, 0, s, walk, chunk, chunks, d_cnt);
+            hipLaunchKernelGGL(k_ex_hub_records, grid_for(R, kExThreads), block, 0, s, walk, chunk, chunks, d_cnt);
         }
         // ---- count
         dispatch_lanes(W, [&](auto w) {
-            hipLaunchKernelGGL(k_ex_count<decltype(w)::value>, ex_grid((long long)R * W), block, 0, s, walk, A->d_col_idx, cnt);
+            hipLaunchKernelGGL(k_ex_count<decltype(w)::value>, grid_for((long long)R * W, kExThreads), block, 0, s, walk, A->d_col_idx, cnt);
         });
         HIPCHK_B(hipGetLastError());
         HIPCHK_B(stage(ms_count));
         if (chunks) {
             hipLaunchKernelGGL(k_ex_count_chunk, dim3((unsigned)chunks), block, 0, s, walk, chunk, A->d_col_idx, sub);
-            hipLaunchKernelGGL(k_ex_hub_finish, ex_grid(chunks), block, 0, s, walk, chunks, chunk, sub, cnt);
+            hipLaunchKernelGGL(k_ex_hub_finish, grid_for(chunks, kExThreads), block, 0, s, walk, chunks, chunk, sub, cnt);
             HIPCHK_B(hipGetLastError());
             HIPCHK_B(stage(ms_hub));
         }
         // ---- scan, out's row_ptr, read-back two
         launch_scan_counts(cnt, R, pre, part, nullptr, s);
-        hipLaunchKernelGGL(k_ex_rows, ex_grid((long long)R + 1), block, 0, s, R, pre, cnt, monotone ? 0 : 1, m->d_row_ptr, big, d_cnt);
+        hipLaunchKernelGGL(k_ex_rows, grid_for((long long)R + 1, kExThreads), block, 0, s, R, pre, cnt, monotone ? 0 : 1, m->d_row_ptr, big, d_cnt);
         HIPCHK_B(hipGetLastError());
         HIPCHK_B(stage(ms_scan));
         HIPCHK_B(hipMemcpyAsync(&kept, pre + R, sizeof kept, hipMemcpyDeviceToHost, s));
@@ -509,7 +500,7 @@ static bspgemm_status extract_run(bspgemm_context *ctx, const bspgemm_matrix *A,
         // ---- emit
         if (kept > 0) {
             dispatch_lanes(W, [&](auto w) {
-                hipLaunchKernelGGL(k_ex_emit<decltype(w)::value>, ex_grid((long long)R * W), block, 0, s, walk, A->d_col_idx, pre,
+                hipLaunchKernelGGL(k_ex_emit<decltype(w)::value>, grid_for((long long)R * W, kExThreads), block, 0, s, walk, A->d_col_idx, pre,
                                    m->d_col_idx);
             });
             HIPCHK_B(hipGetLastError());

@@ -269,10 +269,12 @@ size_t flag_scratch_carve(int *tmp, size_t at, long long E, bool lbs, FlagScratc
 size_t transpose_workspace_ints(long long E, int cols);
 size_t symmetrize_workspace_ints(long long E, int n);
 
-// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip, lcc.hip, pagerank.hip, betweenness.hip, match.hip, sssp.hip) ---
-// What the host side of the algorithms that repeat launches until a read-back says "done" shares.  The loops themselves are
-// each algorithm's own, and so is what it does about an untidy operand.  who: the entry point's name, which every message
-// starts with.
+// ------------------------------------------------------------------ round-based algorithms (cc.hip, scc.hip, kcore.hip, color.hip, bfs_tree.hip, lp.hip, lcc.hip, pagerank.hip, betweenness.hip, extract.hip, match.hip, sssp.hip) ---
+// What the host side of the algorithms that repeat launches until a read-back says "done" shares: the operand checks, the
+// grids (vertex_grid, grid_for), the lanes per vertex (lanes_for_mean, dispatch_lanes), the read-back (round_reset,
+// round_fetch, frontier_head_ok), the failures, the stage clock and the symmetrize opening (symmetrized_operand).  The device
+// side of the same algorithms is wave.hpp and hub_chunks.hpp.  The loops themselves are each algorithm's own, and so is what
+// it does about an untidy operand.  who: the entry point's name, which every message starts with.
 // the graph operand: check_operand with `flags`, then an entry count that an int32 entry index cannot hold
 static inline bspgemm_status check_graph_operand(const bspgemm_context *ctx, const bspgemm_matrix *A, const char *who, unsigned flags)
 {
@@ -330,6 +332,22 @@ static inline bspgemm_status assignment_operand(bspgemm_context *ctx, int n, bsp
 }
 // the grid of a pass with one thread per vertex and one more (row_ptr has n + 1 words)
 static inline dim3 vertex_grid(int n, int threads) { return dim3((unsigned)(((long long)n + 1 + threads - 1) / threads)); }
+// the grid of `threads` threads in workgroups of `block`: one workgroup at least, so that thread 0's resets happen
+static inline dim3 grid_for(long long threads, int block) { return dim3((unsigned)std::max(1ll, (threads + block - 1) / block)); }
+// The lanes per vertex (4, 16 or 64) of a launch whose `rows` rows hold `entries` entries: the smallest W at or above the
+// mean row length / per_lane.  per_lane 1 where a long row is a serial tail of its group, 4 where chunk records bound what a
+// group walks; the measurement behind each choice stands at its call.
+static inline int lanes_for_mean(long long entries, long long rows, int per_lane)
+{
+    if (entries <= 4ll * per_lane * rows) return 4;
+    return entries <= 16ll * per_lane * rows ? 16 : 64;
+}
+// what a read-back may say of the list that is read next, head = {entries, chunk records}: lo <= entries <= hi, and no
+// more records than the chunk array holds.  Anything else: fail_stuck.
+static inline bool frontier_head_ok(int2 head, int lo, int hi, size_t chunk_cap)
+{
+    return head.x >= lo && head.x <= hi && head.y >= 0 && (size_t)head.y <= chunk_cap;
+}
 // A repetition: zero the leading `bytes` of the device flag block, launch, read the block back -- its one synchronisation.
 static inline hipError_t round_reset(void *d_flags, size_t bytes, hipStream_t s) { return hipMemsetAsync(d_flags, 0, bytes, s); }
 static inline hipError_t round_fetch(void *h, const void *d_flags, size_t bytes, hipStream_t s)
@@ -384,6 +402,18 @@ struct StageClock {
     }
     double total() const { return ms_since(t0); }
 };
+// The opening of an algorithm on the simple undirected graph *S = symmetrize(A, DROP_DIAGONAL) (color.hip, match.hip, lp.hip):
+// the workspace grows ONCE, to what the symmetrize takes at most over its stages or, where ask_own, to the call's own
+// own_ints if that is more; then the symmetrize, and the lap into ms_sym.  Only for a call whose sequence of HIP calls and
+// allocations is exactly this: kcore.hip and lcc.hip order theirs differently.
+static inline bspgemm_status symmetrized_operand(bspgemm_context *ctx, const bspgemm_matrix *A, size_t own_ints, bool ask_own,
+                                                 StageClock &clk, double &ms_sym, bspgemm_matrix **S)
+{
+    if (bspgemm_status st = ensure_tmp(ctx, std::max(symmetrize_workspace_ints(A->nnz, A->rows), ask_own ? own_ints : 0))) return st;
+    if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, S)) return st;
+    (void)clk.lap(ms_sym, true);
+    return BSPGEMM_OK;
+}
 
 // ------------------------------------------------------------------ drop-in host steps (dropin.hip) ---
 // one line on stderr for a failed drop-in ("SpGEMM_hip: <status>: <last error>"), returns the status as int

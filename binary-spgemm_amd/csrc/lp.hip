@@ -82,16 +82,6 @@ struct LpFlags {
     u64 slots;              // table slots handed out to the hubs
 };
 
-__device__ __forceinline__ u32 lp_mix32(u32 x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // (count, label) as one word that orders by the larger count, then by the SMALLER label
 __device__ __forceinline__ u64 lp_pack(int count, int label) { return ((u64)(u32)count << 32) | (u32)~(u32)label; }
 __device__ __forceinline__ int lp_label(u64 best) { return (int)~(u32)best; }
@@ -288,7 +278,7 @@ struct LpHubInsert {
     __device__ __forceinline__ void flush()
     {
         if (run == 0) return;
-        u32 at = (u32)(((u64)lp_mix32((u32)(key - 1)) * size) >> 32);   // < size
+        u32 at = (u32)(((u64)mix32((u32)(key - 1)) * size) >> 32);   // < size
         for (u32 probe = 0; probe < size; probe++) {
             const int old = atomicCAS(&tab[2 * (size_t)at], 0, key);
             if (old == 0 || old == key) {
@@ -411,10 +401,8 @@ extern "C" bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, const 
         return WsCursor(tmp).take(d_flags, 1).take(tab_of, n4).take(label[1], n4).take(list, kLpClasses * n4).take(d_changed, shard_ints).ints();
     };
     const size_t own_ints = n > 0 ? carve(nullptr) : 0;
-    if (bspgemm_status st = ensure_tmp(ctx, std::max(symmetrize_workspace_ints(A->nnz, A->rows), own_ints))) return st;
     bspgemm_matrix *S = nullptr;
-    if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &S)) return st;
-    (void)clk.lap(ms_sym, true);
+    if (bspgemm_status st = symmetrized_operand(ctx, A, own_ints, true, clk, ms_sym, &S)) return st;   // (own_ints whatever nnz(A) is)
     hipStream_t s = ctx->stream;
     const long long E = S->nnz;                             // <= INT_MAX: symmetrize refuses more
     const bool edges = E > 0;

@@ -55,7 +55,6 @@ namespace bsp {
 constexpr int kMatchThreads = 256;
 constexpr int kMatchWaves = kMatchThreads / 64;
 constexpr int kMatchListThreads = 1024;  // the seed and the pair launch: one atomic per counter and WORKGROUP
-constexpr int kMatchListWaves = kMatchListThreads / 64;
 constexpr int kMatchChunk = 4096;       // the longest row left to one group of lanes; entries per chunk of a longer one
 constexpr int kMatchDeep = 4;           // steps of a row in flight per trip of the walk, as kColDeep
 constexpr u64 kMatchNone = ~0ull;
@@ -67,26 +66,13 @@ struct MatchFlags {
     u64 walked;             // the degrees of every vertex ever appended: the entries the point launches walk
 };
 
-__device__ __forceinline__ u32 match_mix32(u32 x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// the chunk records of a row: none for one that a group of lanes walks itself.  Host and device.
-__host__ __device__ __forceinline__ int match_chunks_of(int len) { return len > kMatchChunk ? hub_chunks_of<kMatchChunk>(len) : 0; }
-
 // key32 << 32 | w of the edge {u, w}; du = deg_S(u).  order: a bspgemm_match_order.
 __device__ __forceinline__ u64 match_candidate(int order, u32 seed, int u, int du, int w, const int *__restrict__ rpS)
 {
     u32 key = 0;
     if (order != BSPGEMM_MATCH_NATURAL) {
         const u32 a = (u32)min(u, w), b = (u32)max(u, w);
-        const u32 h = match_mix32(match_mix32(a ^ seed) ^ b);
+        const u32 h = mix32(mix32(a ^ seed) ^ b);
         if (order == BSPGEMM_MATCH_RANDOM) {
             key = h;
         } else {
@@ -104,52 +90,16 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_init(int n, int *__rest
     if (v < n && mate) mate[v] = -1;
 }
 
-// What the seed and the pair launch do for the vertices they list (`take`) and the pairs they count (`pair`); called by
-// every thread of a workgroup of kMatchListThreads.  The workgroup's appends, the degrees of the appended vertices (into
-// `walked`) and its pairs go out by ONE atomic each: with wave_append and a wave_count per wave the three counters, which
-// share a cache line, took an atomic per wave each, and the pair launches were bound by them.  A hub's chunk
-// records are taken by its own thread.  A vertex is listed once per round at most, so a list never passes n entries and the
-// records never pass chunk_cap (the host sized it for every hub at once); the stores are bounded all the same.
-struct MatchBlock {
-    long long deg[kMatchListWaves];
-    int cnt[kMatchListWaves], pairs[kMatchListWaves];
-    int base;
-};
+// What the seed and the pair launch do for the vertices they list (`take`) and the pairs they count (`pair`), in workgroups
+// of kMatchListThreads: block_list_append (hub_chunks.hpp), with the pairs as its third sum.  A vertex is listed once per
+// round at most, and a listed vertex has a non-empty row.
+typedef ListBlock<kMatchListThreads, true> MatchBlock;
 
 __device__ __forceinline__ void match_list(bool take, bool pair, int u, const int *__restrict__ rpS, int n, int *list, MatchFlags *fl,
                                            int nx, int2 *chunk, int chunk_cap, MatchBlock &sh)
 {
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const u64 m = __ballot(take);
-    const int du = take ? rpS[u + 1] - rpS[u] : 0;
-    const long long d = m ? wave_sum((long long)du) : 0;     // (wave-uniform)
-    const int p = __popcll(__ballot(pair));
-    if (lane == 0) {
-        sh.cnt[wv] = __popcll(m);
-        sh.deg[wv] = d;
-        sh.pairs[wv] = p;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0, ps = 0;
-        long long dsum = 0;
-#pragma unroll
-        for (int q = 0; q < kMatchListWaves; q++) {
-            const int c = sh.cnt[q];
-            sh.cnt[q] = total;                               // the wave's offset in the workgroup's slice
-            total += c;
-            dsum += sh.deg[q];
-            ps += sh.pairs[q];
-        }
-        sh.base = total ? atomicAdd(&fl->next[nx].x, total) : 0;
-        if (total) atomicAdd(&fl->walked, (u64)dsum);
-        if (ps) atomicAdd(&fl->pairs, ps);
-    }
-    __syncthreads();
-    const int at = sh.base + sh.cnt[wv] + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = u;
-    const int k = match_chunks_of(du);
-    if (k) hub_chunks_emit(u, k, &fl->next[nx].y, chunk, chunk_cap);
+    block_list_append<kMatchListThreads, kMatchChunk, true>(take, pair, u, rpS, n, list, &fl->next[nx], &fl->walked, &fl->pairs, chunk,
+                                                            chunk_cap, sh);
 }
 
 __global__ __launch_bounds__(kMatchListThreads) void k_match_seed(int n, const int *__restrict__ rpS, int *__restrict__ list,
@@ -168,6 +118,8 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_point(int fsize, const 
                                                               const int *__restrict__ colS, const int *__restrict__ mate,
                                                               u64 *__restrict__ best, int order, u32 seed, int2 *reset)
 {
+    // (open code: GroupRow of hub_chunks.hpp tests the row's length in 64 bits, this kernel in 32 -- du is needed as an int
+    // anyway -- and the two compile to other code)
     const long long t = (long long)blockIdx.x * kMatchThreads + threadIdx.x;
     const long long f = t / W;
     const int sub = (int)(t % W);
@@ -219,14 +171,8 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_hub(const int2 *__restr
         const int w = colS[pos];
         if (mate[w] < 0) m = min(m, match_candidate(order, seed, u, du, w, rpS));
     }
-    m = wave_min(m);
-    if (lane_id() == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 1; q < kMatchWaves; q++) m = min(m, part[q]);
-        if (m != kMatchNone) atomicMin(&best[u], m);
-    }
+    m = block_min<kMatchThreads>(m, part);
+    if (threadIdx.x == 0 && m != kMatchNone) atomicMin(&best[u], m);
 }
 
 // one thread per vertex of `list`.  best[] is complete: the point and the hub launch were earlier ones.  mate[] is only
@@ -263,16 +209,6 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_finish(int n, const int
     label[v] = w >= 0 && w < v ? w : (int)v;
 }
 
-static dim3 match_grid(long long threads, int block) { return dim3((unsigned)std::max(1ll, (threads + block - 1) / block)); }
-
-// The lanes per live vertex of a call: the smallest W at or above a QUARTER of the mean degree of the listed vertices, the
-// rule of betweenness.hip -- no group walks more than kMatchChunk entries, so a hub is no serial tail.
-static int match_lanes(long long E, long long listed)
-{
-    if (E <= 16 * listed) return 4;
-    return E <= 64 * listed ? 16 : 64;
-}
-
 }  // namespace bsp
 
 using namespace bsp;
@@ -306,11 +242,8 @@ extern "C" bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const b
         return WsCursor(tmp).take(d_flags, 1).take(best, n4).take(mate, n4).take(list[0], n4).take(list[1], n4).take(chunk, chunk_cap).ints();
     };
     const size_t upper_ints = carve(nullptr, chunk_cap_of(2 * (long long)A->nnz));
-    if (bspgemm_status st = ensure_tmp(ctx, std::max(symmetrize_workspace_ints(A->nnz, A->rows), A->nnz > 0 ? upper_ints : 0)))
-        return st;
     bspgemm_matrix *S = nullptr;
-    if (bspgemm_status st = bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &S)) return st;
-    (void)clk.lap(ms_sym, true);
+    if (bspgemm_status st = symmetrized_operand(ctx, A, upper_ints, A->nnz > 0, clk, ms_sym, &S)) return st;
     hipStream_t s = ctx->stream;
     const int n = S->rows;
     const long long E = S->nnz;                             // <= INT_MAX: symmetrize refuses more
@@ -338,7 +271,7 @@ extern "C" bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const b
     memset(&h_flags, 0, sizeof h_flags);
     if (edges) {
         HIPCHK_B(round_reset(d_flags, sizeof(MatchFlags), s));
-        hipLaunchKernelGGL(k_match_seed, match_grid(n, kMatchListThreads), dim3(kMatchListThreads), 0, s, n, S->d_row_ptr, list[0], d_flags, chunk, (int)chunk_cap);
+        hipLaunchKernelGGL(k_match_seed, grid_for(n, kMatchListThreads), dim3(kMatchListThreads), 0, s, n, S->d_row_ptr, list[0], d_flags, chunk, (int)chunk_cap);
         HIPCHK_B(hipGetLastError());
         HIPCHK_B(clk.lap(ms_seed, true));
         int2 head = make_int2(0, 0);                        // {entries, chunk records} of the list that is read next
@@ -346,8 +279,10 @@ extern "C" bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const b
         HIPCHK_B(hipMemcpyAsync(&head, &d_flags->next[0], sizeof head, hipMemcpyDeviceToHost, s));
         HIPCHK_B(hipStreamSynchronize(s));
         HIPCHK_B(clk.lap(ms_back));
-        if (head.x < 2 || head.x > n || head.y < 0 || (size_t)head.y > chunk_cap) return bail(fail_stuck(who));   // an edge has two ends
-        W = forced_w ? forced_w : match_lanes(E, head.x);
+        if (!frontier_head_ok(head, 2, n, chunk_cap)) return bail(fail_stuck(who));   // an edge has two ends
+        // the lanes per live vertex of the call: a QUARTER of the mean degree of the listed vertices, the rule of
+        // betweenness.hip -- no group walks more than kMatchChunk entries, so a hub is no serial tail
+        W = forced_w ? forced_w : lanes_for_mean(E, head.x, 4);
         while (head.x > 0) {
             if (rounds >= n) return bail(fail_stuck(who));
             rounds++;
@@ -356,7 +291,7 @@ extern "C" bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const b
             double ms_round = 0;
             clk.start();
             dispatch_lanes(W, [&](auto w) {
-                hipLaunchKernelGGL(k_match_point<decltype(w)::value>, match_grid((long long)fsize * W, kMatchThreads), block, 0, s, fsize, list[cur],
+                hipLaunchKernelGGL(k_match_point<decltype(w)::value>, grid_for((long long)fsize * W, kMatchThreads), block, 0, s, fsize, list[cur],
                                    S->d_row_ptr, S->d_col_idx, mate, best, (int)order, (u32)seed, &d_flags->next[cur ^ 1]);
             });
             HIPCHK_B(hipGetLastError());
@@ -369,7 +304,7 @@ extern "C" bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const b
                 HIPCHK_B(clk.lap(ms_hub, true));
                 ms_round += clk.last;
             }
-            hipLaunchKernelGGL(k_match_pair, match_grid(fsize, kMatchListThreads), dim3(kMatchListThreads), 0, s, n, fsize, list[cur], S->d_row_ptr, best, mate,
+            hipLaunchKernelGGL(k_match_pair, grid_for(fsize, kMatchListThreads), dim3(kMatchListThreads), 0, s, n, fsize, list[cur], S->d_row_ptr, best, mate,
                                list[cur ^ 1], d_flags, cur ^ 1, chunk, (int)chunk_cap);
             HIPCHK_B(hipGetLastError());
             HIPCHK_B(clk.lap(ms_pair, true));
@@ -378,7 +313,7 @@ extern "C" bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, const b
             HIPCHK_B(hipStreamSynchronize(s));              // the round's one synchronisation
             HIPCHK_B(clk.lap(ms_back));
             // the smallest live edge of the round was matched, or nobody had a candidate: the list shrinks
-            if (head.x < 0 || head.x >= fsize || head.y < 0 || (size_t)head.y > chunk_cap) return bail(fail_stuck(who));
+            if (!frontier_head_ok(head, 0, fsize - 1, chunk_cap)) return bail(fail_stuck(who));
             cur ^= 1;
         }
         HIPCHK_B(hipMemcpyAsync(&h_flags, d_flags, sizeof h_flags, hipMemcpyDeviceToHost, s));

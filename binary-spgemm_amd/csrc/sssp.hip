@@ -73,7 +73,6 @@ namespace bsp {
 constexpr int kSsspThreads = 256;
 constexpr int kSsspWaves = kSsspThreads / 64;
 constexpr int kSsspListThreads = 1024;  // the settle and the scan launch: one atomic per counter and WORKGROUP, as match.hip
-constexpr int kSsspListWaves = kSsspListThreads / 64;
 constexpr int kSsspSettleBlocks = 256;  // the settle's grid at most: it strides to the candidate count
 constexpr int kSsspChunk = 4096;        // the longest row left to one group of lanes; entries per chunk of a longer one
 constexpr int kSsspDeep = 4;            // steps of a row in flight per trip of the walk, as kMatchDeep
@@ -90,18 +89,6 @@ struct SsspCnt {
     u64 dist_max;
 };
 
-__device__ __forceinline__ u32 sssp_mix32(u32 x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__host__ __device__ __forceinline__ int sssp_chunks_of(int len) { return len > kSsspChunk ? hub_chunks_of<kSsspChunk>(len) : 0; }
-
 // ------------------------------------------------------------------ weights ---------------
 // bspgemm_weights_hashed as an op of sel_walk_entries: w[p] of entry p = (r, c), and the lane's share of the sum
 struct WeightHash {
@@ -115,7 +102,7 @@ struct WeightHash {
     __device__ __forceinline__ void entry(int r, long long p, int c, int)
     {
         const u32 a = symmetric ? (u32)min(r, c) : (u32)r, b = symmetric ? (u32)max(r, c) : (u32)c;
-        const u32 x = wmin + (u32)((u64)sssp_mix32(sssp_mix32(a ^ seed) ^ b) % span);
+        const u32 x = wmin + (u32)((u64)mix32(mix32(a ^ seed) ^ b) % span);
         w[p] = x;
         sum += x;
     }
@@ -153,7 +140,7 @@ __global__ __launch_bounds__(kSsspThreads) void k_sssp_init(int n, int source, c
         cnt->next[0].x = 1;
         cnt->walked = (u64)len;
         cnt->minp = kSsspInf;
-        const int k = sssp_chunks_of(len);
+        const int k = hub_chunks_over<kSsspChunk>(len);
         if (k) hub_chunks_emit(source, k, &cnt->next[0].y, chunk, chunk_cap);
     }
 }
@@ -202,25 +189,17 @@ __global__ __launch_bounds__(kSsspThreads) void k_sssp_relax(int fsize, const in
                                                             const u64 *__restrict__ snap, u64 *dist, int *__restrict__ pend,
                                                             unsigned *stamp, unsigned round, int *cand, SsspCnt *cnt, int nx)
 {
-    const long long t = (long long)blockIdx.x * kSsspThreads + threadIdx.x;
-    const long long f = t / W;
-    const int sub = (int)(t % W);
-    if (t == 0) {
+    GroupRow<W, kSsspThreads> g;
+    if (g.t == 0) {
         cnt->next[nx] = make_int2(0, 0);
         cnt->minp = kSsspInf;
     }
-    long long pos = 0, e = 0;
     u64 su = 0;
-    if (f < fsize) {
-        const int u = list[f];
-        const long long b = rp[u];
-        e = rp[u + 1];
-        if (e - b > kSsspChunk) e = b;                       // (the chunks' row)
-        pos = b + sub;
+    g.template row<kSsspChunk>(fsize, list, 0, rp, [&, sub = g.sub](int u) {
         su = snap[u];
         if (sub == 0) pend[u] = 0;
-    }
-    sssp_walk(pos, e, W, su, col, wt, n, dist, stamp, round, cand, &cnt->cand[round & 1]);
+    });
+    sssp_walk(g.pos, g.e, W, su, col, wt, n, dist, stamp, round, cand, &cnt->cand[round & 1]);
 }
 
 // one workgroup per chunk record chunk[blockIdx.x]
@@ -235,47 +214,16 @@ __global__ __launch_bounds__(kSsspThreads) void k_sssp_hub(const int2 *__restric
     sssp_walk(b + threadIdx.x, e, kSsspThreads, snap[rec.x], col, wt, n, dist, stamp, round, cand, &cnt->cand[round & 1]);
 }
 
-// What the settle and the scan launch do for the vertices they put on a near list (`take`); called by every thread of a
-// workgroup of kSsspListThreads.  The workgroup's appends and the row lengths of the appended vertices (into `walked`) go out
-// by ONE atomic each.  A hub's chunk records are taken by its own thread.  A vertex is listed once per launch at most, so
-// a list never passes n entries and the records never pass chunk_cap (the host sized it for every hub at once); the stores
-// are bounded all the same.  The last barrier frees `sh` for the caller's next trip.
-struct SsspBlock {
-    long long len[kSsspListWaves];
-    int cnt[kSsspListWaves];
-    int base;
-};
+// What the settle and the scan launch do for the vertices they put on a near list (`take`), in workgroups of
+// kSsspListThreads: block_list_append (hub_chunks.hpp).  A vertex is listed once per launch at most.  The barrier frees `sh`
+// for the settle's next trip.
+typedef ListBlock<kSsspListThreads, false> SsspBlock;
 
 __device__ __forceinline__ void sssp_list(bool take, int u, const int *__restrict__ rp, int n, int *list, SsspCnt *c, int nx,
                                           int2 *chunk, int chunk_cap, SsspBlock &sh)
 {
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const u64 m = __ballot(take);
-    const int du = take ? rp[u + 1] - rp[u] : 0;
-    const long long d = m ? wave_sum((long long)du) : 0;     // (wave-uniform)
-    if (lane == 0) {
-        sh.cnt[wv] = __popcll(m);
-        sh.len[wv] = d;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-        long long dsum = 0;
-#pragma unroll
-        for (int q = 0; q < kSsspListWaves; q++) {
-            const int k = sh.cnt[q];
-            sh.cnt[q] = total;                               // the wave's offset in the workgroup's slice
-            total += k;
-            dsum += sh.len[q];
-        }
-        sh.base = total ? atomicAdd(&c->next[nx].x, total) : 0;
-        if (dsum) atomicAdd(&c->walked, (u64)dsum);
-    }
-    __syncthreads();
-    const int at = sh.base + sh.cnt[wv] + __popcll(m & mask_lt(lane));
-    if (take && (unsigned)at < (unsigned)n) list[at] = u;
-    const int k = sssp_chunks_of(du);
-    if (k) hub_chunks_emit(u, k, &c->next[nx].y, chunk, chunk_cap);
+    block_list_append<kSsspListThreads, kSsspChunk, false>(take, false, u, rp, n, list, &c->next[nx], &c->walked, nullptr, chunk,
+                                                           chunk_cap, sh);
     __syncthreads();
 }
 
@@ -313,14 +261,8 @@ __global__ __launch_bounds__(kSsspThreads) void k_sssp_min(int n, const int *__r
     __shared__ u64 part[kSsspWaves];
     const long long v = (long long)blockIdx.x * kSsspThreads + threadIdx.x;
     u64 m = v < n && pend[v] ? snap[v] : kSsspInf;
-    m = wave_min(m);
-    if (lane_id() == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 1; q < kSsspWaves; q++) m = min(m, part[q]);
-        if (m != kSsspInf) atomicMin(&cnt->minp, m);
-    }
+    m = block_min<kSsspThreads>(m, part);
+    if (threadIdx.x == 0 && m != kSsspInf) atomicMin(&cnt->minp, m);
 }
 
 // the bucket that holds the pending minimum m: its exclusive upper end.  Host and device.  No overflow: m < 2^63 (at most
@@ -378,6 +320,7 @@ __global__ __launch_bounds__(kSsspThreads) void k_sssp_finish(int n, int source,
         const int p = parent[v];
         parent[v] = v == source ? source : (!reached || p == INT_MAX ? -1 : p);
     }
+    // (open code: a block_max in the manner of block_min brings a barrier of its own and more registers)
     const u64 m = wave_max(reached ? d : 0ull);
     if (lane_id() == 0) part[threadIdx.x >> 6] = m;
     block_add<kSsspThreads>(reached, &cnt->reached, nullptr, wsum);      // (its barriers cover part[] too)
@@ -387,16 +330,6 @@ __global__ __launch_bounds__(kSsspThreads) void k_sssp_finish(int n, int source,
         for (int q = 1; q < kSsspWaves; q++) mm = max(mm, part[q]);
         if (mm) atomicMax(&cnt->dist_max, mm);
     }
-}
-
-static dim3 sssp_grid(long long threads, int block) { return dim3((unsigned)std::max(1ll, (threads + block - 1) / block)); }
-
-// The lanes per near-list vertex of a call: the smallest W at or above a QUARTER of the mean stored degree, the rule of
-// match.hip -- no group walks more than kSsspChunk entries, so a hub is no serial tail.
-static int sssp_lanes(long long E, long long n)
-{
-    if (E <= 16 * n) return 4;
-    return E <= 64 * n ? 16 : 64;
 }
 
 }  // namespace bsp
@@ -531,7 +464,9 @@ extern "C" bspgemm_status bspgemm_sssp(bspgemm_context *ctx, const bspgemm_matri
     if (bspgemm_status st = use_device(ctx)) return st;
     const long long E = A->nnz;
     const u64 delta = params && params->delta ? params->delta : sssp_default_delta(W->sum, E, n);
-    const int Wl = forced_w ? forced_w : sssp_lanes(E, n);
+    // the lanes per near-list vertex of the call: a QUARTER of the mean stored degree, the rule of match.hip -- no group walks
+    // more than kSsspChunk entries, so a hub is no serial tail
+    const int Wl = forced_w ? forced_w : lanes_for_mean(E, n, 4);
     // The workspace grows ONCE, before anything is launched.  A row longer than the chunk size has fewer than 2 len / chunk
     // chunks, so all hubs together have fewer than 2 nnz / chunk records.
     const size_t n4 = ws_pad4((size_t)n), chunk_cap = (size_t)(2 * E / kSsspChunk + 1);
@@ -551,7 +486,7 @@ extern "C" bspgemm_status bspgemm_sssp(bspgemm_context *ctx, const bspgemm_matri
     hipStream_t s = ctx->stream;
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); return st; };
     const dim3 block(kSsspThreads), lblock(kSsspListThreads);
-    const dim3 vgrid = sssp_grid(n, kSsspThreads), lgrid = sssp_grid(n, kSsspListThreads);
+    const dim3 vgrid = grid_for(n, kSsspThreads), lgrid = grid_for(n, kSsspListThreads);
     const dim3 sgrid(std::min(lgrid.x, (unsigned)kSsspSettleBlocks));
     const int *rp = A->d_row_ptr, *col = A->d_col_idx;
     const u32 *wt = W->d_w;
@@ -570,7 +505,7 @@ extern "C" bspgemm_status bspgemm_sssp(bspgemm_context *ctx, const bspgemm_matri
     u64 T = delta;                                          // the first bucket: [0, delta)
     const long long cap_rounds = 2ll * n + 2;
     for (;;) {
-        if (head.x < 0 || head.x > n || head.y < 0 || (size_t)head.y > chunk_cap) return bail(fail_stuck(who));
+        if (!frontier_head_ok(head, 0, n, chunk_cap)) return bail(fail_stuck(who));
         if (head.x == 0) {                                  // ADVANCE: the bucket of the smallest pending vertex
             clk.start();
             hipLaunchKernelGGL(k_sssp_min, vgrid, block, 0, s, n, pend, snap, d_cnt);
@@ -584,7 +519,7 @@ extern "C" bspgemm_status bspgemm_sssp(bspgemm_context *ctx, const bspgemm_matri
             T = sssp_bucket_end(h.minp, delta);
             buckets++;
             head = h.next[cur];
-            if (head.x <= 0 || head.x > n || head.y < 0 || (size_t)head.y > chunk_cap) return bail(fail_stuck(who));
+            if (!frontier_head_ok(head, 1, n, chunk_cap)) return bail(fail_stuck(who));
         }
         if (rounds >= cap_rounds) return bail(fail_stuck(who));
         rounds++;
@@ -594,7 +529,7 @@ extern "C" bspgemm_status bspgemm_sssp(bspgemm_context *ctx, const bspgemm_matri
         double ms_round = 0;
         clk.start();
         dispatch_lanes(Wl, [&](auto w) {
-            hipLaunchKernelGGL(k_sssp_relax<decltype(w)::value>, sssp_grid((long long)fsize * Wl, kSsspThreads), block, 0, s, fsize,
+            hipLaunchKernelGGL(k_sssp_relax<decltype(w)::value>, grid_for((long long)fsize * Wl, kSsspThreads), block, 0, s, fsize,
                                near[cur], rp, col, wt, n, snap, dist, pend, stamp, round, cand, d_cnt, cur ^ 1);
         });
         HIPCHK_B(hipGetLastError());

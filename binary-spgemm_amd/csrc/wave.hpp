@@ -17,6 +17,17 @@ __device__ __forceinline__ int lane_id()
     return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }
 
+// mix32 of include/bspgemm.h: the hash behind every seeded order and weight.  Part of the public contract; written once.
+__device__ __forceinline__ u32 mix32(u32 x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
 // bits below / up to and including this lane
 __device__ __forceinline__ u64 mask_lt(int lane) { return (1ull << lane) - 1ull; }
 __device__ __forceinline__ u64 mask_le(int lane) { return (2ull << lane) - 1ull; }
@@ -186,6 +197,22 @@ __device__ __forceinline__ void block_add(bool x, int *word, int *also, int *wsu
         if (s && also) atomicAdd(also, s);
     }
     __syncthreads();                                                     // (wsum is free again)
+}
+
+// the workgroup's minimum of x, valid in thread 0 ALONE: the caller sends it on by one atomic.  part: THREADS / 64 words of
+// LDS, not free again before the caller's next barrier.  Called by every thread of the workgroup (THREADS of them).  (There
+// is no block_max: its one candidate, k_sssp_finish, shares block_add's barriers and keeps its open code.)
+template <int THREADS>
+__device__ __forceinline__ u64 block_min(u64 x, u64 *part)
+{
+    x = wave_min(x);
+    if (lane_id() == 0) part[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 1; q < THREADS / 64; q++) x = min(x, part[q]);
+    }
+    return x;
 }
 
 }  // namespace bsp

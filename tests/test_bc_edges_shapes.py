@@ -44,7 +44,10 @@ def test_constants_are_the_sources():
     const = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
     assert (const("kBcHubChunk"), const("kBcThreads")) == (B.HUB_CHUNK, B.THREADS) == (4096, 256)
     assert "for (int j = threadIdx.x; j < k && j < chunk_cap; j += kBcThreads) chunk[j] = make_int2(src, j);" in src
-    assert "return len > kBcHubChunk ? hub_chunks_of<kBcHubChunk>(len) : 0;" in src
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "binary-spgemm_amd", "csrc", "hub_chunks.hpp")) as f:
+        hub = f.read()
+    assert "return len > CHUNK ? hub_chunks_of<CHUNK>(len) : 0;" in hub     # hub_chunks_over<CHUNK>, which betweenness.hip calls
+    assert "hub_chunks_over<kBcHubChunk>(len)" in src
     assert sorted(ALL_CELLS) == sorted(B.CELLS) and len(set(ALL_CELLS)) == len(ALL_CELLS)
 
 
