@@ -15,7 +15,6 @@
  * %.17g).  ms: wall time of bspgemm_betweenness, the operand already on the device.
  */
 #include "cli_common.h"
-#include <errno.h>
 #include <inttypes.h>
 
 static const uint64_t *g_bc;
@@ -35,10 +34,8 @@ static void usage(void)
 
 static long long whole(const char *text, long long lo, long long hi)
 {
-    char *end;
-    errno = 0;
-    const long long x = strtoll(text, &end, 10);
-    if (errno || end == text || *end || x < lo || x > hi) usage();
+    long long x;
+    if (!cli_signed(text, 10, lo, hi, &x)) usage();
     return x;
 }
 
@@ -50,23 +47,22 @@ int main(int argc, char **argv)
     const char *out = NULL;
     if (argc < 2 || argv[1][0] == '-') usage();
     for (int i = 2; i < argc; i++) {
-        if (!strcmp(argv[i], "--all")) all = 1;
-        else if (!strcmp(argv[i], "--symmetrize")) symmetrize = 1;
-        else if (!strcmp(argv[i], "--sources") && i + 1 < argc) { k = whole(argv[++i], 0, 1000000000); counted = 1; }
-        else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed = (uint64_t)whole(argv[++i], 0, 4000000000000000000ll);
-        else if (!strcmp(argv[i], "--top") && i + 1 < argc) top = whole(argv[++i], 0, 1000000000);
-        else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
-        else usage();
+        const char *val;
+        if (cli_flag(argv[i], "--all")) all = 1;
+        else if (cli_flag(argv[i], "--symmetrize")) symmetrize = 1;
+        else if (cli_value(argc, argv, &i, "--sources", &val)) { k = whole(val, 0, 1000000000); counted = 1; }
+        else if (cli_value(argc, argv, &i, "--seed", &val)) seed = (uint64_t)whole(val, 0, 4000000000000000000ll);
+        else if (cli_value(argc, argv, &i, "--top", &val)) top = whole(val, 0, 1000000000);
+        else if (!cli_value(argc, argv, &i, "--out", &out)) usage();
     }
     if (all && counted) usage();
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("betweenness", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *At, *A;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &At), "upload");
-    if (symmetrize) CHECK(bspgemm_matrix_symmetrize(ctx, At, 0u, &A), "bspgemm_matrix_symmetrize");
-    else CHECK(bspgemm_matrix_transpose(ctx, At, &A), "bspgemm_matrix_transpose");
+    cli_session s = cli_open(argv[1], 0, "betweenness");                  /* s.A: the loader's transpose */
+    const uint32_t M = s.M;
+    cli_upload(&s);
+    bspgemm_context *ctx = s.ctx;
+    bspgemm_matrix *A;
+    if (symmetrize) CHECK(bspgemm_matrix_symmetrize(ctx, s.A, 0u, &A), "bspgemm_matrix_symmetrize");
+    else CHECK(bspgemm_matrix_transpose(ctx, s.A, &A), "bspgemm_matrix_transpose");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
     if (all) k = M;
     if (M == 0) k = 0;
@@ -93,15 +89,12 @@ int main(int argc, char **argv)
     for (uint32_t i = 0; i < M && i < (uint32_t)top; i++)
         printf("%d,%" PRIu64 ",%.17g\n", order[i], fixed[order[i]], bc[order[i]]);
     if (out) {
-        FILE *f = fopen(out, "w");
-        if (!f) { fprintf(stderr, "cannot write %s\n", out); exit(1); }
+        FILE *f = cli_create(out);
         for (uint32_t v = 0; v < M; v++) fprintf(f, "%" PRIu64 "\n", fixed[v]);
-        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", out); exit(1); }
+        cli_finish(f, out);
     }
     free(sources); free(fixed); free(bc); free(order);
     bspgemm_matrix_free(A);
-    bspgemm_matrix_free(At);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

@@ -13,7 +13,6 @@
  * n,nnz,nsources,depth,complete,ms.  ms: wall time of bspgemm_bfs, the operand already on the device.
  */
 #include "cli_common.h"
-#include <errno.h>
 #include <limits.h>
 
 int main(int argc, char **argv)
@@ -26,30 +25,25 @@ int main(int argc, char **argv)
     int *sources = malloc((size_t)S * sizeof(int));
     if (!sources) exit(1);
     for (int i = 0; i < S; i++) {
-        char *end;
-        errno = 0;
-        const long v = strtol(argv[2 + i], &end, 10);
-        if (errno || end == argv[2 + i] || *end || v < INT_MIN || v > INT_MAX) {
+        long long v;
+        if (!cli_signed(argv[2 + i], 10, INT_MIN, INT_MAX, &v)) {
             fprintf(stderr, "source %d (\"%s\") is not a vertex id\n", i, argv[2 + i]);
             exit(1);
         }
         sources[i] = (int)v;
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("bfs", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *At, *A;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &At), "upload");
-    CHECK(bspgemm_matrix_transpose(ctx, At, &A), "bspgemm_matrix_transpose");
-    bspgemm_matrix_free(At);
+    cli_session s = cli_open(argv[1], 0, "bfs");
+    cli_upload(&s);
+    bspgemm_context *ctx = s.ctx;
+    bspgemm_matrix *A;                                /* the out-edge operand replaces the loader's transpose */
+    CHECK(bspgemm_matrix_transpose(ctx, s.A, &A), "bspgemm_matrix_transpose");
+    bspgemm_matrix_free(s.A);
+    s.A = A;
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const struct timespec t0 = cli_now();
     bspgemm_result *L;
     int depth = 0, complete = 0;
-    CHECK(bspgemm_bfs(ctx, A, S, sources, 0, &L, &depth, &complete), "bspgemm_bfs");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, ctx, bspgemm_bfs(ctx, A, S, sources, 0, &L, &depth, &complete), "bspgemm_bfs");
     const long long total = bspgemm_result_nnz(L);
     int64_t *rp = malloc(((size_t)S + 1) * sizeof(int64_t));
     int *lv = malloc((size_t)(total > 0 ? total : 1) * sizeof(int));
@@ -65,11 +59,9 @@ int main(int argc, char **argv)
         }
         printf("%d,%lld,%d,%lld\n", sources[i], (long long)(rp[i + 1] - rp[i]), ecc, sum);
     }
-    printf("%u,%u,%d,%d,%d,%.3f\n", M, nnz, S, depth, complete, ms);
+    printf("%u,%u,%d,%d,%d,%.3f\n", s.M, s.nnz, S, depth, complete, ms);
     free(rp); free(lv); free(sources);
     bspgemm_result_free(L);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

@@ -12,7 +12,6 @@
  * of bspgemm_bfs_tree, the operands already on the device.
  */
 #include "cli_common.h"
-#include <errno.h>
 #include <limits.h>
 
 int main(int argc, char **argv)
@@ -20,37 +19,31 @@ int main(int argc, char **argv)
     bspgemm_bfs_direction dir = BSPGEMM_BFS_AUTO;
     int symmetric = 0, bad = argc < 3;
     for (int i = 3; i < argc && !bad; i++) {
-        if (!strcmp(argv[i], "--push")) dir = BSPGEMM_BFS_PUSH;
-        else if (!strcmp(argv[i], "--pull")) dir = BSPGEMM_BFS_PULL;
-        else if (!strcmp(argv[i], "--symmetric")) symmetric = 1;
+        if (cli_flag(argv[i], "--push")) dir = BSPGEMM_BFS_PUSH;
+        else if (cli_flag(argv[i], "--pull")) dir = BSPGEMM_BFS_PULL;
+        else if (cli_flag(argv[i], "--symmetric")) symmetric = 1;
         else bad = 1;
     }
     if (bad) {
         printf("usage: SpGEMM_hip_bfs_tree  path-to-matrix  source  [--push|--pull]  [--symmetric]\n");
         exit(1);
     }
-    char *end;
-    errno = 0;
-    const long src = strtol(argv[2], &end, 10);
-    if (errno || end == argv[2] || *end || src < INT_MIN || src > INT_MAX) {
+    long long src;
+    if (!cli_signed(argv[2], 10, INT_MIN, INT_MAX, &src)) {
         fprintf(stderr, "source (\"%s\") is not a vertex id\n", argv[2]);
         exit(1);
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("bfs_tree", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *At, *A;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &At), "upload");
-    if (symmetric) A = At;
-    else CHECK(bspgemm_matrix_transpose(ctx, At, &A), "bspgemm_matrix_transpose");
+    cli_session s = cli_open(argv[1], 0, "bfs_tree");                     /* s.A: the in-edge operand AT */
+    const uint32_t M = s.M;
+    cli_upload(&s);
+    bspgemm_context *ctx = s.ctx;
+    bspgemm_matrix *A = s.A;
+    if (!symmetric) CHECK(bspgemm_matrix_transpose(ctx, s.A, &A), "bspgemm_matrix_transpose");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const struct timespec t0 = cli_now();
     bspgemm_result *T;
     bspgemm_bfs_tree_info info;
-    CHECK(bspgemm_bfs_tree(ctx, A, At, (int)src, dir, 0, &T, &info), "bspgemm_bfs_tree");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, ctx, bspgemm_bfs_tree(ctx, A, s.A, (int)src, dir, 0, &T, &info), "bspgemm_bfs_tree");
     const long long reached = bspgemm_result_nnz(T);
     int64_t *rp = malloc(((size_t)M + 1) * sizeof(int64_t));
     int *parent = malloc((size_t)(reached > 0 ? reached : 1) * sizeof(int));
@@ -63,13 +56,11 @@ int main(int argc, char **argv)
         sum_levels += level[p];
         sum_parents += parent[p];
     }
-    printf("%ld,%lld,%d,%lld,%lld\n", src, reached, info.depth, sum_levels, sum_parents);
-    printf("%u,%u,%d,%d,%.3f\n", M, nnz, info.push_levels, info.pull_levels, ms);
+    printf("%lld,%lld,%d,%lld,%lld\n", src, reached, info.depth, sum_levels, sum_parents);
+    printf("%u,%u,%d,%d,%.3f\n", M, s.nnz, info.push_levels, info.pull_levels, ms);
     free(rp); free(parent); free(level);
     bspgemm_result_free(T);
     if (!symmetric) bspgemm_matrix_free(A);
-    bspgemm_matrix_free(At);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

@@ -23,44 +23,35 @@ int main(int argc, char **argv)
 {
     const char *labels_path = NULL;
     int iterations = 10;
-    if (argc < 2 || argc % 2 != 0) usage();
-    for (int i = 2; i < argc; i += 2) {
-        if (strcmp(argv[i], "--iterations") == 0) {
-            char *end;
-            const long k = strtol(argv[i + 1], &end, 0);
-            if (end == argv[i + 1] || *end || k < 0 || k > 0x7fffffffL) usage();
+    if (argc < 2) usage();
+    for (int i = 2; i < argc; i++) {
+        const char *val;
+        if (cli_value(argc, argv, &i, "--iterations", &val)) {
+            long long k;                /* (a value that overflows saturates past the bound: errno changes nothing here) */
+            if (!cli_signed(val, 0, 0, 0x7fffffffLL, &k)) usage();
             iterations = (int)k;
-        } else if (strcmp(argv[i], "--labels") == 0) {
-            labels_path = argv[i + 1];
-        } else {
+        } else if (!cli_value(argc, argv, &i, "--labels", &labels_path)) {
             usage();
         }
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("label propagation", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A, *P;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const struct timespec t0 = cli_now();
+    cli_session s = cli_open(argv[1], 0, "label propagation");
+    const uint32_t M = s.M;
+    cli_upload(&s);
+    bspgemm_matrix *P;
     bspgemm_lp_info info;
-    CHECK(bspgemm_label_propagation(ctx, A, NULL, iterations, &P, &info), "bspgemm_label_propagation");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, s.ctx, bspgemm_label_propagation(s.ctx, s.A, NULL, iterations, &P, &info), "bspgemm_label_propagation");
     int *label = malloc(((size_t)M + 1) * sizeof(int));
     int *size = calloc((size_t)M + 1, sizeof(int));
     if (!label || !size) exit(1);
-    CHECK(bspgemm_matrix_download(ctx, P, NULL, label), "download");
+    CHECK(bspgemm_matrix_download(s.ctx, P, NULL, label), "download");
     int largest = 0;
     for (uint32_t v = 0; v < M; v++)
         if (++size[label[v]] > largest) largest = size[label[v]];
     if (labels_path) cli_write_ints(labels_path, label, M);
-    printf("%u,%u,%d,%d,%d,%d,%.3f\n", M, nnz, info.communities, largest, info.iterations, info.converged, ms);
+    printf("%u,%u,%d,%d,%d,%d,%.3f\n", M, s.nnz, info.communities, largest, info.iterations, info.converged, ms);
     free(label); free(size);
     bspgemm_matrix_free(P);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

@@ -17,18 +17,16 @@ int main(int argc, char **argv)
         printf("usage: SpGEMM_hip_closure  path-to-matrix  [path-to-result]\n");
         exit(1);
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("closure", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
+    cli_session s = cli_open(argv[1], 0, "closure");
+    const uint32_t M = s.M;
+    bspgemm_context *ctx = s.ctx = cli_context(0);  /* open, not cli_upload: no synchronise stands before this timer */
+    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)s.Arow, (const int *)s.Acol, &s.A), "upload");
     const struct timespec t0 = cli_now();
     bspgemm_result *T;
     int products = 0;
-    CHECK(bspgemm_closure(ctx, A, 64, &T, &products), "bspgemm_closure");
+    CHECK(bspgemm_closure(ctx, s.A, 64, &T, &products), "bspgemm_closure");
     const double secs = cli_ms(t0, cli_now()) * 1e-3;
-    printf("%s,%u,%u,%d,%lld,%lf\n", argv[1], M, nnz, products, (long long)bspgemm_result_nnz(T), secs);
+    printf("%s,%u,%u,%d,%lld,%lf\n", argv[1], M, s.nnz, products, (long long)bspgemm_result_nnz(T), secs);
     if (argc == 3) {
         const long long tn = bspgemm_result_nnz(T);
         int64_t *rp = malloc(((size_t)M + 1) * sizeof(int64_t));
@@ -39,8 +37,6 @@ int main(int argc, char **argv)
         free(rp); free(ci);
     }
     bspgemm_result_free(T);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

@@ -24,48 +24,40 @@ int main(int argc, char **argv)
     const char *colors_path = NULL;
     bspgemm_color_order order = BSPGEMM_COLOR_RANDOM;
     unsigned seed = 0;
-    if (argc < 2 || argc % 2 != 0) usage();
-    for (int i = 2; i < argc; i += 2) {
-        if (strcmp(argv[i], "--order") == 0) {
-            if (strcmp(argv[i + 1], "natural") == 0) order = BSPGEMM_COLOR_NATURAL;
-            else if (strcmp(argv[i + 1], "random") == 0) order = BSPGEMM_COLOR_RANDOM;
-            else if (strcmp(argv[i + 1], "largest") == 0) order = BSPGEMM_COLOR_LARGEST_FIRST;
+    if (argc < 2) usage();
+    for (int i = 2; i < argc; i++) {
+        const char *val;
+        if (cli_value(argc, argv, &i, "--order", &val)) {
+            if (strcmp(val, "natural") == 0) order = BSPGEMM_COLOR_NATURAL;
+            else if (strcmp(val, "random") == 0) order = BSPGEMM_COLOR_RANDOM;
+            else if (strcmp(val, "largest") == 0) order = BSPGEMM_COLOR_LARGEST_FIRST;
             else usage();
-        } else if (strcmp(argv[i], "--seed") == 0) {
-            char *end;
-            seed = (unsigned)strtoul(argv[i + 1], &end, 0);
-            if (end == argv[i + 1] || *end) usage();
-        } else if (strcmp(argv[i], "--colors") == 0) {
-            colors_path = argv[i + 1];
-        } else {
+        } else if (cli_value(argc, argv, &i, "--seed", &val)) {
+            char *end;                  /* open: no errno or sign check, so "-1" and a value past 2^64 - 1 are taken and wrap */
+            seed = (unsigned)strtoul(val, &end, 0);
+            if (end == val || *end) usage();
+        } else if (!cli_value(argc, argv, &i, "--colors", &colors_path)) {
             usage();
         }
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("colouring", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A, *P;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const struct timespec t0 = cli_now();
+    cli_session s = cli_open(argv[1], 0, "colouring");
+    const uint32_t M = s.M;
+    cli_upload(&s);
+    bspgemm_matrix *P;
     int colors = 0, rounds = 0;
-    CHECK(bspgemm_graph_coloring(ctx, A, order, seed, &P, &colors, &rounds), "bspgemm_graph_coloring");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, s.ctx, bspgemm_graph_coloring(s.ctx, s.A, order, seed, &P, &colors, &rounds), "bspgemm_graph_coloring");
     int *color = malloc(((size_t)M + 1) * sizeof(int));
     int *size = calloc((size_t)M + 1, sizeof(int));
     if (!color || !size) exit(1);
-    CHECK(bspgemm_matrix_download(ctx, P, NULL, color), "download");
+    CHECK(bspgemm_matrix_download(s.ctx, P, NULL, color), "download");
     int largest = 0;
     for (uint32_t v = 0; v < M; v++)
         if (++size[color[v]] > largest) largest = size[color[v]];
     if (colors_path) cli_write_ints(colors_path, color, M);
-    printf("%u,%u,%d,%d,%d,%.3f\n", M, nnz, colors, largest, rounds, ms);
+    printf("%u,%u,%d,%d,%d,%.3f\n", M, s.nnz, colors, largest, rounds, ms);
     free(color); free(size);
     bspgemm_matrix_free(P);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

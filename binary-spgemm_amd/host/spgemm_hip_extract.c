@@ -50,12 +50,10 @@ int main(int argc, char **argv)
     unsigned flags = 0;
     if (argc < 2) usage();
     for (int i = 2; i < argc; i++) {
-        if (strcmp(argv[i], "--keep-shape") == 0) { flags |= BSPGEMM_EXTRACT_KEEP_SHAPE; continue; }
-        if (i + 1 >= argc) usage();
-        if (strcmp(argv[i], "--rows") == 0) rows_path = argv[++i];
-        else if (strcmp(argv[i], "--cols") == 0) cols_path = argv[++i];
-        else if (strcmp(argv[i], "-o") == 0) out_path = argv[++i];
-        else usage();
+        if (cli_flag(argv[i], "--keep-shape")) flags |= BSPGEMM_EXTRACT_KEEP_SHAPE;
+        else if (!cli_value(argc, argv, &i, "--rows", &rows_path) && !cli_value(argc, argv, &i, "--cols", &cols_path) &&
+                 !cli_value(argc, argv, &i, "-o", &out_path))
+            usage();
     }
     uint32_t *Arow, *Acol, M, N, nnz;
     cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
@@ -66,10 +64,8 @@ int main(int argc, char **argv)
     bspgemm_extract_info info;
     CHECK(bspgemm_matrix_upload(ctx, (int)N, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const struct timespec t0 = cli_now();
-    CHECK(bspgemm_matrix_extract(ctx, A, ni, I, nj, J, flags, &S, &info), "bspgemm_matrix_extract");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, ctx, bspgemm_matrix_extract(ctx, A, ni, I, nj, J, flags, &S, &info), "bspgemm_matrix_extract");
     const int rows = bspgemm_matrix_rows(S), cols = bspgemm_matrix_cols(S);
     printf("%d,%d,%lld,%.3f\n", rows, cols, (long long)info.kept, ms);
     printf("%lld,%lld,%d,%d,%d,%d\n", (long long)info.scanned, (long long)info.hub_chunks, info.lanes, info.cols_monotone,

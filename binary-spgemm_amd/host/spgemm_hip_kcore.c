@@ -25,27 +25,21 @@ int main(int argc, char **argv)
 {
     const char *numbers_path = NULL, *out_path = NULL, *k_arg = NULL;
     if (argc < 2) usage();
-    for (int i = 2; i < argc; i += 2) {
-        if (i + 1 >= argc) usage();
-        if (strcmp(argv[i], "--numbers") == 0) numbers_path = argv[i + 1];
-        else if (strcmp(argv[i], "--k") == 0) k_arg = argv[i + 1];
-        else if (strcmp(argv[i], "--out") == 0) out_path = argv[i + 1];
-        else usage();
+    for (int i = 2; i < argc; i++) {
+        if (!cli_value(argc, argv, &i, "--numbers", &numbers_path) && !cli_value(argc, argv, &i, "--k", &k_arg) &&
+            !cli_value(argc, argv, &i, "--out", &out_path))
+            usage();
     }
     if ((k_arg == NULL) != (out_path == NULL)) usage();
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("k-core", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A;
+    cli_session s = cli_open(argv[1], 0, "k-core");
+    const uint32_t M = s.M, nnz = s.nnz;
+    cli_upload(&s);
+    bspgemm_context *ctx = s.ctx;
+    bspgemm_matrix *A = s.A;
     bspgemm_result *R;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const struct timespec t0 = cli_now();
     int degeneracy = 0, rounds = 0;
-    CHECK(bspgemm_core_numbers(ctx, A, &R, &degeneracy, &rounds), "bspgemm_core_numbers");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, ctx, bspgemm_core_numbers(ctx, A, &R, &degeneracy, &rounds), "bspgemm_core_numbers");
     int *core = malloc(((size_t)M + 1) * sizeof(int));
     if (!core) exit(1);
     CHECK(bspgemm_result_download_values(ctx, R, core), "download");
@@ -67,8 +61,6 @@ int main(int argc, char **argv)
     }
     free(core);
     bspgemm_result_free(R);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

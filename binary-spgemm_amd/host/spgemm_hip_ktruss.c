@@ -23,8 +23,8 @@ int main(int argc, char **argv)
     int symmetrize = 0;
     bspgemm_support_method method = BSPGEMM_SUPPORT_PRODUCT;
     while (argc > 1 && strncmp(argv[1], "--", 2) == 0) {     /* the options, in any order */
-        if (strcmp(argv[1], "--symmetrize") == 0) symmetrize = 1;
-        else if (strcmp(argv[1], "--dot") == 0) method = BSPGEMM_SUPPORT_DOT;
+        if (cli_flag(argv[1], "--symmetrize")) symmetrize = 1;
+        else if (cli_flag(argv[1], "--dot")) method = BSPGEMM_SUPPORT_DOT;
         else break;
         argv++;
         argc--;
@@ -34,12 +34,11 @@ int main(int argc, char **argv)
         exit(1);
     }
     const int k = atoi(argv[2]);
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], BSPGEMM_READ_EXPAND_SYMMETRIC, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("k-truss", M, N);
-    bspgemm_context *ctx = cli_context(0);
+    cli_session s = cli_open(argv[1], BSPGEMM_READ_EXPAND_SYMMETRIC, "k-truss");
+    const uint32_t M = s.M, nnz = s.nnz;
+    bspgemm_context *ctx = s.ctx = cli_context(0);  /* open, not cli_upload: a synchronise only after --symmetrize */
     bspgemm_matrix *A, *T;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
+    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)s.Arow, (const int *)s.Acol, &A), "upload");
     if (symmetrize) {
         bspgemm_matrix *U;
         CHECK(bspgemm_matrix_symmetrize(ctx, A, BSPGEMM_SYMMETRIZE_DROP_DIAGONAL, &U), "bspgemm_matrix_symmetrize");
@@ -47,6 +46,7 @@ int main(int argc, char **argv)
         A = U;
         CHECK(bspgemm_synchronize(ctx), "synchronize");
     }
+    s.A = A;
     const struct timespec t0 = cli_now();
     int64_t triangles = 0;
     int iterations = 0, converged = 0;
@@ -65,8 +65,6 @@ int main(int argc, char **argv)
         free(rp); free(ci);
     }
     bspgemm_matrix_free(T);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

@@ -25,30 +25,19 @@ int main(int argc, char **argv)
     unsigned flags = 0;
     if (argc < 2) usage();
     for (int i = 2; i < argc; i++) {
-        if (strcmp(argv[i], "--directed") == 0) {
-            flags = BSPGEMM_LCC_DIRECTED;
-        } else if (strcmp(argv[i], "--out") == 0 && i + 1 < argc) {
-            out_path = argv[++i];
-        } else {
-            usage();
-        }
+        if (cli_flag(argv[i], "--directed")) flags = BSPGEMM_LCC_DIRECTED;
+        else if (!cli_value(argc, argv, &i, "--out", &out_path)) usage();
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("the clustering coefficient", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A;
+    cli_session s = cli_open(argv[1], 0, "the clustering coefficient");
+    const uint32_t M = s.M;
+    cli_upload(&s);
     bspgemm_result *counts;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
     int *degree = malloc(((size_t)M + 1) * sizeof(int));
     double *lcc = malloc(((size_t)M + 1) * sizeof(double));
     if (!degree || !lcc) exit(1);
-    const struct timespec t0 = cli_now();
     bspgemm_lcc_info info;
-    CHECK(bspgemm_local_clustering(ctx, A, flags, &counts, degree, lcc, &info), "bspgemm_local_clustering");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, s.ctx, bspgemm_local_clustering(s.ctx, s.A, flags, &counts, degree, lcc, &info), "bspgemm_local_clustering");
     double sum = 0;
     int max_degree = 0;
     for (uint32_t v = 0; v < M; v++) {
@@ -56,16 +45,13 @@ int main(int argc, char **argv)
         if (degree[v] > max_degree) max_degree = degree[v];
     }
     if (out_path) {
-        FILE *f = fopen(out_path, "w");
-        if (!f) { fprintf(stderr, "cannot write %s\n", out_path); exit(1); }
+        FILE *f = cli_create(out_path);
         for (uint32_t v = 0; v < M; v++) fprintf(f, "%u %.17g\n", v, lcc[v]);
-        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", out_path); exit(1); }
+        cli_finish(f, out_path);
     }
-    printf("%u,%u,%lld,%.17g,%d,%.3f\n", M, nnz, (long long)info.triangles, M ? sum / M : 0.0, max_degree, ms);
+    printf("%u,%u,%lld,%.17g,%d,%.3f\n", M, s.nnz, (long long)info.triangles, M ? sum / M : 0.0, max_degree, ms);
     free(degree); free(lcc);
     bspgemm_result_free(counts);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

@@ -23,49 +23,40 @@ int main(int argc, char **argv)
     const char *out_path = NULL;
     bspgemm_match_order order = BSPGEMM_MATCH_RANDOM;
     unsigned seed = 0;
-    if (argc < 2 || argc % 2 != 0) usage();
-    for (int i = 2; i < argc; i += 2) {
-        if (strcmp(argv[i], "--order") == 0) {
-            if (strcmp(argv[i + 1], "natural") == 0) order = BSPGEMM_MATCH_NATURAL;
-            else if (strcmp(argv[i + 1], "random") == 0) order = BSPGEMM_MATCH_RANDOM;
-            else if (strcmp(argv[i + 1], "light") == 0) order = BSPGEMM_MATCH_LIGHT_FIRST;
+    if (argc < 2) usage();
+    for (int i = 2; i < argc; i++) {
+        const char *val;
+        if (cli_value(argc, argv, &i, "--order", &val)) {
+            if (strcmp(val, "natural") == 0) order = BSPGEMM_MATCH_NATURAL;
+            else if (strcmp(val, "random") == 0) order = BSPGEMM_MATCH_RANDOM;
+            else if (strcmp(val, "light") == 0) order = BSPGEMM_MATCH_LIGHT_FIRST;
             else usage();
-        } else if (strcmp(argv[i], "--seed") == 0) {
-            char *end;
-            seed = (unsigned)strtoul(argv[i + 1], &end, 0);
-            if (end == argv[i + 1] || *end) usage();
-        } else if (strcmp(argv[i], "--out") == 0) {
-            out_path = argv[i + 1];
-        } else {
+        } else if (cli_value(argc, argv, &i, "--seed", &val)) {
+            char *end;                  /* open: no errno or sign check, so "-1" and a value past 2^64 - 1 are taken and wrap */
+            seed = (unsigned)strtoul(val, &end, 0);
+            if (end == val || *end) usage();
+        } else if (!cli_value(argc, argv, &i, "--out", &out_path)) {
             usage();
         }
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("matching", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A, *P;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    cli_session s = cli_open(argv[1], 0, "matching");
+    const uint32_t M = s.M;
+    cli_upload(&s);
+    bspgemm_matrix *P;
     int *mate = malloc(((size_t)M + 1) * sizeof(int));
     if (!mate) exit(1);
-    const struct timespec t0 = cli_now();
     bspgemm_match_info info;
-    CHECK(bspgemm_maximal_matching(ctx, A, order, seed, &P, mate, &info), "bspgemm_maximal_matching");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, s.ctx, bspgemm_maximal_matching(s.ctx, s.A, order, seed, &P, mate, &info), "bspgemm_maximal_matching");
     if (out_path) {
-        FILE *f = fopen(out_path, "w");
-        if (!f) { fprintf(stderr, "cannot write %s\n", out_path); exit(1); }
+        FILE *f = cli_create(out_path);
         for (uint32_t v = 0; v < M; v++)
             if (mate[v] > (int)v) fprintf(f, "%u %d\n", v, mate[v]);
-        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", out_path); exit(1); }
+        cli_finish(f, out_path);
     }
-    printf("%u,%u,%lld,%d,%.3f\n", M, nnz, (long long)info.pairs, info.rounds, ms);
+    printf("%u,%u,%lld,%d,%.3f\n", M, s.nnz, (long long)info.pairs, info.rounds, ms);
     free(mate);
     bspgemm_matrix_free(P);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

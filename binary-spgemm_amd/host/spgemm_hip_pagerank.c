@@ -14,7 +14,6 @@
  * device.
  */
 #include "cli_common.h"
-#include <errno.h>
 #include <inttypes.h>
 
 static const uint64_t *g_rank;
@@ -33,6 +32,7 @@ static void usage(void)
     exit(1);
 }
 
+/* open: every number here goes through strtod ("1e1" iterations are ten), which no whole-number parser accepts */
 static double number(const char *text)
 {
     char *end;
@@ -49,11 +49,12 @@ int main(int argc, char **argv)
     double iterations = 20, damping = 0.85, tolerance = 0.0, top = 10;
     if (argc < 2) usage();
     for (int i = 2; i < argc; i++) {
-        if (!strcmp(argv[i], "--push")) method = BSPGEMM_PR_PUSH;
-        else if (!strcmp(argv[i], "--pull")) method = BSPGEMM_PR_PULL;
-        else if (!strcmp(argv[i], "--symmetric")) symmetric = 1;
-        else if (!strcmp(argv[i], "--tolerance") && i + 1 < argc) tolerance = number(argv[++i]);
-        else if (!strcmp(argv[i], "--top") && i + 1 < argc) top = number(argv[++i]);
+        const char *val;
+        if (cli_flag(argv[i], "--push")) method = BSPGEMM_PR_PUSH;
+        else if (cli_flag(argv[i], "--pull")) method = BSPGEMM_PR_PULL;
+        else if (cli_flag(argv[i], "--symmetric")) symmetric = 1;
+        else if (cli_value(argc, argv, &i, "--tolerance", &val)) tolerance = number(val);
+        else if (cli_value(argc, argv, &i, "--top", &val)) top = number(val);
         else if (argv[i][0] != '-' && positional == 0) { iterations = number(argv[i]); positional = 1; }
         else if (argv[i][0] != '-' && positional == 1) { damping = number(argv[i]); positional = 2; }
         else usage();
@@ -61,14 +62,12 @@ int main(int argc, char **argv)
     if (!(iterations >= 0 && iterations <= 1e9) || iterations != (int)iterations || !(top >= 0 && top <= 1e9) ||
         top != (int)top || !(damping >= 0 && damping <= 1) || !(tolerance >= 0))
         usage();
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("pagerank", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *At, *A;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &At), "upload");
-    if (symmetric) A = At;
-    else CHECK(bspgemm_matrix_transpose(ctx, At, &A), "bspgemm_matrix_transpose");
+    cli_session s = cli_open(argv[1], 0, "pagerank");                     /* s.A: the in-edge operand AT */
+    const uint32_t M = s.M, nnz = s.nnz;
+    cli_upload(&s);
+    bspgemm_context *ctx = s.ctx;
+    bspgemm_matrix *At = s.A, *A = s.A;
+    if (!symmetric) CHECK(bspgemm_matrix_transpose(ctx, At, &A), "bspgemm_matrix_transpose");
     CHECK(bspgemm_synchronize(ctx), "synchronize");
     uint64_t *fixed = malloc(((size_t)M + 1) * sizeof(uint64_t));
     double *rank = malloc(((size_t)M + 1) * sizeof(double));
@@ -87,8 +86,6 @@ int main(int argc, char **argv)
         printf("%d,%" PRIu64 ",%.17g\n", order[k], fixed[order[k]], rank[order[k]]);
     free(fixed); free(rank); free(order);
     if (!symmetric) bspgemm_matrix_free(A);
-    bspgemm_matrix_free(At);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

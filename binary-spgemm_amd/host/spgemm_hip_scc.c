@@ -21,32 +21,25 @@ int main(int argc, char **argv)
         printf("usage: SpGEMM_hip_scc  path-to-matrix  [--labels out.txt]\n");
         exit(1);
     }
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("scc", M, N);
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A, *P;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const struct timespec t0 = cli_now();
+    cli_session s = cli_open(argv[1], 0, "scc");
+    const uint32_t M = s.M;
+    cli_upload(&s);
+    bspgemm_matrix *P;
     int components = 0, rounds = 0, sweeps = 0;
-    CHECK(bspgemm_strongly_connected_components(ctx, A, &P, &components, &rounds, &sweeps),
-          "bspgemm_strongly_connected_components");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, s.ctx, bspgemm_strongly_connected_components(s.ctx, s.A, &P, &components, &rounds, &sweeps),
+              "bspgemm_strongly_connected_components");
     int *label = malloc(((size_t)M + 1) * sizeof(int));
     int *size = calloc((size_t)M + 1, sizeof(int));
     if (!label || !size) exit(1);
-    CHECK(bspgemm_matrix_download(ctx, P, NULL, label), "download");
+    CHECK(bspgemm_matrix_download(s.ctx, P, NULL, label), "download");
     int largest = 0;
     for (uint32_t v = 0; v < M; v++)
         if (++size[label[v]] > largest) largest = size[label[v]];
     if (labels_path) cli_write_ints(labels_path, label, M);
-    printf("%u,%u,%d,%d,%d,%d,%.3f\n", M, nnz, components, largest, rounds, sweeps, ms);
+    printf("%u,%u,%d,%d,%d,%d,%.3f\n", M, s.nnz, components, largest, rounds, sweeps, ms);
     free(label); free(size);
     bspgemm_matrix_free(P);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

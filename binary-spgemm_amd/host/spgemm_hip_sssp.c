@@ -14,8 +14,6 @@
  */
 #include "cli_common.h"
 
-#include <errno.h>
-
 static void usage(void)
 {
     printf("usage: SpGEMM_hip_sssp  path-to-matrix  --source s  [--weights seed:wmin:wmax]  [--symmetric]  [--delta d]  "
@@ -25,11 +23,8 @@ static void usage(void)
 
 static unsigned long long number(const char *text, unsigned long long most)
 {
-    char *end;
-    if (*text == '-') usage();
-    errno = 0;
-    const unsigned long long v = strtoull(text, &end, 0);
-    if (end == text || *end || errno || v > most) usage();                  /* (errno: a value past 2^64 - 1 saturates) */
+    unsigned long long v;
+    if (!cli_unsigned(text, 0, most, &v)) usage();
     return v;
 }
 
@@ -42,15 +37,12 @@ int main(int argc, char **argv)
     bspgemm_sssp_params params = {0, 0, 0};
     if (argc < 2) usage();
     for (int i = 2; i < argc; i++) {
-        if (strcmp(argv[i], "--symmetric") == 0) {
+        const char *val;
+        if (cli_flag(argv[i], "--symmetric")) {
             flags |= BSPGEMM_WEIGHTS_SYMMETRIC;
-            continue;
-        }
-        if (i + 1 >= argc) usage();
-        const char *val = argv[++i];
-        if (strcmp(argv[i - 1], "--source") == 0) {
+        } else if (cli_value(argc, argv, &i, "--source", &val)) {
             source = (long long)number(val, 0x7fffffffull);
-        } else if (strcmp(argv[i - 1], "--weights") == 0) {
+        } else if (cli_value(argc, argv, &i, "--weights", &val)) {
             unsigned long long a, b, c;
             char tail;
             if (sscanf(val, "%llu:%llu:%llu%c", &a, &b, &c, &tail) != 3 || a > 0xffffffffull || b > 0xffffffffull ||
@@ -59,53 +51,43 @@ int main(int argc, char **argv)
             seed = (unsigned)a;
             wmin = (uint32_t)b;
             wmax = (uint32_t)c;
-        } else if (strcmp(argv[i - 1], "--delta") == 0) {
+        } else if (cli_value(argc, argv, &i, "--delta", &val)) {
             params.delta = number(val, ~0ull);
-        } else if (strcmp(argv[i - 1], "--lanes") == 0) {
+        } else if (cli_value(argc, argv, &i, "--lanes", &val)) {
             params.lanes = (int)number(val, 64);
             if (params.lanes != 0 && params.lanes != 4 && params.lanes != 16 && params.lanes != 64) usage();
-        } else if (strcmp(argv[i - 1], "--out") == 0) {
-            out_path = val;
-        } else {
+        } else if (!cli_value(argc, argv, &i, "--out", &out_path)) {
             usage();
         }
     }
     if (source < 0) usage();
-    uint32_t *Arow, *Acol, M, N, nnz;
-    cli_load(argv[1], 0, &Arow, &Acol, &M, &N, &nnz);
-    cli_need_square("shortest paths", M, N);
+    cli_session s = cli_open(argv[1], 0, "shortest paths");
+    const uint32_t M = s.M;
     if (source >= (long long)M) {
         fprintf(stderr, "source %lld is not a vertex of a graph of %u\n", source, M);
         exit(1);
     }
-    bspgemm_context *ctx = cli_context(0);
-    bspgemm_matrix *A;
+    cli_upload(&s);
     bspgemm_weights *W;
-    CHECK(bspgemm_matrix_upload(ctx, (int)M, (int)M, (const int *)Arow, (const int *)Acol, &A), "upload");
-    CHECK(bspgemm_weights_hashed(ctx, A, seed, wmin, wmax, flags, &W), "bspgemm_weights_hashed");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
+    CHECK(bspgemm_weights_hashed(s.ctx, s.A, seed, wmin, wmax, flags, &W), "bspgemm_weights_hashed");
+    CHECK(bspgemm_synchronize(s.ctx), "synchronize");
     uint64_t *dist = malloc(((size_t)M + 1) * sizeof(uint64_t));
     int *parent = malloc(((size_t)M + 1) * sizeof(int));
     if (!dist || !parent) exit(1);
-    const struct timespec t0 = cli_now();
     bspgemm_sssp_info info;
-    CHECK(bspgemm_sssp(ctx, A, W, (int)source, &params, dist, out_path ? parent : NULL, &info), "bspgemm_sssp");
-    CHECK(bspgemm_synchronize(ctx), "synchronize");
-    const double ms = cli_ms(t0, cli_now());
+    double ms;
+    CLI_TIMED(ms, s.ctx, bspgemm_sssp(s.ctx, s.A, W, (int)source, &params, dist, out_path ? parent : NULL, &info), "bspgemm_sssp");
     if (out_path) {
-        FILE *f = fopen(out_path, "w");
-        if (!f) { fprintf(stderr, "cannot write %s\n", out_path); exit(1); }
+        FILE *f = cli_create(out_path);
         for (uint32_t v = 0; v < M; v++)
             if (dist[v] != UINT64_MAX) fprintf(f, "%u %llu %d\n", v, (unsigned long long)dist[v], parent[v]);
-        if (fclose(f)) { fprintf(stderr, "cannot write %s\n", out_path); exit(1); }
+        cli_finish(f, out_path);
     }
-    printf("%u,%u,%lld,%llu,%lld,%llu,%d,%d,%lld,%lld,%lld,%.3f\n", M, nnz, source, (unsigned long long)info.delta,
+    printf("%u,%u,%lld,%llu,%lld,%llu,%d,%d,%lld,%lld,%lld,%.3f\n", M, s.nnz, source, (unsigned long long)info.delta,
            (long long)info.reached, (unsigned long long)info.dist_max, info.rounds, info.buckets, (long long)info.entries_walked,
            (long long)info.improved, (long long)info.hub_chunks, ms);
     free(dist); free(parent);
     bspgemm_weights_free(W);
-    bspgemm_matrix_free(A);
-    bspgemm_destroy(ctx);
-    free(Arow); free(Acol);
+    cli_close(&s);
     return 0;
 }

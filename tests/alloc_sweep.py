@@ -20,11 +20,11 @@ import time
 import numpy as np
 
 import bspgemm
+from abi_kit import SENTINEL, dirtied, last_error
 
 VP = C.c_void_p
 OK, ERR_ALLOC = 0, 2
 FLOW_AUTO, FLOW_UB, FLOW_EXACT = 0, 1, 2
-SENTINEL = 0x5A5A5A5A          # what every output handle holds before the call: a failed call must have made it NULL
 
 
 def L():
@@ -35,19 +35,13 @@ def alloc_state():
     return bspgemm.debug_alloc_state()
 
 
-def last_error():
-    return L().bspgemm_last_error().decode(errors="replace")
-
-
 def _ptr(a):
     return a.ctypes.data if a.size else None
 
 
 def filled(struct_type):
     """an out-struct of 0x5A bytes: a failed call must have zeroed it"""
-    s = struct_type()
-    C.memset(C.byref(s), 0x5A, C.sizeof(s))
-    return s
+    return dirtied(struct_type, 0x5A)
 
 
 def fields(struct, names):

@@ -6,8 +6,7 @@ import re
 import pytest
 
 import bspgemm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_kit import ROOT
 
 
 def _declared_functions():

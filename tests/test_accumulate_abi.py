@@ -10,9 +10,7 @@ import tempfile
 import pytest
 
 import bspgemm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
+from abi_kit import ROOT, header_text
 
 
 def _decl(code, name):
@@ -22,7 +20,7 @@ def _decl(code, name):
 
 
 def test_header_declares_accumulate_and_transitive_closure():
-    text = open(HEADER).read()
+    text = header_text()
     assert re.search(r"#define\s+BSPGEMM_CLOSURE_TRANSITIVE\s+1u\b", text)
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     params = _decl(code, "bspgemm_multiply_accumulate")

@@ -5,9 +5,6 @@ anything is dereferenced -- and the tests' own reference (bc_ref.py) equals a na
 examples worked by hand, and stays within the derived bound of networkx's float64 Brandes.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,10 +12,8 @@ import pytest
 import bspgemm
 import gen
 import bc_ref as B
+from abi_kit import ERR_INVALID, FAKE, header_code, header_text, compile_c99, last_error, dirtied
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 NAME = "bspgemm_betweenness"
 
 STRUCT = ("typedef struct bspgemm_bc_info { uint64_t sigma_max; int64_t reached; int64_t edges_forward; int64_t hub_chunks; "
@@ -27,19 +22,13 @@ DECLARATION = ("bspgemm_status bspgemm_betweenness(bspgemm_context *ctx, const b
                "const int *sources, uint64_t *bc_fixed_host, double *bc_host, bspgemm_bc_info *info);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_it_between_pagerank_and_closure():
-    code = _header_code()
+    code = header_code()
     assert STRUCT in code, "include/bspgemm.h does not declare bspgemm_bc_info as agreed"
     assert DECLARATION in code, "include/bspgemm.h does not declare %s as agreed" % NAME
     assert code.index("bspgemm_pagerank(") < code.index(STRUCT) < code.index(NAME + "(") < code.index("bspgemm_closure(")
     assert "BSPGEMM_OPT_BC_LANES = 13" in code
-    text = open(HEADER).read()
+    text = header_text()
     comment = text.split("typedef struct bspgemm_bc_info")[0].rsplit("/*", 1)[1]
     # the definition is the contract
     for word in ("ONE = 2^32", "level(s) = 0, sigma(s) = 1", "BFS distance", "level(u) == level(v) - 1", "sigma(v) >= 2^63",
@@ -98,26 +87,21 @@ int top_vertex(bspgemm_context *ctx, const bspgemm_matrix *A, int n, int k, doub
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_bad_arguments_are_refused_by_name():
     L = bspgemm.lib()
     fn = getattr(L, NAME)
-    fake = C.c_void_p(64)            # never dereferenced: the bad argument is refused first
+    fake = FAKE            # never dereferenced: the bad argument is refused first
     three = (C.c_int * 3)(0, 1, 2)
     negative = (C.c_int * 3)(0, -1, 2)
 
-    def last():
-        return L.bspgemm_last_error().decode()
+    last = last_error
 
     def call(ctx, A, nsources, sources):
-        info = bspgemm.BcInfo()
-        C.memset(C.byref(info), 0x5A, C.sizeof(info))
+        info = dirtied(bspgemm.BcInfo, 0x5A)
         st = fn(ctx, A, nsources, sources, None, None, C.byref(info))
         assert bytes(info) == bytes(C.sizeof(info)), "info is not zeroed"
         return st

@@ -3,31 +3,20 @@ agreed argument list behind bspgemm_ktruss, the library exports it, the Python v
 NULL arguments and nsources = 0 are refused by name -- and the tests' own reference (bfs_ref.py) agrees with a hand example.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 
 import bfs_ref
 import bspgemm
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, compile_c99, last_error
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 
 DECLARATION = ("bspgemm_status bspgemm_bfs(bspgemm_context *ctx, const bspgemm_matrix *A, int nsources, const int *sources, "
                "int max_depth, bspgemm_result **levels, int *depth, int *complete);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_bfs_behind_ktruss():
-    code = _header_code()
+    code = header_code()
     assert DECLARATION in code, "include/bspgemm.h does not declare bspgemm_bfs as agreed"
     assert code.index("bspgemm_ktruss(") < code.index("bspgemm_bfs(") < code.index("bspgemm_closure(")
 
@@ -63,21 +52,15 @@ int level_d(bspgemm_context *ctx, const bspgemm_matrix *A, int n, int nsources, 
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_and_no_sources_are_refused_by_name():
     L = bspgemm.lib()
-    fake = C.c_void_p(64)            # never dereferenced: the NULL argument or the count is refused first
+    fake = FAKE            # never dereferenced: the NULL argument or the count is refused first
     src = (C.c_int * 2)(0, 1)
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    sentinel, last = SENTINEL, last_error
 
     for ctx, A, sources in ((None, fake, src), (fake, None, src), (fake, fake, None)):
         out, depth, complete = C.c_void_p(sentinel), C.c_int(7), C.c_int(7)

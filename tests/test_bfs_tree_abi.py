@@ -6,9 +6,7 @@ named graph, passes the tree check and a hand example with two candidate parents
 promise, and the host model of the direction rule really changes direction twice on one of them.
 """
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,10 +14,8 @@ import pytest
 import bfs_ref
 import bfs_tree_ref as ref
 import bspgemm
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, header_text, compile_c99, last_error, dirtied
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 
 DECLARATION = ("bspgemm_status bspgemm_bfs_tree(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matrix *AT, "
                "int source, bspgemm_bfs_direction direction, int max_depth, bspgemm_result **tree, "
@@ -30,21 +26,15 @@ STRUCT = ("typedef struct bspgemm_bfs_tree_info { int64_t reached; int64_t edges
           "int complete; int push_levels, pull_levels; int transposed; int canonicalised; } bspgemm_bfs_tree_info;")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_them_between_bfs_and_components():
-    code = _header_code()
+    code = header_code()
     for what in (DECLARATION, ENUM, STRUCT):
         assert what in code, "include/bspgemm.h does not declare as agreed: %s" % what
     assert code.index("bspgemm_bfs(") < code.index(ENUM) < code.index(STRUCT) < code.index("bspgemm_bfs_tree(")
     assert code.index("bspgemm_bfs_tree(") < code.index("bspgemm_connected_components(")
     for name, value in (("BFS_ALPHA", 8), ("BFS_BETA", 9), ("BFS_PUSH_LANES", 10)):
         assert re.search(r"BSPGEMM_OPT_%s\s*=\s*%d\b" % (name, value), code), name
-    text = open(HEADER).read()
+    text = header_text()
     for word in ("bit for bit", "m_f * alpha > m_u", "n_f * beta < n", "BSPGEMM_BFS_TREE_TIMING"):
         assert word in text, word
 
@@ -87,25 +77,17 @@ bspgemm_matrix *children(bspgemm_context *ctx, const bspgemm_matrix *A, const bs
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_are_refused_by_name():
     L = bspgemm.lib()
-    fake = C.c_void_p(64)            # never dereferenced: the NULL argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the NULL argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     def dirty():
-        info = bspgemm.BfsTreeInfo()
-        C.memset(C.byref(info), 0x5A, C.sizeof(info))
-        return info
+        return dirtied(bspgemm.BfsTreeInfo, 0x5A)
 
     for ctx, A in ((None, fake), (fake, None)):
         out, info = C.c_void_p(sentinel), dirty()

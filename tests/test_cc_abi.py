@@ -4,31 +4,20 @@ has it, a C99 caller compiles cleanly, NULL arguments are refused by name -- and
 agrees with a hand example.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 
 import bspgemm
 import cc_ref
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, compile_c99, last_error
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 
 DECLARATION = ("bspgemm_status bspgemm_connected_components(bspgemm_context *ctx, const bspgemm_matrix *A, "
                "bspgemm_matrix **P, int *ncomponents, int *rounds);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_it_between_bfs_and_closure():
-    code = _header_code()
+    code = header_code()
     assert DECLARATION in code, "include/bspgemm.h does not declare bspgemm_connected_components as agreed"
     assert code.index("bspgemm_bfs(") < code.index("bspgemm_connected_components(") < code.index("bspgemm_closure(")
 
@@ -67,20 +56,14 @@ int largest_component(bspgemm_context *ctx, const bspgemm_matrix *A, int n, int 
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_are_refused_by_name():
     L = bspgemm.lib()
-    fake = C.c_void_p(64)            # never dereferenced: the NULL argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the NULL argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     for ctx, A in ((None, fake), (fake, None)):
         out, count, rounds = C.c_void_p(sentinel), C.c_int(7), C.c_int(7)

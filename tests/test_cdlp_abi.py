@@ -6,9 +6,6 @@ vertex implementation on every small graph, reproduces the examples worked by ha
 named graphs.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,10 +14,8 @@ import bspgemm
 import cc_ref
 import cdlp_ref
 import kcore_ref
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, header_text, compile_c99, last_error, dirtied, is_zeroed
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 NAME = "bspgemm_label_propagation"
 
 STRUCT = ("typedef struct bspgemm_lp_info { int iterations; int converged; int communities; int changed; "
@@ -29,19 +24,13 @@ DECLARATION = ("bspgemm_status bspgemm_label_propagation(bspgemm_context *ctx, c
                "int max_iter, bspgemm_matrix **P, bspgemm_lp_info *info);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_it_between_coloring_and_closure():
-    code = _header_code()
+    code = header_code()
     assert STRUCT in code, "include/bspgemm.h does not declare bspgemm_lp_info as agreed"
     assert DECLARATION in code, "include/bspgemm.h does not declare %s as agreed" % NAME
     assert code.index("bspgemm_graph_coloring(") < code.index(STRUCT) < code.index(NAME + "(") < code.index("bspgemm_closure(")
     assert "BSPGEMM_OPT_LP_MIN_CLASS = 11" in code
-    comment = open(HEADER).read().split("typedef struct bspgemm_lp_info")[0].rsplit("/*", 1)[1]
+    comment = header_text().split("typedef struct bspgemm_lp_info")[0].rsplit("/*", 1)[1]
     # the definition is part of the contract, and so is the warning about the oscillation
     for word in ("synchronously", "smallest label among those that occur most often", "OSCILLATES with period 2", "bipartite",
                  "fixpoint", "BSPGEMM_SYMMETRIZE_DROP_DIAGONAL", "BSPGEMM_OPT_LP_MIN_CLASS", "BSPGEMM_LP_TIMING", "max_iter == 0"):
@@ -90,29 +79,20 @@ int community_of_zero(bspgemm_context *ctx, const bspgemm_matrix *A, int n, cons
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_and_a_negative_cap_are_refused_by_name():
     L = bspgemm.lib()
     fn = getattr(L, NAME)
-    fake = C.c_void_p(64)            # never dereferenced: the bad argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the bad argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     def dirty():
-        info = bspgemm.LpInfo()
-        C.memset(C.byref(info), 0x5A, C.sizeof(info))
-        return info
+        return dirtied(bspgemm.LpInfo, 0x5A)
 
-    def zeroed(info):
-        return bytes(info) == bytes(C.sizeof(info))
+    zeroed = is_zeroed
 
     for ctx, A in ((None, fake), (fake, None)):
         out, info = C.c_void_p(sentinel), dirty()

@@ -6,19 +6,14 @@ properties of a greedy colouring on every graph, and breaks ties of the key by t
 """
 import ctypes as C
 import functools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bspgemm
 import color_ref
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, header_text, compile_c99, last_error
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 NAME = "bspgemm_graph_coloring"
 
 ENUM = ("typedef enum bspgemm_color_order { BSPGEMM_COLOR_NATURAL = 1, BSPGEMM_COLOR_RANDOM = 2, "
@@ -27,21 +22,15 @@ DECLARATION = ("bspgemm_status bspgemm_graph_coloring(bspgemm_context *ctx, cons
                "unsigned seed, bspgemm_matrix **P, int *ncolors, int *rounds);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_it_between_scc_and_closure():
-    code = _header_code()
+    code = header_code()
     assert ENUM in code, "include/bspgemm.h does not declare bspgemm_color_order as agreed"
     assert DECLARATION in code, "include/bspgemm.h does not declare %s as agreed" % NAME
     assert code.index("bspgemm_strongly_connected_components(") < code.index(ENUM) < code.index(NAME + "(") \
         < code.index("bspgemm_closure(")
-    comment = open(HEADER).read().split(NAME + "(")[0].rsplit("/*", 1)[1]
+    comment = header_text().split(NAME + "(")[0].rsplit("/*", 1)[1]
     for word in ("0x7feb352d", "0x846ca68b", "0x7fffffff - deg_S(v)", "maximal independent set", "BSPGEMM_COLOR_TIMING"):
-        assert word in open(HEADER).read(), word
+        assert word in header_text(), word
     assert "mix32" in comment and "lexicographically" in comment          # the formula is part of the contract
 
 
@@ -80,21 +69,15 @@ int independent_set(bspgemm_context *ctx, const bspgemm_matrix *A, int n, unsign
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_are_refused_by_name():
     L = bspgemm.lib()
     fn = getattr(L, NAME)
-    fake = C.c_void_p(64)            # never dereferenced: the NULL argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the NULL argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     for ctx, A in ((None, fake), (fake, None)):
         out, colors, rounds = C.c_void_p(sentinel), C.c_int(7), C.c_int(7)

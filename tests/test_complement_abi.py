@@ -10,13 +10,11 @@ import tempfile
 import pytest
 
 import bspgemm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
+from abi_kit import ROOT, header_text
 
 
 def test_header_declares_the_complemented_product():
-    text = open(HEADER).read()
+    text = header_text()
     assert re.search(r"#define\s+BSPGEMM_MASK_COMPLEMENT\s+1u\b", text)
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     m = re.search(r"bspgemm_status\s+bspgemm_multiply_masked_ex\s*\(([^;]*)\)\s*;", code)

@@ -4,15 +4,10 @@ bspgemm_result_values_sum, and carries the definition; the library exports them,
 compiles cleanly, and every argument error that needs no operand is refused by name before anything is dereferenced.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import bspgemm
+from abi_kit import ERR_INVALID, FAKE, header_code, header_text, compile_c99, last_error
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 NAME, NAME_ROWS = "bspgemm_matrix_extract", "bspgemm_matrix_extract_rows_of"
 
 FLAG = "#define BSPGEMM_EXTRACT_KEEP_SHAPE 1u"
@@ -25,20 +20,14 @@ DECLARATION_ROWS = ("bspgemm_status bspgemm_matrix_extract_rows_of(bspgemm_conte
                     "bspgemm_extract_info *info);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_them_between_symmetrize_and_values_sum():
-    code = _header_code()
+    code = header_code()
     for piece in (FLAG, STRUCT, DECLARATION, DECLARATION_ROWS):
         assert piece in code, "include/bspgemm.h does not hold as agreed: " + piece
     assert code.index("bspgemm_matrix_symmetrize(") < code.index(FLAG) < code.index(STRUCT) < code.index(NAME + "(") \
         < code.index(NAME_ROWS + "(") < code.index("bspgemm_result_values_sum(")
     assert "BSPGEMM_OPT_EXTRACT_LANES = 14" in code
-    text = open(HEADER).read()
+    text = header_text()
     comment = text.split("#define BSPGEMM_EXTRACT_KEEP_SHAPE")[0].rsplit("/*", 1)[1]
     # the definition is the contract
     for word in ('NULL means "all, in order"', "out is ni x nj", "(I[r], J[c]) in pattern(A)", "copied that many times",
@@ -94,20 +83,16 @@ long long induced(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_m
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_bad_arguments_are_refused_by_name():
     L = bspgemm.lib()
-    fake = C.c_void_p(64)            # never dereferenced: the bad argument is refused first
+    fake = FAKE            # never dereferenced: the bad argument is refused first
     three = (C.c_int * 3)(0, 1, 2)
 
-    def last():
-        return L.bspgemm_last_error().decode()
+    last = last_error
 
     def zeroed(info, out, armed_out):
         assert bytes(info) == bytes(C.sizeof(info)), "info is not zeroed"

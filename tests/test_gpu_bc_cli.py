@@ -4,17 +4,16 @@ from seeded sources, from all of them and on the symmetrized graph; --out writes
 line on bad arguments.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import bspgemm
 import gen
 import bc_ref as B
+from cli_kit import cli_path, run
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_bc")
+CLI = cli_path("SpGEMM_hip_bc")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bc_uniform97.mtx")
 
 
@@ -54,7 +53,7 @@ def test_cli_matches_the_model(tmp_path, args, symmetrize, sources, k):
     src = np.arange(n) if sources[0] == "all" else B.cli_sources(n, sources[1], sources[2])
     res = B.model(rp, ci, n, src)
     out = str(tmp_path / "fixed.txt")
-    r = subprocess.run([CLI, GOLDEN] + args + ["--out", out], capture_output=True, text=True, timeout=120)
+    r = run(CLI, [GOLDEN] + args + ["--out", out])
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().split("\n")
     assert len(lines) == 1 + k, r.stdout
@@ -73,6 +72,5 @@ def test_cli_matches_the_model(tmp_path, args, symmetrize, sources, k):
 @pytest.mark.parametrize("args", [[], ["--all"], ["g.mtx", "--sideways"], ["g.mtx", "--sources", "-3"], ["g.mtx", "--sources"],
                                   ["g.mtx", "--all", "--sources", "4"], ["g.mtx", "--top", "many"], ["g.mtx", "7"]])
 def test_cli_prints_the_usage_line_on_bad_arguments(tmp_path, args):
-    r = subprocess.run([CLI] + [a.replace("g.mtx", str(tmp_path / "none.mtx")) for a in args], capture_output=True, text=True,
-                       timeout=120)
+    r = run(CLI, [a.replace("g.mtx", str(tmp_path / "none.mtx")) for a in args])
     assert r.returncode != 0 and "usage: SpGEMM_hip_bc" in r.stdout

@@ -3,7 +3,6 @@ the edge i -> j, of a graph that is not symmetric, its lines equal what Context.
 fixes the orientation -- and a bad source ends it with a message.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,16 +10,10 @@ import pytest
 import bfs_ref
 import bspgemm
 import gen
+from cli_kit import cli_path, run, write_edges
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_bfs")
-
-
-def _write_edges(path, rp, ci, n):
-    rows = np.repeat(np.arange(n), np.diff(rp))
-    with open(path, "w") as f:
-        f.write("%%%%MatrixMarket matrix coordinate pattern general\n%d %d %d\n" % (n, n, ci.size))
-        f.write("".join("%d %d\n" % (r + 1, c + 1) for r, c in zip(rows.tolist(), ci.tolist())))
+CLI = cli_path("SpGEMM_hip_bfs")
 
 
 def test_cli_matches_the_api_and_the_reference(tmp_path):
@@ -31,8 +24,8 @@ def test_cli_matches_the_api_and_the_reference(tmp_path):
     back = bfs_ref.distances(*gen._csr_from_pairs(ci, np.repeat(np.arange(n), np.diff(rp)), n), n, sources)
     assert not np.array_equal(dist, back), "the graph must tell an edge from its reverse"
     src = str(tmp_path / "graph.mtx")
-    _write_edges(src, rp, ci, n)
-    r = subprocess.run([CLI, src] + [str(s) for s in sources], capture_output=True, text=True, timeout=120)
+    write_edges(src, rp, ci, n)
+    r = run(CLI, [src] + [str(s) for s in sources])
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().split("\n")
     assert len(lines) == len(sources) + 1, r.stdout
@@ -61,7 +54,7 @@ def test_cli_matches_the_api_and_the_reference(tmp_path):
 def test_cli_refuses_a_bad_source(tmp_path, bad):
     rp, ci, n = gen.rmat(10, 6, (0.57, 0.19, 0.19, 0.05), 7601)
     src = str(tmp_path / "graph.mtx")
-    _write_edges(src, rp, ci, n)
-    r = subprocess.run([CLI, src, "3", bad], capture_output=True, text=True, timeout=120)
+    write_edges(src, rp, ci, n)
+    r = run(CLI, [src, "3", bad])
     assert r.returncode != 0 and not r.stdout.strip()
     assert ("sources[1]" in r.stderr and "bspgemm_bfs" in r.stderr) if bad != "seven" else "not a vertex id" in r.stderr, r.stderr

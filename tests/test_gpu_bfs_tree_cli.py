@@ -4,24 +4,16 @@ fixes the orientation -- under every direction flag; --symmetric on a file that 
 source ends it with a message.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bfs_tree_ref as ref
 import cc_ref
-import bspgemm
+from cli_kit import cli_path, run, write_edges
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_bfs_tree")
-
-
-def _write_edges(path, rp, ci, n):
-    rows = np.repeat(np.arange(n), np.diff(rp))
-    with open(path, "w") as f:
-        f.write("%%%%MatrixMarket matrix coordinate pattern general\n%d %d %d\n" % (n, n, ci.size))
-        f.write("".join("%d %d\n" % (r + 1, c + 1) for r, c in zip(rows.tolist(), ci.tolist())))
+CLI = cli_path("SpGEMM_hip_bfs_tree")
 
 
 def _expect(name, source, direction):
@@ -43,8 +35,8 @@ def test_cli_matches_the_reference(tmp_path, name, flags, direction):
         back = cc_ref.csr(ci, np.repeat(np.arange(n), np.diff(rp)), n)
         assert not np.array_equal(ref.search(rp, ci, n, source)[0], ref.search(back[0], back[1], n, source)[0])
     src = str(tmp_path / "graph.mtx")
-    _write_edges(src, rp, ci, n)
-    r = subprocess.run([CLI, src, str(source)] + flags, capture_output=True, text=True, timeout=120)
+    write_edges(src, rp, ci, n)
+    r = run(CLI, [src, str(source)] + flags)
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().split("\n")
     assert len(lines) == 2, r.stdout
@@ -59,12 +51,12 @@ def test_cli_matches_the_reference(tmp_path, name, flags, direction):
 def test_cli_refuses_a_bad_source(tmp_path, bad):
     rp, ci, n, _ = ref.graph("rmat12_directed")
     src = str(tmp_path / "graph.mtx")
-    _write_edges(src, rp, ci, n)
-    r = subprocess.run([CLI, src, bad], capture_output=True, text=True, timeout=120)
+    write_edges(src, rp, ci, n)
+    r = run(CLI, [src, bad])
     assert r.returncode != 0 and not r.stdout.strip()
     assert ("source" in r.stderr and "bspgemm_bfs_tree" in r.stderr) if bad != "seven" else "not a vertex id" in r.stderr, r.stderr
 
 
 def test_cli_refuses_an_unknown_flag(tmp_path):
-    r = subprocess.run([CLI, str(tmp_path / "none.mtx"), "0", "--sideways"], capture_output=True, text=True, timeout=120)
+    r = run(CLI, [str(tmp_path / "none.mtx"), "0", "--sideways"])
     assert r.returncode != 0 and "usage" in r.stdout

@@ -2,24 +2,16 @@
 entry, its line and its --labels file equal what the scipy reference gives; a missing file ends it like the other drivers.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import bspgemm
 import cc_ref
 import gen
+from cli_kit import assert_missing_file, assert_usage, cli_path, run, write_edges
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_cc")
-
-
-def _write_edges(path, rp, ci, n):
-    rows = np.repeat(np.arange(n), np.diff(rp))
-    with open(path, "w") as f:
-        f.write("%%%%MatrixMarket matrix coordinate pattern general\n%d %d %d\n" % (n, n, ci.size))
-        f.write("".join("%d %d\n" % (r + 1, c + 1) for r, c in zip(rows.tolist(), ci.tolist())))
+CLI = cli_path("SpGEMM_hip_cc")
 
 
 def test_cli_matches_the_reference(tmp_path):
@@ -29,9 +21,9 @@ def test_cli_matches_the_reference(tmp_path):
     largest = int(np.bincount(label).max())
     assert 1 < count < n and 1 < largest < n
     src, out = str(tmp_path / "graph.mtx"), str(tmp_path / "labels.txt")
-    _write_edges(src, rp, ci, n)
+    write_edges(src, rp, ci, n)
     for extra in ([], ["--labels", out]):
-        r = subprocess.run([CLI, src] + extra, capture_output=True, text=True, timeout=120)
+        r = run(CLI, [src] + extra)
         assert r.returncode == 0, r.stderr
         f = r.stdout.strip().split(",")
         assert len(f) == 6 and [int(x) for x in f[:4]] == [n, ci.size, count, largest], r.stdout
@@ -40,9 +32,6 @@ def test_cli_matches_the_reference(tmp_path):
 
 
 def test_cli_usage_and_missing_file(tmp_path):
-    r = subprocess.run([CLI], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 1 and r.stdout.startswith("usage: SpGEMM_hip_cc")
-    r = subprocess.run([CLI, str(tmp_path / "graph.mtx"), "--labels"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 1 and r.stdout.startswith("usage: SpGEMM_hip_cc")
-    r = subprocess.run([CLI, str(tmp_path / "missing.mtx")], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 1 and r.stdout == ""
+    assert_usage(run(CLI, []), "usage: SpGEMM_hip_cc")
+    assert_usage(run(CLI, [str(tmp_path / "graph.mtx"), "--labels"]), "usage: SpGEMM_hip_cc")
+    assert_missing_file(run(CLI, [str(tmp_path / "missing.mtx")]))

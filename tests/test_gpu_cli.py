@@ -5,6 +5,8 @@ import subprocess
 
 import pytest
 
+from cli_kit import assert_missing_file, assert_usage
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "binary-spgemm_amd")
@@ -34,14 +36,12 @@ def test_bench_driver_csv_line():
 
 
 def test_bench_driver_usage_and_bad_file(tmp_path):
-    r = _run([os.path.join(PKG, "SpGEMM_hip")])
-    assert r.returncode == 1 and r.stdout.startswith("usage: mpirun  -n  numtasks  SpGEMM_mpi_omp")
+    assert_usage(_run([os.path.join(PKG, "SpGEMM_hip")]), "usage: mpirun  -n  numtasks  SpGEMM_mpi_omp")
     bad = tmp_path / "bad.mtx"
     bad.write_text("%MatrixMarket matrix coordinate pattern general\n1 1 1\n1 1\n")
     r = _run([os.path.join(PKG, "SpGEMM_hip"), str(bad), "1", "1", "1"])
     assert r.returncode == 1 and "Could not process Matrix Market banner." in r.stdout
-    r = _run([os.path.join(PKG, "SpGEMM_hip"), str(tmp_path / "missing.mtx"), "1", "1", "1"])
-    assert r.returncode == 1 and r.stdout == ""
+    assert_missing_file(_run([os.path.join(PKG, "SpGEMM_hip"), str(tmp_path / "missing.mtx"), "1", "1", "1"]))
     # a good banner with a bad size line: the reference exits 1 WITHOUT a message (final/utils.c:60-61)
     bad.write_text("%%MatrixMarket matrix coordinate pattern general\n% a comment\nthree by three\n")
     for exe, extra in (("SpGEMM_hip", ["1", "1", "1"]), ("SpGEMM_hip_validity", ["1", "1"])):

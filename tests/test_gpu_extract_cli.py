@@ -2,22 +2,21 @@
 of extract_ref.py, the two printed lines carry the shape, `kept` and the info fields, and a bad index ends the program with
 a non-zero status and the library's message."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bspgemm
 import extract_ref as X
+from cli_kit import assert_usage, cli_path, run
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "binary-spgemm_amd", "SpGEMM_hip_extract")
-MTX = os.path.join(ROOT, "tests", "golden", "validity_test.mtx")
+EXE = cli_path("SpGEMM_hip_extract")
+MTX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "validity_test.mtx")
 
 
 def _run(args):
-    return subprocess.run([EXE] + args, capture_output=True, text=True, timeout=300)
+    return run(EXE, args, timeout=300)
 
 
 def _write(path, values):
@@ -57,5 +56,4 @@ def test_no_lists_and_a_bad_index(tmp_path):
     assert r.returncode != 0 and "bspgemm_matrix_extract" in r.stderr and "I[1]" in r.stderr and "row list I" in r.stderr, r.stderr
     r = _run([MTX, "--cols", _write(tmp_path / "cols.txt", [4, 7, 4])])
     assert r.returncode != 0 and "twice" in r.stderr, r.stderr
-    r = _run([MTX, "--rows"])
-    assert r.returncode == 1 and r.stdout.startswith("usage: SpGEMM_hip_extract")
+    assert_usage(_run([MTX, "--rows"]), "usage: SpGEMM_hip_extract")

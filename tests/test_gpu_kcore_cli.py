@@ -3,24 +3,16 @@ entry by entry as a `general` file, its line, its --numbers file and its --k --o
 gives; usage and a missing file end it like the other drivers.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bspgemm
-import gen
 import kcore_ref
+from cli_kit import assert_missing_file, assert_usage, cli_path, run, write_edges
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_kcore")
-
-
-def _write_edges(path, rp, ci, n):
-    rows = np.repeat(np.arange(n), np.diff(rp))
-    with open(path, "w") as f:
-        f.write("%%%%MatrixMarket matrix coordinate pattern general\n%d %d %d\n" % (n, n, ci.size))
-        f.write("".join("%d %d\n" % (r + 1, c + 1) for r, c in zip(rows.tolist(), ci.tolist())))
+CLI = cli_path("SpGEMM_hip_kcore")
 
 
 def test_cli_matches_the_reference(tmp_path):
@@ -30,9 +22,9 @@ def test_cli_matches_the_reference(tmp_path):
     at_top = int((core == top).sum())
     assert top > 3 and 0 < at_top < n
     src, numbers, out = str(tmp_path / "graph.mtx"), str(tmp_path / "numbers.txt"), str(tmp_path / "core.mtx")
-    _write_edges(src, rp, ci, n)
+    write_edges(src, rp, ci, n)
     for extra in ([], ["--numbers", numbers], ["--k", "3", "--out", out], ["--k", "3", "--out", out, "--numbers", numbers]):
-        r = subprocess.run([CLI, src] + extra, capture_output=True, text=True, timeout=120)
+        r = run(CLI, [src] + extra)
         assert r.returncode == 0, r.stderr
         f = r.stdout.strip().split(",")
         assert len(f) == 6 and [int(x) for x in f[:4]] == [n, ci.size, top, at_top], r.stdout
@@ -49,10 +41,7 @@ def test_cli_matches_the_reference(tmp_path):
 
 
 def test_cli_usage_and_missing_file(tmp_path):
-    r = subprocess.run([CLI], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 1 and r.stdout.startswith("usage: SpGEMM_hip_kcore")
+    assert_usage(run(CLI, []), "usage: SpGEMM_hip_kcore")
     for extra in (["--numbers"], ["--k", "3"], ["--out", str(tmp_path / "core.mtx")], ["--labels", "x"]):
-        r = subprocess.run([CLI, str(tmp_path / "graph.mtx")] + extra, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 1 and r.stdout.startswith("usage: SpGEMM_hip_kcore"), extra
-    r = subprocess.run([CLI, str(tmp_path / "missing.mtx")], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 1 and r.stdout == ""
+        assert_usage(run(CLI, [str(tmp_path / "graph.mtx")] + extra), "usage: SpGEMM_hip_kcore", extra)
+    assert_missing_file(run(CLI, [str(tmp_path / "missing.mtx")]))

@@ -2,17 +2,17 @@
 Python view computes, and the truss it writes reads back as that truss.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bspgemm
 import gen
+from cli_kit import cli_path, run
 from ktruss_ref import symmetrise
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_ktruss")
+CLI = cli_path("SpGEMM_hip_ktruss")
 
 
 def test_cli_matches_the_api(tmp_path):
@@ -22,7 +22,7 @@ def test_cli_matches_the_api(tmp_path):
     src, dst = str(tmp_path / "graph.mtx"), str(tmp_path / "truss.mtx")
     bspgemm.write_mtx(src, s_rp, s_ci)
     k = 5
-    r = subprocess.run([CLI, src, str(k), dst], capture_output=True, text=True, timeout=120)
+    r = run(CLI, [src, str(k), dst])
     assert r.returncode == 0, r.stderr
     fields = r.stdout.strip().split(",")
     assert len(fields) == 8, r.stdout
@@ -44,5 +44,5 @@ def test_cli_matches_the_api(tmp_path):
         ctx.close()
     # without the output path nothing is written and the line is the same up to the time
     os.remove(dst)
-    r2 = subprocess.run([CLI, src, str(k)], capture_output=True, text=True, timeout=120)
+    r2 = run(CLI, [src, str(k)])
     assert r2.returncode == 0 and r2.stdout.strip().split(",")[:7] == fields[:7] and not os.path.exists(dst)

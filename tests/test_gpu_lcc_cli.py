@@ -4,27 +4,24 @@ undirected graph, and the directed count does not see the difference), with and 
 input end it like the other drivers.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bspgemm
 import lcc_ref
+from cli_kit import assert_missing_file, assert_not_square, assert_usage, cli_path, run
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_lcc")
+CLI = cli_path("SpGEMM_hip_lcc")
 USAGE = "usage: SpGEMM_hip_lcc"
 
 
 def _write_edges(path, pairs, rows, cols):
+    """(its own: the pairs are written in the order given, which is not row order, so no CSR says it)"""
     with open(path, "w") as f:
         f.write("%%%%MatrixMarket matrix coordinate pattern general\n%d %d %d\n" % (rows, cols, len(pairs)))
         f.write("".join("%d %d\n" % (a + 1, b + 1) for a, b in pairs))
-
-
-def _run(args):
-    return subprocess.run([CLI] + args, capture_output=True, text=True, timeout=120)
 
 
 def _read_out(path, n):
@@ -42,7 +39,7 @@ def test_cli_matches_the_model_on_the_loader_fixture(tmp_path, golden_dir):
     for args, directed in (([], False), (["--directed"], True)):
         num, d, lcc, triangles, _ = lcc_ref.local_clustering(rp, ci, n, directed)
         for extra in ([], ["--out", out]):
-            r = _run([src] + args + extra)
+            r = run(CLI, [src] + args + extra)
             assert r.returncode == 0, r.stderr
             f = r.stdout.strip().split(",")
             assert len(f) == 6, r.stdout
@@ -64,15 +61,15 @@ def test_cli_on_hand_examples(tmp_path):
     out = str(tmp_path / "lcc.txt")
     cyc = str(tmp_path / "cycle.mtx")
     _write_edges(cyc, [(0, 1), (1, 2), (2, 0), (1, 0)], 3, 3)           # a directed 3-cycle with one reciprocal edge
-    r = _run([cyc, "--out", out])
+    r = run(CLI, [cyc, "--out", out])
     assert r.returncode == 0 and r.stdout.strip().split(",")[:5] == ["3", "4", "1", "1", "2"], r.stdout
     assert _read_out(out, 3)[1].tolist() == [1.0, 1.0, 1.0]
-    r = _run([cyc, "--out", out, "--directed"])
+    r = run(CLI, [cyc, "--out", out, "--directed"])
     assert r.returncode == 0 and r.stdout.strip().split(",")[:5] == ["3", "4", "1", "%.17g" % ((0.5 + 0.5 + 1.0) / 3), "2"], r.stdout
     assert _read_out(out, 3)[1].tolist() == [0.5, 0.5, 1.0]
     star = str(tmp_path / "star.mtx")
     _write_edges(star, [(0, 1), (0, 2), (0, 3), (3, 3)], 4, 4)
-    r = _run([star])
+    r = run(CLI, [star])
     assert r.returncode == 0 and r.stdout.strip().split(",")[:5] == ["4", "4", "0", "0", "3"], r.stdout
 
 
@@ -80,11 +77,8 @@ def test_cli_usage_and_bad_input(tmp_path):
     src = str(tmp_path / "graph.mtx")
     _write_edges(src, [(0, 1), (1, 2)], 3, 3)
     for bad in ([], [src, "--out"], [src, "--undirected"], [src, "--directed", "x"], [src, "--out", "a", "--out"]):
-        r = _run(bad)
-        assert r.returncode == 1 and r.stdout.startswith(USAGE), (bad, r.stdout)
-    r = _run([str(tmp_path / "missing.mtx")])
-    assert r.returncode == 1 and r.stdout == ""
+        assert_usage(run(CLI, bad), USAGE, bad)
+    assert_missing_file(run(CLI, [str(tmp_path / "missing.mtx")]))
     rect = str(tmp_path / "rect.mtx")
     _write_edges(rect, [(0, 2), (1, 0)], 2, 3)
-    r = _run([rect])
-    assert r.returncode == 1 and r.stdout == "" and "the clustering coefficient needs a square matrix (2x3)" in r.stderr, (r.stdout, r.stderr)
+    assert_not_square(run(CLI, [rect]), "the clustering coefficient")

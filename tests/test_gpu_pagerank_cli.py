@@ -4,23 +4,14 @@ model gives on the FILE's orientation under --pull and --push; --symmetric on a 
 tolerance; and the usage line on bad arguments.
 """
 import os
-import subprocess
 
-import numpy as np
 import pytest
 
-import bspgemm
 import pagerank_ref as P
+from cli_kit import cli_path, run, write_edges
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_pagerank")
-
-
-def _write_edges(path, rp, ci, n):
-    rows = np.repeat(np.arange(n), np.diff(rp))
-    with open(path, "w") as f:
-        f.write("%%%%MatrixMarket matrix coordinate pattern general\n%d %d %d\n" % (n, n, ci.size))
-        f.write("".join("%d %d\n" % (r + 1, c + 1) for r, c in zip(rows.tolist(), ci.tolist())))
+CLI = cli_path("SpGEMM_hip_pagerank")
 
 
 def _top(res, k):
@@ -44,8 +35,8 @@ def test_cli_matches_the_model(tmp_path, name, args, iterations, damping, tolera
         back = P.pagerank(*P.transposed(rp, ci, n), damping, iterations, tolerance)
         assert [t[0] for t in _top(back, k)] != [t[0] for t in _top(res, k)]
     src = str(tmp_path / "graph.mtx")
-    _write_edges(src, rp, ci, n)
-    r = subprocess.run([CLI, src] + args, capture_output=True, text=True, timeout=120)
+    write_edges(src, rp, ci, n)
+    r = run(CLI, [src] + args)
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().split("\n")
     assert len(lines) == 1 + k, r.stdout
@@ -61,6 +52,5 @@ def test_cli_matches_the_model(tmp_path, name, args, iterations, damping, tolera
 @pytest.mark.parametrize("args", [[], ["g.mtx", "--sideways"], ["g.mtx", "-3"], ["g.mtx", "20", "1.5"], ["g.mtx", "20", "0.85", "9"],
                                   ["g.mtx", "--tolerance"], ["g.mtx", "--top", "many"], ["g.mtx", "2.5"]])
 def test_cli_prints_the_usage_line_on_bad_arguments(tmp_path, args):
-    r = subprocess.run([CLI] + [a.replace("g.mtx", str(tmp_path / "none.mtx")) for a in args], capture_output=True, text=True,
-                       timeout=120)
+    r = run(CLI, [a.replace("g.mtx", str(tmp_path / "none.mtx")) for a in args])
     assert r.returncode != 0 and "usage: SpGEMM_hip_pagerank" in r.stdout

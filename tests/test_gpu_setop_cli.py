@@ -2,7 +2,6 @@
 of its underlying undirected graph; without the flag the driver does what it did before.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,9 +9,10 @@ import pytest
 import bspgemm
 import gen
 import ktruss_ref
+from cli_kit import assert_usage, cli_path, run
 
 pytestmark = pytest.mark.gpu
-CLI = os.path.join(os.path.dirname(bspgemm.LIB_PATH), "SpGEMM_hip_ktruss")
+CLI = cli_path("SpGEMM_hip_ktruss")
 
 
 def test_symmetrize_flag(tmp_path):
@@ -24,7 +24,7 @@ def test_symmetrize_flag(tmp_path):
     s_rp, s_ci = ktruss_ref.symmetrise(rp, ci, n)
     assert s_ci.size > ci.size                                # the file's graph is directed
     k = 4
-    r = subprocess.run([CLI, "--symmetrize", src, str(k), dst], capture_output=True, text=True, timeout=120)
+    r = run(CLI, ["--symmetrize", src, str(k), dst])
     assert r.returncode == 0, r.stderr
     fields = r.stdout.strip().split(",")
     assert len(fields) == 8, r.stdout
@@ -36,7 +36,7 @@ def test_symmetrize_flag(tmp_path):
     assert wm == n and np.array_equal(w_rp, t_rp) and np.array_equal(w_ci, t_ci)
 
     # without the flag: the line of the API on the operand as loaded
-    r2 = subprocess.run([CLI, src, str(k)], capture_output=True, text=True, timeout=120)
+    r2 = run(CLI, [src, str(k)])
     assert r2.returncode == 0, r2.stderr
     plain = r2.stdout.strip().split(",")
     ctx = bspgemm.Context(0)
@@ -49,5 +49,4 @@ def test_symmetrize_flag(tmp_path):
     finally:
         ctx.close()
     # the flag does not change the usage check
-    r3 = subprocess.run([CLI, "--symmetrize", src], capture_output=True, text=True, timeout=120)
-    assert r3.returncode == 1 and r3.stdout.startswith("usage: SpGEMM_hip_ktruss")
+    assert_usage(run(CLI, ["--symmetrize", src]), "usage: SpGEMM_hip_ktruss")

@@ -6,9 +6,6 @@ the shapes they promise.
 """
 import ctypes as C
 import functools
-import os
-import re
-import subprocess
 
 import networkx as nx
 import numpy as np
@@ -16,10 +13,8 @@ import pytest
 
 import bspgemm
 import kcore_ref
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, compile_c99, last_error
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 
 DECLARATIONS = {
     "bspgemm_core_numbers":
@@ -31,14 +26,8 @@ DECLARATIONS = {
 }
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_them_between_components_and_closure():
-    code = _header_code()
+    code = header_code()
     for name, decl in DECLARATIONS.items():
         assert decl in code, "include/bspgemm.h does not declare %s as agreed" % name
     assert (code.index("bspgemm_connected_components(") < code.index("bspgemm_core_numbers(") < code.index("bspgemm_kcore(")
@@ -86,20 +75,14 @@ long long innermost_core(bspgemm_context *ctx, const bspgemm_matrix *A, int n, i
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_are_refused_by_name():
     L = bspgemm.lib()
-    fake = C.c_void_p(64)            # never dereferenced: the NULL argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the NULL argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     for ctx, A in ((None, fake), (fake, None)):
         out, top, rounds = C.c_void_p(sentinel), C.c_int(7), C.c_int(7)

@@ -6,9 +6,6 @@ set-per-vertex implementation on every small graph, reproduces the examples work
 header promises.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,10 +15,8 @@ import cc_ref
 import gen
 import kcore_ref
 import lcc_ref
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, header_text, compile_c99, last_error, dirtied, is_zeroed
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 NAME = "bspgemm_local_clustering"
 
 FLAG = "#define BSPGEMM_LCC_DIRECTED 1u"
@@ -31,19 +26,13 @@ DECLARATION = ("bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, co
                "bspgemm_result **counts, int *degree_host, double *lcc_host, bspgemm_lcc_info *info);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_it_between_label_propagation_and_closure():
-    code = _header_code()
+    code = header_code()
     assert FLAG in code and STRUCT in code, "include/bspgemm.h does not declare BSPGEMM_LCC_DIRECTED and bspgemm_lcc_info as agreed"
     assert DECLARATION in code, "include/bspgemm.h does not declare %s as agreed" % NAME
     assert code.index("bspgemm_label_propagation(") < code.index(FLAG) < code.index(STRUCT) < code.index(NAME + "(") \
         < code.index("bspgemm_closure(")
-    comment = open(HEADER).read().split("#define BSPGEMM_LCC_DIRECTED")[0].rsplit("/*", 1)[1]
+    comment = header_text().split("#define BSPGEMM_LCC_DIRECTED")[0].rsplit("/*", 1)[1]
     # the definition is the contract
     for word in ("BSPGEMM_SYMMETRIZE_DROP_DIAGONAL", "2 * triangles(v)", "BSPGEMM_LCC_DIRECTED", "repeats count once",
                  "union of in- and out-neighbours", "invariant under", "in-edges", "symmetric A", "0.0 when d(v) < 2",
@@ -96,29 +85,20 @@ int clustered(bspgemm_context *ctx, const bspgemm_matrix *A, int n, int least, b
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_and_unknown_flags_are_refused_by_name():
     L = bspgemm.lib()
     fn = getattr(L, NAME)
-    fake = C.c_void_p(64)            # never dereferenced: the bad argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the bad argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     def dirty():
-        info = bspgemm.LccInfo()
-        C.memset(C.byref(info), 0x5A, C.sizeof(info))
-        return info
+        return dirtied(bspgemm.LccInfo, 0x5A)
 
-    def zeroed(info):
-        return bytes(info) == bytes(C.sizeof(info))
+    zeroed = is_zeroed
 
     for ctx, A in ((None, fake), (fake, None)):
         out, info = C.c_void_p(sentinel), dirty()

@@ -10,14 +10,13 @@ import tempfile
 import pytest
 
 import bspgemm
+from abi_kit import ROOT, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
 NAMES = ("bspgemm_multiply_masked_count", "bspgemm_result_values_device", "bspgemm_result_download_values")
 
 
 def _code():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
 
 
 def _params(code, ret, name):
@@ -35,7 +34,7 @@ def test_header_declares_the_three_functions():
     assert p == ["const bspgemm_result *C"], p
     p = _params(code, "bspgemm_status", "bspgemm_result_download_values")
     assert p == ["bspgemm_context *ctx", "const bspgemm_result *C", "int *values"], p
-    text = open(HEADER).read()
+    text = header_text()
     assert "PLUS_PAIR" in text and "final/SpGEMM_mpi_omp.c:232-288" in text
     assert "BSPGEMM_ERR_OVERFLOW" in text.split("bspgemm_multiply_masked_count(")[0].split("bspgemm_multiply_accumulate(")[-1]
 

@@ -14,14 +14,13 @@ import bspgemm
 import dot_ref
 import gen
 import ktruss_ref
+from abi_kit import ROOT, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
 NAMES = ("bspgemm_multiply_masked_dot", "bspgemm_triangle_count_ex", "bspgemm_ktruss_ex")
 
 
 def _code():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
 
 
 def _params(code, ret, name):
@@ -48,7 +47,7 @@ def test_header_declares_the_functions_the_struct_the_enum_and_the_option():
     assert re.search(r"typedef enum bspgemm_support_method \{ BSPGEMM_SUPPORT_PRODUCT = 0, BSPGEMM_SUPPORT_DOT = 1 \} "
                      r"bspgemm_support_method;", flat)
     assert re.search(r"BSPGEMM_OPT_DOT_LIGHT\s*=\s*7\b", flat)
-    text = open(HEADER).read()
+    text = header_text()
     doc = text.split("bspgemm_multiply_masked_dot(bspgemm_context")[0].split("bspgemm_ktruss(bspgemm_context")[-1]
     for word in ("serial tail", "BSPGEMM_ERR_ALLOC", "ONE synchronisation", "bspgemm_multiply_masked_count"):
         assert word in doc, word

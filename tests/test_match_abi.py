@@ -8,19 +8,14 @@ the graphs are built for.
 """
 import ctypes as C
 import functools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bspgemm
 import match_ref
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, header_text, compile_c99, last_error, dirtied
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 NAME = "bspgemm_maximal_matching"
 
 ENUM = ("typedef enum bspgemm_match_order { BSPGEMM_MATCH_NATURAL = 1, BSPGEMM_MATCH_RANDOM = 2, "
@@ -31,21 +26,15 @@ DECLARATION = ("bspgemm_status bspgemm_maximal_matching(bspgemm_context *ctx, co
                "unsigned seed, bspgemm_matrix **P, int *mate_host, bspgemm_match_info *info);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_it_between_betweenness_and_closure():
-    code = _header_code()
+    code = header_code()
     assert ENUM in code, "include/bspgemm.h does not declare bspgemm_match_order as agreed"
     assert STRUCT in code, "include/bspgemm.h does not declare bspgemm_match_info as agreed"
     assert DECLARATION in code, "include/bspgemm.h does not declare %s as agreed" % NAME
     assert code.index("bspgemm_betweenness(") < code.index(ENUM) < code.index(STRUCT) < code.index(NAME + "(") \
         < code.index("bspgemm_closure(")
     assert "BSPGEMM_OPT_MATCH_LANES = 15" in code
-    text = open(HEADER).read()
+    text = header_text()
     comment = text.split(NAME + "(")[0].rsplit("/*", 6)[1]               # (the struct's five field comments follow it)
     for word in ("0x7feb352d", "0x846ca68b", "0xffff", "lexicographically", "mix32", "(key32, a, b)", "min(v, mate(v))",
                  "BSPGEMM_OPT_MATCH_LANES", "BSPGEMM_MATCH_TIMING", "statistics", "walked AGAIN"):
@@ -98,27 +87,18 @@ bspgemm_result *coarsen(bspgemm_context *ctx, const bspgemm_matrix *A, int n, un
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_and_unknown_orders_are_refused_by_name():
     L = bspgemm.lib()
     fn = getattr(L, NAME)
-    fake = C.c_void_p(64)            # never dereferenced: the NULL argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the NULL argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     def info7():
-        info = bspgemm.MatchInfo()
-        for f, _ in info._fields_:
-            setattr(info, f, 7)
-        return info
+        return dirtied(bspgemm.MatchInfo, 7)
 
     for ctx, A in ((None, fake), (fake, None)):
         out, info = C.c_void_p(sentinel), info7()

@@ -6,9 +6,6 @@ Python integers, reproduces the examples worked by hand, keeps the mass under 2^
 power iteration.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,10 +14,8 @@ import bspgemm
 import gen
 import kcore_ref
 import pagerank_ref as P
+from abi_kit import ERR_INVALID, FAKE, header_code, header_text, compile_c99, last_error, dirtied
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 NAME = "bspgemm_pagerank"
 
 ENUM = "typedef enum bspgemm_pr_method { BSPGEMM_PR_AUTO = 0, BSPGEMM_PR_PULL = 1, BSPGEMM_PR_PUSH = 2 } bspgemm_pr_method;"
@@ -31,20 +26,14 @@ DECLARATION = ("bspgemm_status bspgemm_pagerank(bspgemm_context *ctx, const bspg
                "double *rank_host, bspgemm_pr_info *info);")
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_it_between_local_clustering_and_closure():
-    code = _header_code()
+    code = header_code()
     assert ENUM in code and STRUCT in code, "include/bspgemm.h does not declare bspgemm_pr_method and bspgemm_pr_info as agreed"
     assert DECLARATION in code, "include/bspgemm.h does not declare %s as agreed" % NAME
     assert code.index("bspgemm_local_clustering(") < code.index(ENUM) < code.index(STRUCT) < code.index(NAME + "(") \
         < code.index("bspgemm_closure(")
     assert "BSPGEMM_OPT_PR_MIN_CLASS = 12" in code
-    text = open(HEADER).read()
+    text = header_text()
     comment = text.split("typedef enum bspgemm_pr_method")[0].rsplit("/*", 1)[1]
     # the definition is the contract
     for word in ("ONE = 2^62", "q = floor(ONE / n)", "floor(damping * 4294967296.0 + 0.5)", "B = ((2^32 - D) * q) >> 32",
@@ -98,25 +87,20 @@ int top_vertex(bspgemm_context *ctx, const bspgemm_matrix *A, const bspgemm_matr
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_bad_arguments_are_refused_by_name():
     L = bspgemm.lib()
     fn = getattr(L, NAME)
-    fake = C.c_void_p(64)            # never dereferenced: the bad argument is refused first
+    fake = FAKE            # never dereferenced: the bad argument is refused first
     nan = float("nan")
 
-    def last():
-        return L.bspgemm_last_error().decode()
+    last = last_error
 
     def call(ctx, A, method=1, damping=0.85, max_iter=20, tolerance=0.0):
-        info = bspgemm.PrInfo()
-        C.memset(C.byref(info), 0x5A, C.sizeof(info))
+        info = dirtied(bspgemm.PrInfo, 0x5A)
         st = fn(ctx, A, None, method, damping, max_iter, tolerance, None, None, C.byref(info))
         assert bytes(info) == bytes(C.sizeof(info)), "info is not zeroed"
         return st

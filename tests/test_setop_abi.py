@@ -3,9 +3,7 @@ with the agreed argument lists, the library exports them, the Python view has th
 arguments are refused by name -- and the tests' own reference (setop_ref.py) agrees with scipy and with ktruss_ref.
 """
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import scipy.sparse as sp
@@ -14,10 +12,8 @@ import bspgemm
 import gen
 import ktruss_ref
 from setop_ref import canonical_ref, setop_ref, symmetrize_ref, transpose_ref
+from abi_kit import ERR_INVALID, FAKE, SENTINEL, header_code, compile_c99, last_error
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
 
 DECLARATIONS = {
     "bspgemm_matrix_setop":
@@ -32,14 +28,8 @@ DECLARATIONS = {
 NAMES = sorted(DECLARATIONS)
 
 
-def _header_code():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.sub(r"\s+", " ", text)
-
-
 def test_header_declares_the_functions_and_the_enum():
-    code = _header_code()
+    code = header_code()
     for name, decl in DECLARATIONS.items():
         assert re.sub(r"\s+", " ", decl) in code, "include/bspgemm.h does not declare %s as agreed" % name
     m = re.search(r"typedef enum bspgemm_setop \{(.*?)\} bspgemm_setop;", code)
@@ -87,20 +77,14 @@ int truss_of_directed(bspgemm_context *ctx, const bspgemm_matrix *A, int k, int6
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_null_arguments_are_refused_by_name():
     L = bspgemm.lib()
-    fake = C.c_void_p(64)            # never dereferenced: the NULL argument is refused first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the NULL argument is refused first
+    sentinel, last = SENTINEL, last_error
 
     for args in ((None, fake, fake), (fake, None, fake), (fake, fake, None)):
         out = C.c_void_p(sentinel)

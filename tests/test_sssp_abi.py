@@ -6,17 +6,14 @@ under delta = 1, 16, the default and 2^64 - 1, the counts of the hand examples, 
 import ctypes as C
 import functools
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bspgemm
 import sssp_ref
+from abi_kit import ROOT, ERR_INVALID, FAKE, SENTINEL, header_code, compile_c99, last_error, dirtied
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_INVALID = 1
 NAME = "bspgemm_sssp"
 SYMBOLS = ("bspgemm_weights_upload", "bspgemm_weights_hashed", "bspgemm_weights_download", "bspgemm_weights_nnz",
            "bspgemm_weights_sum", "bspgemm_weights_free", "bspgemm_sssp")
@@ -37,13 +34,8 @@ int main(void)
 """
 
 
-def _header_code():
-    text = open(os.path.join(ROOT, "include", "bspgemm.h")).read()
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
 def test_header_declares_the_handle_the_structs_and_the_constant():
-    code = _header_code()
+    code = header_code()
     assert "typedef struct bspgemm_weights bspgemm_weights;" in code
     assert "#define BSPGEMM_WEIGHTS_SYMMETRIC 1u" in code
     assert "typedef struct bspgemm_sssp_params { uint64_t delta; int lanes; int reserved; } bspgemm_sssp_params;" in code
@@ -70,25 +62,17 @@ def test_library_exports_and_python_view():
 
 
 def test_c99_caller_compiles(tmp_path):
-    src = tmp_path / "caller.c"
-    src.write_text(C99_CALLER)
-    r = subprocess.run(["cc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                        "-c", str(src), "-o", str(tmp_path / "caller.o")], capture_output=True, text=True)
+    r = compile_c99(tmp_path, C99_CALLER)
     assert r.returncode == 0, r.stderr
 
 
 def test_the_calls_refuse_by_name_before_anything_is_dereferenced():
     L = bspgemm.lib()
-    fake = C.c_void_p(64)            # never dereferenced: the refusal comes first
-    sentinel = 0x5A5A5A5A
-
-    def last():
-        return L.bspgemm_last_error().decode()
+    fake = FAKE            # never dereferenced: the refusal comes first
+    sentinel, last = SENTINEL, last_error
 
     def info7():
-        info = bspgemm.SsspInfo()
-        C.memset(C.byref(info), 7, C.sizeof(info))
-        return info
+        return dirtied(bspgemm.SsspInfo, 7)
 
     dist, parent = np.full(4, 9, np.uint64), np.full(4, 9, np.int32)
 

@@ -6,8 +6,8 @@ import os
 import re
 
 import state_cases
+from abi_kit import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # what every case goes through on its way in and out (state_cases.Ops.upload, _matrix, _result; the tests' scribble)
 PLUMBING = {

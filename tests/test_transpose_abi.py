@@ -10,14 +10,11 @@ import tempfile
 import numpy as np
 
 import bspgemm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "bspgemm.h")
-ERR_INVALID = 1
+from abi_kit import ROOT, ERR_INVALID, header_text
 
 
 def _decl(name):
-    code = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    code = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
     m = re.search(r"bspgemm_status\s+%s\s*\(([^;]*)\)\s*;" % name, code)
     assert m, "%s is not declared" % name
     return [p.strip() for p in m.group(1).split(",")]
@@ -28,7 +25,7 @@ def test_header_declares_both_functions():
     assert len(t) == 3 and t[2].startswith("bspgemm_matrix **"), t
     d = _decl("bspgemm_matrix_download")
     assert len(d) == 4 and d[2].startswith("int *") and d[3].startswith("int *"), d
-    text = open(HEADER).read()
+    text = header_text()
     assert "final/utils.c:77" in text and "final/coo2csc.c" in text
 
 
