@@ -754,6 +754,16 @@ hipError_t result_alloc(bspgemm_context *ctx, void **out, size_t bytes)
     return e;
 }
 
+bspgemm_status counted_result_new(bspgemm_context *ctx, int rows, long long entries, bspgemm_result **out)
+{
+    bspgemm_result *R = *out = new (std::nothrow) bspgemm_result{ctx, rows, entries, nullptr, nullptr, entries};
+    if (!R) return FAIL(BSPGEMM_ERR_ALLOC, "result");
+    HIPCHK(result_alloc(ctx, reinterpret_cast<void **>(&R->d_row_ptr), result_bytes_rowptr(rows)));
+    HIPCHK(result_alloc(ctx, reinterpret_cast<void **>(&R->d_col_idx), result_bytes_colidx(entries)));
+    HIPCHK(result_alloc(ctx, reinterpret_cast<void **>(&R->d_values), result_bytes_colidx(entries)));
+    return BSPGEMM_OK;
+}
+
 void result_release(bspgemm_context *ctx, void *p, size_t bytes)
 {
     if (!p) return;

@@ -12,15 +12,17 @@
 //   k_dot_count   entry-parallel over F in select's geometry (sel_rows.hpp: a workgroup owns kSelTile consecutive mask
 //                 entries whatever rows they belong to, a lane four per 16-byte load).  Entry p = (i, j): the two row
 //                 extents; j >= B.rows (tested unsigned, before it indexes B.row_ptr) or m = min(|A_i|, |B_j|) == 0 gives
-//                 vals[p] = 0.  LIGHT, m <= T: the lane walks the shorter row and searches the longer one
-//                 (sel_lower_bound) from a lower bound that only advances; vals[p] = the hits.  HEAVY, m > T: the lane
-//                 writes nothing and remembers the entry; when the walk is over the wave appends its heavy entries
-//                 {p, i} to a list (ballot, one atomicAdd per wave, rank by popcount: wave_append of wave.hpp).
+//                 vals[p] = 0.  LIGHT, m <= T: the lane walks the shorter row and searches the longer one from a lower
+//                 bound that only advances (isect_lane); vals[p] = the hits.  HEAVY, m > T: the lane writes nothing and
+//                 notes the entry; when the walk is over the wave appends its heavy entries {p, i} to a list
+//                 (IsectHeavy: ballot, one atomicAdd per wave, rank by popcount).
 //   k_dot_heavy   a fixed grid, one wave per list entry, striding over the list; its length is read from device memory (the
-//                 launch follows k_dot_count on the stream, nothing in between).  The lanes stride over the shorter row 64
-//                 elements per step, kDotDeep steps in flight; each lane searches the longer row (the kDotDeep searches of
-//                 a trip in lockstep, from the lane's own advancing lower bound), the wave adds the popcount of the hit
-//                 ballot, lane 0 stores vals[p].
+//                 launch follows k_dot_count on the stream, nothing in between: IsectHeavyList).  The lanes stride over
+//                 the shorter row 64 elements per step, kIsectDeep steps in flight; each lane searches the longer row
+//                 from its own advancing lower bound (isect_wave), the wave adds the popcount of the hit ballot, lane 0
+//                 stores vals[p].
+// The intersections, the list and their constants are sel_rows.hpp's, shared with lcc.hip; what a hit is worth (here: one)
+// is written at the call.
 //   filter        vals > 0: select's value flags, scan and scatter (F's columns, then vals), and k_dot_row_ptr for the
 //                 int64 row_ptr of the result.
 // The one synchronisation reads the error word, the heavy count and the kept count.  An operand that the check found not
@@ -39,19 +41,11 @@
 
 namespace bsp {
 
-constexpr int kDotWaves = kSelThreads / 64;
-constexpr int kDotDeep = 4;             // 64-element steps of the shorter row in flight per trip (kColDeep of color.hip)
-constexpr int kDotHeavyGrid = 2048;     // workgroups of k_dot_heavy: 8192 waves (eight per SIMD of 256 CUs) stride over the list
-constexpr int kDotEntries = 4 * kSelSteps;   // mask entries a lane walks
-
 struct DotCounters {
     unsigned err;           // the canonical checks: two bits per operand (kSetErrRange, kSetErrOrder), A / B / F
     int heavy;              // entries appended to the heavy list
     int pad[2];
 };
-
-// The heavy list is appended to by wave_append (wave.hpp).  A mask entry is appended at most once, so the list never
-// passes nnz(F) entries; the store is bounded all the same.
 
 // The count as an op of sel_walk_entries.  A's and B's columns are only compared, never used as an index; F's column is
 // tested unsigned against B.rows before it indexes B.row_ptr.
@@ -60,8 +54,7 @@ struct DotCount {
     int brows, T;
     int *__restrict__ vals;
     int a0, alen;                       // the extent of A's row of the mask row the lane is in
-    unsigned heavy;                     // bit s: the lane's s-th entry is heavy
-    int hrow[kDotEntries];              // its row
+    IsectHeavy heavy;
     __device__ __forceinline__ void load(int, long long) {}
     __device__ __forceinline__ void row(int r)
     {
@@ -76,20 +69,12 @@ struct DotCount {
             const bool a_short = alen <= blen;
             const int m = a_short ? alen : blen;
             if (m > T) {                                     // heavy: k_dot_heavy stores vals[p]
-                heavy |= 1u << s;
-                hrow[s] = r;
+                heavy.note(s, r);
                 return;
             }
             const int *__restrict__ x = a_short ? colA + a0 : colB + b0;     // walked
             const int *__restrict__ y = a_short ? colB + b0 : colA + a0;     // searched
-            const int ylen = a_short ? blen : alen;
-            int lo = 0;
-            for (int q = 0; q < m; q++) {
-                const int c = x[q];
-                lo = sel_lower_bound(y, lo, ylen, c);
-                if (lo >= ylen) break;
-                count += y[lo] == c ? 1 : 0;
-            }
+            isect_lane(x, m, y, a_short ? blen : alen, [&](bool hit, int, int, int) { count += hit ? 1 : 0; });
         }
         vals[p] = count;
     }
@@ -101,19 +86,12 @@ __global__ __launch_bounds__(kSelThreads) void k_dot_count(const int *__restrict
                                                           const int *__restrict__ rpB, const int *__restrict__ colB, int brows,
                                                           int T, int *__restrict__ vals, int2 *__restrict__ list, int *nheavy)
 {
-    DotCount op = {rpA, colA, rpB, colB, brows, T, vals, 0, 0, 0u, {}};
+    DotCount op = {rpA, colA, rpB, colB, brows, T, vals, 0, 0, {0u, {}}};
     sel_walk_entries<false>(rpF, colF, rows, E, vec, tile_row, op);      // (F's columns are read again by the scatter)
-    if (__ballot(op.heavy != 0u) == 0) return;                           // (wave-uniform)
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
-#pragma unroll
-    for (int s = 0; s < kDotEntries; s++) {
-        const long long p = w0 + (s >> 2) * kSelGroup + 4 * lane + (s & 3);  // the lane's s-th entry (sel_walk_entries)
-        wave_append((op.heavy >> s) & 1u, int2{(int)p, op.hrow[s]}, list, nheavy, E, lane);
-    }
+    op.heavy.append(list, nheavy, E);
 }
 
-// one wave per entry of `list`; *nheavy (clamped to cap) entries, written by k_dot_count
+// one wave per entry of `list`, striding over it
 __global__ __launch_bounds__(kSelThreads) void k_dot_heavy(const int *__restrict__ colF, const int *__restrict__ rpA,
                                                           const int *__restrict__ colA, const int *__restrict__ rpB,
                                                           const int *__restrict__ colB, int rows, int brows,
@@ -121,12 +99,10 @@ __global__ __launch_bounds__(kSelThreads) void k_dot_heavy(const int *__restrict
                                                           long long cap, int *__restrict__ vals)
 {
     const int lane = lane_id(), w = threadIdx.x >> 6;
-    long long n = *nheavy;
-    if (n > cap) n = cap;
-    for (long long h = (long long)blockIdx.x * kDotWaves + w; h < n; h += (long long)gridDim.x * kDotWaves) {   // (wave-uniform)
-        const int2 e = list[h];
-        const int p = wave_first(e.x), i = wave_first(e.y);
-        if ((unsigned long long)p >= (unsigned long long)cap || (unsigned)i >= (unsigned)rows) continue;   // (k_dot_count wrote neither)
+    const IsectHeavyList hl(list, nheavy, cap, rows);
+    for (long long h = (long long)blockIdx.x * kIsectWaves + w; h < hl.n; h += (long long)gridDim.x * kIsectWaves) {   // (wave-uniform)
+        int p, i;
+        if (!hl.entry(h, p, i)) continue;
         const int j = wave_first(colF[p]);
         int total = 0;
         if ((unsigned)j < (unsigned)brows) {
@@ -134,45 +110,8 @@ __global__ __launch_bounds__(kSelThreads) void k_dot_heavy(const int *__restrict
             const bool a_short = alen <= blen;
             const int *__restrict__ x = a_short ? colA + a0 : colB + b0;     // strided over
             const int *__restrict__ y = a_short ? colB + b0 : colA + a0;     // searched
-            const int xlen = a_short ? alen : blen, ylen = a_short ? blen : alen;
-            int from = 0;                                    // the lane's lower bound: its elements ascend from trip to trip
-            // (ylen == 0 only with xlen == 0: the loop does not run and y is never read)
-            for (int b = 0; b < xlen; b += 64 * kDotDeep) {
-                int c[kDotDeep], lo[kDotDeep], hi[kDotDeep];
-                bool in[kDotDeep];
-#pragma unroll
-                for (int q = 0; q < kDotDeep; q++) {
-                    in[q] = b + 64 * q + lane < xlen;
-                    c[q] = in[q] ? x[b + 64 * q + lane] : 0;
-                    lo[q] = from;
-                    hi[q] = in[q] ? ylen : from;
-                }
-                // the kDotDeep lower bounds in lockstep: one load each per round, all in flight together
-                for (;;) {
-                    int mid[kDotDeep], v[kDotDeep];
-                    bool any = false;
-#pragma unroll
-                    for (int q = 0; q < kDotDeep; q++) {
-                        mid[q] = lo[q] + ((hi[q] - lo[q]) >> 1);
-                        any |= lo[q] < hi[q];
-                        v[q] = lo[q] < hi[q] ? y[mid[q]] : 0;
-                    }
-                    if (!any) break;
-#pragma unroll
-                    for (int q = 0; q < kDotDeep; q++) {
-                        if (lo[q] < hi[q]) {
-                            if (v[q] < c[q]) lo[q] = mid[q] + 1;
-                            else hi[q] = mid[q];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < kDotDeep; q++) {
-                    const bool hit = in[q] && lo[q] < ylen && y[lo[q]] == c[q];
-                    total += __popcll(__ballot(hit));
-                    if (in[q]) from = lo[q];
-                }
-            }
+            isect_wave<kIsectDeep>(x, a_short ? alen : blen, y, a_short ? blen : alen, lane,
+                                   [&](bool hit, int, int, int) { total += __popcll(__ballot(hit)); });
         }
         if (lane == 0) vals[p] = total;
     }
@@ -234,7 +173,7 @@ static bspgemm_status dot_run(bspgemm_context *ctx, const bspgemm_matrix *A, con
         hipLaunchKernelGGL(k_dot_count, dim3(select_tiles(E)), dim3(kSelThreads), 0, s, F->d_row_ptr, F->d_col_idx, F->rows, E,
                            aligned16(F->d_col_idx), ctx->tile_row, A->d_row_ptr, A->d_col_idx, B->d_row_ptr, B->d_col_idx, B->rows,
                            T, vals, list, &d_cnt->heavy);
-        hipLaunchKernelGGL(k_dot_heavy, dim3(kDotHeavyGrid), dim3(kSelThreads), 0, s, F->d_col_idx, A->d_row_ptr, A->d_col_idx,
+        hipLaunchKernelGGL(k_dot_heavy, dim3(kIsectHeavyGrid), dim3(kSelThreads), 0, s, F->d_col_idx, A->d_row_ptr, A->d_col_idx,
                            B->d_row_ptr, B->d_col_idx, rows, B->rows, list, &d_cnt->heavy, E, vals);
         launch_select_flags_value(vals, E, BSPGEMM_CMP_GT, 0, sc.flags, sc.cnt, s);
         launch_scan_counts(sc.cnt, sc.words, sc.pre, sc.part, nullptr, s);
@@ -275,13 +214,9 @@ static bspgemm_status dot_run(bspgemm_context *ctx, const bspgemm_matrix *A, con
     if (h.heavy < 0 || h.heavy > E || kept < 0 || kept > E) return FAIL(BSPGEMM_ERR_HIP, "bspgemm_multiply_masked_dot: counters out of range");
 
     // the result object: an ordinary counted result, allocated the way a product's is
-    bspgemm_result *R = new (std::nothrow) bspgemm_result{ctx, rows, kept, nullptr, nullptr, 0};
-    if (!R) return FAIL(BSPGEMM_ERR_ALLOC, "result");
+    bspgemm_result *R = nullptr;
     auto bail = [&](bspgemm_status st) { hipStreamSynchronize(s); bspgemm_result_free(R); return st; };
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_row_ptr), result_bytes_rowptr(rows)));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_col_idx), result_bytes_colidx(kept)));
-    R->col_cap = kept;
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_values), result_bytes_colidx(kept)));
+    if (bspgemm_status st = counted_result_new(ctx, rows, kept, &R)) return bail(st);
     if (E > 0) {
         launch_select_scatter(F->d_col_idx, E, sc.flags, sc.pre, R->d_col_idx, s);
         launch_select_scatter(vals, E, sc.flags, sc.pre, R->d_values, s);

@@ -251,6 +251,10 @@ hipError_t result_alloc(bspgemm_context *ctx, void **out, size_t bytes);
 void result_release(bspgemm_context *ctx, void *p, size_t bytes);
 static inline size_t result_bytes_rowptr(int rows) { return ((size_t)rows + 1) * sizeof(long long); }
 static inline size_t result_bytes_colidx(long long nnz) { return ((size_t)nnz + 4) * sizeof(int); }
+// A counted result of `rows` rows with exactly `entries` entries (nnz == col_cap == entries), nothing written yet: the
+// handle, then d_row_ptr, d_col_idx and d_values by result_alloc, in that order.  After a failure *R is NULL or a handle
+// that bspgemm_result_free takes, so the caller's `bail` frees it whichever step failed.
+bspgemm_status counted_result_new(bspgemm_context *ctx, int rows, long long entries, bspgemm_result **R);
 
 // Scratch of the flag-word passes over E entries (select.hip, setop.hip), carved from ctx->tmp (kept between calls, like
 // the transpose's): the flag words (one per 64 entries, whole tiles), the int64 scan of their counts, the scan's partials,

@@ -162,11 +162,7 @@ static bspgemm_status kcore_numbers(bspgemm_context *ctx, const bspgemm_matrix *
         carve(ctx->tmp);
     }
     // the result, allocated as a product's is: its values are the core array while the levels run
-    R = new (std::nothrow) bspgemm_result{ctx, n, n, nullptr, nullptr, n};
-    if (!R) return bail(FAIL(BSPGEMM_ERR_ALLOC, "result"));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_row_ptr), result_bytes_rowptr(n)));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_col_idx), result_bytes_colidx(n)));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&R->d_values), result_bytes_colidx(n)));
+    if (bspgemm_status st = counted_result_new(ctx, n, n, &R)) return bail(st);
     int *core = R->d_values;
     const dim3 vgrid = vertex_grid(n, kKcThreads), block(kKcThreads);
     // without edges every vertex is isolated: core 0, nothing to peel

@@ -22,15 +22,16 @@
 //   k_lcc_count    entry-parallel over T.  j is tested unsigned against n before it indexes row_ptr.  m = min(|T_i|, |T_j|):
 //                  0 nothing; LIGHT, m <= BSPGEMM_OPT_DOT_LIGHT: the lane walks the shorter row and searches the longer one
 //                  from a lower bound that only advances, crediting as above; HEAVY: the lane remembers the entry and the
-//                  wave appends its heavy entries {p, i} to a list (one atomic per wave: wave_append of wave.hpp).
-//                  The wave's hits go to the 64-bit triangle counter by one atomic.
+//                  wave appends its heavy entries {p, i} to a list (one atomic per wave).  The wave's hits go to the 64-bit
+//                  triangle counter by one atomic.
 //   k_lcc_heavy    a fixed grid, one wave per list entry; a workgroup takes kLccChunk consecutive entries of the list at a
 //                  time and drains its cache behind each chunk; the list's length is read from device memory (the launch
 //                  follows k_lcc_count on the stream).  The lanes stride over the shorter row 64 elements per step,
-//                  kLccDeep steps in flight, the searches of a trip in lockstep (k_dot_heavy's structure).  A hitting lane
-//                  credits w(i, j) to k (lcc_credit; the k of a step are distinct), the wave reduces the two weighted sums
-//                  and its hits, and lane 0 adds the sums to num[i] and num[j]; the hits go to the triangle counter once
-//                  per wave, at its end.
+//                  kIsectDeep steps in flight.  A hitting lane credits w(i, j) to k (lcc_credit; the k of a step are
+//                  distinct), the wave reduces the two weighted sums and its hits, and lane 0 adds the sums to num[i] and
+//                  num[j]; the hits go to the triangle counter once per wave, at its end.
+// The two intersections (isect_lane, isect_wave), the heavy list (IsectHeavy, IsectHeavyList) and their constants are
+// sel_rows.hpp's, shared with dot.hip; the credits of a hit are written at the two calls.
 // One synchronisation reads the counters (heavy entries, triangles, reciprocal) and, where the caller asked for degrees or
 // coefficients, S.row_ptr and num; the coefficients are computed on the host in double from those integers.
 //
@@ -52,10 +53,6 @@
 
 namespace bsp {
 
-constexpr int kLccWaves = kSelThreads / 64;
-constexpr int kLccDeep = 4;             // 64-element steps of the shorter row in flight per trip (kDotDeep of dot.hip)
-constexpr int kLccHeavyGrid = 2048;     // workgroups of k_lcc_heavy: 8192 waves (eight per SIMD of 256 CUs) share the list's chunks
-constexpr int kLccEntries = 4 * kSelSteps;   // entries of T a lane walks
 constexpr int kLccChunk = 64;           // consecutive list entries that a workgroup of k_lcc_heavy takes at a time
 
 struct LccCounters {
@@ -117,9 +114,6 @@ __device__ __forceinline__ void lcc_cache_drain(int *tag, int *val, int *num)
     __syncthreads();
 }
 
-// The heavy list is appended to by wave_append (wave.hpp).  An entry of T is appended at most once, so the list never
-// passes nnz(T) entries; the store is bounded all the same.
-
 // row v of the result holds (v, v); its value starts at 0
 __global__ __launch_bounds__(256) void k_lcc_init(int n, long long *__restrict__ row_ptr, int *__restrict__ col_idx,
                                                   int *__restrict__ num)
@@ -176,8 +170,7 @@ struct LccCount {
     int a0, alen;                       // the extent of the row the lane is in
     int cur, acc;                       // that row, and the credit it is owed so far
     int hits;
-    unsigned heavy;                     // bit s: the lane's s-th entry is heavy
-    int hrow[kLccEntries];              // its row
+    IsectHeavy heavy;
     __device__ __forceinline__ void load(int, long long) {}
     __device__ __forceinline__ void flush()
     {
@@ -201,28 +194,20 @@ struct LccCount {
         const int m = a_short ? alen : blen;
         if (m == 0) return;
         if (m > T) {                                         // heavy: k_lcc_heavy credits the entry's triangles
-            heavy |= 1u << s;
-            hrow[s] = r;
+            heavy.note(s, r);
             return;
         }
         const int x0 = a_short ? a0 : b0, y0 = a_short ? b0 : a0;   // walked, searched
-        const int *__restrict__ x = col + x0;
-        const int *__restrict__ y = col + y0;
-        const int ylen = a_short ? blen : alen;
         const int wij = DIRECTED ? wgt[p] : 2;
         int sx = 0, sy = 0;                                  // the weights of the hits' entries in the walked / searched row
-        int lo = 0;
-        for (int q = 0; q < m; q++) {
-            const int c = x[q];
-            lo = sel_lower_bound(y, lo, ylen, c);
-            if (lo >= ylen) break;
-            if (y[lo] == c) {
+        isect_lane(col + x0, m, col + y0, a_short ? blen : alen, [&](bool hit, int q, int at, int c) {
+            if (hit) {
                 hits++;
                 if ((unsigned)c < (unsigned)n) lcc_credit(tag, val, num, c, wij);
                 sx += DIRECTED ? wgt[x0 + q] : 2;
-                sy += DIRECTED ? wgt[y0 + lo] : 2;
+                sy += DIRECTED ? wgt[y0 + at] : 2;
             }
-        }
+        });
         const int wik = a_short ? sx : sy, wjk = a_short ? sy : sx;
         if (wik) atomicAdd(&num[j], wik);
         acc += wjk;
@@ -237,23 +222,16 @@ __global__ __launch_bounds__(kSelThreads) void k_lcc_count(const int *__restrict
 {
     __shared__ int tag[kLccSlots], val[kLccSlots];
     lcc_cache_clear(tag, val);                                           // (the walk's staging barrier follows)
-    LccCount<DIRECTED> op = {rpT, colT, wgt, n, T, num, tag, val, 0, 0, -1, 0, 0, 0u, {}};
+    LccCount<DIRECTED> op = {rpT, colT, wgt, n, T, num, tag, val, 0, 0, -1, 0, 0, {0u, {}}};
     sel_walk_entries<false>(rpT, colT, n, E, vec, tile_row, op);
     lcc_cache_flush(tag, val, num);
-    const int lane = lane_id(), w = threadIdx.x >> 6;
     op.flush();
     const int hits = wave_sum(op.hits);
-    if (hits && lane == 0) atomicAdd(&cnt->triangles, (u64)hits);
-    if (__ballot(op.heavy != 0u) == 0) return;                           // (wave-uniform)
-    const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
-#pragma unroll
-    for (int s = 0; s < kLccEntries; s++) {
-        const long long p = w0 + (s >> 2) * kSelGroup + 4 * lane + (s & 3);  // the lane's s-th entry (sel_walk_entries)
-        wave_append((op.heavy >> s) & 1u, int2{(int)p, op.hrow[s]}, list, &cnt->heavy, E, lane);
-    }
+    if (hits && lane_id() == 0) atomicAdd(&cnt->triangles, (u64)hits);
+    op.heavy.append(list, &cnt->heavy, E);
 }
 
-// one wave per entry of `list`; cnt->heavy (clamped to cap) entries, written by k_lcc_count
+// one wave per entry of `list`, k_lcc_count's
 template <bool DIRECTED>
 __global__ __launch_bounds__(kSelThreads) void k_lcc_heavy(const int *__restrict__ rp, const int *__restrict__ col, int n,
                                                           const unsigned char *__restrict__ wgt, const int2 *__restrict__ list,
@@ -263,8 +241,8 @@ __global__ __launch_bounds__(kSelThreads) void k_lcc_heavy(const int *__restrict
     lcc_cache_clear(tag, val);
     __syncthreads();
     const int lane = lane_id(), w = threadIdx.x >> 6;
-    long long nh = cnt->heavy;                               // (k_lcc_count's: nothing in this launch appends)
-    if (nh > cap) nh = cap;
+    const IsectHeavyList hl(list, &cnt->heavy, cap, n);
+    const long long nh = hl.n;                               // (k_lcc_count's: nothing in this launch appends)
     int triangles = 0;                                       // the wave's hits over all its entries (at most nnz(S) / 6 in all)
     // A workgroup takes `chunk` CONSECUTIVE list entries at a time, its waves striding inside the chunk, and drains its
     // cache behind every chunk: neighbours in the list are neighbours in T (a wave appends up to 64 entries out of 256
@@ -272,64 +250,28 @@ __global__ __launch_bounds__(kSelThreads) void k_lcc_heavy(const int *__restrict
     // cache; entries dealt out one by one over the grid share nothing.  A short list gets shorter chunks, so that it still
     // spreads over the grid.
     long long chunk = (nh + gridDim.x - 1) / gridDim.x;
-    chunk = chunk > kLccChunk ? kLccChunk : ((chunk + kLccWaves - 1) / kLccWaves) * kLccWaves;
+    chunk = chunk > kLccChunk ? kLccChunk : ((chunk + kIsectWaves - 1) / kIsectWaves) * kIsectWaves;
     for (long long h0 = (long long)blockIdx.x * chunk; h0 < nh; h0 += (long long)gridDim.x * chunk) {   // (workgroup-uniform)
         const long long h1 = h0 + chunk < nh ? h0 + chunk : nh;
-        for (long long h = h0 + w; h < h1; h += kLccWaves) {                                                   // (wave-uniform)
-            const int2 e = list[h];
-            const int p = wave_first(e.x), i = wave_first(e.y);
-            if ((unsigned long long)p >= (unsigned long long)cap || (unsigned)i >= (unsigned)n) continue;   // (k_lcc_count wrote neither)
+        for (long long h = h0 + w; h < h1; h += kIsectWaves) {                                                 // (wave-uniform)
+            int p, i;
+            if (!hl.entry(h, p, i)) continue;
             const int j = wave_first(col[p]);
             if ((unsigned)j >= (unsigned)n) continue;
             const int a0 = rp[i], alen = rp[i + 1] - a0, b0 = rp[j], blen = rp[j + 1] - b0;
             const bool a_short = alen <= blen;
             const int x0 = a_short ? a0 : b0, y0 = a_short ? b0 : a0;       // strided over, searched
-            const int *__restrict__ x = col + x0;
-            const int *__restrict__ y = col + y0;
-            const int xlen = a_short ? alen : blen, ylen = a_short ? blen : alen;
             const int wij = DIRECTED ? wgt[p] : 2;
             int sx = 0, sy = 0, hits = 0;
-            int from = 0;                                        // the lane's lower bound: its elements ascend from trip to trip
-            for (int b = 0; b < xlen; b += 64 * kLccDeep) {
-                int c[kLccDeep], lo[kLccDeep], hi[kLccDeep];
-                bool in[kLccDeep];
-#pragma unroll
-                for (int q = 0; q < kLccDeep; q++) {
-                    in[q] = b + 64 * q + lane < xlen;
-                    c[q] = in[q] ? x[b + 64 * q + lane] : 0;
-                    lo[q] = from;
-                    hi[q] = in[q] ? ylen : from;
-                }
-                // the kLccDeep lower bounds in lockstep: one load each per round, all in flight together
-                for (;;) {
-                    int mid[kLccDeep], v[kLccDeep];
-                    bool any = false;
-#pragma unroll
-                    for (int q = 0; q < kLccDeep; q++) {
-                        mid[q] = lo[q] + ((hi[q] - lo[q]) >> 1);
-                        any |= lo[q] < hi[q];
-                        v[q] = lo[q] < hi[q] ? y[mid[q]] : 0;
-                    }
-                    if (!any) break;
-#pragma unroll
-                    for (int q = 0; q < kLccDeep; q++) {
-                        if (lo[q] < hi[q]) {
-                            if (v[q] < c[q]) lo[q] = mid[q] + 1;
-                            else hi[q] = mid[q];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < kLccDeep; q++) {
-                    if (in[q] && lo[q] < ylen && y[lo[q]] == c[q]) {
-                        hits++;
-                        if ((unsigned)c[q] < (unsigned)n) lcc_credit(tag, val, num, c[q], wij);
-                        sx += DIRECTED ? wgt[x0 + b + 64 * q + lane] : 2;
-                        sy += DIRECTED ? wgt[y0 + lo[q]] : 2;
-                    }
-                    if (in[q]) from = lo[q];
-                }
-            }
+            isect_wave<kIsectDeep>(col + x0, a_short ? alen : blen, col + y0, a_short ? blen : alen, lane,
+                                   [&](bool hit, int q, int at, int c) {
+                                       if (hit) {           // (the k of a step are distinct)
+                                           hits++;
+                                           if ((unsigned)c < (unsigned)n) lcc_credit(tag, val, num, c, wij);
+                                           sx += DIRECTED ? wgt[x0 + q] : 2;
+                                           sy += DIRECTED ? wgt[y0 + at] : 2;
+                                       }
+                                   });
             sx = wave_sum(sx);
             sy = wave_sum(sy);
             hits = wave_sum(hits);
@@ -437,11 +379,7 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
         if (!h_num) return bail(FAIL(BSPGEMM_ERR_ALLOC, "bspgemm_local_clustering: host memory for the counts"));
     }
     // the result, allocated as a product's is: its values are num[] while the kernels run
-    res = new (std::nothrow) bspgemm_result{ctx, n, n, nullptr, nullptr, n};
-    if (!res) return bail(FAIL(BSPGEMM_ERR_ALLOC, "result"));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&res->d_row_ptr), result_bytes_rowptr(n)));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&res->d_col_idx), result_bytes_colidx(n)));
-    HIPCHK_B(result_alloc(ctx, reinterpret_cast<void **>(&res->d_values), result_bytes_colidx(n)));
+    if (bspgemm_status st2 = counted_result_new(ctx, n, n, &res)) return bail(st2);
     int *num = res->d_values;
     hipLaunchKernelGGL(k_lcc_init, vertex_grid(n, 256), dim3(256), 0, s, n, res->d_row_ptr, res->d_col_idx, num);
     HIPCHK_B(hipGetLastError());
@@ -462,13 +400,13 @@ extern "C" bspgemm_status bspgemm_local_clustering(bspgemm_context *ctx, const b
             hipLaunchKernelGGL(k_lcc_count<true>, grid, block, 0, s, T->d_row_ptr, T->d_col_idx, n, E, vec, ctx->tile_row, wgt,
                                ctx->dot_light, num, list, d_cnt);
             HIPCHK_B(stage(ms_count));
-            hipLaunchKernelGGL(k_lcc_heavy<true>, dim3(kLccHeavyGrid), block, 0, s, T->d_row_ptr, T->d_col_idx, n, wgt, list, E,
+            hipLaunchKernelGGL(k_lcc_heavy<true>, dim3(kIsectHeavyGrid), block, 0, s, T->d_row_ptr, T->d_col_idx, n, wgt, list, E,
                                num, d_cnt);
         } else {
             hipLaunchKernelGGL(k_lcc_count<false>, grid, block, 0, s, T->d_row_ptr, T->d_col_idx, n, E, vec, ctx->tile_row, wgt,
                                ctx->dot_light, num, list, d_cnt);
             HIPCHK_B(stage(ms_count));
-            hipLaunchKernelGGL(k_lcc_heavy<false>, dim3(kLccHeavyGrid), block, 0, s, T->d_row_ptr, T->d_col_idx, n, wgt, list, E,
+            hipLaunchKernelGGL(k_lcc_heavy<false>, dim3(kIsectHeavyGrid), block, 0, s, T->d_row_ptr, T->d_col_idx, n, wgt, list, E,
                                num, d_cnt);
         }
         HIPCHK_B(hipGetLastError());

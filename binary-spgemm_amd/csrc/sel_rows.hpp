@@ -1,8 +1,13 @@
 // sel_rows.hpp -- device code that the entry-parallel passes share: the tile geometry, the 16-byte entry loads, the DPP join
 // of a lane's four flags into the 64-bit flag word of 64 entries, the search of an entry's row in the tile's window of
 // row_ptr (staged in LDS; tile_row comes from k_sel_tile_rows), the lower bound of a column in a row of another operand,
-// and the walk itself.  Who uses what:
-//     sel_walk_entries   the walk over a tile's entries with an op (load / row / entry): k_merge_disjoint (bfs.hip)
+// the walk itself, and the intersection of two ascending rows on top of the two.  Who uses what:
+//     sel_walk_entries   the walk over a tile's entries with an op (load / row / entry): k_merge_disjoint (bfs.hip),
+//                        k_dot_count (dot.hip), k_lcc_weights, k_lcc_count (lcc.hip)
+//     isect_lane,        the light intersection inside that walk and the list of the entries too long for it: k_dot_count,
+//     IsectHeavy         k_lcc_count
+//     IsectHeavyList,    the list as the second kernel reads it, and one wave's intersection of a listed entry: k_dot_heavy
+//     isect_wave         (a plain grid stride over the list), k_lcc_heavy (chunks of the list, lcc.hip says why)
 //     sel_sweep_graph    the same walk behind the graph adapter (range check, self-loop skip, changed / bad words) with
 //                        an op (row / edge): k_cc_hook (cc.hip), k_scc_mark, k_scc_forward, k_scc_backward (scc.hip)
 //     SelTileRows alone  k_set_flags (setop.hip): it also needs row_begin, the column in front of the lane's four and a
@@ -175,6 +180,110 @@ __device__ __forceinline__ void sel_walk_entries(const int *__restrict__ row_ptr
         }
     }
 }
+
+// ------------------------------------------------------------------ row intersections (dot.hip, lcc.hip) ---
+// The common elements of two strictly ascending rows.  An entry whose shorter row has at most T elements is intersected by
+// its lane inside the walk (isect_lane); a longer one goes to a list {p, row} (IsectHeavy) that a second kernel walks, one
+// wave per entry (IsectHeavyList, isect_wave).  What a hit is worth is the caller's: f(hit, place in x, place in y, column).
+constexpr int kIsectWaves = kSelThreads / 64;
+constexpr int kIsectDeep = 4;               // 64-element steps of the shorter row in flight per trip (kColDeep of color.hip)
+constexpr int kIsectHeavyGrid = 2048;       // workgroups of a heavy kernel: 8192 waves (eight per SIMD of 256 CUs) share the list
+constexpr int kIsectEntries = 4 * kSelSteps;   // entries a lane walks in sel_walk_entries
+
+// One lane walks x[0, m) and searches y[0, ylen) from a lower bound that only advances; it ends when y is used up.
+template <typename F>
+__device__ __forceinline__ void isect_lane(const int *__restrict__ x, int m, const int *__restrict__ y, int ylen, F &&f)
+{
+    int lo = 0;
+    for (int q = 0; q < m; q++) {
+        const int c = x[q];
+        lo = sel_lower_bound(y, lo, ylen, c);
+        if (lo >= ylen) break;
+        f(y[lo] == c, q, lo, c);
+    }
+}
+
+// One wave: the lanes stride over x[0, xlen) 64 elements per step, DEEP steps in flight.  EVERY lane calls f for every slot
+// of a trip, with hit == false (and nothing else of meaning) past the end of x, so f may ballot.  Wave-uniform control flow.
+template <int DEEP, typename F>
+__device__ __forceinline__ void isect_wave(const int *__restrict__ x, int xlen, const int *__restrict__ y, int ylen, int lane,
+                                           F &&f)
+{
+    int from = 0;                                            // the lane's lower bound: its elements ascend from trip to trip
+    // (ylen == 0 only with xlen == 0: the loop does not run and y is never read)
+    for (int b = 0; b < xlen; b += 64 * DEEP) {
+        int c[DEEP], lo[DEEP], hi[DEEP];
+        bool in[DEEP];
+#pragma unroll
+        for (int q = 0; q < DEEP; q++) {
+            in[q] = b + 64 * q + lane < xlen;
+            c[q] = in[q] ? x[b + 64 * q + lane] : 0;
+            lo[q] = from;
+            hi[q] = in[q] ? ylen : from;
+        }
+        // the DEEP lower bounds in lockstep: one load each per round, all in flight together
+        for (;;) {
+            int mid[DEEP], v[DEEP];
+            bool any = false;
+#pragma unroll
+            for (int q = 0; q < DEEP; q++) {
+                mid[q] = lo[q] + ((hi[q] - lo[q]) >> 1);
+                any |= lo[q] < hi[q];
+                v[q] = lo[q] < hi[q] ? y[mid[q]] : 0;
+            }
+            if (!any) break;
+#pragma unroll
+            for (int q = 0; q < DEEP; q++) {
+                if (lo[q] < hi[q]) {
+                    if (v[q] < c[q]) lo[q] = mid[q] + 1;
+                    else hi[q] = mid[q];
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < DEEP; q++) {
+            f(in[q] && lo[q] < ylen && y[lo[q]] == c[q], b + 64 * q + lane, lo[q], c[q]);
+            if (in[q]) from = lo[q];
+        }
+    }
+}
+
+// The heavy entries of a lane of sel_walk_entries: an op notes them in entry(), the kernel appends them behind the walk.
+struct IsectHeavy {
+    unsigned mask;                      // bit s: the lane's s-th entry is heavy
+    int row[kIsectEntries];             // its row
+    __device__ __forceinline__ void note(int s, int r) { mask |= 1u << s, row[s] = r; }
+    // {p, row} of every noted entry to list[*counter ...] (wave_append: ballot, one atomicAdd per wave, rank by popcount).
+    // An entry is appended at most once, so the list never passes E entries; the store is bounded all the same.
+    __device__ __forceinline__ void append(int2 *list, int *counter, long long E) const
+    {
+        if (__ballot(mask != 0u) == 0) return;                           // (wave-uniform)
+        const int lane = lane_id(), w = threadIdx.x >> 6;
+        const long long w0 = (long long)blockIdx.x * kSelTile + w * kSelWaveSpan;
+#pragma unroll
+        for (int s = 0; s < kIsectEntries; s++) {
+            const long long p = w0 + (s >> 2) * kSelGroup + 4 * lane + (s & 3);  // the lane's s-th entry (sel_walk_entries)
+            wave_append((mask >> s) & 1u, int2{(int)p, row[s]}, list, counter, E, lane);
+        }
+    }
+};
+
+// The list as a heavy kernel reads it: its length comes from device memory (the launch follows the count kernel on the
+// stream, nothing in between appends), clamped to cap.
+struct IsectHeavyList {
+    const int2 *__restrict__ list;
+    long long n, cap;
+    int rows;
+    __device__ __forceinline__ IsectHeavyList(const int2 *__restrict__ l, const int *counter, long long c, int r)
+        : list(l), n(*counter > c ? c : *counter), cap(c), rows(r) {}
+    // slot h < n: the wave-uniform entry p and its row i; false: skip the slot (the count kernel wrote neither)
+    __device__ __forceinline__ bool entry(long long h, int &p, int &i) const
+    {
+        const int2 e = list[h];
+        p = wave_first(e.x), i = wave_first(e.y);
+        return (unsigned long long)p < (unsigned long long)cap && (unsigned)i < (unsigned)rows;
+    }
+};
 
 // The two words that every graph sweep reports, at the head of the algorithm's flag block (CcFlags, SccFlags)
 struct SweepFlags {

@@ -17,7 +17,7 @@ import kcore_ref
 
 K_SEL_TILE = cc_ref.K_SEL_TILE          # csrc/kernels.hpp kSelTile
 K_SEL_STAGE = cc_ref.K_SEL_STAGE        # csrc/sel_rows.hpp kSelStage
-K_DEEP = 4                              # csrc/lcc.hip kLccDeep: 64-element steps the heavy kernel has in flight
+K_DEEP = 4                              # csrc/sel_rows.hpp kIsectDeep: 64-element steps a heavy kernel has in flight
 LIGHT_DEFAULT = 32                      # BSPGEMM_OPT_DOT_LIGHT's default
 HALF = "tril"                           # the half of S that csrc/lcc.hip walks: info.heavy_entries depends on it, no result does
 

@@ -1,7 +1,8 @@
 """bspgemm_multiply_masked_dot on the GPU against the scipy model (tests/dot_ref.py): row_ptr, col_idx and values compared
 completely, every shape under dot_light = 0 (every entry with two non-empty rows goes to the one-wave-per-entry kernel),
 the default and 2^30 (none does), with info.heavy_entries asserted accordingly.  The shapes are the smallest at which
-each piece can go wrong: every shorter-row length 0 .. 130 with each kind of intersection, deep heavy entries, the tile
+each piece can go wrong: every shorter-row length 0 .. 130 with each kind of intersection, shorter rows at the edges of
+one and two trips of the one-wave kernel, deep heavy entries, the tile
 edges of the entry walk (kSelTile = 4096), rectangular operands, non-canonical input, wrapped arrays off 16-byte
 alignment, empty operands, one handle in all three roles, equivalence with the counting product, determinism, errors and
 the result object."""
@@ -14,6 +15,7 @@ import bspgemm
 import dot_ref
 import gen
 import ktruss_ref
+import lcc_ref
 from dot_ref import csr
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +103,20 @@ def _at(exp, i, j):
 
 
 # ---------------------------------------------------------------- 1. length sweep ------------------------------------
+def _row_pair(kind, m, top, rng):
+    """a shorter row of m entries and a longer one of m + 3 with the given kind of intersection; every column below top"""
+    evens, odds = list(range(2, 2 * m + 2, 2)), list(range(3, 2 * (m + 3) + 3, 2))
+    if kind == "empty":
+        return evens, odds
+    if kind == "first":                                 # only the first element of both rows
+        return ([0] + evens[1:]) if m else [], [0] + odds[1:]
+    if kind == "last":                                  # only the last element of both rows
+        return (evens[:-1] + [top]) if m else [], odds[:-1] + [top]
+    if kind == "all":                                   # every element of the shorter row
+        return [odds[t] for t in np.sort(rng.choice(m + 3, size=m, replace=False))], odds
+    return evens, evens                                 # "equal": the same row on both sides
+
+
 def _length_sweep():
     """mask entries (r, r): the shorter row has m = 0 .. 130 entries, the longer one m + 3 (A the shorter for even m, B for
     odd m), five kinds of intersection each"""
@@ -109,18 +125,7 @@ def _length_sweep():
     a_rows, b_rows = [], []
     for kind in ("empty", "first", "last", "all", "equal"):
         for m in range(131):
-            evens, odds = list(range(2, 2 * m + 2, 2)), list(range(3, 2 * (m + 3) + 3, 2))
-            if kind == "empty":
-                short, long_ = evens, odds
-            elif kind == "first":                       # only the first element of both rows
-                short, long_ = ([0] + evens[1:]) if m else [], [0] + odds[1:]
-            elif kind == "last":                        # only the last element of both rows
-                short, long_ = (evens[:-1] + [top]) if m else [], odds[:-1] + [top]
-            elif kind == "all":                         # every element of the shorter row
-                long_ = odds
-                short = [odds[t] for t in np.sort(rng.choice(m + 3, size=m, replace=False))]
-            else:                                       # the same row on both sides
-                short, long_ = evens, evens
+            short, long_ = _row_pair(kind, m, top, rng)
             a_short = m % 2 == 0
             a_rows.append(short if a_short else long_)
             b_rows.append(long_ if a_short else short)
@@ -136,6 +141,32 @@ def test_length_sweep(ctx):
     assert set(shorter.tolist()) >= set(range(131))
     assert exp[2].max() == 130 and (exp[2] == 1).sum() >= 2 * 130     # every element / one element
     bad = _check(ctx, a, b, f, n, n, cols, n, "length sweep")
+    assert not bad, bad
+
+
+def test_deep_trip_edges(ctx):
+    """the shorter row ends one element before, at and one element behind one and two trips of the one-wave kernel (64
+    lanes times the 4 steps in flight, lcc_ref.K_DEEP): kinds "all" and "empty" of the length sweep, either operand the
+    shorter"""
+    rng = np.random.default_rng(7102)
+    trip = 64 * lcc_ref.K_DEEP
+    ms = [t * trip + d for t in (1, 2) for d in (-1, 0, 1)]
+    assert ms == [255, 256, 257, 511, 512, 513]
+    a_rows, b_rows, hits = [], [], []
+    for kind in ("all", "empty"):
+        for m in ms:
+            for a_short in (True, False):
+                short, long_ = _row_pair(kind, m, None, rng)
+                a_rows.append(short if a_short else long_)
+                b_rows.append(long_ if a_short else short)
+                hits.append(m if kind == "all" else 0)
+    n, cols = len(a_rows), 2 * (ms[-1] + 3) + 3
+    assert n == 24 and cols < 1100
+    a, b, f = csr(a_rows), csr(b_rows), csr([[r] for r in range(n)])
+    exp = dot_ref.dot_ref(a, b, f, n, n, cols, n)
+    assert [_at(exp, r, r) for r in range(n)] == hits
+    assert dot_ref.heavy_at_zero(a, b, f, n, n, cols, n) == (n, n)     # every entry goes to the one-wave kernel at dot_light 0
+    bad = _check(ctx, a, b, f, n, n, cols, n, "deep trip edges")
     assert not bad, bad
 
 
